@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""bench.py --gpus N --steps K --warmup W [--workload demo_1|demo1|cfg4tree|...] [--shard | --replicas]
+"""bench.py --gpus N --steps K --warmup W [--workload demo_1|demo1|cfg4tree|...] [--shard | --replicas] [--full] [--dump-outputs DIR]
 
 A step = one planning cycle of the headless closed loop (mind_amd.closed_loop, mirroring simulator.py:58-103 /
 agent.py:277-331): 5 simulator steps of 0.02 s (observation fan-out, 10 Hz planner trigger, ego plant) containing one
@@ -9,13 +9,17 @@ MINDPlanner.plan() = AIME scenario tree (every tree node through the HIP predict
 Default workload = BASELINE.json configs[1]: the closed loop on the reference's recorded scene demo_1 (compact fixture
 tests/golden/scenes/demo_1.npz).  The trained checkpoint is not in the reference tree; the recorded scenes run with the
 BRANCHING formula weights (mind_amd/weights.py, variant "branching": the reference itself then expands 6 scenes in two AIME
-rounds and solves 5 scenario trees per plan on demo_1 -- the load a trained checkpoint produces), the plain formula weights
-(one expansion, one or two trees per plan) are reported beside it as `plain_formula_weights`.
+rounds and solves 5 scenario trees per plan on demo_1 -- the load a trained checkpoint produces); with --full the plain formula
+weights (one expansion, one or two trees per plan) are reported beside it as `plain_formula_weights`.
+
+A plain run sets up, warms up (W cycles), times the K cycles and prints the line.  --full adds everything else the line can carry:
+the extra workloads, sizes and precisions, the rocprofv3 traffic passes of the roofline and the CPU baseline.  --dump-outputs DIR
+writes what the last timed cycle computed (dump_outputs) for an output-for-output comparison of two builds.
 
 Multi-GPU (one process per GPU; plain `python bench.py --gpus N` spawns the N ranks itself through
 torch.distributed.run, under a launcher it reads RANK / LOCAL_RANK / WORLD_SIZE):
   * default workload: every rank runs its own closed loop (independent scenes: weak scaling, no data-path collective),
-    and the line also carries `tree_replicas` (every rank plans the full cfg4 tree of a scene of its own: weak scaling of the node
+    and with --full the line also carries `tree_replicas` (every rank plans the full cfg4 tree of a scene of its own: weak scaling of the node
     throughput) and `tree_sharded`: the full cfg4 scenario tree planned ONCE by all ranks together (AIME rounds
     block-sharded, contingency solves round-robin, RCCL all-gather / broadcast per round: strong scaling);
   * --workload cfg4tree / stress128tree (or --shard): that sharded plan is the headline (`scaling: strong`);
@@ -837,6 +841,34 @@ EXTRAS_FILE = "bench_extras.json"
 LINE_LIMIT = 4096
 
 
+def _f64(x):
+    if hasattr(x, "detach"):
+        x = x.detach().cpu().numpy()
+    return np.asarray(x, dtype=np.float64)
+
+
+def dump_outputs(m, d):
+    """--dump-outputs DIR: what the last timed planning cycle handed its caller (MINDPlanner.plan's control and
+    [[scenario tree], [trajectory tree]], the closed loop's ego state), one float64 .npy per array, a few KB in all.  The inputs
+    (recorded scene or seeded synthetic world, formula weights) are the same from run to run, so two builds compare file by file."""
+    os.makedirs(d, exist_ok=True)
+    pl, sim = m["pl"], m["sim"]
+    scen, traj = sim.last_result
+    tt, st = traj[0], scen[0]
+    keys = list(st.nodes)
+    arrs = {"ego_state": sim.state, "ctrl": sim.ctrl, "traj_xs": tt._arrays[0], "traj_us": tt._arrays[1],
+            "tree_costs": pl.timing["tree_costs"], "best_tree": [pl.timing["best_traj_idx"]],
+            # scenario tree of the chosen plan, nodes in insertion order: parent index (-1 = root), then the probability, predicted positions,
+            # covariances and target points of every node, flattened and concatenated, with each node's element count
+            "scen_parent": [keys.index(st.nodes[k].parent_key) if st.nodes[k].parent_key in st.nodes else -1 for k in keys]}
+    for i, name in enumerate(("scen_prob", "scen_pos", "scen_cov", "scen_tgt")):
+        parts = [_f64(st.nodes[k].data[i]).ravel() for k in keys]
+        arrs[name] = np.concatenate(parts) if parts else np.zeros(0)
+        arrs[name + "_sizes"] = [p.size for p in parts]
+    for name, v in arrs.items():
+        np.save(os.path.join(d, name + ".npy"), _f64(v))
+
+
 def _sig(v, n=5):
     """floats to n significant digits (the line is a record, not an archive); containers recursively"""
     if isinstance(v, float):
@@ -959,7 +991,12 @@ def main():
     ap.add_argument("--replicas", action="store_true", help="N > 1: independent closed loops per rank even for a full-tree workload")
     ap.add_argument("--prec", default=HEADLINE_PREC, choices=list(PREC_DTYPE),
                     help="arithmetic of the predictor's MFMA contractions for the headline measurement (default: the fp32-class one; bf16x3 is reported beside it)")
-    ap.add_argument("--headline-first", action="store_true", help="measure the headline before the extra workloads (the default runs them first: a fresh box warms up on them)")
+    ap.add_argument("--headline-first", action="store_true", help="with --full: measure the headline before the extra workloads (the default runs them first: a fresh box warms up on them)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the extra workloads and precisions, the rocprofv3 traffic passes and the CPU baseline "
+                         "(a plain run sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed planning cycle handed its caller as DIR/<name>.npy (float64)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench.py needs a GPU"
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -987,9 +1024,9 @@ def main():
             return run_concurrent_groups(args)
         return run_concurrent_processes(args) if args.processes else run_concurrent(args)
     shard = world > 1 and not args.replicas and (args.shard or args.workload in FULL_TREE)
-    extras = not args.no_extras and args.workload == "demo_1"
-    # The demo-size measurements of the line (plain weights, synthetic branching, the other recorded scenes, config 3, exact fp32: seconds of
-    # closed loops) run BEFORE the headline: a fresh box (the driver's, gpurun's) needs a few seconds of work to reach its steady state -- the first
+    extras = args.full and not args.no_extras and args.workload == "demo_1"
+    # With --full, the demo-size measurements of the line (plain weights, synthetic branching, the other recorded scenes, config 3, exact fp32: seconds of
+    # closed loops) run BEFORE the headline: a fresh box needs a few seconds of work to reach its steady state -- the first
     # invocation of the day measured the same AIME rounds at 2.07 ms of host wall instead of 1.78 (profiles/r05v_*: 1 233-1 374 sim steps/s
     # first, 1 470-1 500 from the second process on) -- and the closed loop's rate is what a loop that has been running delivers.  The full-tree
     # workloads run AFTER it (behind their 200 GB arenas the same process runs the small loop 10 % slower).  --headline-first: the old order.
@@ -1133,11 +1170,13 @@ def main():
     if m["collectives"] is not None:
         out["collectives_per_plan"] = m["collectives"][0] / args.steps
         out["gathered_mb_per_plan"] = m["collectives"][1] / args.steps / 1e6
+    if args.dump_outputs and rank == 0:
+        dump_outputs(m, args.dump_outputs)
     if args.headline_first:
         run_extras_guarded(True)
     run_extras_guarded(False)
     out.update(pre)
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         if not args.no_traffic and out.get("roofline"):
             tb, det = measure_traffic(args.workload, out["roofline"]["algorithmic_bytes_per_launch"], prec=args.prec)
             out["roofline"]["traffic"] = tb

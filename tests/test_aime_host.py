@@ -225,19 +225,22 @@ def test_batched_tree_evaluation_equals_per_tree():
 
 
 from oracle import ref_harness as _rh  # noqa: E402
+from ref_golden import Recorded  # noqa: E402
 
 
 @pytest.mark.reference
-@pytest.mark.skipif(not _rh.available(), reason="reference tree not present")
 def test_planner_helpers_match_reference_live():
-    """Build container only: MINDPlanner.resample_target_lane and evaluate_traj_tree (planner.py:147-198) of the imported
+    """Against recorded values of the imported reference (tests/ref_golden.py): MINDPlanner.resample_target_lane and evaluate_traj_tree (planner.py:147-198) of the imported
     reference on random inputs against this package's vectorised versions."""
     from types import SimpleNamespace
     from mind_amd.planners.mind.trajectory_tree import to_traj_tree
-    m = _rh.ref_modules()
-    RefPlanner = m["planners.mind.planner"].MINDPlanner
-    RefTree, RefNode = m["planners.basic.tree"].Tree, m["planners.basic.tree"].Node
-    ref, mine = RefPlanner.__new__(RefPlanner), MINDPlanner.__new__(MINDPlanner)
+    rec = Recorded("planner_helpers")
+
+    def ref():
+        m = _rh.ref_modules()
+        RefPlanner = m["planners.mind.planner"].MINDPlanner
+        return RefPlanner.__new__(RefPlanner), m["planners.basic.tree"].Tree, m["planners.basic.tree"].Node
+    mine = MINDPlanner.__new__(MINDPlanner)
     rng = np.random.default_rng(11)
     for trial in range(6):
         P = int(rng.integers(3, 40))
@@ -247,7 +250,7 @@ def test_planner_helpers_match_reference_live():
                 np.eye(3, dtype=np.float32)[rng.integers(0, 3, P)], np.eye(3, dtype=np.float32)[rng.integers(0, 3, P)],
                 rng.integers(0, 2, P).astype(np.float32), rng.integers(0, 2, P).astype(np.float32)]
         lcl = SimpleNamespace(target_lane=lane, target_lane_info=info, target_velocity=float(rng.uniform(2, 9)))
-        wl, wi = ref.resample_target_lane(lcl)
+        wl, wi = rec(("resample", trial), lambda: ref()[0].resample_target_lane(lcl))
         gl, gi = mine.resample_target_lane(lcl)
         assert np.asarray(gl).dtype == np.asarray(wl).dtype and np.array_equal(gl, wl)
         assert len(gi) == len(wi) and all(np.array_equal(a, b) for a, b in zip(gi, wi))
@@ -258,33 +261,34 @@ def test_planner_helpers_match_reference_live():
         us = rng.normal(size=(M, 2))
         x0 = xs[0] * 0.9
         tt = to_traj_tree(dict(parent=par), x0, xs, us)
-        rt = RefTree()
-        rt.add_node(RefNode(-1, None, [x0, np.zeros(2)]))
-        for k in range(M):
-            rt.add_node(RefNode(k, int(par[k]), [xs[k], us[k]]))
-        want = ref.evaluate_traj_tree(lcl, rt)
+
+        def evaluate():
+            planner, RefTree, RefNode = ref()
+            rt = RefTree()
+            rt.add_node(RefNode(-1, None, [x0, np.zeros(2)]))
+            for k in range(M):
+                rt.add_node(RefNode(k, int(par[k]), [xs[k], us[k]]))
+            return planner.evaluate_traj_tree(lcl, rt)
+        want = rec(("evaluate", trial), evaluate)
         assert abs(mine.evaluate_traj_tree(lcl, tt) - want) <= 1e-12 * abs(want)
         assert abs(mine.evaluate_traj_trees(lcl, [tt])[0] - want) <= 1e-12 * abs(want)
 
 
 @pytest.mark.reference
-@pytest.mark.skipif(not _rh.available(), reason="reference tree not present")
 def test_observation_bookkeeping_matches_reference_live():
-    """Build container only: MINDPlanner.update_observation (planner.py:65-95: 50-frame sliding tracks, dummy states for
+    """Against recorded values of the imported reference (tests/ref_golden.py): MINDPlanner.update_observation (planner.py:65-95: 50-frame sliding tracks, dummy states for
     agents missing from a frame) followed by get_agent_trajectories (utils.py:245-342) of the imported reference, fed with a
     random appear / disappear pattern over 75 frames -- tracks, flags, padding, type one-hots and agent order after every
     frame from the tenth on."""
     import torch as _torch
     from types import SimpleNamespace as NS
-    m = _rh.ref_modules()
-    ref = m["planners.mind.planner"].MINDPlanner.__new__(m["planners.mind.planner"].MINDPlanner)
-    ref.agent_obs, ref.obs_len = {}, 50
     mine = MINDPlanner.__new__(MINDPlanner)
     mine.agent_obs, mine.obs_len = {}, 50
     rng = np.random.default_rng(21)
     ids = ["AV"] + [str(100 + i) for i in range(9)]
     types = [list(_rh.ObjectType)[i % 7] for i in range(10)]
     present = {i: True for i in ids}
+    frames = []                                                                # the inputs first (one rng stream), then both sides
     for frame in range(75):
         for i in ids[1:]:
             if rng.random() < 0.12:
@@ -295,17 +299,28 @@ def test_observation_bookkeeping_matches_reference_live():
         ego = obs("AV")
         exo = [obs(i) for i in ids[1:] if present[i]]
         rng.shuffle(exo)                                                       # first-appearance order defines the agent order
-        lcl = NS(ego_agent=ego, exo_agents=exo)
-        ref.update_observation(lcl)
+        frames.append(NS(ego_agent=ego, exo_agents=exo))
+
+    def ref():
+        m = _rh.ref_modules()
+        ref = m["planners.mind.planner"].MINDPlanner.__new__(m["planners.mind.planner"].MINDPlanner)
+        ref.agent_obs, ref.obs_len = {}, 50
+        out = []
+        for frame, lcl in enumerate(frames):
+            ref.update_observation(lcl)
+            want = m["planners.mind.utils"].get_agent_trajectories(ref.agent_obs, _torch.device("cpu")) if frame >= 10 else None
+            out.append((list(ref.agent_obs), want))
+        return out
+    wants = Recorded("observation_bookkeeping")("frames75_seed21", ref)
+    for frame, lcl in enumerate(frames):
+        ref_ids, want = wants[frame]
         mine.update_observation(lcl)
-        assert list(ref.agent_obs) == list(mine.agent_obs)
+        assert ref_ids == list(mine.agent_obs)
         if frame < 10:
             continue
-        want = m["planners.mind.utils"].get_agent_trajectories(ref.agent_obs, _torch.device("cpu"))
         got = U.get_agent_trajectories(mine.agent_obs)
         assert got[5] == want[5] and got[6] == want[6], frame
         for g_, w_ in zip(got[:5], want[:5]):
-            w_ = w_.numpy()
             assert g_.dtype == w_.dtype and g_.shape == w_.shape and np.array_equal(g_, w_), frame
 
 

@@ -1,11 +1,12 @@
 """f1: closed-loop driver.  CPU: plant and trigger logic (plant pinned against the imported reference
-in the build container); GPU: a short closed loop with the real planner."""
+recorded in tests/golden/ref_live); GPU: a short closed loop with the real planner."""
 import numpy as np
 import pytest
 
 from mind_amd.closed_loop import ClosedLoopSim, kine_propagate
 from mind_amd.synth import SynthWorld
 from oracle import ref_harness as rh
+from ref_golden import Recorded
 
 
 def test_kine_propagate_values():
@@ -17,14 +18,17 @@ def test_kine_propagate_values():
 
 
 @pytest.mark.reference
-@pytest.mark.skipif(not rh.available(), reason="reference tree not present")
 def test_kine_propagate_matches_reference():
-    rh.install()
-    from common.kinematics import kine_propagate as ref
+    rec = Recorded("kine_propagate")
+
+    def ref(st, ct):
+        rh.install()
+        from common.kinematics import kine_propagate as ref
+        return ref(st, ct, 0.02, 3.0, 15.0, np.deg2rad(45.0))
     rng = np.random.default_rng(0)
-    for _ in range(50):
+    for i in range(50):
         st, ct = rng.normal(size=4) * [10, 10, 5, 1], rng.normal(size=2) * [4, 0.5]
-        assert np.array_equal(ref(st, ct, 0.02, 3.0, 15.0, np.deg2rad(45.0)), kine_propagate(st, ct, 0.02, 3.0, 15.0, np.deg2rad(45.0)))
+        assert np.array_equal(rec(i, lambda: ref(st, ct)), kine_propagate(st, ct, 0.02, 3.0, 15.0, np.deg2rad(45.0)))
 
 
 class _StubPlanner:

@@ -101,7 +101,7 @@ def test_bench_prints_one_contract_json_line(tmp_path):
     import subprocess
     import sys
     extras = str(tmp_path / "bench_extras.json")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--tree-steps", "2"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--tree-steps", "2"],
                          capture_output=True, text=True, timeout=900, env=dict(os.environ, MIND_BENCH_EXTRAS=extras))
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]

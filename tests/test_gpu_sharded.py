@@ -140,7 +140,7 @@ def test_bench_spawns_its_own_ranks_and_checks_the_world_size(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env["MIND_BENCH_EXTRAS"] = str(tmp_path / "bench_extras.json")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--backend", "gloo",
-                          "--tree-steps", "1"], env=env, capture_output=True, text=True, timeout=900)
+                          "--full", "--tree-steps", "1"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1

@@ -1,5 +1,5 @@
 """CPU: the C tree-iLQR oracle against golden vectors captured from the imported reference
-(tests/golden/gen_golden.py: ilqr, potential) and, in the build container, against the reference itself."""
+(tests/golden/gen_golden.py: ilqr, potential) and against recorded values of the reference itself (tests/ref_golden.py)."""
 import os
 
 import numpy as np
@@ -8,6 +8,7 @@ import pytest
 from mind_amd.synth import scripted_scenario_tree
 from oracle import ilqr as oi
 from oracle import ref_harness as rh
+from ref_golden import Recorded
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G = dict(np.load(os.path.join(ROOT, "tests", "golden", "ilqr.npz")))
@@ -57,68 +58,74 @@ def test_flatten_every_even_substep_and_lifo_order():
 
 
 @pytest.mark.reference
-@pytest.mark.skipif(not rh.available(), reason="reference tree not present")
 def test_oracle_matches_imported_reference_live():
-    m = rh.ref_modules()
-    Tree, Node = m["planners.basic.tree"].Tree, m["planners.basic.tree"].Node
-    TTO = m["planners.mind.trajectory_tree"].TrajectoryTreeOptimizer
-    cfgmod = m["planners.mind.configs.planning.demo_1"]
     sst = scripted_scenario_tree("lead", 5, seed=3)
-    tree = Tree()
-    for k, p, d in sst["nodes"]:
-        tree.add_node(Node(k, p, d))
-    opt = TTO(cfgmod.TrajTreeCfg())
-    opt.init_warm_start_cost_tree(tree, sst["state"], sst["ctrl"], sst["target_lane"], sst["target_vel"])
-    xs_w, us_w = opt.warm_start_solve()
-    opt.init_cost_tree(tree, sst["state"], sst["ctrl"], sst["target_lane"], sst["target_vel"])
-    opt.solve(us_w)
+
+    def ref():
+        m = rh.ref_modules()
+        Tree, Node = m["planners.basic.tree"].Tree, m["planners.basic.tree"].Node
+        TTO = m["planners.mind.trajectory_tree"].TrajectoryTreeOptimizer
+        cfgmod = m["planners.mind.configs.planning.demo_1"]
+        tree = Tree()
+        for k, p, d in sst["nodes"]:
+            tree.add_node(Node(k, p, d))
+        opt = TTO(cfgmod.TrajTreeCfg())
+        opt.init_warm_start_cost_tree(tree, sst["state"], sst["ctrl"], sst["target_lane"], sst["target_vel"])
+        xs_w, us_w = opt.warm_start_solve()
+        opt.init_cost_tree(tree, sst["state"], sst["ctrl"], sst["target_lane"], sst["target_vel"])
+        opt.solve(us_w)
+        return np.array(xs_w), np.array(opt.ilqr.xs), float(opt.ilqr._mu)
+    xs_w, xs_f, mu = Recorded("oracle_ilqr_live")("lead5", ref)
     flat, w, f = oi.contingency(oi.default_cfg(), sst["nodes"], sst["state"], sst["ctrl"], sst["target_lane"], sst["target_vel"])
-    assert np.abs(w["xs"] - xs_w).max() < 1e-9 and np.abs(f["xs"] - opt.ilqr.xs).max() < 1e-8
-    assert f["mu"] == opt.ilqr._mu
+    assert np.abs(w["xs"] - xs_w).max() < 1e-9 and np.abs(f["xs"] - xs_f).max() < 1e-8
+    assert f["mu"] == mu
 
 
 @pytest.mark.reference
-@pytest.mark.skipif(not rh.available(), reason="reference tree not present")
 @pytest.mark.parametrize("kind,a", [("lead", 5), ("branch3", 6)])
 def test_oracle_iteration_trace_equals_the_imported_references(kind, a):
     """iLQR.fit's loop (planners/ilqr/solver.py:133-158) ITERATION BY ITERATION: the Levenberg-Marquardt value every backward pass runs
     with, the cost of the nominal trajectory when the line search starts and its outcome, recorded by wrapping the imported reference's
     _backward_pass / _backtrack_line_search, against the rows of the C oracle's loop (oracle_ilqr_last_trace; the same rows come out of
     the HIP kernel through mind_last_ilqr_trace: tests/test_gpu_ilqr.py::test_iteration_trace_equals_the_oracles)."""
-    m = rh.ref_modules()
-    Tree, Node = m["planners.basic.tree"].Tree, m["planners.basic.tree"].Node
-    TTO = m["planners.mind.trajectory_tree"].TrajectoryTreeOptimizer
-    iLQR = m["planners.ilqr.solver"].iLQR
-    cfgmod = m["planners.mind.configs.planning.demo_1"]
     sst = scripted_scenario_tree(kind, a, seed=3)
-    tree = Tree()
-    for k, p, d in sst["nodes"]:
-        tree.add_node(Node(k, p, d))
-    fits = []
-    o_bp, o_ls, o_fit = iLQR._backward_pass, iLQR._backtrack_line_search, iLQR.fit
 
-    def bp(self):
-        fits[-1].append([float(self._mu), float(self.J_opt), -2.0])
-        return o_bp(self)
+    def ref():
+        m = rh.ref_modules()
+        Tree, Node = m["planners.basic.tree"].Tree, m["planners.basic.tree"].Node
+        TTO = m["planners.mind.trajectory_tree"].TrajectoryTreeOptimizer
+        iLQR = m["planners.ilqr.solver"].iLQR
+        cfgmod = m["planners.mind.configs.planning.demo_1"]
+        tree = Tree()
+        for k, p, d in sst["nodes"]:
+            tree.add_node(Node(k, p, d))
+        fits = []
+        o_bp, o_ls, o_fit = iLQR._backward_pass, iLQR._backtrack_line_search, iLQR.fit
 
-    def ls(self, alphas):
-        acc, conv = o_ls(self, alphas)
-        fits[-1][-1][2] = 1.0 if acc else -1.0
-        return acc, conv
+        def bp(self):
+            fits[-1].append([float(self._mu), float(self.J_opt), -2.0])
+            return o_bp(self)
 
-    def fit(self, *args, **kw):
-        fits.append([])
-        return o_fit(self, *args, **kw)
+        def ls(self, alphas):
+            acc, conv = o_ls(self, alphas)
+            fits[-1][-1][2] = 1.0 if acc else -1.0
+            return acc, conv
 
-    iLQR._backward_pass, iLQR._backtrack_line_search, iLQR.fit = bp, ls, fit
-    try:
-        opt = TTO(cfgmod.TrajTreeCfg())
-        opt.init_warm_start_cost_tree(tree, sst["state"], sst["ctrl"], sst["target_lane"], sst["target_vel"])
-        xs_w, us_w = opt.warm_start_solve()
-        opt.init_cost_tree(tree, sst["state"], sst["ctrl"], sst["target_lane"], sst["target_vel"])
-        opt.solve(us_w)
-    finally:
-        iLQR._backward_pass, iLQR._backtrack_line_search, iLQR.fit = o_bp, o_ls, o_fit
+        def fit(self, *args, **kw):
+            fits.append([])
+            return o_fit(self, *args, **kw)
+
+        iLQR._backward_pass, iLQR._backtrack_line_search, iLQR.fit = bp, ls, fit
+        try:
+            opt = TTO(cfgmod.TrajTreeCfg())
+            opt.init_warm_start_cost_tree(tree, sst["state"], sst["ctrl"], sst["target_lane"], sst["target_vel"])
+            xs_w, us_w = opt.warm_start_solve()
+            opt.init_cost_tree(tree, sst["state"], sst["ctrl"], sst["target_lane"], sst["target_vel"])
+            opt.solve(us_w)
+        finally:
+            iLQR._backward_pass, iLQR._backtrack_line_search, iLQR.fit = o_bp, o_ls, o_fit
+        return fits
+    fits = Recorded("oracle_ilqr_trace")(f"{kind}{a}", ref)
     cfg = oi.default_cfg()
     flat = oi.flatten(sst["nodes"])
     x0 = oi.init_state(sst["state"], sst["ctrl"])

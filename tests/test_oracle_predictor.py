@@ -1,5 +1,5 @@
 """CPU: the oracle predictor restatement against the committed golden vectors (captured from the
-imported reference by tests/golden/gen_golden.py) and, in the build container, against the reference itself."""
+imported reference by tests/golden/gen_golden.py) and against recorded values of the reference itself (tests/ref_golden.py)."""
 import numpy as np
 import pytest
 import torch
@@ -8,6 +8,7 @@ from mind_amd.synth import predictor_batch
 from mind_amd.weights import formula_state_dict, state_dict_spec
 from oracle import predictor as op
 from oracle import ref_harness as rh
+from ref_golden import Recorded
 
 CASES = [(3, 4, 1, 1), (8, 20, 2, 1), (40, 55, 1, 1), (2, 2, 1, 3)]
 TOL = 2e-5   # fp32 forward; reference-vs-fp64 itself differs by ~2.5e-6 on O(1..10) outputs
@@ -64,18 +65,21 @@ def test_rpe_diagonal_and_coincident():
 
 
 @pytest.mark.reference
-@pytest.mark.skipif(not rh.available(), reason="reference tree not present")
 def test_oracle_matches_imported_reference(formula_sd):
-    m = rh.ref_modules()
-    net = rh.build_ref_network(formula_sd)
-    sd_ref = net.state_dict()
-    assert [k for k, _ in state_dict_spec()] == list(sd_ref.keys())
-    get_rpe = m["planners.mind.utils"].get_rpe
     tb = to_t(predictor_batch(6, 9, 2, seed=7))
-    rpes = [{"scene": get_rpe(c, v)[0], "scene_mask": None} for c, v in zip(tb["CTRS"], tb["VECS"])]
-    rc, rr, ra = net((tb["ACTORS"], tb["ACTOR_IDCS"], tb["LANES"], tb["LANE_IDCS"], rpes, tb["TGT_NODES"], tb["TGT_RPE"]))
+
+    def ref():
+        m = rh.ref_modules()
+        net = rh.build_ref_network(formula_sd)
+        get_rpe = m["planners.mind.utils"].get_rpe
+        rpes = [{"scene": get_rpe(c, v)[0], "scene_mask": None} for c, v in zip(tb["CTRS"], tb["VECS"])]
+        with torch.no_grad():
+            rc, rr, ra = net((tb["ACTORS"], tb["ACTOR_IDCS"], tb["LANES"], tb["LANE_IDCS"], rpes, tb["TGT_NODES"], tb["TGT_RPE"]))
+        return list(net.state_dict().keys()), [rc[b] for b in range(2)], [rr[b] for b in range(2)], [ra[b][0] for b in range(2)]
+    keys, rc, rr, ra = Recorded("oracle_predictor")("batch6x9x2_seed7", ref)
+    assert [k for k, _ in state_dict_spec()] == keys
     oc, orr, ov = op.forward(formula_sd, tb)
     for b in range(2):
-        assert (rc[b] - oc[b]).abs().max() < 1e-6
-        assert (rr[b] - orr[b]).abs().max() < TOL
-        assert (ra[b][0] - ov[b]).abs().max() < TOL
+        assert (torch.as_tensor(rc[b]) - oc[b]).abs().max() < 1e-6
+        assert (torch.as_tensor(rr[b]) - orr[b]).abs().max() < TOL
+        assert (torch.as_tensor(ra[b]) - ov[b]).abs().max() < TOL

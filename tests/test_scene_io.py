@@ -5,7 +5,7 @@ Two layers, two kinds of evidence:
     resampling, target lane).  tests/golden/scene_io.npz holds what the reference's code produced on its four
     demo scenes (tests/golden/gen_golden.py scenes) -> exact comparison.
   * mind_amd.av2_lite restates the two av2 readers underneath (av2 is not importable here): UNPINNED, checked by
-    geometry invariants and, in the build container, against the raw files.
+    geometry invariants and against the raw files (tests/golden/raw).
 """
 import glob
 import json
@@ -17,6 +17,7 @@ import pytest
 from mind_amd import av2_lite, scene_io
 from mind_amd.closed_loop import ClosedLoopSim
 from oracle import ref_harness as rh
+from ref_golden import Recorded
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = np.load(os.path.join(ROOT, "tests", "golden", "scene_io.npz"))
@@ -103,19 +104,19 @@ def test_scenario_tables(scenes, name):
 
 
 @pytest.mark.reference
-@pytest.mark.skipif(not rh.available(), reason="reference tree not present")
 @pytest.mark.parametrize("name", DEMOS)
 def test_raw_file_readers_match_fixture(scenes, name):
-    """Build container only: the JSON / parquet readers reproduce the committed compact scene files."""
+    """The JSON / parquet readers reproduce the committed compact scene files from the recorded AV2 files (tests/golden/raw: the
+    reference's data/<seq_id>/); the scene's closed-loop agent as the reference's configs/<name>.json sets it up."""
     seq = scene_io.DEMO_SCENES[name]
-    d = os.path.join(rh.REF_ROOT, "data", seq)
+    d = os.path.join(ROOT, "tests", "golden", "raw", seq)
     smap = av2_lite.StaticMap.from_json(os.path.join(d, f"log_map_archive_{seq}.json"))
     sc = av2_lite.load_argoverse_scenario_parquet(os.path.join(d, f"scenario_{seq}.parquet"))
     a, b = smap.to_arrays(), scenes[name][0].to_arrays()
     assert a.keys() == b.keys() and all(np.array_equal(a[k], b[k]) for k in a)
     a, b = sc.to_arrays(), scenes[name][1].to_arrays()
     assert a.keys() == b.keys() and all(np.array_equal(a[k], b[k]) for k in a)
-    cfg = json.load(open(os.path.join(rh.REF_ROOT, "configs", name + ".json")))
+    cfg = Recorded("scene_configs")(name, lambda: json.load(open(os.path.join(rh.REF_ROOT, "configs", name + ".json"))))
     assert cfg["seq_id"] == seq
     assert json.loads(scenes[name][2]["cl_agent"]) == {k: cfg["cl_agents"][0][k] for k in
                                                        ("id", "enable_timestep", "semantic_lane", "target_velocity")}
@@ -322,16 +323,24 @@ def test_track_selection_rules_on_a_toy_scenario():
 
 
 @pytest.mark.reference
-@pytest.mark.skipif(not rh.available(), reason="reference tree not present")
 def test_toy_scenario_matches_reference_loader():
-    """Build container only: the reference's own ArgoAgentLoader.get_trajs_info on random toy scenarios (tracks with holes,
+    """Against recorded values of the imported reference (tests/ref_golden.py): the reference's own ArgoAgentLoader.get_trajs_info on random toy scenarios (tracks with holes,
     late starts, off-lane stretches) against load_trajs_info -- the golden scenes do not exercise every drop rule."""
     import importlib
     import sys
     from types import SimpleNamespace as NS
-    rh.install()
-    loader_mod = importlib.import_module("loader")
-    ser = sys.modules["av2.datasets.motion_forecasting.scenario_serialization"]
+    rec = Recorded("toy_scenario_loader")
+
+    def ref(scen):
+        rh.install()
+        loader_mod = importlib.import_module("loader")
+        ser = sys.modules["av2.datasets.motion_forecasting.scenario_serialization"]
+        orig = ser.load_argoverse_scenario_parquet
+        ser.load_argoverse_scenario_parquet = lambda path: scen
+        try:
+            return loader_mod.ArgoAgentLoader("unused").get_trajs_info(smp)
+        finally:
+            ser.load_argoverse_scenario_parquet = orig
     rng = np.random.default_rng(7)
     smp = scene_io.SemanticMap()
     xs = np.arange(0.0, 300.0, 3.0)
@@ -351,12 +360,7 @@ def test_toy_scenario_matches_reference_loader():
             cat = rh.TrackCategory.FOCAL_TRACK if i == 0 else rh.TrackCategory[cats[i % 3]]
             tracks.append(rh.Track(tid, st, list(rh.ObjectType)[i % 5], cat))
         scen = NS(tracks=tracks, focal_track_id="focal")
-        orig = ser.load_argoverse_scenario_parquet
-        ser.load_argoverse_scenario_parquet = lambda path: scen
-        try:
-            want = loader_mod.ArgoAgentLoader("unused").get_trajs_info(smp)
-        finally:
-            ser.load_argoverse_scenario_parquet = orig
+        want = rec(trial, lambda: ref(scen))
         got = scene_io.load_trajs_info(scen, smp)
         assert got[4] == want[4] and got[5] == want[5], trial
         assert [t[0].name for t in got[3]] == [t[0].name for t in want[3]]
@@ -366,13 +370,17 @@ def test_toy_scenario_matches_reference_loader():
 
 
 @pytest.mark.reference
-@pytest.mark.skipif(not rh.available(), reason="reference tree not present")
 def test_target_lane_branches_match_reference_agent():
-    """Build container only: CustomizedAgent.get_target_lane / get_closest_semantic_lane (agent.py:179-250) on toy lanes and
+    """Against recorded values of the imported reference (tests/ref_golden.py): CustomizedAgent.get_target_lane / get_closest_semantic_lane (agent.py:179-250) on toy lanes and
     random recorded paths -- closest lane found / not found, explicit lane id, with and without the recorded path."""
     import importlib
-    rh.install()
-    agent_mod = importlib.import_module("agent")
+    rec = Recorded("target_lane_branches")
+
+    def ref_agent(pos, ang, v):
+        rh.install()
+        ag = importlib.import_module("agent").CustomizedAgent()
+        ag.traj_info = [pos, ang, np.full(546, v, np.float32), np.ones(546, np.int16)]
+        return ag
     rng = np.random.default_rng(3)
     xs = np.arange(0.0, 160.0, 2.5)
     smp = scene_io.SemanticMap()
@@ -387,16 +395,14 @@ def test_target_lane_branches_match_reference_agent():
         t = np.arange(0, 546)[:, None] * 0.02
         pos = (np.array([[x0, y0]]) + v * t * np.array([[np.cos(yaw), np.sin(yaw)]]) + rng.normal(size=(546, 2)) * 0.01).astype(np.float32)
         ang = np.full(546, yaw, np.float32)
-        ag = agent_mod.CustomizedAgent()
-        ag.traj_info = [pos, ang, np.full(546, v, np.float32), np.ones(546, np.int16)]
-        want_c = ag.get_closest_semantic_lane(smp, pos, ang)
+        want_c = rec((trial, "closest"), lambda: ref_agent(pos, ang, v).get_closest_semantic_lane(smp, pos, ang))
         assert scene_io.get_closest_semantic_lane(smp, pos, ang) == want_c
         seen.add(want_c)
         for use_traj in (False, True):
             for lane_id in (None, 1, 2):
                 if v < 0.05 and (use_traj or want_c is None):
                     continue                                             # a standing agent has a one-point path: both sides index [-2]
-                want, want_info = ag.get_target_lane(smp, use_traj, lane_id)
+                want, want_info = rec((trial, use_traj, lane_id), lambda: ref_agent(pos, ang, v).get_target_lane(smp, use_traj, lane_id))
                 got, got_info = scene_io.target_lane_for(smp, pos, ang, use_traj, lane_id)
                 assert got.dtype == want.dtype and np.array_equal(got, want), (trial, use_traj, lane_id)
                 assert (got_info is None) == (want_info is None)
@@ -404,27 +410,34 @@ def test_target_lane_branches_match_reference_agent():
 
 
 @pytest.mark.reference
-@pytest.mark.skipif(not rh.available(), reason="reference tree not present")
 def test_local_semantic_map_matches_reference(scenes):
-    """Build container only: LocalSemanticMap (common/semantic_map.py:176-233) on the recorded demo_1 map: closest semantic
+    """Against recorded values of the imported reference (tests/ref_golden.py): LocalSemanticMap (common/semantic_map.py:176-233) on the recorded demo_1 map: closest semantic
     lane for random poses, observation split into ego / exo."""
     import importlib
     from types import SimpleNamespace as NS
-    rh.install()
-    ref_mod = importlib.import_module("common.semantic_map")
+    rec = Recorded("local_semantic_map")
     smp = scene_io.SemanticMap.from_static_map(scenes["demo_1"][0])
-    ref_smp = NS(map_data=None, semantic_lanes=smp.semantic_lanes, semantic_lanes_infos=smp.semantic_lanes_infos)
-    mine, ref = scene_io.LocalSemanticMap("AV", smp), ref_mod.LocalSemanticMap("AV", ref_smp)
+    mine = scene_io.LocalSemanticMap("AV", smp)
+
+    def ref():
+        rh.install()
+        ref_smp = NS(map_data=None, semantic_lanes=smp.semantic_lanes, semantic_lanes_infos=smp.semantic_lanes_infos)
+        return importlib.import_module("common.semantic_map").LocalSemanticMap("AV", ref_smp)
     rng = np.random.default_rng(5)
     lo, hi = np.array(smp.limits)[:, 0], np.array(smp.limits)[:, 1]
     hits = 0
-    for _ in range(200):
+    for i in range(200):
         p, a = rng.uniform(lo, hi), rng.uniform(-np.pi, np.pi)
-        want = ref.get_closest_semantic_lane(p, a)
+        want = rec(("closest", i), lambda: ref().get_closest_semantic_lane(p, a))
         assert mine.get_closest_semantic_lane(p, a) == want
         hits += want is not None
     assert 20 < hits <= 200
     agents = [NS(id=i, state=None) for i in ("7", "AV", "9")]
     mine.update_observation(agents)
-    ref.update_observation(agents)
-    assert mine.ego_agent is ref.ego_agent and [a.id for a in mine.exo_agents] == [a.id for a in ref.exo_agents] == ["7", "9"]
+
+    def ref_split():
+        r = ref()
+        r.update_observation(agents)
+        return agents.index(r.ego_agent), [a.id for a in r.exo_agents]
+    ego, exo = rec("split", ref_split)
+    assert mine.ego_agent is agents[ego] and [a.id for a in mine.exo_agents] == exo == ["7", "9"]

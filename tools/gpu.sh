@@ -42,7 +42,7 @@ final|finalbench)
   tail -25 $O/pytest_gpu_full.txt > $O/pytest_gpu.txt
   fi
   timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2
-  ( time MIND_BENCH_EXTRAS=$ROOT/$O/bench_extras.json timeout 1500 python bench.py > $O/bench.json 2> $O/bench.err ) 2>&1 | grep real
+  ( time MIND_BENCH_EXTRAS=$ROOT/$O/bench_extras.json timeout 1500 python bench.py --full > $O/bench.json 2> $O/bench.err ) 2>&1 | grep real
   tail -2 $O/bench.err; wc -c $O/bench.json
   python - <<PY
 import json
@@ -68,7 +68,7 @@ PY
   ;;
 quick)
   timeout 900 python -m pytest tests/test_gpu_predictor.py tests/test_gpu_aime_native.py tests/test_gpu_aime_golden.py tests/test_gpu_plan.py -m gpu -q -x 2>&1 | tail -15 | tee $O/pytest.txt
-  timeout 600 python bench.py --no-traffic > $O/bench.json 2> $O/bench.err; tail -3 $O/bench.err; line headline < $O/bench.json
+  timeout 600 python bench.py --full --no-traffic > $O/bench.json 2> $O/bench.err; tail -3 $O/bench.err; line headline < $O/bench.json
   ;;
 tests)
   timeout 2400 python -m pytest "$@" -m gpu -q -s 2>&1 | tail -40 | tee $O/pytest.txt
