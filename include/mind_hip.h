@@ -582,6 +582,74 @@ int mind_loop_last_plan(mind_loop *loop, mind_aime_plan_out *plan, const double 
 int mind_loop_export(mind_loop *loop, int cap, int *n, int32_t *track, int32_t *count, double *rows);
 
 /* ------------------------------------------------------------------------------------------------
+ * MINDPlanner.plan() behind ONE call, for a caller that keeps the simulator: the reference's simulator.py / agent.py (agent.py:317-331
+ * update_observation -> update_state_ctrl -> plan), a world whose observations are noisy or react to the ego, a co-simulation that
+ * delivers one frame at a time -- nothing that could be tabulated ahead of time as mind_loop_desc wants it.  The caller pushes one
+ * observation frame per planner trigger (mind_planner_observe = MINDPlanner.update_observation, planner.py:50-64) and asks for a plan
+ * with the current ego state (mind_planner_plan = MINDPlanner.plan, planner.py:66-145): get_agent_trajectories (utils.py:245-342; AV
+ * first, tracks whose last state is unobserved dropped, windows left-padded) -> mind_fill_tracks -> mind_aime_plan with the device-built
+ * root and the plan-begun contingency solves -> collect -> evaluate_traj_tree of every candidate (planner.py:180-198; priced while the
+ * solves still run) -> the reference's strict `<` scan (planner.py:131-136) -> first control (planner.py:138-141).  It is the cycle of
+ * mind_loop, the same code on the same kernels: a mind_loop step and a mind_planner_plan on the same windows give the same bits.
+ * The plant, the clock and who is visible stay with the caller.
+ * mind_planner_observe / _reset / _export touch no device and work on a planner created with ctx = NULL; every other call on such a
+ * planner returns MIND_ESTATE.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct mind_planner mind_planner;
+#define MIND_PLANNER_EGO_KEY (-0x7fffffffffffffffLL - 1)   /* the key under which the ego's own track ("AV") is reported; not a caller's key */
+typedef struct {
+  /* what does not change with the frame; the fields mind_loop_desc has under the same names, with the same meaning */
+  double time_ahead; float min_vel, dist_thres; int max_depth, max_rounds, pred_len; float prob_floor;
+  const mind_ilqr_cfg *cfg_warm, *cfg_full;      /* copied */
+  int speculative;
+  int ego_type_slot;            /* one-hot slot of the ego's object type (utils.py:245-342)                                     */
+} mind_planner_desc;
+
+typedef struct {
+  long long n_plans;            /* plans computed since the planner was created (resets do not clear it)                         */
+  /* the last plan (zero while the planner holds none: before the first plan, after a reset, after a plan that failed) */
+  int n_agents, n_trees, best, n_expanded, n_rounds, n_traj_nodes;
+  const double *costs;          /* [n_trees] library-owned, valid until the planner's next plan                                 */
+  double ctrl[2];               /* the chosen control (a, delta)                                                                 */
+  double aime_s, ilqr_s, total_s;
+  mind_loop_totals tot;         /* running totals over every plan of the planner                                                 */
+} mind_planner_out;
+
+/* ctx: a context with weights loaded (not sharded), or NULL for a planner that only keeps windows */
+int mind_planner_create(mind_ctx *ctx, const mind_planner_desc *desc, mind_planner **out);
+int mind_planner_destroy(mind_planner *planner);
+/* ClosedLoopSim._start_episode: the windows are cleared and the last plan is forgotten (mind_planner_last_plan reports MIND_ESTATE until
+ * the next plan); the scene tables and the running totals stay */
+int mind_planner_reset(mind_planner *planner);
+/* MINDPlanner.update_observation (planner.py:50-64) for one frame: ego[5] and rows[n][5] = (x, y, heading, vx, vy) as the caller's
+ * to_object_state built them (float32 recordings and numpy's elementary functions are the caller's business, as with
+ * mind_loop_desc.ego_obs), `timestep` the frame's ObjectState.timestep.  Tracks are keyed by caller-chosen integers: a key seen for the
+ * first time joins behind the tracks known so far (type_slot is read then), a known track missing from the frame repeats its last state
+ * with observed = false, windows hold 50 frames.  MIND_EINVAL (nothing changed): a NULL pointer, n < 0, a key twice in one frame,
+ * MIND_PLANNER_EGO_KEY among the keys, a type slot outside 0..6. */
+int mind_planner_observe(mind_planner *planner, int timestep, const double *ego, int n, const long long *track_key, const int32_t *type_slot,
+                         const double *rows);
+/* The scene tables mind_loop_desc takes once, settable at any time between two plans (a target lane that changes during the run):
+ * lane_pts [n_lanes,11,2] float64 + lane_flags [n_lanes,6]; the resampled target lane [n,2] + info [n,12] float32 (n >= 12);
+ * gt_tgt_lane [n,2] float64 + target velocity of the contingency solves; lcl_smp.target_lane [n,2] in its own dtype for the candidate
+ * evaluation (which reads the same target velocity).  Tables are copied; a call with a table equal to the planner's copy changes nothing.
+ * The next plan carries the tables to the device in its own staging upload, as every mind_aime_plan does. */
+int mind_planner_set_lanes(mind_planner *planner, int n_lanes, const double *lane_pts, const int32_t *lane_flags);
+int mind_planner_set_target_lane(mind_planner *planner, int n, const float *lane, const float *info);
+int mind_planner_set_solve_lane(mind_planner *planner, int n, const double *lane, double target_vel);
+int mind_planner_set_eval_lane(mind_planner *planner, int n, const void *lane, int is_f32);
+/* The cycle (MINDPlanner.update_state_ctrl + plan): state = the ego's (x, y, v, yaw), ctrl = the control in force (a, delta).
+ * MIND_ESTATE: no observation yet, a table not set, a sharded context; MIND_ESTATE "unsupported: ..." has the meaning it has in
+ * mind_loop_advance: the plan is left to the round-by-round host path.  Whatever the code, the windows are intact: the caller may set
+ * what was missing and plan again, or take the windows over (mind_planner_export).  *out is filled in every case. */
+int mind_planner_plan(mind_planner *planner, const double *state, const double *ctrl, mind_planner_out *out);
+/* as mind_loop_last_plan; agent_keys [n_agents] = the keys of the plan's agents, MIND_PLANNER_EGO_KEY first */
+int mind_planner_last_plan(mind_planner *planner, mind_aime_plan_out *plan, const double **xs, const double **us, const mind_ilqr_stats **stats_warm,
+                           const mind_ilqr_stats **stats_full, const long long **agent_keys, const float **types, double *x0);
+/* as mind_loop_export: the tracks in first-appearance order (the ego first, under MIND_PLANNER_EGO_KEY, once it has a frame) */
+int mind_planner_export(mind_planner *planner, int cap, int *n, long long *key, int32_t *count, double *rows);
+
+/* ------------------------------------------------------------------------------------------------
  * planners/ilqr call surface (iLQR.fit over a TreeCost of arbitrary PotentialField / StatePotential /
  * StateConstraint / ControlPotential objects; solver.py:80-167, cost.py:326-446, potential.py:62-264).
  * The grid is what PotentialField.__init__ receives: field_offset, resolution, xx[0,:], yy[:,0].

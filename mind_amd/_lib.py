@@ -142,12 +142,30 @@ class LoopOut(C.Structure):        # mind_loop_out
                 ("tot", LoopTotals)]
 
 
+PLANNER_EGO_KEY = -(1 << 63)        # MIND_PLANNER_EGO_KEY
+
+
+class PlannerDesc(C.Structure):    # mind_planner_desc
+    _fields_ = [("time_ahead", C.c_double), ("min_vel", C.c_float), ("dist_thres", C.c_float), ("max_depth", C.c_int), ("max_rounds", C.c_int),
+                ("pred_len", C.c_int), ("prob_floor", C.c_float), ("cfg_warm", C.c_void_p), ("cfg_full", C.c_void_p), ("speculative", C.c_int),
+                ("ego_type_slot", C.c_int)]
+
+
+class PlannerOut(C.Structure):     # mind_planner_out
+    _fields_ = [("n_plans", C.c_longlong),
+                ("n_agents", C.c_int), ("n_trees", C.c_int), ("best", C.c_int), ("n_expanded", C.c_int), ("n_rounds", C.c_int), ("n_traj_nodes", C.c_int),
+                ("costs", C.POINTER(C.c_double)), ("ctrl", C.c_double * 2), ("aime_s", C.c_double), ("ilqr_s", C.c_double), ("total_s", C.c_double),
+                ("tot", LoopTotals)]
+
+
 EXPORTS = ["mind_ctx_create", "mind_ctx_destroy", "mind_last_error_string", "mind_ctx_synchronize",
            "mind_weights_load", "mind_predict_batch", "mind_last_fusion_stats", "mind_set_profiling",
            "mind_ilqr_solve_trees", "mind_ilqr_contingency", "mind_ilqr_solve_fields", "mind_cost_eval", "mind_lane_dist_field", "mind_aime_world", "mind_aime_rebase", "mind_debug_set_layers",
            "mind_debug_read", "mind_set_pair_precision", "mind_get_pair_precision", "mind_debug_pack_bfrag", "mind_debug_pack_conv_frag", "mind_debug_pair_schedule", "mind_set_tuning", "mind_last_ilqr_stats", "mind_aime_plan", "mind_last_ilqr_profile", "mind_eval_traj_trees", "mind_last_ilqr_trace", "mind_ilqr_contingency_begin", "mind_ilqr_finish", "mind_fill_tracks", "mind_ilqr_contingency_begin_plan", "mind_debug_trig", "mind_aime_plan_begin", "mind_aime_plan_poll", "mind_aime_plan_finish", "mind_ctx_busy", "mind_ilqr_finish_plan",
            "mind_set_exchange", "mind_last_exchange_stats",
-           "mind_loop_create", "mind_loop_destroy", "mind_loop_reset", "mind_loop_advance", "mind_loop_state", "mind_loop_last_plan", "mind_loop_export"]
+           "mind_loop_create", "mind_loop_destroy", "mind_loop_reset", "mind_loop_advance", "mind_loop_state", "mind_loop_last_plan", "mind_loop_export",
+           "mind_planner_create", "mind_planner_destroy", "mind_planner_reset", "mind_planner_observe", "mind_planner_set_lanes", "mind_planner_set_target_lane",
+           "mind_planner_set_solve_lane", "mind_planner_set_eval_lane", "mind_planner_plan", "mind_planner_last_plan", "mind_planner_export"]
 
 # transport of the sharded mind_aime_plan (include/mind_hip.h): int fn(void *user, int op, void *send, void *recv, int64 bytes)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64)
@@ -227,6 +245,17 @@ def load():
     lib.mind_loop_state.argtypes = [C.c_void_p, C.POINTER(LoopOut)]
     lib.mind_loop_last_plan.argtypes = [C.c_void_p, C.POINTER(AimePlanOut)] + [C.POINTER(C.c_void_p)] * 6 + [C.c_void_p]
     lib.mind_loop_export.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.mind_planner_create.argtypes = [C.c_void_p, C.POINTER(PlannerDesc), C.POINTER(C.c_void_p)]
+    lib.mind_planner_destroy.argtypes = [C.c_void_p]
+    lib.mind_planner_reset.argtypes = [C.c_void_p]
+    lib.mind_planner_observe.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.mind_planner_set_lanes.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lib.mind_planner_set_target_lane.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lib.mind_planner_set_solve_lane.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_double]
+    lib.mind_planner_set_eval_lane.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    lib.mind_planner_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PlannerOut)]
+    lib.mind_planner_last_plan.argtypes = [C.c_void_p, C.POINTER(AimePlanOut)] + [C.POINTER(C.c_void_p)] * 6 + [C.c_void_p]
+    lib.mind_planner_export.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p]
     for n in EXPORTS:
         getattr(lib, n)
         if n not in ("mind_last_error_string", "mind_debug_read"):

@@ -2,10 +2,14 @@
 // Host code only: the device work is what mind_aime_plan / the plan-begun contingency solves already do; this file is the part of the
 // cycle the interpreter used to run between them (reference: simulator.py:51-107, agent.py:255-331, planner.py:50-145, utils.py:245-342,
 // kinematics.py:22-36; this repo's Python form of the same steps: mind_amd/closed_loop.py, planners/mind/planner.py).
+// mind_planner_*: the same planning cycle for a caller that keeps the simulator and pushes one observation frame at a time
+// ("MINDPlanner.plan() behind ONE call").  Both objects own a mind_cycle: the windows, the scene tables, the last plan and the speculation
+// state; cycle_plan / cycle_speculate / cycle_solve_speculated below are the one body of the cycle.
 // Included at the end of mind_hip.hip (needs mind_ctx, fail, mind_aime_plan, mind_ilqr_finish, np_pairwise / eval_nodes).
 #pragma once
 #pragma STDC FP_CONTRACT OFF
 #include <chrono>
+#include <unordered_map>
 
 namespace {
 
@@ -13,7 +17,9 @@ constexpr int LOOP_OBS = 50;        // MINDPlanner.obs_len (planner.py:14)
 constexpr int LOOP_ROW = 7;         // observed, x, y, heading, vx, vy, timestep
 
 struct LoopTrack {
-  int track = 0;                    // index into the world's tracks
+  int track = 0;                    // mind_loop: index into the world's tracks
+  long long key = 0;                // mind_planner: the caller's key of the track (mind_loop: the track index again)
+  int slot = 6;                     // one-hot slot of the track's object type
   int count = 0, head = 0;          // rows in the window, position of the oldest
   double rows[LOOP_OBS][LOOP_ROW];
   const double *last() const { return rows[(head + count - 1) % LOOP_OBS]; }
@@ -27,36 +33,38 @@ struct LoopTrack {
 
 }  // namespace
 
-struct mind_loop {
+// what a planning cycle reads that does not change with the frame (mind_loop_desc / mind_planner_desc + the sizes of the tables below)
+struct CycleParams {
+  int n_lanes = 0, n_lane_pts = 0;
+  double time_ahead = 0.0; float min_vel = 0.f, dist_thres = 0.f; int max_depth = 0, max_rounds = 0, pred_len = 0; float prob_floor = 0.f;
+  int solve_n_lane_pts = 0; double target_vel = 0.0;
+  int eval_n_lane_pts = 0, eval_lane_is_f32 = 0;
+  int speculative = 0;
+};
+
+// the state of one planner's cycles: shared by mind_loop (windows fed from its tables) and mind_planner (windows fed by the caller)
+struct mind_cycle {
   mind_ctx *c = nullptr;
-  mind_loop_desc d;
-  // copies of the caller's tables
-  std::vector<double> ego_state, ego_obs, exo_obs, lane_pts, solve_lane, eval_lane_f64;
-  std::vector<uint8_t> exo_valid;
-  std::vector<int32_t> timestep, type_slot, lane_flags;
-  std::vector<float> target_lane, target_lane_info, eval_lane_f32, ego_trig32;
+  const char *who = "mind_loop";    // prefix of the error messages
+  CycleParams p;
+  // copies of the caller's scene tables
+  std::vector<double> lane_pts, solve_lane, eval_lane_f64;
+  std::vector<int32_t> lane_flags;
+  std::vector<float> target_lane, target_lane_info, eval_lane_f32;
   mind_ilqr_cfg cfg_warm, cfg_full;
-  // simulator state (ClosedLoopSim)
-  double sim_time = 0.0, last_trigger = -1.0;
-  bool have_trigger = false, enabled = false;
-  bool state_recorded = false;      // the plant state is the recorded one of row state_row (taken over in this step, not propagated yet)
-  int state_row = 0;
-  bool tan_valid = false;
-  double tan_arg = 0.0, tan_val = 0.0;
-  double state[4] = {0, 0, 0, 0}, ctrl[2] = {0, 0};
-  long long n_steps = 0, n_plans = 0, ep_steps = 0;
+  double state[4] = {0, 0, 0, 0}, ctrl[2] = {0, 0};      // ego plant state the plan starts from, control in force / chosen by the plan
   // observation windows (MINDPlanner.agent_obs): tracks in first-appearance order, AV first
   std::vector<LoopTrack> obs;
-  std::vector<int> slot_of_track;       // world track -> index in obs, -1 = not seen yet
   // per-plan scratch + the last plan
   std::vector<double> raw, eval_st, eval_ct, costs, per;
   std::vector<char> early_seen;      // candidate trees priced while the solves of the others still ran
   std::vector<float> f_pos, f_ang, f_vel, f_pad, f_types;
   std::vector<int16_t> i_typ, i_have;
-  std::vector<int32_t> kept, slots, counts;
+  std::vector<int32_t> kept, kept_obs, slots, counts;        // kept: world track of every agent of the plan, kept_obs: its index in obs
+  std::vector<long long> kept_keys;
   mind_aime_plan_out po;
-  bool have_plan = false, half_step = false;
-  long long plan_gen = -1;          // mind_ctx::pl_gen of the loop's last plan
+  bool have_plan = false;
+  long long plan_gen = -1;          // mind_ctx::pl_gen of the last plan
   std::chrono::steady_clock::time_point t_plan_end;
   // speculative warm start (TrajectoryTreeOptimizer.speculate_warm / _take_speculation, this repo's trajectory_tree.py): the warm-start fits of the
   // PREVIOUS plan's tree shapes run on a second context beside the AIME rounds; a tree whose shape recurs takes its warm-start controls from there
@@ -72,10 +80,38 @@ struct mind_loop {
   long long warm_speculated = 0, warm_hits = 0;
   double plan_x0[6];
   int last_agents = 0, last_nodes = 0, best = -1, last_agents_plan = 0;
-  bool sol_owned = false;           // the last plan's solve results are the loop's own arrays (a speculated cycle), not the context's
+  bool sol_owned = false;           // the last plan's solve results are the cycle's own arrays (a speculated cycle), not the context's
   double aime_s = 0, ilqr_s = 0, total_s = 0;
   mind_loop_totals tot;
+  mind_cycle() { memset(&po, 0, sizeof(po)); memset(&tot, 0, sizeof(tot)); }
+};
+
+struct mind_loop : mind_cycle {
+  mind_loop_desc d;
+  // copies of the caller's tables
+  std::vector<double> ego_state, ego_obs, exo_obs;
+  std::vector<uint8_t> exo_valid;
+  std::vector<int32_t> timestep, type_slot;
+  std::vector<float> ego_trig32;
+  // simulator state (ClosedLoopSim)
+  double sim_time = 0.0, last_trigger = -1.0;
+  bool have_trigger = false, enabled = false;
+  bool state_recorded = false;      // the plant state is the recorded one of row state_row (taken over in this step, not propagated yet)
+  int state_row = 0;
+  bool tan_valid = false;
+  double tan_arg = 0.0, tan_val = 0.0;
+  long long n_steps = 0, n_plans = 0, ep_steps = 0;
+  std::vector<int> slot_of_track;       // world track -> index in obs, -1 = not seen yet
+  bool half_step = false;
   bool planned_last = false;
+};
+
+struct mind_planner : mind_cycle {
+  std::unordered_map<long long, int> slot_of_key;       // caller's key -> index in obs
+  std::vector<long long> frame_keys;                    // (scratch: the duplicate check of a frame)
+  std::vector<char> frame_seen;
+  bool have_lanes = false, have_target = false, have_solve = false, have_eval = false;
+  long long n_plans = 0, n_uploads = 0;                 // n_uploads: set_* calls that really changed a table
 };
 
 namespace {
@@ -128,7 +164,7 @@ void loop_observe(mind_loop *L, int r) {
   row[6] = (double)L->timestep[r];
   if (L->obs.empty()) {
     L->obs.emplace_back();
-    L->obs[0].track = 0;
+    L->obs[0].track = 0; L->obs[0].key = 0; L->obs[0].slot = L->type_slot[0];
     L->slot_of_track[0] = 0;
   }
   const size_t known_before = L->obs.size();
@@ -142,7 +178,7 @@ void loop_observe(mind_loop *L, int r) {
     if (s < 0) {
       s = (int)L->obs.size();
       L->obs.emplace_back();
-      L->obs[s].track = i;
+      L->obs[s].track = i; L->obs[s].key = i; L->obs[s].slot = L->type_slot[i];
       L->slot_of_track[i] = s;
     }
     const double *e = L->exo_obs.data() + ((size_t)r * nt + i) * 5;
@@ -198,15 +234,20 @@ void loop_propagate(mind_loop *L) {
 
 // TrajectoryTreeOptimizer.speculate_warm: the warm-start fit (lane term only: it sees the cost tree's shape, the ego state, the target lane and
 // velocity -- no prediction) of every shape of the previous plan, begun on the side context; returns at once
-int loop_speculate(mind_loop *L, const double *x0) {
+int cycle_speculate(mind_cycle *L, const double *x0) {
   mind_ctx *c = L->c;
-  const mind_loop_desc &d = L->d;
+  const CycleParams &d = L->p;
   L->spec_pending = false;
   if (!d.speculative || L->last_shapes.empty()) return MIND_OK;
   if (L->spec_skip > 0) { L->spec_skip -= 1; L->spec_last = -1; return MIND_OK; }
   if (!L->side) {
-    if (hipSetDevice(c->device) != hipSuccess || hipStreamCreateWithFlags(&L->side_stream, hipStreamNonBlocking) != hipSuccess) return MIND_OK;
-    if (mind_ctx_create(c->device, (void *)L->side_stream, &L->side) != MIND_OK) { L->side = nullptr; return MIND_OK; }
+    if (hipSetDevice(c->device) != hipSuccess || hipStreamCreateWithFlags(&L->side_stream, hipStreamNonBlocking) != hipSuccess) { L->side_stream = nullptr; return MIND_OK; }
+    if (mind_ctx_create(c->device, (void *)L->side_stream, &L->side) != MIND_OK) {
+      // no side context on this device: this object plans without speculation from here on (and does not create a stream per plan)
+      (void)hipStreamDestroy(L->side_stream);
+      L->side = nullptr; L->side_stream = nullptr; L->p.speculative = 0; L->last_shapes.clear();
+      return MIND_OK;
+    }
   }
   mind_ctx *sc = L->side;
   if (sc->il_finish) (void)mind_ilqr_finish(sc);
@@ -237,9 +278,9 @@ int loop_speculate(mind_loop *L, const double *x0) {
 
 // TrajectoryTreeOptimizer.solve_batch with a speculation in flight: trees whose shape was guessed right run the full fit only (from the
 // speculated warm-start controls), the others both fits on the side context beside them.  Results into L->sol_* (tree order).
-int loop_solve_speculated(mind_loop *L, const double *x0) {
+int cycle_solve_speculated(mind_cycle *L, const double *x0) {
   mind_ctx *c = L->c, *sc = L->side;
-  const mind_loop_desc &d = L->d;
+  const CycleParams &d = L->p;
   const int nt = L->po.n_trees, a = L->last_agents_plan;
   const int32_t *off = L->po.tree_off;
   const int M = off[nt];
@@ -288,7 +329,7 @@ int loop_solve_speculated(mind_loop *L, const double *x0) {
       (void)mind_set_tuning(sc, "ilqr_wgs", c->ilqr_wgs);
       rc = mind_ilqr_contingency_begin(sc, &L->cfg_warm, &L->cfg_full, misses.data(), (int)misses.size(), x0, L->solve_lane.data(), d.solve_n_lane_pts, d.target_vel,
                                        L->miss_xs.data(), L->miss_us.data(), L->miss_stw.data(), L->miss_stf.data());
-      if (rc) return fail(c, rc, "mind_loop: %s", sc->err.c_str());
+      if (rc) return fail(c, rc, "%s: %s", L->who, sc->err.c_str());
       miss_on_side = true;
     } else {
       if ((rc = mind_ilqr_contingency(c, &L->cfg_warm, &L->cfg_full, misses.data(), (int)misses.size(), x0, L->solve_lane.data(), d.solve_n_lane_pts, d.target_vel,
@@ -320,7 +361,7 @@ int loop_solve_speculated(mind_loop *L, const double *x0) {
       o += m;
     }
   }
-  if (miss_on_side && (rc = mind_ilqr_finish(sc))) return fail(c, rc, "mind_loop: %s", sc->err.c_str());
+  if (miss_on_side && (rc = mind_ilqr_finish(sc))) return fail(c, rc, "%s: %s", L->who, sc->err.c_str());
   size_t o = 0;
   for (size_t k = 0; k < miss_idx.size(); ++k) {
     const int t = miss_idx[k], m = off[t + 1] - off[t];
@@ -332,10 +373,11 @@ int loop_solve_speculated(mind_loop *L, const double *x0) {
   return MIND_OK;
 }
 
-// MINDPlanner.plan (planner.py:66-145) of the enabled agent
-int loop_plan(mind_loop *L) {
+// MINDPlanner.plan (planner.py:66-145) on the windows L->obs, from the ego state L->state and the control in force L->ctrl; the chosen control
+// replaces L->ctrl
+int cycle_plan(mind_cycle *L) {
   mind_ctx *c = L->c;
-  const mind_loop_desc &d = L->d;
+  const CycleParams &d = L->p;
   const auto t0 = std::chrono::steady_clock::now();
   // MIND_LOOP_TRACE=1: host time stamps of the cycle's sections on stderr (diagnostic, as MIND_PLAN_TRACE inside the plan)
   static const bool loop_trace = getenv("MIND_LOOP_TRACE") != nullptr;
@@ -345,24 +387,24 @@ int loop_plan(mind_loop *L) {
   if (loop_trace && L->have_plan) fprintf(stderr, "[loop] %8.1f us since the last plan's end (evaluation excluded: steps, observation)\n",
                                           std::chrono::duration<double, std::micro>(t0 - L->t_plan_end).count());
   // ---- get_agent_trajectories (utils.py:245-342): AV first, tracks whose last state is unobserved are dropped, windows left-padded
-  L->kept.clear(); L->slots.clear();
+  L->kept.clear(); L->kept_keys.clear(); L->kept_obs.clear(); L->slots.clear();
   for (size_t s = 0; s < L->obs.size(); ++s) {
     const LoopTrack &t = L->obs[s];
     if (t.last()[0] == 0.0) continue;
-    L->kept.push_back(t.track);
-    L->slots.push_back(L->type_slot[t.track]);
+    L->kept.push_back(t.track); L->kept_keys.push_back(t.key); L->kept_obs.push_back((int32_t)s);
+    L->slots.push_back(t.slot);
   }
   const int a = (int)L->kept.size(), T = LOOP_OBS;
   L->raw.assign((size_t)a * T * 6, 0.0);
   for (int i = 0; i < a; ++i) {
-    const LoopTrack &t = L->obs[L->slot_of_track[L->kept[i]]];
+    const LoopTrack &t = L->obs[L->kept_obs[i]];
     for (int k = 0; k < t.count; ++k)
       memcpy(L->raw.data() + ((size_t)i * T + (T - t.count + k)) * 6, t.rows[(t.head + k) % LOOP_OBS], 6 * sizeof(double));
   }
   L->f_pos.resize((size_t)a * T * 2); L->f_ang.resize((size_t)a * T); L->f_vel.resize((size_t)a * T * 2);
   L->i_typ.resize((size_t)a * T * 7); L->i_have.resize((size_t)a * T);
   int rc = mind_fill_tracks(L->raw.data(), a, T, L->slots.data(), L->f_pos.data(), L->f_ang.data(), L->f_vel.data(), L->i_typ.data(), L->i_have.data());
-  if (rc) return fail(c, rc, "mind_loop: mind_fill_tracks failed");
+  if (rc) return fail(c, rc, "%s: mind_fill_tracks failed", L->who);
   TRL("tracks filled");
   L->f_pad.resize((size_t)a * T); L->f_types.resize((size_t)a * T * 7);
   for (size_t i = 0; i < L->f_pad.size(); ++i) L->f_pad[i] = (float)L->i_have[i];
@@ -383,7 +425,7 @@ int loop_plan(mind_loop *L) {
   x0[0] = L->state[0]; x0[1] = L->state[1]; x0[2] = L->state[2]; x0[3] = L->state[3]; x0[4] = L->ctrl[0]; x0[5] = L->ctrl[1];
   // warm-start fits of the previous plan's tree shapes start now, beside the predictor; with one in flight the plan does not begin the
   // solves itself (TrajectoryTreeOptimizer.plan_solve_args returns None then)
-  if ((rc = loop_speculate(L, x0))) return rc;
+  if ((rc = cycle_speculate(L, x0))) return rc;
   if (!L->spec_pending) {
     pi.solve_cfg_warm = &L->cfg_warm; pi.solve_cfg_full = &L->cfg_full;
     pi.solve_x0 = x0; pi.solve_lane = L->solve_lane.data(); pi.solve_n_lane_pts = d.solve_n_lane_pts; pi.solve_target_vel = d.target_vel;
@@ -395,7 +437,7 @@ int loop_plan(mind_loop *L) {
   const auto t1 = std::chrono::steady_clock::now();
   TRL("plan returned (solves begun)");
   const int nt = L->po.n_trees;
-  if (nt <= 0) return fail(c, MIND_ESTATE, "mind_loop: the plan returned no scenario tree");
+  if (nt <= 0) return fail(c, MIND_ESTATE, "%s: the plan returned no scenario tree", L->who);
   const int32_t *off = L->po.tree_off;
   const int M = off[nt];
   bool early_done = false;        // the candidates were priced while the solves ran (below)
@@ -403,13 +445,13 @@ int loop_plan(mind_loop *L) {
   const mind_ilqr_stats *stw, *stf;
   L->last_agents_plan = a;
   if (L->spec_pending) {
-    if ((rc = loop_solve_speculated(L, x0))) return rc;
+    if ((rc = cycle_solve_speculated(L, x0))) return rc;
     xs = L->sol_xs.data(); us = L->sol_us.data(); stw = L->sol_stw.data(); stf = L->sol_stf.data();
     L->sol_owned = true;
   } else {
-    if (!L->po.solves_begun) return fail(c, MIND_ESTATE, "mind_loop: the plan could not begin its contingency solves (%s)", c->err.c_str());
+    if (!L->po.solves_begun) return fail(c, MIND_ESTATE, "%s: the plan could not begin its contingency solves (%s)", L->who, c->err.c_str());
     // ---- collect the solves (mind_ilqr_finish_plan without the copy: the results stay in the context until its next plan)
-    if (!c->il_finish || !c->il_finish_owned) return fail(c, MIND_ESTATE, "mind_loop: no plan-begun tree-iLQR call is pending");
+    if (!c->il_finish || !c->il_finish_owned) return fail(c, MIND_ESTATE, "%s: no plan-begun tree-iLQR call is pending", L->who);
     // ---- a launch of small trees writes every tree's results to the host and marks it when they are complete: price the candidates as they
     //      arrive (evaluate_traj_tree of one tree is independent of the others), beside the trees the device is still solving -- only the
     //      last one's evaluation stays between the kernel's end and the chosen control
@@ -433,7 +475,7 @@ int loop_plan(mind_loop *L) {
           memcpy(L->eval_ct.data() + 2, E.us + (size_t)off[t] * 2, (size_t)m * 2 * sizeof(double));
           const int32_t cnt1 = m + 1;
           if ((rc = mind_eval_traj_trees(L->eval_st.data(), L->eval_ct.data(), &cnt1, 1, elane_e, d.eval_lane_is_f32, d.eval_n_lane_pts, d.target_vel, &L->costs[t])))
-            return fail(c, rc, "mind_loop: mind_eval_traj_trees failed");
+            return fail(c, rc, "%s: mind_eval_traj_trees failed", L->who);
           L->early_seen[t] = 1; --left; any = true;
         }
         if (!any && (++spins & 0x3ffu) == 0u &&
@@ -442,7 +484,7 @@ int loop_plan(mind_loop *L) {
       early_done = left == 0;
     }
     if ((rc = mind_ilqr_finish(c))) return rc;
-    if ((size_t)M * 6 != c->pl_sol_xs.size() || (size_t)nt != c->pl_sol_stf.size()) return fail(c, MIND_ESTATE, "mind_loop: the solves' results do not fit the plan");
+    if ((size_t)M * 6 != c->pl_sol_xs.size() || (size_t)nt != c->pl_sol_stf.size()) return fail(c, MIND_ESTATE, "%s: the solves' results do not fit the plan", L->who);
     xs = c->pl_sol_xs.data(); us = c->pl_sol_us.data(); stw = c->pl_sol_stw.data(); stf = c->pl_sol_stf.data();
     L->sol_owned = false;
   }
@@ -472,19 +514,19 @@ int loop_plan(mind_loop *L) {
   }
   const void *elane = d.eval_lane_is_f32 ? (const void *)L->eval_lane_f32.data() : (const void *)L->eval_lane_f64.data();
   if ((rc = mind_eval_traj_trees(L->eval_st.data(), L->eval_ct.data(), L->counts.data(), nt, elane, d.eval_lane_is_f32, d.eval_n_lane_pts, d.target_vel, L->costs.data())))
-    return fail(c, rc, "mind_loop: mind_eval_traj_trees failed");
+    return fail(c, rc, "%s: mind_eval_traj_trees failed", L->who);
   }
   // ---- the reference's strict `<` scan (planner.py:131-136): the first minimum, a NaN never wins
   int best = -1;
   double min_cost = INFINITY;
   for (int t = 0; t < nt; ++t)
     if (L->costs[t] < min_cost) { min_cost = L->costs[t]; best = t; }
-  if (best < 0) return fail(c, MIND_ESTATE, "mind_loop: no candidate tree has a finite cost");
+  if (best < 0) return fail(c, MIND_ESTATE, "%s: no candidate tree has a finite cost", L->who);
   // first control: (a, delta) of the state of the root's first child (planner.py:138-141, Q15)
   int first = -1;
   for (int k = off[best]; k < off[best + 1]; ++k)
     if (L->po.flat_parent[k] == -1) { first = k; break; }
-  if (first < 0) return fail(c, MIND_ESTATE, "mind_loop: the chosen tree has no root child");
+  if (first < 0) return fail(c, MIND_ESTATE, "%s: the chosen tree has no root child", L->who);
   L->ctrl[0] = xs[(size_t)first * 6 + 4]; L->ctrl[1] = xs[(size_t)first * 6 + 5];
   L->best = best; L->last_agents = a; L->last_nodes = M; L->have_plan = true; L->plan_gen = c->pl_gen;
   // accounting (TrajectoryTreeOptimizer.counters, MINDPlanner.timing_sum; bench.py's live kernel durations when profiling is on)
@@ -534,7 +576,7 @@ int loop_step(mind_loop *L) {
       L->have_trigger = true; L->last_trigger = L->sim_time;
       loop_observe(L, r);
       if (L->enabled) {
-        const int rc = loop_plan(L);
+        const int rc = cycle_plan(L);
         if (rc) {
           // the observation update of this step is done and must not be repeated: a caller that takes the loop over finishes the step itself
           L->half_step = true;
@@ -565,6 +607,12 @@ extern "C" int mind_loop_create(mind_ctx *c, const mind_loop_desc *d, mind_loop 
   mind_loop *L = new (std::nothrow) mind_loop();
   if (!L) return fail(c, MIND_ENOMEM, "mind_loop_create: out of memory");
   L->c = c; L->d = *d;
+  CycleParams &cp = L->p;
+  cp.n_lanes = d->n_lanes; cp.n_lane_pts = d->n_lane_pts;
+  cp.time_ahead = d->time_ahead; cp.min_vel = d->min_vel; cp.dist_thres = d->dist_thres; cp.max_depth = d->max_depth; cp.max_rounds = d->max_rounds;
+  cp.pred_len = d->pred_len; cp.prob_floor = d->prob_floor;
+  cp.solve_n_lane_pts = d->solve_n_lane_pts; cp.target_vel = d->target_vel;
+  cp.eval_n_lane_pts = d->eval_n_lane_pts; cp.eval_lane_is_f32 = d->eval_lane_is_f32; cp.speculative = d->speculative;
   const size_t S = (size_t)d->n_steps, nt = (size_t)d->n_tracks;
   L->ego_state.assign(d->ego_state, d->ego_state + S * 4);
   L->ego_obs.assign(d->ego_obs, d->ego_obs + S * 5);
@@ -586,18 +634,21 @@ extern "C" int mind_loop_create(mind_ctx *c, const mind_loop_desc *d, mind_loop 
   L->d.lane_flags = nullptr; L->d.target_lane = nullptr; L->d.target_lane_info = nullptr; L->d.cfg_warm = nullptr; L->d.cfg_full = nullptr;
   L->d.solve_lane = nullptr; L->d.eval_lane = nullptr;
   L->slot_of_track.assign(nt, -1);
-  memset(&L->po, 0, sizeof(L->po));
-  memset(&L->tot, 0, sizeof(L->tot));
   (void)mind_loop_reset(L);
   *out = L;
   return MIND_OK;
 }
 
-extern "C" int mind_loop_destroy(mind_loop *L) {
+static void cycle_release(mind_cycle *L) {
   if (L && L->side) {
     (void)mind_ctx_destroy(L->side);
     if (L->side_stream) (void)hipStreamDestroy(L->side_stream);
+    L->side = nullptr; L->side_stream = nullptr;
   }
+}
+
+extern "C" int mind_loop_destroy(mind_loop *L) {
+  cycle_release(L);
   delete L;
   return MIND_OK;
 }
@@ -663,6 +714,201 @@ extern "C" int mind_loop_export(mind_loop *L, int cap, int *n, int32_t *track, i
   for (int s = 0; s < *n; ++s) {
     const LoopTrack &t = L->obs[s];
     track[s] = t.track; count[s] = t.count;
+    for (int k = 0; k < t.count; ++k)
+      memcpy(rows + ((size_t)s * LOOP_OBS + k) * LOOP_ROW, t.rows[(t.head + k) % LOOP_OBS], LOOP_ROW * sizeof(double));
+  }
+  return MIND_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// mind_planner_*: MINDPlanner.update_observation / plan (planner.py:50-145) of a caller that keeps the simulator itself
+// ---------------------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+void planner_fill_out(const mind_planner *P, mind_planner_out *o) {
+  memset(o, 0, sizeof(*o));
+  o->n_plans = P->n_plans;
+  if (P->have_plan) {
+    o->n_agents = P->last_agents; o->n_trees = P->po.n_trees; o->best = P->best;
+    o->n_expanded = P->po.n_expanded; o->n_rounds = P->po.n_rounds; o->n_traj_nodes = P->last_nodes;
+    o->costs = P->costs.data();
+    memcpy(o->ctrl, P->ctrl, sizeof(o->ctrl));
+    o->aime_s = P->aime_s; o->ilqr_s = P->ilqr_s; o->total_s = P->total_s;
+  }
+  o->tot = P->tot;
+}
+
+// copies a table when it differs from the planner's copy; returns whether it did
+template <class T> bool planner_take(std::vector<T> &dst, const T *src, size_t n) {
+  if (dst.size() == n && (n == 0 || memcmp(dst.data(), src, n * sizeof(T)) == 0)) return false;
+  dst.assign(src, src + n);
+  return true;
+}
+
+}  // namespace
+
+extern "C" int mind_planner_reset(mind_planner *P);
+extern "C" int mind_planner_create(mind_ctx *c, const mind_planner_desc *d, mind_planner **out) {
+  if (!d || !out) return MIND_EINVAL;
+  if (c && !c->have_weights) return fail(c, MIND_ESTATE, "weights not loaded");
+  if (!d->cfg_warm || !d->cfg_full || d->max_rounds <= 0 || d->max_rounds > 32 || d->pred_len < 2 || d->pred_len > 60 || d->ego_type_slot < 0 || d->ego_type_slot > 6)
+    return fail(c, MIND_EINVAL, "mind_planner_create: bad argument");
+  mind_planner *P = new (std::nothrow) mind_planner();
+  if (!P) return fail(c, MIND_ENOMEM, "mind_planner_create: out of memory");
+  P->c = c; P->who = "mind_planner";
+  CycleParams &cp = P->p;
+  cp.time_ahead = d->time_ahead; cp.min_vel = d->min_vel; cp.dist_thres = d->dist_thres; cp.max_depth = d->max_depth; cp.max_rounds = d->max_rounds;
+  cp.pred_len = d->pred_len; cp.prob_floor = d->prob_floor; cp.speculative = d->speculative;
+  P->cfg_warm = *d->cfg_warm; P->cfg_full = *d->cfg_full;
+  P->obs.emplace_back();                      // the ego's window: always the first track
+  P->obs[0].key = MIND_PLANNER_EGO_KEY; P->obs[0].slot = d->ego_type_slot;
+  *out = P;
+  return MIND_OK;
+}
+
+extern "C" int mind_planner_destroy(mind_planner *P) {
+  cycle_release(P);
+  delete P;
+  return MIND_OK;
+}
+
+extern "C" int mind_planner_reset(mind_planner *P) {
+  if (!P) return MIND_EINVAL;
+  if (P->spec_pending && P->side) { (void)mind_ilqr_finish(P->side); P->spec_pending = false; }
+  const int ego_slot = P->obs.empty() ? 6 : P->obs[0].slot;
+  P->obs.clear();
+  P->obs.emplace_back();
+  P->obs[0].key = MIND_PLANNER_EGO_KEY; P->obs[0].slot = ego_slot;
+  P->slot_of_key.clear();
+  P->have_plan = false;                       // (the last plan belongs to the episode that ended)
+  return MIND_OK;
+}
+
+extern "C" int mind_planner_observe(mind_planner *P, int timestep, const double *ego, int n, const long long *track_key, const int32_t *type_slot, const double *rows) {
+  if (!P || !ego || n < 0 || (n > 0 && (!track_key || !type_slot || !rows))) return P ? fail(P->c, MIND_EINVAL, "mind_planner_observe: bad argument") : MIND_EINVAL;
+  // nothing is changed by a frame that is refused
+  P->frame_keys.assign(track_key, track_key + n);
+  std::sort(P->frame_keys.begin(), P->frame_keys.end());
+  for (int i = 0; i < n; ++i) {
+    if (P->frame_keys[i] == MIND_PLANNER_EGO_KEY) return fail(P->c, MIND_EINVAL, "mind_planner_observe: MIND_PLANNER_EGO_KEY names the ego's own track");
+    if (i > 0 && P->frame_keys[i] == P->frame_keys[i - 1]) return fail(P->c, MIND_EINVAL, "mind_planner_observe: track key %lld twice in one frame", P->frame_keys[i]);
+    if (type_slot[i] < 0 || type_slot[i] > 6) return fail(P->c, MIND_EINVAL, "mind_planner_observe: type slot %d of track %d", (int)type_slot[i], i);
+  }
+  double row[LOOP_ROW];
+  row[0] = 1.0; memcpy(row + 1, ego, 5 * sizeof(double)); row[6] = (double)timestep;
+  const size_t known_before = P->obs.size();
+  P->obs[0].push(row);
+  P->frame_seen.assign(known_before, 0);
+  // agents reported in this frame, in the caller's order; a key seen for the first time joins the table behind the others
+  for (int i = 0; i < n; ++i) {
+    int s;
+    auto it = P->slot_of_key.find(track_key[i]);
+    if (it == P->slot_of_key.end()) {
+      s = (int)P->obs.size();
+      P->obs.emplace_back();
+      P->obs[s].key = track_key[i]; P->obs[s].track = s; P->obs[s].slot = type_slot[i];
+      P->slot_of_key.emplace(track_key[i], s);
+    } else {
+      s = it->second;
+      P->frame_seen[s] = 1;
+    }
+    row[0] = 1.0; memcpy(row + 1, rows + (size_t)i * 5, 5 * sizeof(double)); row[6] = (double)timestep;
+    P->obs[s].push(row);
+  }
+  // tracks not reported: their last state again, unobserved (planner.py:58-62)
+  for (size_t s = 1; s < known_before; ++s) {
+    if (P->frame_seen[s]) continue;
+    LoopTrack &t = P->obs[s];
+    memcpy(row, t.last(), sizeof(row));
+    row[0] = 0.0;
+    t.push(row);
+  }
+  return MIND_OK;
+}
+
+extern "C" int mind_planner_set_lanes(mind_planner *P, int n_lanes, const double *lane_pts, const int32_t *lane_flags) {
+  if (!P) return MIND_EINVAL;
+  if (!P->c) return MIND_ESTATE;
+  if (n_lanes <= 0 || !lane_pts || !lane_flags) return fail(P->c, MIND_EINVAL, "mind_planner_set_lanes: bad argument");
+  bool ch = planner_take(P->lane_pts, lane_pts, (size_t)n_lanes * 22);
+  ch = planner_take(P->lane_flags, lane_flags, (size_t)n_lanes * 6) || ch;
+  P->p.n_lanes = n_lanes; P->have_lanes = true; P->n_uploads += ch;
+  return MIND_OK;
+}
+
+extern "C" int mind_planner_set_target_lane(mind_planner *P, int n, const float *lane, const float *info) {
+  if (!P) return MIND_EINVAL;
+  if (!P->c) return MIND_ESTATE;
+  if (!lane || !info) return fail(P->c, MIND_EINVAL, "mind_planner_set_target_lane: bad argument");
+  if (n < 12) return fail(P->c, MIND_EINVAL, "mind_planner_set_target_lane: a target lane of %d points (the plan needs 12)", n);
+  bool ch = planner_take(P->target_lane, lane, (size_t)n * 2);
+  ch = planner_take(P->target_lane_info, info, (size_t)n * 12) || ch;
+  P->p.n_lane_pts = n; P->have_target = true; P->n_uploads += ch;
+  return MIND_OK;
+}
+
+extern "C" int mind_planner_set_solve_lane(mind_planner *P, int n, const double *lane, double target_vel) {
+  if (!P) return MIND_EINVAL;
+  if (!P->c) return MIND_ESTATE;
+  if (n < 2 || !lane) return fail(P->c, MIND_EINVAL, "mind_planner_set_solve_lane: bad argument");
+  const bool ch = planner_take(P->solve_lane, lane, (size_t)n * 2);
+  P->p.solve_n_lane_pts = n; P->p.target_vel = target_vel; P->have_solve = true; P->n_uploads += ch;
+  return MIND_OK;
+}
+
+extern "C" int mind_planner_set_eval_lane(mind_planner *P, int n, const void *lane, int is_f32) {
+  if (!P) return MIND_EINVAL;
+  if (!P->c) return MIND_ESTATE;
+  if (n < 2 || !lane) return fail(P->c, MIND_EINVAL, "mind_planner_set_eval_lane: bad argument");
+  bool ch;
+  if (is_f32) { ch = planner_take(P->eval_lane_f32, (const float *)lane, (size_t)n * 2); P->eval_lane_f64.clear(); }
+  else { ch = planner_take(P->eval_lane_f64, (const double *)lane, (size_t)n * 2); P->eval_lane_f32.clear(); }
+  P->p.eval_n_lane_pts = n; P->p.eval_lane_is_f32 = is_f32 ? 1 : 0; P->have_eval = true; P->n_uploads += ch;
+  return MIND_OK;
+}
+
+extern "C" int mind_planner_plan(mind_planner *P, const double *state, const double *ctrl, mind_planner_out *out) {
+  if (!P || !state || !ctrl || !out) return MIND_EINVAL;
+  if (!P->c) return MIND_ESTATE;
+  mind_ctx *c = P->c;
+  if (c->xfn) return fail(c, MIND_ESTATE, "mind_planner_plan: the context is sharded (mind_set_exchange): the native cycle plans on one GPU");
+  if (P->obs[0].count == 0) return fail(c, MIND_ESTATE, "mind_planner_plan: no observation yet (mind_planner_observe)");
+  if (!P->have_lanes) return fail(c, MIND_ESTATE, "mind_planner_plan: the lane tables are not set (mind_planner_set_lanes)");
+  if (!P->have_target || !P->have_solve || !P->have_eval)
+    return fail(c, MIND_ESTATE, "mind_planner_plan: the target lane is not set (mind_planner_set_target_lane / _set_solve_lane / _set_eval_lane)");
+  memcpy(P->state, state, 4 * sizeof(double));
+  memcpy(P->ctrl, ctrl, 2 * sizeof(double));
+  const int rc = cycle_plan(P);
+  if (rc == MIND_OK) P->n_plans += 1;
+  planner_fill_out(P, out);
+  return rc;
+}
+
+extern "C" int mind_planner_last_plan(mind_planner *P, mind_aime_plan_out *plan, const double **xs, const double **us, const mind_ilqr_stats **stats_warm,
+                                      const mind_ilqr_stats **stats_full, const long long **agent_keys, const float **types, double *x0) {
+  if (!P || !plan) return MIND_EINVAL;
+  if (!P->c) return MIND_ESTATE;
+  if (!P->have_plan) return fail(P->c, MIND_ESTATE, "mind_planner_last_plan: the planner holds no plan");
+  if (P->plan_gen != P->c->pl_gen) return fail(P->c, MIND_ESTATE, "mind_planner_last_plan: the context has planned again since (another planner shares it): the plan's tables are gone");
+  *plan = P->po;
+  if (xs) *xs = P->sol_owned ? P->sol_xs.data() : P->c->pl_sol_xs.data();
+  if (us) *us = P->sol_owned ? P->sol_us.data() : P->c->pl_sol_us.data();
+  if (stats_warm) *stats_warm = P->sol_owned ? P->sol_stw.data() : P->c->pl_sol_stw.data();
+  if (stats_full) *stats_full = P->sol_owned ? P->sol_stf.data() : P->c->pl_sol_stf.data();
+  if (agent_keys) *agent_keys = P->kept_keys.data();
+  if (types) *types = P->f_types.data();
+  if (x0) memcpy(x0, P->plan_x0, 6 * sizeof(double));
+  return MIND_OK;
+}
+
+extern "C" int mind_planner_export(mind_planner *P, int cap, int *n, long long *key, int32_t *count, double *rows) {
+  if (!P || !n) return MIND_EINVAL;
+  const int first = P->obs[0].count ? 0 : 1;      // (the ego's window exists from creation on: it is a track once it has a frame)
+  *n = (int)P->obs.size() - first;
+  if (*n > cap || (*n > 0 && (!key || !count || !rows))) return MIND_EINVAL;
+  for (int s = 0; s < *n; ++s) {
+    const LoopTrack &t = P->obs[s + first];
+    key[s] = t.key; count[s] = t.count;
     for (int k = 0; k < t.count; ++k)
       memcpy(rows + ((size_t)s * LOOP_OBS + k) * LOOP_ROW, t.rows[(t.head + k) % LOOP_OBS], LOOP_ROW * sizeof(double));
   }

@@ -42,11 +42,33 @@ def contextlib_null():
     return contextlib.nullcontext()
 
 
+class _AgentObs(dict):
+    """MINDPlanner.agent_obs: a driver that starts an episode clears it (ClosedLoopSim._start_episode); while the windows live in the
+    library (native_plan) that clears them there as well"""
+    __slots__ = ("_planner",)
+
+    def __init__(self, planner):
+        super().__init__()
+        self._planner = planner
+
+    def clear(self):
+        nl = getattr(self._planner, "_native", None)
+        if nl is not None:
+            nl.reset()
+        super().clear()
+
+
 class MINDPlanner:
+    # update_observation / plan behind one native call each (mind_amd/native_plan.py) for planners whose config does not say: off unless
+    # mind_amd.dropin.install(native_plan=True) switched it on for the planners the reference's agent.py constructs
+    native_plan_default = False
+
     def __init__(self, config_dir):
         self.obs_len = 50
         self.plan_len = 50
-        self.agent_obs = {}
+        self.agent_obs = _AgentObs(self)
+        self._native = None            # the NativePlan while the windows live in the library
+        self.native_plan_stats = {"native": 0, "fallback": 0, "reason": None}
         self.state = None
         self.ctrl = None
         self.gt_tgt_lane = None
@@ -59,6 +81,7 @@ class MINDPlanner:
         else:
             with open(config_dir, "r") as f:
                 self.planner_cfg = json.load(f)
+        self.native_plan = bool(self.planner_cfg.get("native_plan", type(self).native_plan_default))
         self.init_device()
         self.init_network()
         self.init_scen_tree_gen()
@@ -114,6 +137,10 @@ class MINDPlanner:
 
     def update_observation(self, lcl_smp):
         """50-frame sliding Track per agent; agents missing from this frame get an unobserved dummy."""
+        if getattr(self, "native_plan", False) or getattr(self, "_native", None) is not None:
+            nl = self._native_plan_now(lcl_smp)
+            if nl is not None:
+                return nl.observe(lcl_smp)         # (the windows live in the library: agent_obs stays empty)
         seen = {"AV"}
         ego = lcl_smp.ego_agent
         if "AV" not in self.agent_obs:
@@ -159,7 +186,55 @@ class MINDPlanner:
 
     # ------------------------------------------------------------------------------------------
     def plan(self, lcl_smp):
-        return self.plan_end(self.plan_begin(lcl_smp))
+        nl = getattr(self, "_native", None)
+        if nl is None:
+            return self.plan_end(self.plan_begin(lcl_smp))
+        why = "native_plan switched off" if not self.native_plan else nl.stale()
+        if why is not None:            # the planner is no longer the case the library's copy was made for: the Python path from here on
+            nl.hand_back(why)
+            self.native_plan_stats["fallback"] += 1
+            return self.plan_end(self.plan_begin(lcl_smp))
+        res = nl.plan(lcl_smp)
+        if not isinstance(res, str):
+            self.native_plan_stats["native"] += 1
+            return res
+        # a cycle the library leaves to the Python path ("unsupported: ...", a scene table it does not take): that path plans it from a copy
+        # of the windows; the library keeps its own and takes the next frame again
+        self.native_plan_stats["fallback"] += 1
+        self.native_plan_stats["reason"] = res
+        nl.export_windows()
+        try:
+            with self._on_own_stream():
+                begun = self._plan_begin(lcl_smp, None)
+            return self.plan_end(begun)
+        finally:
+            dict.clear(self.agent_obs)
+            nl.rebase()
+
+    def _native_plan_now(self, lcl_smp):
+        """the NativePlan that takes this frame, or None: one is created on the first frame of an episode (empty windows) when native_plan
+        is on and NativePlan.why_not has no objection; one that no longer fits the planner is handed back"""
+        nl = self._native
+        if nl is not None:
+            why = "native_plan switched off" if not self.native_plan else nl.stale()
+            if why is None:
+                return nl
+            self._native_hand_back(why)
+            return None
+        if len(self.agent_obs):
+            return None
+        from ...native_plan import NativePlan
+        why = NativePlan.why_not(self, lcl_smp)
+        if why is not None:
+            self.native_plan_stats["reason"] = why
+            return None
+        self._native = NativePlan(self, lcl_smp)
+        return self._native
+
+    def _native_hand_back(self, reason):
+        nl = getattr(self, "_native", None)
+        if nl is not None:
+            nl.hand_back(reason)
 
     def _on_own_stream(self):
         """A planner with a context of its own (planner config "own_context", runtime.new_runtime) runs its kernels on that context's
@@ -172,6 +247,7 @@ class MINDPlanner:
         return torch.cuda.stream(ts)
 
     def plan_begin(self, lcl_smp, idle_hook=None):
+        self._native_hand_back("plan_begin: a driver that plans in halves")       # (no-op on the Python path)
         with self._on_own_stream():
             return self._plan_begin(lcl_smp, idle_hook)
 
@@ -239,6 +315,7 @@ class MINDPlanner:
 
     def plan_start(self, lcl_smp):
         """host work before the AIME rounds + the start of the native plan; returns a token for plan_started_ready / plan_begin_finish"""
+        self._native_hand_back("plan_start: a driver that plans in pieces")
         with self._torch_free():
             import time
             t0 = time.perf_counter()
@@ -316,10 +393,11 @@ class MINDPlanner:
             ts[k] += self.timing[k]
 
     def plan_rounds(self, lcl_smp):
-        """plan() as a generator over the AIME rounds (ScenarioTreeGenerator.branch_aime_rounds): yields each round's
+        """(a planner whose windows live in the library hands them back first.)  plan() as a generator over the AIME rounds (ScenarioTreeGenerator.branch_aime_rounds): yields each round's
         (scenes, predictor inputs), is sent the predictor outputs, returns plan()'s result.  mind_amd.fused drives several
         planners' generators in lock-step and answers all their rounds with ONE predictor batch (BASELINE config 3)."""
         import time
+        self._native_hand_back("plan_rounds: a driver that answers the rounds itself")
         t0 = time.perf_counter()
         self.scen_tree_gen.reset()
         lane, info = self.resample_target_lane(lcl_smp)
