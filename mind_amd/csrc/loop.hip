@@ -29,6 +29,11 @@ struct LoopTrack {
     else { dst = rows[head]; head = (head + 1) % LOOP_OBS; }            // object_states.pop(0)
     memcpy(dst, r, LOOP_ROW * sizeof(double));
   }
+  void push_observed(const double *v, double timestep) {       // v: x, y, heading, vx, vy
+    double row[LOOP_ROW];
+    row[0] = 1.0; memcpy(row + 1, v, 5 * sizeof(double)); row[6] = timestep;
+    push(row);
+  }
 };
 
 }  // namespace
@@ -84,6 +89,12 @@ struct mind_cycle {
   double aime_s = 0, ilqr_s = 0, total_s = 0;
   mind_loop_totals tot;
   mind_cycle() { memset(&po, 0, sizeof(po)); memset(&tot, 0, sizeof(tot)); }
+  // a track seen for the first time joins the table behind the others; returns its index in obs
+  int add_track(int track, long long key, int slot) {
+    obs.emplace_back();
+    obs.back().track = track; obs.back().key = key; obs.back().slot = slot;
+    return (int)obs.size() - 1;
+  }
 };
 
 struct mind_loop : mind_cycle {
@@ -116,6 +127,75 @@ struct mind_planner : mind_cycle {
 
 namespace {
 
+// the cycle's fields of mind_loop_desc / mind_planner_desc
+template <class Desc> void cycle_params_from(CycleParams &cp, const Desc &d) {
+  cp.time_ahead = d.time_ahead; cp.min_vel = d.min_vel; cp.dist_thres = d.dist_thres; cp.max_depth = d.max_depth; cp.max_rounds = d.max_rounds;
+  cp.pred_len = d.pred_len; cp.prob_floor = d.prob_floor; cp.speculative = d.speculative;
+}
+
+// the last plan's fields and the running totals of mind_loop_out / mind_planner_out
+template <class Out> void cycle_fill_plan_out(const mind_cycle *L, Out *o) {
+  if (L->have_plan) {
+    o->n_agents = L->last_agents; o->n_trees = L->po.n_trees; o->best = L->best;
+    o->n_expanded = L->po.n_expanded; o->n_rounds = L->po.n_rounds;
+    o->n_traj_nodes = L->last_nodes;        // (kept by value: the plan's tables are the context's and may be another plan's by now)
+    o->costs = L->costs.data();
+    o->aime_s = L->aime_s; o->ilqr_s = L->ilqr_s; o->total_s = L->total_s;
+  }
+  o->tot = L->tot;
+}
+
+// a reset finishes a speculation that is still running on the side context (mind_loop_reset keeps have_plan, mind_planner_reset clears it: ADVICE.md item 3)
+void cycle_drop_speculation(mind_cycle *L) {
+  if (L->spec_pending && L->side) { (void)mind_ilqr_finish(L->side); L->spec_pending = false; }
+}
+
+// tracks not reported in this frame (seen(s, track) false): their last state again, unobserved (planner.py:58-62)
+template <class Seen> void cycle_repeat_unseen(mind_cycle *L, size_t known_before, Seen seen) {
+  double row[LOOP_ROW];
+  for (size_t s = 1; s < known_before; ++s) {
+    LoopTrack &t = L->obs[s];
+    if (seen(s, t)) continue;
+    memcpy(row, t.last(), sizeof(row));
+    row[0] = 0.0;
+    t.push(row);
+  }
+}
+
+// *_last_plan: `idents` names the plan's agents the way the owner's callers do (world tracks / caller's keys)
+template <class Id> int cycle_last_plan(mind_cycle *L, const std::vector<Id> &idents, mind_aime_plan_out *plan, const double **xs, const double **us,
+                                        const mind_ilqr_stats **stats_warm, const mind_ilqr_stats **stats_full, const Id **agents, const float **types, double *x0) {
+  if (!L->have_plan) return fail(L->c, MIND_ESTATE, "%s_last_plan: no plan is held", L->who);
+  if (L->plan_gen != L->c->pl_gen) return fail(L->c, MIND_ESTATE, "%s_last_plan: the context has planned again since (another planner shares it): the plan's tables are gone", L->who);
+  *plan = L->po;
+  if (xs) *xs = L->sol_owned ? L->sol_xs.data() : L->c->pl_sol_xs.data();
+  if (us) *us = L->sol_owned ? L->sol_us.data() : L->c->pl_sol_us.data();
+  if (stats_warm) *stats_warm = L->sol_owned ? L->sol_stw.data() : L->c->pl_sol_stw.data();
+  if (stats_full) *stats_full = L->sol_owned ? L->sol_stf.data() : L->c->pl_sol_stf.data();
+  if (agents) *agents = idents.data();
+  if (types) *types = L->f_types.data();
+  if (x0) memcpy(x0, L->plan_x0, 6 * sizeof(double));
+  return MIND_OK;
+}
+
+// *_export: the windows obs[first .. first + n), oldest row first, each named by the member `id` of its track
+template <class M, class Id> void cycle_export_rows(const mind_cycle *L, int first, int n, M LoopTrack::*id, Id *ident, int32_t *count, double *rows) {
+  for (int s = 0; s < n; ++s) {
+    const LoopTrack &t = L->obs[s + first];
+    ident[s] = t.*id; count[s] = t.count;
+    for (int k = 0; k < t.count; ++k)
+      memcpy(rows + ((size_t)s * LOOP_OBS + k) * LOOP_ROW, t.rows[(t.head + k) % LOOP_OBS], LOOP_ROW * sizeof(double));
+  }
+}
+
+// one candidate of mind_eval_traj_trees at node `o` of eval_st / eval_ct: the root (x0, zero control) + the tree's m trajectory nodes
+void cycle_stage_candidate(mind_cycle *L, size_t o, const double *x0, const double *xs, const double *us, int m) {
+  memcpy(L->eval_st.data() + o * 6, x0, 6 * sizeof(double));
+  L->eval_ct[o * 2] = 0.0; L->eval_ct[o * 2 + 1] = 0.0;
+  memcpy(L->eval_st.data() + (o + 1) * 6, xs, (size_t)m * 6 * sizeof(double));
+  memcpy(L->eval_ct.data() + (o + 1) * 2, us, (size_t)m * 2 * sizeof(double));
+}
+
 int loop_row(const mind_loop *L, long long n) {
   if (n < L->d.n_steps) return (int)n;
   return L->d.clamp_last ? L->d.n_steps - 1 : -1;
@@ -129,14 +209,7 @@ void loop_fill_out(const mind_loop *L, mind_loop_out *o) {
   o->sim_time = L->sim_time; o->last_trigger = L->have_trigger ? L->last_trigger : -1.0;
   memcpy(o->state, L->state, sizeof(o->state));
   memcpy(o->ctrl, L->ctrl, sizeof(o->ctrl));
-  if (L->have_plan) {
-    o->n_agents = L->last_agents; o->n_trees = L->po.n_trees; o->best = L->best;
-    o->n_expanded = L->po.n_expanded; o->n_rounds = L->po.n_rounds;
-    o->n_traj_nodes = L->last_nodes;        // (kept by value: the plan's tables are the context's and may be another plan's by now)
-    o->costs = L->costs.data();
-    o->aime_s = L->aime_s; o->ilqr_s = L->ilqr_s; o->total_s = L->total_s;
-  }
-  o->tot = L->tot;
+  cycle_fill_plan_out(L, o);
 }
 
 void loop_sincos(const mind_loop *L, double x, double *sc) {
@@ -147,53 +220,29 @@ void loop_sincos(const mind_loop *L, double x, double *sc) {
 // MINDPlanner.update_observation (planner.py:50-64) on the tables' row `r`
 void loop_observe(mind_loop *L, int r) {
   const int nt = L->d.n_tracks;
-  double row[LOOP_ROW];
+  const double ts = (double)L->timestep[r];
+  if (L->obs.empty()) L->slot_of_track[0] = L->add_track(0, 0, L->type_slot[0]);
+  const size_t known_before = L->obs.size();
   // ego: its plant state once enabled, the recording before (ClosedLoopSim._observation); to_object_state (planner.py:61-64).  The recorded
   // ego's entry -- before the take-over and at the take-over step, when the plant state IS the recorded one -- comes from the caller's table
   // (a float32 recording makes numpy evaluate it with its float32 cosine: only the driver's own code reproduces that)
-  if (!L->enabled || L->state_recorded) {
-    const double *e = L->ego_obs.data() + (size_t)r * 5;
-    row[0] = 1.0; row[1] = e[0]; row[2] = e[1]; row[3] = e[2]; row[4] = e[3]; row[5] = e[4];
-  } else {
+  if (!L->enabled || L->state_recorded) L->obs[0].push_observed(L->ego_obs.data() + (size_t)r * 5, ts);
+  else {
     const double *es = L->state;
     double sc[2];
     loop_sincos(L, es[3], sc);
-    row[0] = 1.0; row[1] = es[0]; row[2] = es[1]; row[3] = es[3];
-    row[4] = es[2] * sc[1]; row[5] = es[2] * sc[0];
+    const double v[5] = {es[0], es[1], es[3], es[2] * sc[1], es[2] * sc[0]};
+    L->obs[0].push_observed(v, ts);
   }
-  row[6] = (double)L->timestep[r];
-  if (L->obs.empty()) {
-    L->obs.emplace_back();
-    L->obs[0].track = 0; L->obs[0].key = 0; L->obs[0].slot = L->type_slot[0];
-    L->slot_of_track[0] = 0;
-  }
-  const size_t known_before = L->obs.size();
-  L->obs[0].push(row);
   // exo agents reported at this step, in the world's order; a track seen for the first time joins the table behind the others
-  std::vector<uint8_t> &seen = L->exo_valid;       // (read only)
-  const uint8_t *val = seen.data() + (size_t)r * nt;
+  const uint8_t *val = L->exo_valid.data() + (size_t)r * nt;
   for (int i = 1; i < nt; ++i) {
     if (!val[i]) continue;
     int s = L->slot_of_track[i];
-    if (s < 0) {
-      s = (int)L->obs.size();
-      L->obs.emplace_back();
-      L->obs[s].track = i; L->obs[s].key = i; L->obs[s].slot = L->type_slot[i];
-      L->slot_of_track[i] = s;
-    }
-    const double *e = L->exo_obs.data() + ((size_t)r * nt + i) * 5;
-    row[0] = 1.0; row[1] = e[0]; row[2] = e[1]; row[3] = e[2]; row[4] = e[3]; row[5] = e[4];
-    row[6] = (double)L->timestep[r];
-    L->obs[s].push(row);
+    if (s < 0) s = L->slot_of_track[i] = L->add_track(i, i, L->type_slot[i]);
+    L->obs[s].push_observed(L->exo_obs.data() + ((size_t)r * nt + i) * 5, ts);
   }
-  // tracks not reported: their last state again, unobserved (planner.py:58-62)
-  for (size_t s = 1; s < known_before; ++s) {
-    LoopTrack &t = L->obs[s];
-    if (val[t.track]) continue;
-    memcpy(row, t.last(), sizeof(row));
-    row[0] = 0.0;
-    t.push(row);
-  }
+  cycle_repeat_unseen(L, known_before, [&](size_t, const LoopTrack &t) { return val[t.track] != 0; });
 }
 
 // kine_propagate (common/kinematics.py:22-36) with the simulator's plant constants (agent.py:298-299)
@@ -469,10 +518,7 @@ int cycle_plan(mind_cycle *L) {
           if (L->early_seen[t] || __atomic_load_n((const unsigned *)&E.done[t], __ATOMIC_ACQUIRE) != E.gen) continue;
           const int m = off[t + 1] - off[t];
           L->eval_st.resize((size_t)(m + 1) * 6); L->eval_ct.resize((size_t)(m + 1) * 2);
-          memcpy(L->eval_st.data(), x0, 6 * sizeof(double));
-          L->eval_ct[0] = 0.0; L->eval_ct[1] = 0.0;
-          memcpy(L->eval_st.data() + 6, E.xs + (size_t)off[t] * 6, (size_t)m * 6 * sizeof(double));
-          memcpy(L->eval_ct.data() + 2, E.us + (size_t)off[t] * 2, (size_t)m * 2 * sizeof(double));
+          cycle_stage_candidate(L, 0, x0, E.xs + (size_t)off[t] * 6, E.us + (size_t)off[t] * 2, m);
           const int32_t cnt1 = m + 1;
           if ((rc = mind_eval_traj_trees(L->eval_st.data(), L->eval_ct.data(), &cnt1, 1, elane_e, d.eval_lane_is_f32, d.eval_n_lane_pts, d.target_vel, &L->costs[t])))
             return fail(c, rc, "%s: mind_eval_traj_trees failed", L->who);
@@ -505,10 +551,7 @@ int cycle_plan(mind_cycle *L) {
   size_t o = 0;
   for (int t = 0; t < nt; ++t) {
     const int m = off[t + 1] - off[t];
-    memcpy(L->eval_st.data() + o * 6, x0, 6 * sizeof(double));
-    L->eval_ct[o * 2] = 0.0; L->eval_ct[o * 2 + 1] = 0.0;
-    memcpy(L->eval_st.data() + (o + 1) * 6, xs + (size_t)off[t] * 6, (size_t)m * 6 * sizeof(double));
-    memcpy(L->eval_ct.data() + (o + 1) * 2, us + (size_t)off[t] * 2, (size_t)m * 2 * sizeof(double));
+    cycle_stage_candidate(L, o, x0, xs + (size_t)off[t] * 6, us + (size_t)off[t] * 2, m);
     L->counts[t] = m + 1;
     o += (size_t)m + 1;
   }
@@ -608,11 +651,10 @@ extern "C" int mind_loop_create(mind_ctx *c, const mind_loop_desc *d, mind_loop 
   if (!L) return fail(c, MIND_ENOMEM, "mind_loop_create: out of memory");
   L->c = c; L->d = *d;
   CycleParams &cp = L->p;
+  cycle_params_from(cp, *d);
   cp.n_lanes = d->n_lanes; cp.n_lane_pts = d->n_lane_pts;
-  cp.time_ahead = d->time_ahead; cp.min_vel = d->min_vel; cp.dist_thres = d->dist_thres; cp.max_depth = d->max_depth; cp.max_rounds = d->max_rounds;
-  cp.pred_len = d->pred_len; cp.prob_floor = d->prob_floor;
   cp.solve_n_lane_pts = d->solve_n_lane_pts; cp.target_vel = d->target_vel;
-  cp.eval_n_lane_pts = d->eval_n_lane_pts; cp.eval_lane_is_f32 = d->eval_lane_is_f32; cp.speculative = d->speculative;
+  cp.eval_n_lane_pts = d->eval_n_lane_pts; cp.eval_lane_is_f32 = d->eval_lane_is_f32;
   const size_t S = (size_t)d->n_steps, nt = (size_t)d->n_tracks;
   L->ego_state.assign(d->ego_state, d->ego_state + S * 4);
   L->ego_obs.assign(d->ego_obs, d->ego_obs + S * 5);
@@ -658,7 +700,7 @@ extern "C" int mind_loop_reset(mind_loop *L) {
   L->sim_time = 0.0; L->have_trigger = false; L->last_trigger = -1.0; L->enabled = false; L->half_step = false;
   memcpy(L->state, L->ego_state.data(), 4 * sizeof(double));        // world.agent_state(0, 0.0)
   L->state_recorded = false; L->tan_valid = false;
-  if (L->spec_pending && L->side) { (void)mind_ilqr_finish(L->side); L->spec_pending = false; }
+  cycle_drop_speculation(L);
   L->ctrl[0] = 0.0; L->ctrl[1] = 0.0;
   L->ep_steps = 0;
   L->obs.clear();
@@ -694,29 +736,14 @@ extern "C" int mind_loop_state(mind_loop *L, mind_loop_out *out) {
 extern "C" int mind_loop_last_plan(mind_loop *L, mind_aime_plan_out *plan, const double **xs, const double **us, const mind_ilqr_stats **stats_warm,
                                    const mind_ilqr_stats **stats_full, const int32_t **agent_tracks, const float **types, double *x0) {
   if (!L || !plan) return MIND_EINVAL;
-  if (!L->have_plan) return fail(L->c, MIND_ESTATE, "mind_loop_last_plan: the loop holds no plan");
-  if (L->plan_gen != L->c->pl_gen) return fail(L->c, MIND_ESTATE, "mind_loop_last_plan: the context has planned again since (another planner shares it): the loop's plan tables are gone");
-  *plan = L->po;
-  if (xs) *xs = L->sol_owned ? L->sol_xs.data() : L->c->pl_sol_xs.data();
-  if (us) *us = L->sol_owned ? L->sol_us.data() : L->c->pl_sol_us.data();
-  if (stats_warm) *stats_warm = L->sol_owned ? L->sol_stw.data() : L->c->pl_sol_stw.data();
-  if (stats_full) *stats_full = L->sol_owned ? L->sol_stf.data() : L->c->pl_sol_stf.data();
-  if (agent_tracks) *agent_tracks = L->kept.data();
-  if (types) *types = L->f_types.data();
-  if (x0) memcpy(x0, L->plan_x0, 6 * sizeof(double));
-  return MIND_OK;
+  return cycle_last_plan(L, L->kept, plan, xs, us, stats_warm, stats_full, agent_tracks, types, x0);
 }
 
 extern "C" int mind_loop_export(mind_loop *L, int cap, int *n, int32_t *track, int32_t *count, double *rows) {
   if (!L || !n) return MIND_EINVAL;
   *n = (int)L->obs.size();
   if (*n > cap || !track || !count || !rows) return MIND_EINVAL;
-  for (int s = 0; s < *n; ++s) {
-    const LoopTrack &t = L->obs[s];
-    track[s] = t.track; count[s] = t.count;
-    for (int k = 0; k < t.count; ++k)
-      memcpy(rows + ((size_t)s * LOOP_OBS + k) * LOOP_ROW, t.rows[(t.head + k) % LOOP_OBS], LOOP_ROW * sizeof(double));
-  }
+  cycle_export_rows(L, 0, *n, &LoopTrack::track, track, count, rows);
   return MIND_OK;
 }
 
@@ -728,14 +755,8 @@ namespace {
 void planner_fill_out(const mind_planner *P, mind_planner_out *o) {
   memset(o, 0, sizeof(*o));
   o->n_plans = P->n_plans;
-  if (P->have_plan) {
-    o->n_agents = P->last_agents; o->n_trees = P->po.n_trees; o->best = P->best;
-    o->n_expanded = P->po.n_expanded; o->n_rounds = P->po.n_rounds; o->n_traj_nodes = P->last_nodes;
-    o->costs = P->costs.data();
-    memcpy(o->ctrl, P->ctrl, sizeof(o->ctrl));
-    o->aime_s = P->aime_s; o->ilqr_s = P->ilqr_s; o->total_s = P->total_s;
-  }
-  o->tot = P->tot;
+  if (P->have_plan) memcpy(o->ctrl, P->ctrl, sizeof(o->ctrl));
+  cycle_fill_plan_out(P, o);
 }
 
 // copies a table when it differs from the planner's copy; returns whether it did
@@ -756,12 +777,9 @@ extern "C" int mind_planner_create(mind_ctx *c, const mind_planner_desc *d, mind
   mind_planner *P = new (std::nothrow) mind_planner();
   if (!P) return fail(c, MIND_ENOMEM, "mind_planner_create: out of memory");
   P->c = c; P->who = "mind_planner";
-  CycleParams &cp = P->p;
-  cp.time_ahead = d->time_ahead; cp.min_vel = d->min_vel; cp.dist_thres = d->dist_thres; cp.max_depth = d->max_depth; cp.max_rounds = d->max_rounds;
-  cp.pred_len = d->pred_len; cp.prob_floor = d->prob_floor; cp.speculative = d->speculative;
+  cycle_params_from(P->p, *d);
   P->cfg_warm = *d->cfg_warm; P->cfg_full = *d->cfg_full;
-  P->obs.emplace_back();                      // the ego's window: always the first track
-  P->obs[0].key = MIND_PLANNER_EGO_KEY; P->obs[0].slot = d->ego_type_slot;
+  P->add_track(0, MIND_PLANNER_EGO_KEY, d->ego_type_slot);      // the ego's window: always the first track
   *out = P;
   return MIND_OK;
 }
@@ -774,11 +792,10 @@ extern "C" int mind_planner_destroy(mind_planner *P) {
 
 extern "C" int mind_planner_reset(mind_planner *P) {
   if (!P) return MIND_EINVAL;
-  if (P->spec_pending && P->side) { (void)mind_ilqr_finish(P->side); P->spec_pending = false; }
+  cycle_drop_speculation(P);
   const int ego_slot = P->obs.empty() ? 6 : P->obs[0].slot;
   P->obs.clear();
-  P->obs.emplace_back();
-  P->obs[0].key = MIND_PLANNER_EGO_KEY; P->obs[0].slot = ego_slot;
+  P->add_track(0, MIND_PLANNER_EGO_KEY, ego_slot);
   P->slot_of_key.clear();
   P->have_plan = false;                       // (the last plan belongs to the episode that ended)
   return MIND_OK;
@@ -794,35 +811,23 @@ extern "C" int mind_planner_observe(mind_planner *P, int timestep, const double 
     if (i > 0 && P->frame_keys[i] == P->frame_keys[i - 1]) return fail(P->c, MIND_EINVAL, "mind_planner_observe: track key %lld twice in one frame", P->frame_keys[i]);
     if (type_slot[i] < 0 || type_slot[i] > 6) return fail(P->c, MIND_EINVAL, "mind_planner_observe: type slot %d of track %d", (int)type_slot[i], i);
   }
-  double row[LOOP_ROW];
-  row[0] = 1.0; memcpy(row + 1, ego, 5 * sizeof(double)); row[6] = (double)timestep;
   const size_t known_before = P->obs.size();
-  P->obs[0].push(row);
+  P->obs[0].push_observed(ego, (double)timestep);
   P->frame_seen.assign(known_before, 0);
-  // agents reported in this frame, in the caller's order; a key seen for the first time joins the table behind the others
+  // agents reported in this frame, in the caller's order
   for (int i = 0; i < n; ++i) {
     int s;
     auto it = P->slot_of_key.find(track_key[i]);
     if (it == P->slot_of_key.end()) {
-      s = (int)P->obs.size();
-      P->obs.emplace_back();
-      P->obs[s].key = track_key[i]; P->obs[s].track = s; P->obs[s].slot = type_slot[i];
+      s = P->add_track((int)P->obs.size(), track_key[i], type_slot[i]);
       P->slot_of_key.emplace(track_key[i], s);
     } else {
       s = it->second;
       P->frame_seen[s] = 1;
     }
-    row[0] = 1.0; memcpy(row + 1, rows + (size_t)i * 5, 5 * sizeof(double)); row[6] = (double)timestep;
-    P->obs[s].push(row);
+    P->obs[s].push_observed(rows + (size_t)i * 5, (double)timestep);
   }
-  // tracks not reported: their last state again, unobserved (planner.py:58-62)
-  for (size_t s = 1; s < known_before; ++s) {
-    if (P->frame_seen[s]) continue;
-    LoopTrack &t = P->obs[s];
-    memcpy(row, t.last(), sizeof(row));
-    row[0] = 0.0;
-    t.push(row);
-  }
+  cycle_repeat_unseen(P, known_before, [&](size_t s, const LoopTrack &) { return P->frame_seen[s] != 0; });
   return MIND_OK;
 }
 
@@ -888,17 +893,7 @@ extern "C" int mind_planner_last_plan(mind_planner *P, mind_aime_plan_out *plan,
                                       const mind_ilqr_stats **stats_full, const long long **agent_keys, const float **types, double *x0) {
   if (!P || !plan) return MIND_EINVAL;
   if (!P->c) return MIND_ESTATE;
-  if (!P->have_plan) return fail(P->c, MIND_ESTATE, "mind_planner_last_plan: the planner holds no plan");
-  if (P->plan_gen != P->c->pl_gen) return fail(P->c, MIND_ESTATE, "mind_planner_last_plan: the context has planned again since (another planner shares it): the plan's tables are gone");
-  *plan = P->po;
-  if (xs) *xs = P->sol_owned ? P->sol_xs.data() : P->c->pl_sol_xs.data();
-  if (us) *us = P->sol_owned ? P->sol_us.data() : P->c->pl_sol_us.data();
-  if (stats_warm) *stats_warm = P->sol_owned ? P->sol_stw.data() : P->c->pl_sol_stw.data();
-  if (stats_full) *stats_full = P->sol_owned ? P->sol_stf.data() : P->c->pl_sol_stf.data();
-  if (agent_keys) *agent_keys = P->kept_keys.data();
-  if (types) *types = P->f_types.data();
-  if (x0) memcpy(x0, P->plan_x0, 6 * sizeof(double));
-  return MIND_OK;
+  return cycle_last_plan(P, P->kept_keys, plan, xs, us, stats_warm, stats_full, agent_keys, types, x0);
 }
 
 extern "C" int mind_planner_export(mind_planner *P, int cap, int *n, long long *key, int32_t *count, double *rows) {
@@ -906,11 +901,6 @@ extern "C" int mind_planner_export(mind_planner *P, int cap, int *n, long long *
   const int first = P->obs[0].count ? 0 : 1;      // (the ego's window exists from creation on: it is a track once it has a frame)
   *n = (int)P->obs.size() - first;
   if (*n > cap || (*n > 0 && (!key || !count || !rows))) return MIND_EINVAL;
-  for (int s = 0; s < *n; ++s) {
-    const LoopTrack &t = P->obs[s + first];
-    key[s] = t.key; count[s] = t.count;
-    for (int k = 0; k < t.count; ++k)
-      memcpy(rows + ((size_t)s * LOOP_OBS + k) * LOOP_ROW, t.rows[(t.head + k) % LOOP_OBS], LOOP_ROW * sizeof(double));
-  }
+  cycle_export_rows(P, first, *n, &LoopTrack::key, key, count, rows);
   return MIND_OK;
 }

@@ -14,6 +14,9 @@ A loop applies while the planner is the plain native case (HIP predictor, native
 contingency solves, native evaluation, no shard, no scripted modes, no injected solver).  The predicate is re-checked before every call;
 when it stops holding -- a test flips `device_root`, a driver calls `step_begin` / `plan_start` itself -- the loop is handed back:
 the windows are exported into `planner.agent_obs` and the simulator carries on with its Python steps from the same state.
+
+What a `NativeLoop` shares with `NativePlan` (native_plan.py) -- the planner-side predicate, the staleness check, the cycle's descriptor
+fields, the totals bookkeeping, the last plan's trees, the rebuild of `agent_obs` -- is `NativeCycle`, mind_amd/native_cycle.py.
 """
 import ctypes as C
 import os
@@ -21,6 +24,7 @@ import os
 import numpy as np
 
 from . import _lib
+from .native_cycle import NativeCycle, lane_reason, planner_reason, rebuild_agent_obs, state_reason
 
 
 _TRIG_CB = []
@@ -48,47 +52,36 @@ def _numpy_trig_callbacks():
     return _TRIG_CB[0]
 
 
-class NativeLoop:
+class NativeLoop(NativeCycle):
+    _who = "mind_loop"
+    pl = property(lambda self: self.sim.planner)
+
     @staticmethod
     def why_not(sim):
         """None when the native loop applies to this simulator + planner + world, else the reason (a string)"""
-        from .planners.mind.planner import MINDPlanner
-        pl, w = sim.planner, sim.world
+        w = sim.world
         if os.environ.get("MIND_NATIVE_LOOP", "1") == "0":
             return "MIND_NATIVE_LOOP=0"
-        if type(pl) is not MINDPlanner:
-            return "the planner is not a MINDPlanner"
-        gen, opt, net = pl.scen_tree_gen, pl.traj_tree_opt, pl.network
-        if gen.network is not net or type(net).__name__ != "ScenePredNet" or getattr(net, "rt", None) is None or not getattr(net, "_loaded", False):
-            return "the generator's network is not the HIP predictor itself"
-        if not (gen.native_aime and gen.device_glue and gen.device_select and gen.device_root) or gen.shard is not None or gen.ego_idx != 0 or gen.config is None:
-            return "the native AIME plan with the device-built root is not selected"
-        if gen.obs_len != 50 or pl.obs_len != 50 or not (2 <= gen.pred_len <= 60):
-            return "horizons"
-        if opt.solver is not None or opt.shard is not None or not opt.overlap or opt._runtime() is not net.rt:
-            return "the contingency solves are not the plain case"
-        if os.environ.get("MIND_PLAN_BEGINS_SOLVES", "1") == "0" or not getattr(pl, "_native_eval", True):
-            return "plan-begun solves / native evaluation switched off"
+        why = planner_reason(sim.planner)
+        if why is not None:
+            return why
         for name in ("agent_state", "object_type", "agent_ids", "n_agents", "target_lane", "target_lane_info", "target_velocity"):
             if not hasattr(w, name):
                 return f"the world has no {name}"
-        if np.asarray(w.agent_state(0, 0.0)).dtype not in (np.float32, np.float64):
-            return "agent states are neither float32 nor float64"
+        why = state_reason(w.agent_state(0, 0.0))
+        if why is not None:
+            return why
         if sim.episode_plans is None and not hasattr(w, "max_step"):
             return "an open-ended world without a last step"
-        lane = np.asarray(w.target_lane)
-        if lane.dtype not in (np.float32, np.float64) or lane.ndim != 2 or lane.shape[1] != 2 or np.any(np.all(lane[1:] == lane[:-1], axis=1)):
-            return "the target lane is not a float polyline without zero-length segments"
-        return None
+        return lane_reason(w.target_lane)
 
     def __init__(self, sim):
         from types import SimpleNamespace
         from .planners.mind import utils as U
-        from .planners.mind.trajectory_tree import ilqr_cfg_from, _cfg_fingerprint
-        self.sim, self.lib = sim, _lib.load()
+        self.sim = sim
         pl, w = sim.planner, sim.world
-        gen, opt = pl.scen_tree_gen, pl.traj_tree_opt
-        self.rt = pl.network.rt
+        gen = pl.scen_tree_gen
+        self._cycle_init(pl)
         # ---- the scene's planner constants, built by the planner's own code
         lcl = SimpleNamespace(target_lane=w.target_lane, target_lane_info=w.target_lane_info, target_velocity=w.target_velocity)
         lane, info = pl.resample_target_lane(lcl)
@@ -99,20 +92,15 @@ class NativeLoop:
         if st["num_lanes"] == 0:
             raise ValueError("no lanes")
         gen.n_lanes = int(st["num_lanes"])
-        keep = self._keep = {}
+        keep = self._keep
         f32 = lambda x: np.ascontiguousarray(x, np.float32)
         keep["tl"], keep["ti"] = f32(gen.target_lane), f32(gen.target_lane_info)
         keep["lpts"], keep["lfl"] = np.ascontiguousarray(st["pts"], np.float64), np.ascontiguousarray(st["flags"], np.int32)
-        keep["cw"], keep["cf"] = ilqr_cfg_from(opt.config, "w_opt_cfg"), ilqr_cfg_from(opt.config, "opt_cfg")
         keep["gt"] = np.ascontiguousarray(np.asarray(pl.gt_tgt_lane, np.float64))
         ev = np.asarray(w.target_lane)
         keep["ev"] = np.ascontiguousarray(ev)
-        # what must stay as it is for the loop to remain this planner's plan (checked before every call)
-        self._gt_obj, self._gen_cfg, self._opt_cfg, self._net = pl.gt_tgt_lane, gen.config, opt.config, pl.network
-        self._scen_fp = (gen.config.tar_time_ahead, gen.config.tar_dist_thres, gen.config.max_depth, gen.pred_len)
-        self._opt_fp = (_cfg_fingerprint(opt.config, "w_opt_cfg"), _cfg_fingerprint(opt.config, "opt_cfg"))
-        self._fp = _cfg_fingerprint
-        self._world_fp = (w.target_lane, w.target_lane_info, w.target_velocity)
+        # what must stay the same object for the loop to remain this planner's plan, beside NativeCycle's (ok(), before every call)
+        self._gt_obj, self._world_fp = pl.gt_tgt_lane, (w.target_lane, w.target_lane_info, w.target_velocity)
         # ---- the replayed scene, one row per simulator step
         self._tabulate()
         d = _lib.LoopDesc()
@@ -130,39 +118,10 @@ class NativeLoop:
         d.wheelbase, d.max_speed, d.max_steer, d.max_acc, d.max_dec = float(sim.WB), float(sim.MAX_SPD), float(sim.MAX_STR), 6.0, -6.0
         d.n_lanes, d.lane_pts, d.lane_flags = int(st["num_lanes"]), keep["lpts"].ctypes.data, keep["lfl"].ctypes.data
         d.n_lane_pts, d.target_lane, d.target_lane_info = len(keep["tl"]), keep["tl"].ctypes.data, keep["ti"].ctypes.data
-        cfg = gen.config
-        d.time_ahead, d.min_vel, d.dist_thres = float(cfg.tar_time_ahead), 0.5, float(cfg.tar_dist_thres)
-        d.max_depth, d.max_rounds, d.pred_len, d.prob_floor = int(cfg.max_depth), 16, int(gen.pred_len), 0.0
-        d.cfg_warm, d.cfg_full = C.addressof(keep["cw"]), C.addressof(keep["cf"])
+        self._fill_cycle_desc(d)
         d.solve_n_lane_pts, d.solve_lane, d.target_vel = len(keep["gt"]), keep["gt"].ctypes.data, float(w.target_velocity)
         d.eval_n_lane_pts, d.eval_lane_is_f32, d.eval_lane = len(keep["ev"]), int(keep["ev"].dtype == np.float32), keep["ev"].ctypes.data
-        # the optimizer's speculative warm start inside the loop (a second context of the loop's own): opt-in, MIND_NATIVE_SPECULATE=1 --
-        # a lone loop gains nothing from it (profiles/r06q_*), several loops sharing the device do
-        self.speculative = bool(opt.speculative) and os.environ.get("MIND_NATIVE_SPECULATE", "0") == "1"
-        d.speculative = int(self.speculative)
-        h = C.c_void_p()
-        rc = self.lib.mind_loop_create(self.rt.ctx, C.byref(d), C.byref(h))
-        _lib.check(self.lib, self.rt.ctx, rc, "mind_loop_create")
-        self.h = h
-        self._ctx_value = self.rt.ctx.value
-        self.out = _lib.LoopOut()
-        self._out_ref = C.byref(self.out)
-        self._result = None            # the last plan's [[scenario tree], [trajectory tree]] once somebody asked for it
-        cn, ts = opt.counters, pl.timing_sum
-        self._base = dict(plans=ts["plans"], aime_s=ts["aime_s"], ilqr_s=ts["ilqr_s"], total_s=ts["total_s"], n_expanded=gen.n_expanded, solves=cn["solves"],
-                          iterations=cn["iterations"], node_iterations=cn.get("node_iterations", 0), node_iterations_exo=cn.get("node_iterations_exo", 0),
-                          warm_speculated=cn.get("warm_speculated", 0), warm_hits=cn.get("warm_hits", 0))
-
-    def close(self):
-        h, self.h = getattr(self, "h", None), None
-        if h is not None:
-            self.lib.mind_loop_destroy(h)         # (host memory only: safe after the context is gone)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:      # noqa: BLE001
-            pass
+        self._create(d, _lib.LoopOut())
 
     # ------------------------------------------------------------------------------------------
     def _tabulate(self):
@@ -222,16 +181,9 @@ class NativeLoop:
     # ------------------------------------------------------------------------------------------
     def ok(self):
         """the planner is still the case this loop was built for (cheap: attribute reads and two small fingerprints)"""
-        pl = self.sim.planner
-        gen, opt, w = pl.scen_tree_gen, pl.traj_tree_opt, self.sim.world
-        cfg = gen.config
-        ctx = self.rt.ctx         # (a runtime that was closed, or re-created, under the loop: the library's loop holds the old context)
-        return (self.h is not None and ctx is not None and ctx.value == self._ctx_value and gen.native_aime and gen.device_root and gen.device_glue and gen.device_select and gen.shard is None
-                and gen.network is self._net and pl.network is self._net and opt.solver is None and opt.shard is None and opt.overlap
-                and (not self.speculative or opt.speculative) and pl.gt_tgt_lane is self._gt_obj and cfg is self._gen_cfg and opt.config is self._opt_cfg and pl._native_eval
-                and (cfg.tar_time_ahead, cfg.tar_dist_thres, cfg.max_depth, gen.pred_len) == self._scen_fp
-                and w.target_lane is self._world_fp[0] and w.target_lane_info is self._world_fp[1] and w.target_velocity == self._world_fp[2]
-                and (self._fp(self._opt_cfg, "w_opt_cfg"), self._fp(self._opt_cfg, "opt_cfg")) == self._opt_fp)
+        w = self.sim.world
+        return (self.stale() is None and self.pl.gt_tgt_lane is self._gt_obj
+                and w.target_lane is self._world_fp[0] and w.target_lane_info is self._world_fp[1] and w.target_velocity == self._world_fp[2])
 
     def advance(self, until_plans=0, until_time=-1.0, max_steps=1):
         """mind_loop_advance + the simulator's / planner's mirrors of what happened; returns the number of plans computed"""
@@ -239,8 +191,7 @@ class NativeLoop:
         p0, s0 = o.n_plans, o.n_steps
         rc = self.lib.mind_loop_advance(self.h, int(until_plans), float(until_time), int(max_steps), self._out_ref)
         if rc != 0:
-            msg = self.lib.mind_last_error_string(self.rt.ctx) or b""
-            if rc == _lib.MIND_ESTATE and msg.startswith(b"unsupported"):
+            if self._unsupported(rc) is not None:
                 return self._finish_step_on_the_host(p0, s0)
             _lib.check(self.lib, self.rt.ctx, rc, "mind_loop_advance")
         return self._mirror(p0, s0)
@@ -255,73 +206,22 @@ class NativeLoop:
         if dp:
             sim.n_plans += dp
             self._result = None
-            pl = sim.planner
-            gen, opt = pl.scen_tree_gen, pl.traj_tree_opt
-            nt = o.n_trees
-            pl.timing = {"aime_s": o.aime_s, "ilqr_s": o.ilqr_s, "total_s": o.total_s, "nodes_expanded": o.n_expanded, "n_scen_trees": nt,
-                         "best_traj_idx": o.best, "tree_costs": o.costs[:nt]}
-            # the running totals are the library's (several plans may have run in this call): base values at the loop's creation + its sums
-            t, b = o.tot, self._base
-            ts, cn = pl.timing_sum, opt.counters
-            ts["plans"], ts["aime_s"], ts["ilqr_s"], ts["total_s"] = b["plans"] + t.plans, b["aime_s"] + t.aime_s, b["ilqr_s"] + t.ilqr_s, b["total_s"] + t.total_s
-            gen.n_expanded = b["n_expanded"] + t.expansions
-            cn["solves"], cn["iterations"] = b["solves"] + 2 * t.scen_trees, b["iterations"] + t.iterations
-            cn["node_iterations"], cn["node_iterations_exo"] = b["node_iterations"] + t.node_iterations, b["node_iterations_exo"] + t.node_iterations_exo
-            cn["warm_speculated"], cn["warm_hits"] = b["warm_speculated"] + t.warm_speculated, b["warm_hits"] + t.warm_hits
-            gen.n_native_plans += dp
-            gen.branch_depth = o.n_rounds
+            self._mirror_plan(dp)
         return dp
-
-    def totals(self):
-        """mind_loop_totals as a dict (running sums over the loop's plans; kernel durations only while profiling is on)"""
-        t = self.out.tot
-        d = {k: getattr(t, k) for k, _ in _lib.LoopTotals._fields_ if k != "ilqr_prof"}
-        d["ilqr_prof"] = list(t.ilqr_prof)
-        return d
 
     # ------------------------------------------------------------------------------------------
     def last_result(self):
-        """[[scenario tree], [trajectory tree]] of the last plan (MINDPlanner.plan's third return value), built from the library's tables (raises
-        MindError when another planner has planned on the shared context since: read the result before that, as a recorder does every step)"""
-        if self._result is not None:
-            return self._result
-        if self.out.n_plans == 0:
+        """NativeCycle._last_result; None before the first plan"""
+        if self._result is None and self.out.n_plans == 0:
             return None
-        if self.rt.ctx is None or self.rt.ctx.value != self._ctx_value:
-            raise _lib.MindError("the runtime of this loop was closed: its last plan can no longer be read")
-        from .planners.mind.trajectory_tree import to_traj_tree
-        pl = self.sim.planner
-        gen, opt, w = pl.scen_tree_gen, pl.traj_tree_opt, self.sim.world
-        po = _lib.AimePlanOut()
-        ptr = [C.c_void_p() for _ in range(6)]
-        x0 = np.zeros(6)
-        rc = self.lib.mind_loop_last_plan(self.h, C.byref(po), *[C.byref(p) for p in ptr], x0.ctypes.data)
-        _lib.check(self.lib, self.rt.ctx, rc, "mind_loop_last_plan")
-        a, nt = self.out.n_agents, po.n_trees
-        res = self.rt._aime_plan_result(0, po, a, int(self._keep["lfl"].shape[0]))
-        tracks = np.frombuffer(C.string_at(ptr[4], a * 4), np.int32)
-        types = np.frombuffer(C.string_at(ptr[5], a * 50 * 7 * 4), np.float32).reshape(a, 50, 7).astype(np.int16)
-        root = {"TRAJS_TYPE": types, "TRAJS_TID": ["AV" if t == 0 else w.agent_ids[t] for t in tracks],
-                "TRAJS_CAT": ["av" if i == 0 else "exo" for i in range(a)]}
-        scen = gen._native_trees(res, root, None, count=False)
-        off = np.frombuffer(C.string_at(po.tree_off, (nt + 1) * 4), np.int32)
-        M = int(off[-1])
-        xs = np.frombuffer(C.string_at(ptr[0], M * 48), np.float64).reshape(M, 6)
-        us = np.frombuffer(C.string_at(ptr[1], M * 16), np.float64).reshape(M, 2)
-        stats = lambda p: [dict(iterations=s.iterations, converged=s.converged, J=s.J, mu=s.mu)
-                           for s in C.cast(p, C.POINTER(_lib.IlqrStats * nt)).contents]
-        opt.debug = dict(warm=stats(ptr[2]), full=stats(ptr[3]))
-        trajs = [to_traj_tree(t._flat, x0, xs[off[i]:off[i + 1]], us[off[i]:off[i + 1]], opt.config.action_size) for i, t in enumerate(scen)]
-        self._all = (scen, trajs)
-        b = self.out.best
-        self._result = [[scen[b]], [trajs[b]]]
-        return self._result
+        ids = self.sim.world.agent_ids
+        return self._last_result(int(self._keep["lfl"].shape[0]), np.int32, lambda t: "AV" if t == 0 else ids[t])
 
     # ------------------------------------------------------------------------------------------
     def hand_back(self):
         """the simulator continues with its Python steps: the windows go into planner.agent_obs (Track objects with their array mirrors,
         as MINDPlanner.update_observation keeps them), the simulator's fields are the loop's; the loop is closed"""
-        from .planners.mind.planner import ObjectState, Track, TrackCategory
+        from .planners.mind.planner import TrackCategory
         sim = self.sim
         pl, w = sim.planner, sim.world
         self.lib.mind_loop_state(self.h, self._out_ref)
@@ -329,25 +229,10 @@ class NativeLoop:
         sim.sim_time, sim.enabled = o.sim_time, bool(o.enabled)
         sim.last_trigger = o.last_trigger if o.last_trigger >= 0.0 else None
         sim.state, sim.ctrl = np.array(o.state), np.array(o.ctrl)
-        n_tracks = self._tab["valid"].shape[1]
-        n = C.c_int(0)
-        track, count = np.zeros(n_tracks, np.int32), np.zeros(n_tracks, np.int32)
-        rows = np.zeros((n_tracks, 50, 7))
-        rc = self.lib.mind_loop_export(self.h, n_tracks, C.byref(n), track.ctypes.data, count.ctypes.data, rows.ctypes.data)
-        _lib.check(self.lib, self.rt.ctx, rc, "mind_loop_export")
+        exported = self._exported_windows(self._tab["valid"].shape[1], np.int32)
         pl.agent_obs.clear()
-        for s in range(n.value):
-            ti, cn = int(track[s]), int(count[s])
-            tid = "AV" if ti == 0 else w.agent_ids[ti]
-            tr = Track(tid, [ObjectState(bool(r[0]), int(r[6]), (r[1], r[2]), r[3], (r[4], r[5])) for r in rows[s, :cn]], w.object_type(ti),
-                       TrackCategory.FOCAL_TRACK if ti == 0 else TrackCategory.TRACK_FRAGMENT)
-            try:
-                buf = np.empty((4 * pl.obs_len, 6))
-                buf[:cn] = rows[s, :cn, :6]
-                tr._buf, tr._i, tr._n, tr._arr = buf, cn, cn, buf[0:cn]
-            except AttributeError:
-                pass
-            pl.agent_obs[tid] = tr
+        rebuild_agent_obs(pl, *exported, lambda ti: ("AV" if ti == 0 else w.agent_ids[ti], w.object_type(ti),
+                                                     TrackCategory.FOCAL_TRACK if ti == 0 else TrackCategory.TRACK_FRAGMENT))
         if sim.enabled:
             pl.update_state_ctrl(sim.state, sim.ctrl)
         ctx = self.rt.ctx

@@ -30,6 +30,20 @@ except Exception:   # same field order as av2 0.2.1 (constructed positionally, p
         TRACK_FRAGMENT, UNSCORED_TRACK, SCORED_TRACK, FOCAL_TRACK = range(4)
 
 
+def track_from_rows(track_id, rows, object_type, category, obs_len):
+    """the Track that MINDPlanner.update_observation holds after these frames, array mirror included: rows [count <= obs_len, 7] =
+    (observed, x, y, heading, vx, vy, timestep), oldest first (the windows a native cycle exports: mind_amd/native_cycle.py)"""
+    tr = Track(track_id, [ObjectState(bool(r[0]), int(r[6]), (r[1], r[2]), r[3], (r[4], r[5])) for r in rows], object_type, category)
+    cn = len(rows)
+    try:
+        buf = np.empty((4 * obs_len, 6))
+        buf[:cn] = rows[:, :6]
+        tr._buf, tr._i, tr._n, tr._arr = buf, cn, cn, buf[0:cn]
+    except AttributeError:      # immutable Track type (update_observation below)
+        pass
+    return tr
+
+
 def _import_cfg(name):
     try:
         return import_module(name)

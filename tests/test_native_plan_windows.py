@@ -121,6 +121,57 @@ def test_windows_equal_update_observation():
         lib.mind_planner_destroy(h)
 
 
+def test_exported_windows_rebuild_agent_obs():
+    """the hand-back path (NativePlan.export_windows / NativeLoop.hand_back) without a device: the library's exported windows, rebuilt into
+    an empty planner's agent_obs by native_cycle.rebuild_agent_obs, are the Tracks update_observation holds for the same frames -- and
+    stay so when both planners carry on in Python across the array mirror's compaction (a wrong _i / _n / _buf shows there)"""
+    from mind_amd.native_cycle import rebuild_agent_obs
+    from mind_amd.planners.mind.planner import TrackCategory
+    lib = _lib.load()
+    h, pl, rebuilt = _null_planner(lib), _python_planner(), _python_planner()
+    keys, ids, types = {}, {}, {}
+    try:
+        frames = _frames(75, seed=3)
+        for f, frame in enumerate(frames):
+            lcl = _lcl(frame, f)
+            types.update((a.id, a.type) for a in lcl.exo_agents)
+            pl.update_observation(lcl)
+            assert _push(lib, h, pl, lcl, keys, ids) == 0
+        cap, n = 16, C.c_int(0)
+        key, count, rows = np.zeros(cap, np.int64), np.zeros(cap, np.int32), np.zeros((cap, 50, 7))
+        assert lib.mind_planner_export(h, cap, C.byref(n), key.ctypes.data, count.ctypes.data, rows.ctypes.data) == 0
+    finally:
+        lib.mind_planner_destroy(h)
+    rebuild_agent_obs(rebuilt, n.value, key, count, rows, lambda k: ("AV", "vehicle", TrackCategory.FOCAL_TRACK) if k == _lib.PLANNER_EGO_KEY else
+                      (ids[k], types[ids[k]], TrackCategory.TRACK_FRAGMENT))
+
+    def assert_same(where):
+        assert list(rebuilt.agent_obs) == list(pl.agent_obs) and len(pl.agent_obs) == 7, where
+        for tid, want in pl.agent_obs.items():
+            got = rebuilt.agent_obs[tid]
+            assert got.track_id == want.track_id == tid and got.object_type == want.object_type and got.category == want.category, (where, tid)
+            assert len(got.object_states) == len(want.object_states), (where, tid)
+            for a, b in zip(got.object_states, want.object_states):
+                assert (a.observed, a.timestep, tuple(a.position), a.heading, tuple(a.velocity)) == \
+                       (b.observed, b.timestep, tuple(b.position), b.heading, tuple(b.velocity)), (where, tid)
+                assert type(a.observed) is bool and type(a.timestep) is int, (where, tid)
+            assert got._arr.shape == want._arr.shape and np.array_equal(got._arr, want._arr), (where, tid)
+
+    assert_same("rebuilt")
+    assert max(len(t.object_states) for t in pl.agent_obs.values()) == 50
+    compacted = {id(p): set() for p in (pl, rebuilt)}
+    for f, frame in enumerate(_frames(170, seed=7)):
+        lcl = _lcl(frame, 75 + f)
+        for p in (pl, rebuilt):
+            before = {tid: t._i for tid, t in p.agent_obs.items()}
+            p.update_observation(lcl)
+            compacted[id(p)].update(tid for tid, i in before.items() if p.agent_obs[tid]._i <= i)
+        assert_same(75 + f)
+    # both planners' mirrors were compacted on the way (at 4 * obs_len appends, so at different frames for the two); "late2", 15 frames old
+    # at the export, does not get there in either
+    assert all(c == set(pl.agent_obs) - {"late2"} for c in compacted.values()), compacted
+
+
 def test_float32_states_are_the_callers_business():
     """a float32 recording: the caller's to_object_state evaluates numpy's float32 cosine; the library stores what it is given"""
     lib = _lib.load()
