@@ -83,6 +83,11 @@ int mind_predict_batch(mind_ctx *ctx, const mind_scene_batch *in, mind_pred_out 
 /* Per-kernel timing of the last mind_predict_batch measured with HIP events on the context stream:
  * returns the number of fusion pair-kernel launches and their summed milliseconds. */
 int mind_last_fusion_stats(mind_ctx *ctx, int *n_launches, float *total_ms, double *pairs_processed);
+/* The ActorNet of the last mind_predict_batch: layerwise = 1 when the layer-wise batched kernels ran (mind_set_tuning "actor_lw_min"), 0 for
+ * a per-actor kernel; its number of launches and of actor chunks (1 / 1 for a per-actor kernel); total_ms = the time from its first
+ * launch to its last on the context stream (HIP events; 0 unless profiling is on, and 0 for the predictor calls inside mind_aime_plan,
+ * which do not drain the stream per call).  Any output may be NULL. */
+int mind_last_actor_stats(mind_ctx *ctx, int *layerwise, int *n_launches, int *n_chunks, float *total_ms);
 /* Duration of the tree-iLQR kernel of the last mind_ilqr_* call on this context (HIP events on the context stream; 0 unless
  * profiling is on), its number of cost trees and the workgroups per tree it ran with. */
 int mind_last_ilqr_stats(mind_ctx *ctx, float *kernel_ms, int *n_trees, int *workgroups_per_tree);
@@ -137,7 +142,13 @@ int mind_set_pair_precision(mind_ctx *ctx, int mode);
  * the host staging / travel in the kernel arguments), "early_eval" (mind_loop prices a candidate tree as soon as the pending launch marks it
  * complete), "glue_fused" (mind_aime_plan's pruning decisions and branch-time bits from one launch, k_aime_select_branch); MIND_GLUE_FUSED, MIND_UPLOAD_KERNEL_MAX, MIND_ILQR_HOST_OUT_MAX, MIND_DEC_MIRROR, MIND_TAB_HOST_MAX, MIND_TAB_SMALL, MIND_EARLY_EVAL,
  * "actor_f32" (0: the fp32 VALU ActorNet instead of the fp32-MFMA one under the exact-fp32 setting), "actor_f32_min" / "actor_f32_pair_min" (actors per
- * call from which the fp32-MFMA ActorNet runs with two actors per workgroup, under every setting / under exact fp32; default never), "enc_mfma" (0: the fp32 VALU ActorNet / decoder kernels under every precision), "actor_split" (6: three-way operand split,
+ * call from which the fp32-MFMA ActorNet runs with two actors per workgroup, under every setting / under exact fp32; default never),
+ * "actor_lw_min" (actors per call from which the layer-wise batched ActorNet -- actor_lw_kernels.hip: one conv-as-GEMM launch and one GroupNorm
+ * launch per layer over chunks of actors, the layer's weight fragments stationary in LDS -- replaces k_actor_mfma<NP> under the bf16x6 / bf16x3 /
+ * bf16 settings; default 1 << 30 = never; bit-identical to k_actor_mfma<NP>, so calls, rounds and ranks may differ in which of the two they take;
+ * MIND_PAIR_F32, "enc_mfma" 0 and "actor_f32_min" keep their precedence; MIND_ACTOR_LW_MIN at context creation), "actor_lw_chunk" (its actors per
+ * chunk, 0 = the default of 1024; the scratch arena is one chunk, 137 472 bytes per actor; for tests and A/B runs only: same bits for every value),
+ * "enc_mfma" (0: the fp32 VALU ActorNet / decoder kernels under every precision), "actor_split" (6: three-way operand split,
  * fp32-class; 3: two-way), "xcd_order" (XCD-aware job order of the pair kernel), "tok_mfma" (1: the per-token epilogue / prologue of the fusion layers on the fp32 MFMA kernel k_token_mfma instead of the fp32 VALU one; off by default: measured slower), "tok_small_max" (batches of at most this many tokens run k_token with four tokens per workgroup instead of eight; same bits), "tgt_side" (0: the context stream waits for the target embedding before the fusion layers), "dec_overlap" (0: the decoder's actor part as one kernel behind
  * k_dec_scene instead of its actor_proj half beside it on the side stream; bit-identical).  Environment: MIND_DEC_MFMA_MIN, MIND_ENC_MFMA,
  * MIND_ACTOR_SPLIT, MIND_XCD_ORDER, MIND_ILQR_WGS, MIND_DEC_OVERLAP at context creation. */
@@ -155,6 +166,14 @@ int mind_debug_pack_bfrag(const float *w, int row_stride, uint32_t *out);
  * negative error.  Needs no GPU. */
 int mind_debug_pair_schedule(const int *scene_tokens, const int *scene_actors, int n_scenes, int n_cu, int last_layer, int *out_jobs, int cap,
                              int *out_info);
+
+/* host-only helper (tests): the launch list of the layer-wise batched ActorNet for a call of n_actors actors in the arithmetic np (6, 3, 1 =
+ * bf16x6, bf16x3, bf16; anything else: MIND_EINVAL) with `chunk` actors per chunk (0 = the default) -- exactly what mind_predict_batch issues.
+ * out_launches receives up to cap records of 16 long long in issue order: {stage 0..25 (-1: the input split), kind (0 input split, 1 conv,
+ * 2 GroupNorm epilogue), grid x, grid y, threads per workgroup, LDS bytes, first actor of the chunk, actors in the chunk, Cin, Cout, kernel
+ * size, stride, Tin, Tout, fragment bytes a conv workgroup keeps stationary, 1 for the stage that writes actor_feat}.  out_info[3] = {chunk
+ * size, arena bytes, number of launches}.  Returns the number of launches or a negative error.  Needs no GPU. */
+int mind_debug_actor_lw_plan(int n_actors, int np, int chunk, long long *out_launches, int cap, long long *out_info);
 
 /* host-only helper (tests): the bf16 hi / mid / lo MFMA A-operand packing of one Conv1d weight [co][ci][ksz] (torch layout) for the
  * ActorNet GEMMs of actor_mfma_kernels.hip: [co/16][k-step][part 3 = hi, mid, lo][lane 64][4] dwords, GEMM index k = tap * ci_pad + ci

@@ -23,6 +23,7 @@
 #include "pair_tile6_kernels.hip"
 #include "token_mfma_kernels.hip"
 #include "actor_mfma_kernels.hip"
+#include "actor_lw_kernels.hip"
 #include "actor_f32_kernels.hip"
 #include "dec_mfma_kernels.hip"
 #include "ilqr_kernels.hip"
@@ -158,6 +159,16 @@ struct mind_ctx {
   // last bits -- than the whole round (a workload that wants it sets 0, as with "dec_mfma_min")
   bool actor_f32 = true;
   int actor_f32_min = 1 << 30, actor_f32_pair_min = 1 << 30;
+  // layer-wise batched ActorNet (actor_lw_kernels.hip): actors per call from which it replaces k_actor_mfma<NP> ("actor_lw_min" /
+  // MIND_ACTOR_LW_MIN; default never; bit-identical, so ranks and rounds may differ in which one they take), actors per chunk
+  // ("actor_lw_chunk", 0 = LW_CHUNK; tests and A/B runs), its scratch arena (one chunk, allocated at first use)
+  int actor_lw_min = 1 << 30, actor_lw_chunk = 0;
+  DevBuf actor_lw_arena;
+  std::vector<LwLaunch> actor_lw_plan;
+  // the ActorNet of the last mind_predict_batch (mind_last_actor_stats)
+  int last_actor_lw = 0, last_actor_launches = 0, last_actor_chunks = 0;
+  float actor_ms = 0.f;
+  hipEvent_t ev_act0 = nullptr, ev_act1 = nullptr;
   bool xcd_order = true;        // XCD-aware job order for big batches (MIND_XCD_ORDER=0 switches it off, for A/B measurements)
   int pair_prec = 3;            // arithmetic of the pair kernel: 0 = fp32 MFMA, 1 = bf16x3 (two-way split operands), 2 = bf16, 3 = bf16x6 (exact three-way split: fp32 class, default)
   // bf16 arithmetics: k_pair_t (tile-native edge tensor, pair_tile_kernels.hip; default) or the row-major k_pair_bf of rounds 2-3
@@ -358,6 +369,8 @@ extern "C" int mind_ctx_create(int device, void *stream, mind_ctx **out) {
   if (const char *me = getenv("MIND_ENC_MFMA")) c->enc_mfma = !(me[0] == '0');
   if (const char *me = getenv("MIND_ACTOR_F32")) c->actor_f32 = !(me[0] == '0');
   if (const char *me = getenv("MIND_ACTOR_F32_MIN")) c->actor_f32_min = atoi(me);
+  if (const char *me = getenv("MIND_ACTOR_LW_MIN")) c->actor_lw_min = atoi(me);
+  lw_set_attributes();
   (void)hipFuncSetAttribute((const void *)k_actor_f32<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_actor_f32_lds_bytes(1));
   (void)hipFuncSetAttribute((const void *)k_actor_f32<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_actor_f32_lds_bytes(2));
   if (const char *de = getenv("MIND_DEC_MFMA_MIN")) c->dec_mfma_min = atoi(de);
@@ -438,6 +451,9 @@ extern "C" int mind_ctx_destroy(mind_ctx *c) {
   if (c->ev_tgt) (void)hipEventDestroy(c->ev_tgt);
   if (c->ev_stage) (void)hipEventDestroy(c->ev_stage);
   if (c->ev_cls) (void)hipEventDestroy(c->ev_cls);
+  if (c->actor_lw_arena.p) (void)hipFree(c->actor_lw_arena.p);
+  if (c->ev_act0) (void)hipEventDestroy(c->ev_act0);
+  if (c->ev_act1) (void)hipEventDestroy(c->ev_act1);
   if (c->ev_il0) (void)hipEventDestroy(c->ev_il0);
   if (c->ev_il1) (void)hipEventDestroy(c->ev_il1);
   if (c->side) { (void)hipStreamSynchronize(c->side); (void)hipStreamDestroy(c->side); }
@@ -462,6 +478,8 @@ extern "C" int mind_set_tuning(mind_ctx *c, const char *name, int value) {
   else if (n == "actor_f32") c->actor_f32 = value != 0;
   else if (n == "actor_f32_min") c->actor_f32_min = value;
   else if (n == "actor_f32_pair_min") c->actor_f32_pair_min = value;
+  else if (n == "actor_lw_min") c->actor_lw_min = value;
+  else if (n == "actor_lw_chunk") c->actor_lw_chunk = value < 0 ? 0 : value;
   else if (n == "actor_split") c->actor_np = value == 3 ? 3 : 6;
   else if (n == "xcd_order") c->xcd_order = value != 0;
   else if (n == "pair_tile") c->pair_tile = value != 0;
@@ -622,6 +640,40 @@ extern "C" int mind_last_fusion_stats(mind_ctx *c, int *n_launches, float *total
   if (total_ms) *total_ms = c->pair_ms;
   if (pairs) *pairs = c->pairs_done;
   return MIND_OK;
+}
+
+extern "C" int mind_last_actor_stats(mind_ctx *c, int *layerwise, int *n_launches, int *n_chunks, float *total_ms) {
+  if (!c) return MIND_EINVAL;
+  if (layerwise) *layerwise = c->last_actor_lw;
+  if (n_launches) *n_launches = c->last_actor_launches;
+  if (n_chunks) *n_chunks = c->last_actor_chunks;
+  if (total_ms) *total_ms = c->actor_ms;
+  return MIND_OK;
+}
+
+// the layer-wise ActorNet's launch list as mind_predict_batch issues it (lw_build_plan, actor_lw_kernels.hip), for a host-side check
+extern "C" int mind_debug_actor_lw_plan(int n_actors, int np, int chunk, long long *out_launches, int cap, long long *out_info) {
+  if (n_actors <= 0 || chunk < 0 || (np != 1 && np != 3 && np != 6) || (cap > 0 && !out_launches) || cap < 0) return MIND_EINVAL;
+  if (chunk == 0) chunk = LW_CHUNK;
+  std::vector<LwLaunch> plan;
+  lw_build_plan(n_actors, chunk, plan);
+  LwStage S[LW_NSTAGE];
+  lw_stages(S);
+  const int nparts = np == 6 ? 3 : (np == 3 ? 2 : 1);
+  for (size_t i = 0; i < plan.size() && (int)i < cap; ++i) {
+    const LwLaunch &L = plan[i];
+    long long *o = out_launches + 16 * i;
+    o[0] = L.stage; o[1] = L.kind; o[2] = L.gx; o[3] = L.gy; o[4] = L.block; o[5] = L.lds; o[6] = L.a0; o[7] = L.n;
+    for (int k = 8; k < 16; ++k) o[k] = 0;
+    if (L.stage >= 0) {
+      const LwStage &st = S[L.stage];
+      o[8] = st.cin; o[9] = st.cout; o[10] = st.ksz; o[11] = st.stride; o[12] = st.tin; o[13] = st.tout;
+      // fragment bytes the conv workgroup keeps stationary (the parts the arithmetic reads), and whether the stage ends in the output row
+      o[14] = L.kind == 1 ? (long long)L.lds / 3 * nparts : 0; o[15] = st.final;
+    }
+  }
+  if (out_info) { out_info[0] = chunk; out_info[1] = (long long)lw_arena_bytes(chunk); out_info[2] = (long long)plan.size(); }
+  return (int)plan.size();
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -1405,18 +1457,47 @@ extern "C" int mind_predict_batch(mind_ctx *c, const mind_scene_batch *in, mind_
   // ... and the fp32-MFMA kernel (plain fp32 operands on the matrix core: the reference's arithmetic class): the ActorNet of the exact-fp32
   // setting, and -- two actors per workgroup -- of every setting on full-tree rounds (thousands of actors per call)
   const bool f32_pair = c->actor_f32 && A >= (c->pair_prec == 0 ? c->actor_f32_pair_min : c->actor_f32_min);
+  const bool act_timed = c->profiling && !c->ev_defer;      // (inside a plan nothing drains the stream per call: no ActorNet time there)
+  if (act_timed && !c->ev_act0) {
+    HIPCHK(c, hipEventCreate(&c->ev_act0));
+    HIPCHK(c, hipEventCreate(&c->ev_act1));
+  }
+  c->last_actor_lw = 0; c->last_actor_launches = 1; c->last_actor_chunks = 1; c->actor_ms = 0.f;
+  if (act_timed) HIPCHK(c, hipEventRecord(c->ev_act0, st));
   if (f32_pair)
     hipLaunchKernelGGL(k_actor_f32<2>, dim3((A + 1) / 2), dim3(AF_T), mind_actor_f32_lds_bytes(2), st, in->actors, A, actor_feat, c->actorFW);
   else if (c->pair_prec == 0 && c->actor_f32 && c->enc_mfma)
     hipLaunchKernelGGL(k_actor_f32<1>, dim3(A), dim3(AF_T), mind_actor_f32_lds_bytes(1), st, in->actors, A, actor_feat, c->actorFW);
   else if (c->pair_prec == 0 || !c->enc_mfma)
     hipLaunchKernelGGL(k_actor_net, dim3(A), dim3(AT), mind_actor_lds_bytes(), st, in->actors, A, actor_feat, c->actorW);
+  else if (A >= c->actor_lw_min) {
+    // rounds of thousands of actors: the same arithmetic layer by layer over chunks of actors, the weight fragments stationary
+    // (actor_lw_kernels.hip; bit-identical to k_actor_mfma<NP>)
+    const int chunk = c->actor_lw_chunk > 0 ? c->actor_lw_chunk : LW_CHUNK;
+    const size_t need = lw_arena_bytes(chunk);
+    if (c->actor_lw_arena.cap < need) {
+      HIPCHK(c, hipStreamSynchronize(st));
+      if (c->actor_lw_arena.p) (void)hipFree(c->actor_lw_arena.p);
+      c->actor_lw_arena.p = nullptr; c->actor_lw_arena.cap = 0;
+      if (hipMalloc(&c->actor_lw_arena.p, need) != hipSuccess) return fail(c, MIND_ENOMEM, "hipMalloc(%zu) for the layer-wise ActorNet's arena failed", need);
+      c->actor_lw_arena.cap = need;
+    }
+    lw_build_plan(A, chunk, c->actor_lw_plan);
+    const int np = (c->pair_prec == 3 || (c->pair_prec == 1 && c->actor_np == 6)) ? 6 : (c->pair_prec == 1 ? 3 : 1);
+    u32 *arena = (u32 *)c->actor_lw_arena.p;
+    const int nl = np == 6 ? lw_run<6>(c->actor_lw_plan, st, arena, in->actors, actor_feat, c->actorBW)
+                 : np == 3 ? lw_run<3>(c->actor_lw_plan, st, arena, in->actors, actor_feat, c->actorBW)
+                           : lw_run<1>(c->actor_lw_plan, st, arena, in->actors, actor_feat, c->actorBW);
+    if (nl < 0) return fail(c, MIND_ESTATE, "layer-wise ActorNet: a stage has no kernel");
+    c->last_actor_lw = 1; c->last_actor_launches = nl; c->last_actor_chunks = (A + chunk - 1) / chunk;
+  }
   else if (c->pair_prec == 3 || (c->pair_prec == 1 && c->actor_np == 6))
     hipLaunchKernelGGL(k_actor_mfma<6>, dim3(A), dim3(AM_T), mind_actor_mfma_lds_bytes(), st, in->actors, A, actor_feat, c->actorBW);
   else if (c->pair_prec == 1)
     hipLaunchKernelGGL(k_actor_mfma<3>, dim3(A), dim3(AM_T), mind_actor_mfma_lds_bytes(), st, in->actors, A, actor_feat, c->actorBW);
   else
     hipLaunchKernelGGL(k_actor_mfma<1>, dim3(A), dim3(AM_T), mind_actor_mfma_lds_bytes(), st, in->actors, A, actor_feat, c->actorBW);
+  if (act_timed) HIPCHK(c, hipEventRecord(c->ev_act1, st));
   if (!lane_feat) {
     float *lf = out->lane_feat ? out->lane_feat : (float *)c->lane_feat.p;
     if (Ltot > 0)
@@ -1640,6 +1721,7 @@ extern "C" int mind_predict_batch(mind_ctx *c, const mind_scene_batch *in, mind_
       HIPCHK(c, hipEventElapsedTime(&ms, c->ev[2 * L], c->ev[2 * L + 1]));
       c->pair_ms += ms;
     }
+    if (c->ev_act0) HIPCHK(c, hipEventElapsedTime(&c->actor_ms, c->ev_act0, c->ev_act1));
   }
   return MIND_OK;
 }

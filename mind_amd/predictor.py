@@ -255,6 +255,13 @@ class HipPredictor:
         self.lib.mind_last_fusion_stats(self.ctx, C.byref(n), C.byref(ms), C.byref(pairs))
         return n.value, ms.value, pairs.value
 
+    def last_actor_stats(self):
+        """ActorNet of the last predictor call (mind_last_actor_stats): dict(layerwise = 1 when the layer-wise batched kernels ran, launches,
+        chunks, ms = first launch to last on the context stream, 0 unless profiling)"""
+        lw, n, ch, ms = C.c_int(), C.c_int(), C.c_int(), C.c_float()
+        _lib.check(self.lib, self.ctx, self.lib.mind_last_actor_stats(self.ctx, C.byref(lw), C.byref(n), C.byref(ch), C.byref(ms)), "mind_last_actor_stats")
+        return dict(layerwise=lw.value, launches=n.value, chunks=ch.value, ms=ms.value)
+
     def debug_set_layers(self, n):
         _lib.check(self.lib, self.ctx, self.lib.mind_debug_set_layers(self.ctx, n), "mind_debug_set_layers")
 
