@@ -88,6 +88,14 @@ int mind_last_fusion_stats(mind_ctx *ctx, int *n_launches, float *total_ms, doub
  * launch to its last on the context stream (HIP events; 0 unless profiling is on, and 0 for the predictor calls inside mind_aime_plan,
  * which do not drain the stream per call).  Any output may be NULL. */
 int mind_last_actor_stats(mind_ctx *ctx, int *layerwise, int *n_launches, int *n_chunks, float *total_ms);
+/* The token stage (init + the epilogue / prologue behind each fusion layer) of the last mind_predict_batch: layerwise = 1 when a run of
+ * scenes took the layer-wise kernels (mind_set_tuning "tok_lw_min_n" / "tok_lw_min"), the launches of all its token steps, the token chunks
+ * the layer-wise runs were cut into (0 when none ran), total_ms = the summed time of those launches (HIP events around every one; 0 unless
+ * profiling is on, and 0 for the predictor calls inside mind_aime_plan).  Any output may be NULL. */
+int mind_last_token_stats(mind_ctx *ctx, int *layerwise, int *n_launches, int *n_chunks, float *total_ms);
+/* ... and that time by kernel: out_ms[0..6] = the layer-wise stages (init, merge + V, out-projection + LN2, FFN 1, FFN 2 + LN3, S / T / q,
+ * folded K query), out_ms[7] = the one-kernel forms (k_token, k_token_m, k_token_mfma).  Writes min(cap, 8) floats, returns 8. */
+int mind_last_token_stage_ms(mind_ctx *ctx, float *out_ms, int cap);
 /* Duration of the tree-iLQR kernel of the last mind_ilqr_* call on this context (HIP events on the context stream; 0 unless
  * profiling is on), its number of cost trees and the workgroups per tree it ran with. */
 int mind_last_ilqr_stats(mind_ctx *ctx, float *kernel_ms, int *n_trees, int *workgroups_per_tree);
@@ -148,6 +156,12 @@ int mind_set_pair_precision(mind_ctx *ctx, int mode);
  * bf16 settings; default 1 << 30 = never; bit-identical to k_actor_mfma<NP>, so calls, rounds and ranks may differ in which of the two they take;
  * MIND_PAIR_F32, "enc_mfma" 0 and "actor_f32_min" keep their precedence; MIND_ACTOR_LW_MIN at context creation), "actor_lw_chunk" (its actors per
  * chunk, 0 = the default of 1024; the scratch arena is one chunk, 137 472 bytes per actor; for tests and A/B runs only: same bits for every value),
+ * "tok_lw_min_n" (a SCENE of at least this many tokens takes the fp32-MFMA token class -- the bits of k_token_mfma<0> -- whatever its batch, round or
+ * rank; "tok_mfma" 1 still puts every scene there and "tok_bf_min_n" keeps its precedence under bf16x3 / bf16; default 1 << 30 = never;
+ * MIND_TOK_LW_MIN_N), "tok_lw_min" (a run of consecutive scenes of that class with at least this many tokens runs the layer-wise token kernels --
+ * token_lw_kernels.hip: one launch per stage over chunks of tokens, the stage's weight fragments stationary in registers -- instead of
+ * k_token_mfma<0>; bit-identical to it, so calls, rounds and ranks may differ; default 1 << 30 = never; MIND_TOK_LW_MIN), "tok_lw_chunk" (its tokens
+ * per chunk, 0 = the default of 32 768; the scratch arena is one chunk, 2 560 bytes per token; same bits for every value),
  * "enc_mfma" (0: the fp32 VALU ActorNet / decoder kernels under every precision), "actor_split" (6: three-way operand split,
  * fp32-class; 3: two-way), "xcd_order" (XCD-aware job order of the pair kernel), "tok_mfma" (1: the per-token epilogue / prologue of the fusion layers on the fp32 MFMA kernel k_token_mfma instead of the fp32 VALU one; off by default: measured slower), "tok_small_max" (batches of at most this many tokens run k_token with four tokens per workgroup instead of eight; same bits), "tgt_side" (0: the context stream waits for the target embedding before the fusion layers), "dec_overlap" (0: the decoder's actor part as one kernel behind
  * k_dec_scene instead of its actor_proj half beside it on the side stream; bit-identical).  Environment: MIND_DEC_MFMA_MIN, MIND_ENC_MFMA,
@@ -174,6 +188,14 @@ int mind_debug_pair_schedule(const int *scene_tokens, const int *scene_actors, i
  * size, stride, Tin, Tout, fragment bytes a conv workgroup keeps stationary, 1 for the stage that writes actor_feat}.  out_info[3] = {chunk
  * size, arena bytes, number of launches}.  Returns the number of launches or a negative error.  Needs no GPU. */
 int mind_debug_actor_lw_plan(int n_actors, int np, int chunk, long long *out_launches, int cap, long long *out_info);
+
+/* host-only helper (tests): the launch list of the layer-wise token stage for one token step of `mode` (1|4 init, 2|4 behind fusion layers
+ * 0-4, 2|8 behind the last; | 16 or | 16|32 for the bf16 / bf16x6 QK formats; anything else: MIND_EINVAL) over a run of n_tokens tokens with
+ * `chunk` tokens per chunk (0 = the default), grids sized for 256 compute units.  out_launches receives up to cap records of 8 long long in
+ * issue order: {stage (0 init, 1 merge + V, 2 out-projection + LN2, 3 FFN 1, 4 FFN 2 + LN3, 5 S / T / q, 6 folded K query), grid x, grid y,
+ * threads per workgroup, LDS bytes, first token of the chunk, tokens in the chunk, 16-token tiles in the chunk}.  out_info[4] = {chunk size,
+ * arena bytes, number of launches, number of chunks}.  Returns the number of launches or a negative error.  Needs no GPU. */
+int mind_debug_token_lw_plan(int n_tokens, int mode, int chunk, long long *out_launches, int cap, long long *out_info);
 
 /* host-only helper (tests): the bf16 hi / mid / lo MFMA A-operand packing of one Conv1d weight [co][ci][ksz] (torch layout) for the
  * ActorNet GEMMs of actor_mfma_kernels.hip: [co/16][k-step][part 3 = hi, mid, lo][lane 64][4] dwords, GEMM index k = tap * ci_pad + ci

@@ -24,6 +24,7 @@
 #include "token_mfma_kernels.hip"
 #include "actor_mfma_kernels.hip"
 #include "actor_lw_kernels.hip"
+#include "token_lw_kernels.hip"
 #include "actor_f32_kernels.hip"
 #include "dec_mfma_kernels.hip"
 #include "ilqr_kernels.hip"
@@ -97,6 +98,20 @@ struct mind_ctx {
   // 0.80 ms for the largest, the same as the VALU kernel (which is LDS-bound there) -- with 97 KB of LDS the MFMA kernel keeps one
   // four-wave workgroup per CU and waits on its partial-sum and fragment loads instead (profiles/r03bb); opt-in until it is faster
   int tok_bf_min_n = 0;
+  // layer-wise token stage (token_lw_kernels.hip; the bits of k_token_mfma<0>).  "tok_lw_min_n" / MIND_TOK_LW_MIN_N: a SCENE of at least this
+  // many tokens takes the fp32-MFMA token class (by the scene's own N: its result does not depend on its batch, round or rank); "tok_lw_min" /
+  // MIND_TOK_LW_MIN: a run of consecutive scenes of that class with at least this many tokens runs layer-wise, a shorter one k_token_mfma<0>
+  // (the same bits, so this rule may look at the batch).  Both default to never.  "tok_lw_chunk": tokens per chunk (0 = TL_CHUNK); the arena
+  // holds one chunk and is allocated at first use
+  int tok_lw_min_n = 1 << 30, tok_lw_min = 1 << 30, tok_lw_chunk = 0;
+  DevBuf tok_lw_arena;
+  std::vector<TlLaunch> tok_lw_plan;
+  // the token stage of the last mind_predict_batch (mind_last_token_stats): launches of all seven token steps, time per layer-wise stage
+  // ([TL_NSTAGE]: the one-kernel forms) from HIP events around every launch with profiling on
+  int last_tok_lw = 0, last_tok_launches = 0, last_tok_chunks = 0;
+  float tok_ms = 0.f, tok_stage_ms[TL_NSTAGE + 1] = {};
+  std::vector<hipEvent_t> ev_tok;
+  std::vector<int> ev_tok_tag;
   bool tok_merge = true;        // small token launches merge their independent projections (k_token_m; MIND_TOK_MERGE=0 / "tok_merge": the plain kernel)
   int tok_small_max = 2048;     // batches of at most this many tokens run k_token with 4 tokens per workgroup ("tok_small_max")
   const float *WAe[6], *WAp[6], *vtab[6], *rtab = nullptr;
@@ -385,6 +400,8 @@ extern "C" int mind_ctx_create(int device, void *stream, mind_ctx **out) {
   if (const char *te = getenv("MIND_DEC_MW")) c->dec_mw = !(te[0] == '0');
   if (const char *te = getenv("MIND_DEC_CLS_SIDE")) c->dec_cls_side = !(te[0] == '0');
   if (const char *te = getenv("MIND_TOK_BF_MIN_N")) c->tok_bf_min_n = atoi(te);
+  if (const char *te = getenv("MIND_TOK_LW_MIN_N")) c->tok_lw_min_n = atoi(te);
+  if (const char *te = getenv("MIND_TOK_LW_MIN")) c->tok_lw_min = atoi(te);
   if (const char *te = getenv("MIND_TGT_SIDE")) c->tgt_side = !(te[0] == '0');
   if (const char *te = getenv("MIND_PL_TAB_SIDE")) c->pl_tab_side = !(te[0] == '0');
   (void)hipFuncSetAttribute((const void *)k_token_mfma<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_token_mfma_lds_bytes());
@@ -452,6 +469,8 @@ extern "C" int mind_ctx_destroy(mind_ctx *c) {
   if (c->ev_stage) (void)hipEventDestroy(c->ev_stage);
   if (c->ev_cls) (void)hipEventDestroy(c->ev_cls);
   if (c->actor_lw_arena.p) (void)hipFree(c->actor_lw_arena.p);
+  if (c->tok_lw_arena.p) (void)hipFree(c->tok_lw_arena.p);
+  for (hipEvent_t e : c->ev_tok) (void)hipEventDestroy(e);
   if (c->ev_act0) (void)hipEventDestroy(c->ev_act0);
   if (c->ev_act1) (void)hipEventDestroy(c->ev_act1);
   if (c->ev_il0) (void)hipEventDestroy(c->ev_il0);
@@ -491,6 +510,9 @@ extern "C" int mind_set_tuning(mind_ctx *c, const char *name, int value) {
   else if (n == "dec_mw") c->dec_mw = value != 0;
   else if (n == "dec_cls_side") c->dec_cls_side = value != 0;
   else if (n == "tok_bf_min_n") c->tok_bf_min_n = (int)value;
+  else if (n == "tok_lw_min_n") c->tok_lw_min_n = value;
+  else if (n == "tok_lw_min") c->tok_lw_min = value;
+  else if (n == "tok_lw_chunk") c->tok_lw_chunk = value < 0 ? 0 : value;
   else if (n == "tgt_side") c->tgt_side = value != 0;
   else if (n == "pl_tab_side") c->pl_tab_side = value != 0;
   else if (n == "ilqr_chunk") c->ilqr_chunk = value < 0 ? 0 : (int)value;
@@ -649,6 +671,39 @@ extern "C" int mind_last_actor_stats(mind_ctx *c, int *layerwise, int *n_launche
   if (n_chunks) *n_chunks = c->last_actor_chunks;
   if (total_ms) *total_ms = c->actor_ms;
   return MIND_OK;
+}
+
+extern "C" int mind_last_token_stats(mind_ctx *c, int *layerwise, int *n_launches, int *n_chunks, float *total_ms) {
+  if (!c) return MIND_EINVAL;
+  if (layerwise) *layerwise = c->last_tok_lw;
+  if (n_launches) *n_launches = c->last_tok_launches;
+  if (n_chunks) *n_chunks = c->last_tok_chunks;
+  if (total_ms) *total_ms = c->tok_ms;
+  return MIND_OK;
+}
+
+extern "C" int mind_last_token_stage_ms(mind_ctx *c, float *out_ms, int cap) {
+  if (!c || cap < 0 || (cap > 0 && !out_ms)) return MIND_EINVAL;
+  for (int i = 0; i < cap && i <= TL_NSTAGE; ++i) out_ms[i] = c->tok_stage_ms[i];
+  return TL_NSTAGE + 1;
+}
+
+// the layer-wise token stage's launch list for one token launch of `mode` over a run of n_tokens tokens (tl_build_plan, token_lw_kernels.hip)
+extern "C" int mind_debug_token_lw_plan(int n_tokens, int mode, int chunk, long long *out_launches, int cap, long long *out_info) {
+  if (n_tokens <= 0 || chunk < 0 || !tl_mode_ok(mode) || (cap > 0 && !out_launches) || cap < 0) return MIND_EINVAL;
+  if (chunk == 0) chunk = TL_CHUNK;
+  std::vector<TlLaunch> plan;
+  tl_build_plan(n_tokens, mode, chunk, TL_NCU_PLAN, plan);
+  for (size_t i = 0; i < plan.size() && (int)i < cap; ++i) {
+    const TlLaunch &L = plan[i];
+    long long *o = out_launches + 8 * i;
+    o[0] = L.stage; o[1] = L.gx; o[2] = L.gy; o[3] = L.block; o[4] = L.lds; o[5] = L.t0; o[6] = L.n; o[7] = (L.n + TM_TOK - 1) / TM_TOK;
+  }
+  if (out_info) {
+    out_info[0] = chunk; out_info[1] = (long long)tl_arena_bytes(chunk); out_info[2] = (long long)plan.size();
+    out_info[3] = (n_tokens + chunk - 1) / chunk;
+  }
+  return (int)plan.size();
 }
 
 // the layer-wise ActorNet's launch list as mind_predict_batch issues it (lw_build_plan, actor_lw_kernels.hip), for a host-side check
@@ -1526,6 +1581,8 @@ extern "C" int mind_predict_batch(mind_ctx *c, const mind_scene_batch *in, mind_
   // launches take four tokens per workgroup (more workgroups, half the LDS operand traffic each; bit-identical to eight)
   const int qsplit = c->pair_prec == 3 ? 48 : c->pair_prec != 0 ? 16 : 0;      // the bf16 pair kernels read the folded query as hi / lo (bf16x6: hi / mid / lo) fragments
   const size_t tokm_lds = mind_token_mfma_lds_bytes();
+  // ... and scenes of at least tok_lw_min_n tokens the fp32-MFMA class (kind 1; tok_bf_min_n keeps its precedence under bf16x3 / bf16): a run
+  // of them with at least tok_lw_min tokens runs layer-wise (token_lw_kernels.hip), a shorter run k_token_mfma<0> -- the same bits
   struct TokRun { int t0, n, kind; };                  // kind 0: VALU, 1: fp32 MFMA (opt-in), 2: bf16 split MFMA
   std::vector<TokRun> tok_runs;
   {
@@ -1533,16 +1590,60 @@ extern "C" int mind_predict_batch(mind_ctx *c, const mind_scene_batch *in, mind_
     for (int b = 0; b < Bn; ++b) {
       const int N = (in->actor_off[b + 1] - in->actor_off[b]) + (in->lane_off[b + 1] - in->lane_off[b]) + 1;
       // (the two-way-split token kernel is not an fp32-class arithmetic: never under bf16x6)
-      const int kind = c->tok_mfma ? 1 : (c->pair_prec != 0 && c->pair_prec != 3 && c->tok_bf_min_n > 0 && N >= c->tok_bf_min_n) ? 2 : 0;
+      const int kind = c->tok_mfma ? 1 : (c->pair_prec != 0 && c->pair_prec != 3 && c->tok_bf_min_n > 0 && N >= c->tok_bf_min_n) ? 2
+                       : N >= c->tok_lw_min_n ? 1 : 0;
       if (!tok_runs.empty() && tok_runs.back().kind == kind) tok_runs.back().n += N;
       else tok_runs.push_back({t0, N, kind});
       t0 += N;
     }
   }
-  auto launch_tokens = [&](int mode, int Lw) {
+  const int tl_chunk = c->tok_lw_chunk > 0 ? c->tok_lw_chunk : TL_CHUNK;
+  c->last_tok_lw = 0; c->last_tok_launches = 0; c->last_tok_chunks = 0; c->tok_ms = 0.f;
+  for (float &v : c->tok_stage_ms) v = 0.f;
+  for (const TokRun &r : tok_runs)
+    if (r.kind == 1 && r.n >= c->tok_lw_min) {
+      c->last_tok_lw = 1;
+      c->last_tok_chunks += (r.n + tl_chunk - 1) / tl_chunk;
+    }
+  if (c->last_tok_lw && c->tok_lw_arena.cap < tl_arena_bytes(tl_chunk)) {
+    const size_t need = tl_arena_bytes(tl_chunk);
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (c->tok_lw_arena.p) (void)hipFree(c->tok_lw_arena.p);
+    c->tok_lw_arena.p = nullptr; c->tok_lw_arena.cap = 0;
+    if (hipMalloc(&c->tok_lw_arena.p, need) != hipSuccess) return fail(c, MIND_ENOMEM, "hipMalloc(%zu) for the layer-wise token stage's arena failed", need);
+    c->tok_lw_arena.cap = need;
+  }
+  // (HIP events around every token launch with profiling on, outside a plan: mind_last_token_stats / mind_last_token_stage_ms)
+  const bool tok_timed = c->profiling && !c->ev_defer;
+  size_t ev_tok_used = 0;
+  auto tok_mark = [&](int tag) -> hipError_t {
+    if (!tok_timed) return hipSuccess;
+    if (ev_tok_used == c->ev_tok.size()) {
+      hipEvent_t e;
+      const hipError_t rc_ = hipEventCreate(&e);
+      if (rc_ != hipSuccess) return rc_;
+      c->ev_tok.push_back(e);
+      c->ev_tok_tag.push_back(0);
+    }
+    c->ev_tok_tag[ev_tok_used] = tag;
+    return hipEventRecord(c->ev_tok[ev_tok_used++], st);
+  };
+  auto launch_tokens = [&](int mode, int Lw) -> int {
+    HIPCHK(c, tok_mark(-1));
     for (const TokRun &r : tok_runs) {
       const TokMeta *m_ = dmeta + r.t0;
       float *x_ = x + (size_t)r.t0 * 128, *ST_ = ST + (size_t)r.t0 * 256, *QK_ = QK + (size_t)r.t0 * qk_stride;
+      if (r.kind == 1 && r.n >= c->tok_lw_min) {
+        tl_build_plan(r.n, mode, tl_chunk, c->n_cu, c->tok_lw_plan);
+        for (const TlLaunch &L : c->tok_lw_plan) {
+          if (tl_launch(L, st, mode, m_, actor_feat, lane_feat, x_, part, ST_, QK_, qk_stride, c->tokW[Lw], c->tokWM[Lw], (float *)c->tok_lw_arena.p, tl_chunk))
+            return fail(c, MIND_ESTATE, "layer-wise token stage: a stage has no kernel");
+          HIPCHK(c, tok_mark(L.stage));
+        }
+        c->last_tok_launches += (int)c->tok_lw_plan.size();
+        continue;
+      }
+      c->last_tok_launches++;
       if (r.kind == 0) {
         const bool small = r.n <= c->tok_small_max;
         const int tpw = small ? TOK_TPW_SMALL : TOK_TPW_BIG;
@@ -1556,9 +1657,11 @@ extern "C" int mind_predict_batch(mind_ctx *c, const mind_scene_batch *in, mind_
         hipLaunchKernelGGL(k_token_mfma<1>, dim3((r.n + TM_TOK - 1) / TM_TOK), dim3(TM_THREADS), tokm_lds, st, m_, r.n, mode, actor_feat, lane_feat, x_,
                            part, ST_, QK_, c->tokW[Lw], c->tokWB[Lw]);
       }
+      HIPCHK(c, tok_mark(TL_NSTAGE));
     }
+    return MIND_OK;
   };
-  launch_tokens(1 | 4 | qsplit, 0);
+  if ((rc = launch_tokens(1 | 4 | qsplit, 0))) return rc;
   int grid = njobs < c->n_cu ? njobs : c->n_cu;      // jobs are dealt wave-major over the workgroups
   const size_t lds = mind_pair_lds_bytes();
   c->n_pair_launch = 0;
@@ -1627,7 +1730,7 @@ extern "C" int mind_predict_batch(mind_ctx *c, const mind_scene_batch *in, mind_
     c->n_pair_launch++;
     c->pairs_done += (L == 5) ? pairs_l5 : pairs_full;
     const int mode = 2 | (L < 5 ? 4 : 8) | qsplit;
-    launch_tokens(mode, L + 1);
+    if ((rc = launch_tokens(mode, L + 1))) return rc;
   }
   // ---- decoder
   const int *d_actor_row = (const int *)ts->rows.p;
@@ -1722,6 +1825,13 @@ extern "C" int mind_predict_batch(mind_ctx *c, const mind_scene_batch *in, mind_
       c->pair_ms += ms;
     }
     if (c->ev_act0) HIPCHK(c, hipEventElapsedTime(&c->actor_ms, c->ev_act0, c->ev_act1));
+    for (size_t i = 1; i < ev_tok_used; ++i) {
+      if (c->ev_tok_tag[i] < 0) continue;
+      float ms = 0.f;
+      HIPCHK(c, hipEventElapsedTime(&ms, c->ev_tok[i - 1], c->ev_tok[i]));
+      c->tok_stage_ms[c->ev_tok_tag[i]] += ms;
+      c->tok_ms += ms;
+    }
   }
   return MIND_OK;
 }

@@ -262,6 +262,16 @@ class HipPredictor:
         _lib.check(self.lib, self.ctx, self.lib.mind_last_actor_stats(self.ctx, C.byref(lw), C.byref(n), C.byref(ch), C.byref(ms)), "mind_last_actor_stats")
         return dict(layerwise=lw.value, launches=n.value, chunks=ch.value, ms=ms.value)
 
+    def last_token_stats(self):
+        """Token stage of the last predictor call (mind_last_token_stats): dict(layerwise = 1 when a run took the layer-wise kernels, launches of
+        all token steps, chunks of the layer-wise runs, ms = summed launch times, stage_ms = by kernel (mind_last_token_stage_ms); 0 unless
+        profiling)"""
+        lw, n, ch, ms = C.c_int(), C.c_int(), C.c_int(), C.c_float()
+        _lib.check(self.lib, self.ctx, self.lib.mind_last_token_stats(self.ctx, C.byref(lw), C.byref(n), C.byref(ch), C.byref(ms)), "mind_last_token_stats")
+        st = (C.c_float * 8)()
+        self.lib.mind_last_token_stage_ms(self.ctx, st, 8)
+        return dict(layerwise=lw.value, launches=n.value, chunks=ch.value, ms=ms.value, stage_ms=[float(v) for v in st])
+
     def debug_set_layers(self, n):
         _lib.check(self.lib, self.ctx, self.lib.mind_debug_set_layers(self.ctx, n), "mind_debug_set_layers")
 
