@@ -173,13 +173,35 @@ int mind_get_pair_precision(mind_ctx *ctx);   /* -> mode, or MIND_EINVAL */
 int mind_debug_pack_bfrag(const float *w, int row_stride, uint32_t *out);
 
 /* host-only helper (tests): the pair kernels' job schedule (mind_amd/csrc/pair_jobs.h) for a batch of n_scenes scenes of scene_tokens[b]
- * tokens on a device of n_cu compute units -- exactly what mind_predict_batch builds.  last_layer != 0: the list of the last fusion layer
+ * tokens on a device of n_cu compute units -- mind_predict_batch's own builder, with "xcd_order" on.  last_layer != 0: the list of the last fusion layer
  * (actor + cls columns only; scene_actors[b] actors per scene).  out_jobs receives up to cap records of six ints
  * {scene, column, first tile, one past the last tile, partial slot, wave slot = wave * grid + workgroup} in list order without the empty
  * padding jobs; out_info[4] = {jobs per column of scene 0, grid, list length with padding, number of jobs}.  Returns the number of jobs or a
  * negative error.  Needs no GPU. */
 int mind_debug_pair_schedule(const int *scene_tokens, const int *scene_actors, int n_scenes, int n_cu, int last_layer, int *out_jobs, int cap,
                              int *out_info);
+
+/* host-only helper (tests): which kernels a mind_predict_batch call runs -- the record of pred_choose (mind_amd/csrc/pred_choice.h), the
+ * function the call itself decides with -- for a fresh context's knobs with the n_knobs (name, value) pairs of mind_set_tuning applied, the
+ * arithmetic pair_prec (0..3), a device of n_cu compute units, with or without the internal side stream, and n_scenes scenes of
+ * scene_actors[b] actors and scene_lanes[b] lanes.  out receives up to cap long long of the record: a header
+ *   [0] header length (32)  [1] token runs  [2] parts np of the MFMA contractions outside the pair kernel (6, 3, 1)
+ *   [3] ActorNet form (0 k_actor_net, 1 k_actor_f32, 2 k_actor_mfma, 3 layer-wise)  [4] its template argument (actors per workgroup of
+ *   k_actor_f32, np of the MFMA forms, 0)  [5] workgroups of a per-actor form's launch  [6] actors per chunk, [7] chunks, [8] launches (1 / 1
+ *   for a per-actor form: mind_last_actor_stats)
+ *   [9] QK format bits of the token kernels' mode (0, 16, 48)  [10] dwords of folded query per token  [11] edge tensor tile-native
+ *   [12] ... and bf16  [13] its bytes per token pair  [14] tokens per chunk of a layer-wise token run  [15] some run is layer-wise
+ *   [16] chunks of all layer-wise runs (mind_last_token_stats)
+ *   [17] pair-kernel family (0 k_pair, 1 k_pair_bf, 2 k_pair_t, 3 k_pair_t6)  [18] parts of k_pair_bf / k_pair_t (3, 1; else 0)
+ *   [19] the last fusion layer walks its own list of consumed columns  [20] XCD grouping factor of the full job list, [21] of that list
+ *   [22] decoder actor part (0 k_dec_actor<0>, 1 k_dec_actor<1> + <2> over two streams, 2 k_dec_actor_mfma)  [23] np of the MFMA form, else 0
+ *   [24] fp32 decoder  [25] split over two streams  [26] k_dec_scene_mw wanted  [27] its workgroups  [28] k_dec_scene_c + k_dec_cls
+ *   [29] the context stream waits for the target embedding before the fusion layers  [30], [31] 0
+ * and one row {first token, tokens, kind (0 VALU, 1 fp32 MFMA, 2 bf16 split MFMA), layer-wise, small (four tokens per workgroup), merged
+ * (k_token_m)} per token run.  Returns the length of the full record, or MIND_EINVAL for an unknown knob, pair_prec outside 0..3, a scene
+ * with no actor or a negative lane count, or a null pointer.  Needs no GPU and no context. */
+int mind_debug_predict_choice(const char *const *knob_names, const int *knob_values, int n_knobs, int pair_prec, int n_cu, int have_side,
+                              const int *scene_actors, const int *scene_lanes, int n_scenes, long long *out, int cap);
 
 /* host-only helper (tests): the launch list of the layer-wise batched ActorNet for a call of n_actors actors in the arithmetic np (6, 3, 1 =
  * bf16x6, bf16x3, bf16; anything else: MIND_EINVAL) with `chunk` actors per chunk (0 = the default) -- exactly what mind_predict_batch issues.

@@ -161,7 +161,7 @@ class PlannerOut(C.Structure):     # mind_planner_out
 EXPORTS = ["mind_ctx_create", "mind_ctx_destroy", "mind_last_error_string", "mind_ctx_synchronize",
            "mind_weights_load", "mind_predict_batch", "mind_last_fusion_stats", "mind_last_actor_stats", "mind_debug_actor_lw_plan", "mind_last_token_stats", "mind_last_token_stage_ms", "mind_debug_token_lw_plan", "mind_set_profiling",
            "mind_ilqr_solve_trees", "mind_ilqr_contingency", "mind_ilqr_solve_fields", "mind_cost_eval", "mind_lane_dist_field", "mind_aime_world", "mind_aime_rebase", "mind_debug_set_layers",
-           "mind_debug_read", "mind_set_pair_precision", "mind_get_pair_precision", "mind_debug_pack_bfrag", "mind_debug_pack_conv_frag", "mind_debug_pair_schedule", "mind_set_tuning", "mind_last_ilqr_stats", "mind_aime_plan", "mind_last_ilqr_profile", "mind_eval_traj_trees", "mind_last_ilqr_trace", "mind_ilqr_contingency_begin", "mind_ilqr_finish", "mind_fill_tracks", "mind_ilqr_contingency_begin_plan", "mind_debug_trig", "mind_aime_plan_begin", "mind_aime_plan_poll", "mind_aime_plan_finish", "mind_ctx_busy", "mind_ilqr_finish_plan",
+           "mind_debug_read", "mind_set_pair_precision", "mind_get_pair_precision", "mind_debug_pack_bfrag", "mind_debug_pack_conv_frag", "mind_debug_pair_schedule", "mind_debug_predict_choice", "mind_set_tuning", "mind_last_ilqr_stats", "mind_aime_plan", "mind_last_ilqr_profile", "mind_eval_traj_trees", "mind_last_ilqr_trace", "mind_ilqr_contingency_begin", "mind_ilqr_finish", "mind_fill_tracks", "mind_ilqr_contingency_begin_plan", "mind_debug_trig", "mind_aime_plan_begin", "mind_aime_plan_poll", "mind_aime_plan_finish", "mind_ctx_busy", "mind_ilqr_finish_plan",
            "mind_set_exchange", "mind_last_exchange_stats",
            "mind_loop_create", "mind_loop_destroy", "mind_loop_reset", "mind_loop_advance", "mind_loop_state", "mind_loop_last_plan", "mind_loop_export",
            "mind_planner_create", "mind_planner_destroy", "mind_planner_reset", "mind_planner_observe", "mind_planner_set_lanes", "mind_planner_set_target_lane",
@@ -237,6 +237,8 @@ def load():
     lib.mind_get_pair_precision.argtypes = [C.c_void_p]
     lib.mind_debug_pack_bfrag.argtypes = [C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_uint32)]
     lib.mind_debug_pair_schedule.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]
+    lib.mind_debug_predict_choice.argtypes = [C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                              C.c_int, C.POINTER(C.c_longlong), C.c_int]
     lib.mind_debug_trig.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double)]
     lib.mind_debug_pack_conv_frag.argtypes = [C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_size_t]
     lib.mind_debug_set_layers.argtypes = [C.c_void_p, C.c_int]
@@ -268,6 +270,33 @@ def load():
     lib.mind_debug_read.restype = C.c_int64
     _lib = lib
     return lib
+
+
+# header of mind_debug_predict_choice's record (include/mind_hip.h)
+PRED_CHOICE_FIELDS = ("header", "n_runs", "np", "actor_form", "actor_arg", "actor_grid", "actor_chunk", "actor_chunks", "actor_launches", "qsplit", "qk_stride",
+                      "tiled", "edge_bf16", "edge_pair_bytes", "tok_chunk", "tok_lw", "tok_chunks", "pair_family", "pair_np", "l5_jobs5", "xcd_lanes",
+                      "xcd_lanes5", "dec_actor", "dec_np", "fp32_dec", "split_dec", "want_mw", "mw_blocks", "cls_on_side", "tgt_wait_first")
+PAIR_PREC = ("f32", "bf16x3", "bf16", "bf16x6")
+
+
+def predict_choice(knobs, prec, scenes, n_cu=256, have_side=True):
+    """pred_choose's record (mind_debug_predict_choice; no GPU) for mind_set_tuning pairs `knobs`, the arithmetic `prec` (name or 0..3) and
+    scenes [(actors, lanes), ...]: dict of PRED_CHOICE_FIELDS + "runs" = [(t0, n, kind, layerwise, small, merged), ...]; None when rejected"""
+    lib = load()
+    names = (C.c_char_p * max(1, len(knobs)))(*[k.encode() for k in knobs])
+    vals = (C.c_int * max(1, len(knobs)))(*[int(v) for v in knobs.values()])
+    sa = (C.c_int * len(scenes))(*[a for a, _ in scenes])
+    sl = (C.c_int * len(scenes))(*[l for _, l in scenes])
+    cap = 32 + 6 * len(scenes)
+    out = (C.c_longlong * cap)()
+    n = lib.mind_debug_predict_choice(names, vals, len(knobs), PAIR_PREC.index(prec) if isinstance(prec, str) else prec, n_cu, int(have_side),
+                                      sa, sl, len(scenes), out, cap)
+    if n == MIND_EINVAL:
+        return None
+    assert 0 < n <= cap and out[0] == 32 and n == 32 + 6 * out[1], n
+    d = dict(zip(PRED_CHOICE_FIELDS, out[:30]))
+    d["runs"] = [tuple(out[32 + 6 * i:38 + 6 * i]) for i in range(out[1])]
+    return d
 
 
 class MindError(RuntimeError):

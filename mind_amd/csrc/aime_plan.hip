@@ -302,7 +302,7 @@ extern "C" int mind_aime_plan(mind_ctx *c, const mind_aime_plan_in *in, mind_aim
     if ((int)c->pl_world.size() <= round) c->pl_world.resize(round + 1);
     float *d_world = nullptr;
     const int Ntok = a + l + 1;
-    const double edge_mb = (double)Ntok * (((Ntok + 15) / 16) * 16) * (c->pair_prec == 2 && c->pair_tile ? 256.0 : 512.0) / (1024.0 * 1024.0);
+    const double edge_mb = (double)Ntok * (((Ntok + 15) / 16) * 16) * pred_edge_pair_bytes(c->pt, c->pair_prec) / (1024.0 * 1024.0);
     const int chunk = std::max(1, (int)std::min<double>((double)(Bk > 0 ? Bk : 1), (double)c->plan_chunk_mb / edge_mb));
     if (Bk > 0) {
       if ((rc = ensure(c, c->pl_world[round], (size_t)A * 6 * T * 6 * sizeof(float)))) return rc;

@@ -29,6 +29,7 @@
 #include "dec_mfma_kernels.hip"
 #include "ilqr_kernels.hip"
 #include "pair_jobs.h"
+#include "pred_choice.h"
 #include "aime_kernels.hip"
 
 namespace {
@@ -87,23 +88,8 @@ struct mind_ctx {
   TokWeights tokW[7];  // [L]: epilogue of layer L-1 (L>=1) + prologue of layer L (L<=5); [0] = init
   TokWeightsM tokWM[7]; // the same matrices as fp32 MFMA A fragments (k_token_mfma<0>)
   TokWeightsM tokWB[7]; // ... and as bf16 hi / lo A fragments (k_token_mfma<1>: scenes of >= tok_bf_min_n tokens)
-  // token kernel on the fp32 MFMA (k_token_mfma; MIND_TOK_MFMA=1 / mind_set_tuning("tok_mfma")).  Opt-in: measured on the MI355X it is
-  // SLOWER than the VALU kernel -- 41 vs 30 us per launch at demo size (6 workgroups), 315 vs 282 us average on the full cfg4 tree
-  // (profiles/r03o_*, r03p_*): 640 fp32 MFMAs of 32 cycles per wave and launch are 8.5 us by themselves and the weight stream (64 KB per
-  // projection and workgroup) is the same; a bf16-split variant would cut the MFMA time, not the rest
-  bool tok_mfma = false;
-  bool tgt_side = true;         // the target polyline's encoder + embedding stay on the side stream through the fusion layers ("tgt_side")
-  // scenes of at least this many tokens run k_token_mfma<1> (bf16 hi + lo split operands) under the bf16 arithmetics ("tok_bf_min_n";
-  // 0 = never, the default).  Measured on the cfg4 full tree (N = 321, launches of up to 69 k tokens): 221 us per launch on average and
-  // 0.80 ms for the largest, the same as the VALU kernel (which is LDS-bound there) -- with 97 KB of LDS the MFMA kernel keeps one
-  // four-wave workgroup per CU and waits on its partial-sum and fragment loads instead (profiles/r03bb); opt-in until it is faster
-  int tok_bf_min_n = 0;
-  // layer-wise token stage (token_lw_kernels.hip; the bits of k_token_mfma<0>).  "tok_lw_min_n" / MIND_TOK_LW_MIN_N: a SCENE of at least this
-  // many tokens takes the fp32-MFMA token class (by the scene's own N: its result does not depend on its batch, round or rank); "tok_lw_min" /
-  // MIND_TOK_LW_MIN: a run of consecutive scenes of that class with at least this many tokens runs layer-wise, a shorter one k_token_mfma<0>
-  // (the same bits, so this rule may look at the batch).  Both default to never.  "tok_lw_chunk": tokens per chunk (0 = TL_CHUNK); the arena
-  // holds one chunk and is allocated at first use
-  int tok_lw_min_n = 1 << 30, tok_lw_min = 1 << 30, tok_lw_chunk = 0;
+  PredTuning pt;       // the predictor's kernel-selection knobs (pred_choice.h)
+  // layer-wise token stage (token_lw_kernels.hip): its scratch arena holds one chunk and is allocated at first use
   DevBuf tok_lw_arena;
   std::vector<TlLaunch> tok_lw_plan;
   // the token stage of the last mind_predict_batch (mind_last_token_stats): launches of all seven token steps, time per layer-wise stage
@@ -112,8 +98,6 @@ struct mind_ctx {
   float tok_ms = 0.f, tok_stage_ms[TL_NSTAGE + 1] = {};
   std::vector<hipEvent_t> ev_tok;
   std::vector<int> ev_tok_tag;
-  bool tok_merge = true;        // small token launches merge their independent projections (k_token_m; MIND_TOK_MERGE=0 / "tok_merge": the plain kernel)
-  int tok_small_max = 2048;     // batches of at most this many tokens run k_token with 4 tokens per workgroup ("tok_small_max")
   const float *WAe[6], *WAp[6], *vtab[6], *rtab = nullptr;
   const u32 *WBe[6], *WBp[6];   // bf16 hi / lo fragments of the same matrices (pair_bf16_kernels.hip)
   const u32 *WLe[6], *WLp[6];   // the third part of the exact three-way split (hi + mid + lo; mid = the two-way split's lo): k_pair_t6
@@ -123,7 +107,6 @@ struct mind_ctx {
   TableSet tabs[MIND_TABLE_SETS];
   long long tab_clock = 0;
   long long n_table_hits = 0;
-  int actor_np = 6;             // partial products per term of the MFMA ActorNet under bf16x3: 6 (three-way split, fp32-class) or 3 (MIND_ACTOR_SPLIT=3)
   // nodes per forward step of a narrow tree's line search ("ilqr_chunk"; 0: whole segments, the default).  Measured on the recorded
   // demo_1 loop: chunks of 6 / 8 / 12 nodes cost 2.10 / 2.05 / 2.04 ms per launch against 1.99 for whole segments (round 3: the cost
   // waves shared the SIMDs' float64 pipe with five state-chain waves); with the chains of a level packed into ONE wave and the cost
@@ -165,30 +148,14 @@ struct mind_ctx {
   struct IlEarly { const double *xs = nullptr, *us = nullptr; volatile unsigned *done = nullptr; unsigned gen = 0; int n_trees = 0; long nodes = 0; } il_early;
   unsigned il_gen = 0;
   long long il_spec_req = 0, il_spec_hit = 0;       // last launch, all trees and fits: passes the speculator was asked in / results the master took
-  int dec_mfma_min = 1 << 30;   // agents per call from which the decoder's actor part runs on the MFMA kernel (MIND_DEC_MFMA_MIN; default: never)
-  bool enc_mfma = true;         // MFMA ActorNet under the bf16x3 / bf16 settings (MIND_ENC_MFMA=0: the fp32 VALU kernel, for A/B)
-  // fp32-MFMA ActorNet (k_actor_f32): "actor_f32" 1 (default) = the ActorNet of the exact-fp32 setting (0: the fp32 VALU kernel, for A/B);
-  // "actor_f32_min" = actors per call from which every setting takes it with TWO actors per workgroup (the 256-channel layers' weight stream is
-  // then shared by two actors: 7.1 vs 8.1 ms for the 13.8 k actors of a cfg4 round); "actor_f32_pair_min" = the same threshold inside the
-  // exact-fp32 setting.  Both default to never: a threshold on the batch size would give the blocks of a sharded round another kernel -- other
-  // last bits -- than the whole round (a workload that wants it sets 0, as with "dec_mfma_min")
-  bool actor_f32 = true;
-  int actor_f32_min = 1 << 30, actor_f32_pair_min = 1 << 30;
-  // layer-wise batched ActorNet (actor_lw_kernels.hip): actors per call from which it replaces k_actor_mfma<NP> ("actor_lw_min" /
-  // MIND_ACTOR_LW_MIN; default never; bit-identical, so ranks and rounds may differ in which one they take), actors per chunk
-  // ("actor_lw_chunk", 0 = LW_CHUNK; tests and A/B runs), its scratch arena (one chunk, allocated at first use)
-  int actor_lw_min = 1 << 30, actor_lw_chunk = 0;
+  // layer-wise batched ActorNet (actor_lw_kernels.hip): its scratch arena (one chunk, allocated at first use)
   DevBuf actor_lw_arena;
   std::vector<LwLaunch> actor_lw_plan;
   // the ActorNet of the last mind_predict_batch (mind_last_actor_stats)
   int last_actor_lw = 0, last_actor_launches = 0, last_actor_chunks = 0;
   float actor_ms = 0.f;
   hipEvent_t ev_act0 = nullptr, ev_act1 = nullptr;
-  bool xcd_order = true;        // XCD-aware job order for big batches (MIND_XCD_ORDER=0 switches it off, for A/B measurements)
   int pair_prec = 3;            // arithmetic of the pair kernel: 0 = fp32 MFMA, 1 = bf16x3 (two-way split operands), 2 = bf16, 3 = bf16x6 (exact three-way split: fp32 class, default)
-  // bf16 arithmetics: k_pair_t (tile-native edge tensor, pair_tile_kernels.hip; default) or the row-major k_pair_bf of rounds 2-3
-  // (mind_set_tuning("pair_tile", 0) / MIND_PAIR_TILE=0, kept for same-box A/B measurements)
-  bool pair_tile = true;
   // mind_aime_plan: a round whose edge tensor would exceed this many MB goes through the predictor in chunks of scenes ("plan_chunk_mb";
   // 96 GB by default: a third of the MI355X's HBM; the scenes of a round are independent, so chunking changes nothing but the launch sizes)
   int plan_chunk_mb = 96 * 1024;
@@ -242,17 +209,6 @@ struct mind_ctx {
   int pl_plan_agents = 0;       // agents per scene of the plan those tables belong to
   long long pl_gen = 0;         // plans begun on this context so far: whoever holds a plan's library-owned tables (mind_loop) checks they are still that plan's
   DevBuf pl_flat;
-  bool dec_overlap = true;      // actor_proj of the decoder on the side stream beside k_dec_scene (mind_set_tuning("dec_overlap"))
-  // k_dec_scene_mw: eight workgroups per scene on the decoder's five big stages (bit-identical to the one-workgroup kernel), possible whenever
-  // every workgroup of the launch is resident, i.e. for calls of at most n_cu / 8 scenes.  Opt-in ("dec_mw" / MIND_DEC_MW=1): measured 88.6
-  // against 94.9 us per demo-size launch (profiles/r06aa_*) -- only ctx_proj's second layer is really bound by one CU's L2 port (30 k -> 20 k
-  // cycles); the feed-forward layers are bound by their 24 accumulators per thread and win 2-4 k cycles each, less the 36 KB exchange --
-  // 12 us per plan, not worth eight spinning workgroups per scene when several scenes share the device
-  bool dec_mw = false;
-  // the decoder's cls head as its own launch on the side stream beside the actor part's head ("dec_cls_side" / MIND_DEC_CLS_SIDE=1).  Opt-in:
-  // bit-identical, but the second launch and its two event waits cost more than the ~10 us of overlap (1 609-1 630 against 1 632-1 652
-  // sim steps/s, profiles/r06am_*)
-  bool dec_cls_side = false;
   DevBuf dec_xbuf, dec_bars;
   unsigned *dec_abort = nullptr;      // host-visible abort word of its barriers (page-locked, mapped)
   int rb_cur = 0, rb_gen = 0;     // re-basing arenas: which one the last call filled, its generation and geometry
@@ -332,6 +288,18 @@ static int ensure(mind_ctx *c, DevBuf &b, size_t bytes) {
   return MIND_OK;
 }
 
+// a scratch arena of exactly `bytes` (no growth margin: tens of MB to GB, sized by a knob), re-allocated behind a drained stream
+static int ensure_exact(mind_ctx *c, DevBuf &b, size_t bytes, const char *what) {
+  if (bytes <= b.cap) return MIND_OK;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (b.p) (void)hipFree(b.p);
+  b.p = nullptr;
+  b.cap = 0;
+  if (hipMalloc(&b.p, bytes) != hipSuccess) return fail(c, MIND_ENOMEM, "hipMalloc(%zu) for %s failed", bytes, what);
+  b.cap = bytes;
+  return MIND_OK;
+}
+
 extern "C" int mind_ctx_create(int device, void *stream, mind_ctx **out) {
   if (!out) return MIND_EINVAL;
   *out = nullptr;
@@ -363,8 +331,8 @@ extern "C" int mind_ctx_create(int device, void *stream, mind_ctx **out) {
   (void)hipFuncSetAttribute((const void *)k_pair_t<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_pair_bf_lds_bytes());
   (void)hipFuncSetAttribute((const void *)k_pair_t6<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_pair_bf_lds_bytes());
   (void)hipFuncSetAttribute((const void *)k_pair_t6<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_pair_bf_lds_bytes());
-  if (const char *te = getenv("MIND_PAIR_TILE")) c->pair_tile = !(te[0] == '0');
-  if (const char *xe = getenv("MIND_XCD_ORDER")) c->xcd_order = !(xe[0] == '0');
+  if (const char *te = getenv("MIND_PAIR_TILE")) c->pt.pair_tile = !(te[0] == '0');
+  if (const char *xe = getenv("MIND_XCD_ORDER")) c->pt.xcd_order = !(xe[0] == '0');
 
   if (const char *pe = getenv("MIND_PAIR_PREC")) {
     const std::string v = pe;
@@ -379,30 +347,30 @@ extern "C" int mind_ctx_create(int device, void *stream, mind_ctx **out) {
   (void)hipFuncSetAttribute((const void *)k_dec_actor_mfma<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_dec_actor_mfma_lds_bytes());
   (void)hipFuncSetAttribute((const void *)k_dec_actor_mfma<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_dec_actor_mfma_lds_bytes());
   (void)hipFuncSetAttribute((const void *)k_dec_actor_mfma<6>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_dec_actor_mfma_lds_bytes());
-  if (const char *se = getenv("MIND_ACTOR_SPLIT")) c->actor_np = atoi(se) == 3 ? 3 : 6;
+  if (const char *se = getenv("MIND_ACTOR_SPLIT")) c->pt.actor_np = atoi(se) == 3 ? 3 : 6;
   (void)hipFuncSetAttribute((const void *)k_actor_mfma<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_actor_mfma_lds_bytes());
-  if (const char *me = getenv("MIND_ENC_MFMA")) c->enc_mfma = !(me[0] == '0');
-  if (const char *me = getenv("MIND_ACTOR_F32")) c->actor_f32 = !(me[0] == '0');
-  if (const char *me = getenv("MIND_ACTOR_F32_MIN")) c->actor_f32_min = atoi(me);
-  if (const char *me = getenv("MIND_ACTOR_LW_MIN")) c->actor_lw_min = atoi(me);
+  if (const char *me = getenv("MIND_ENC_MFMA")) c->pt.enc_mfma = !(me[0] == '0');
+  if (const char *me = getenv("MIND_ACTOR_F32")) c->pt.actor_f32 = !(me[0] == '0');
+  if (const char *me = getenv("MIND_ACTOR_F32_MIN")) c->pt.actor_f32_min = atoi(me);
+  if (const char *me = getenv("MIND_ACTOR_LW_MIN")) c->pt.actor_lw_min = atoi(me);
   lw_set_attributes();
   (void)hipFuncSetAttribute((const void *)k_actor_f32<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_actor_f32_lds_bytes(1));
   (void)hipFuncSetAttribute((const void *)k_actor_f32<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_actor_f32_lds_bytes(2));
-  if (const char *de = getenv("MIND_DEC_MFMA_MIN")) c->dec_mfma_min = atoi(de);
-  if (const char *oe = getenv("MIND_DEC_OVERLAP")) c->dec_overlap = !(oe[0] == '0');
+  if (const char *de = getenv("MIND_DEC_MFMA_MIN")) c->pt.dec_mfma_min = atoi(de);
+  if (const char *oe = getenv("MIND_DEC_OVERLAP")) c->pt.dec_overlap = !(oe[0] == '0');
   (void)hipFuncSetAttribute((const void *)k_ilqr<true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)il_lds_bytes(0));
   (void)hipFuncSetAttribute((const void *)k_ilqr<false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)il_lds_bytes(0));
   (void)hipFuncSetAttribute((const void *)k_ilqr<false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)il_lds_bytes(0));
   (void)hipFuncSetAttribute((const void *)k_ilqr<false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)il_lds_bytes(0));
-  if (const char *te = getenv("MIND_TOK_MFMA")) c->tok_mfma = !(te[0] == '0');
-  if (const char *te = getenv("MIND_TOK_SMALL_MAX")) c->tok_small_max = atoi(te);
-  if (const char *te = getenv("MIND_TOK_MERGE")) c->tok_merge = !(te[0] == '0');
-  if (const char *te = getenv("MIND_DEC_MW")) c->dec_mw = !(te[0] == '0');
-  if (const char *te = getenv("MIND_DEC_CLS_SIDE")) c->dec_cls_side = !(te[0] == '0');
-  if (const char *te = getenv("MIND_TOK_BF_MIN_N")) c->tok_bf_min_n = atoi(te);
-  if (const char *te = getenv("MIND_TOK_LW_MIN_N")) c->tok_lw_min_n = atoi(te);
-  if (const char *te = getenv("MIND_TOK_LW_MIN")) c->tok_lw_min = atoi(te);
-  if (const char *te = getenv("MIND_TGT_SIDE")) c->tgt_side = !(te[0] == '0');
+  if (const char *te = getenv("MIND_TOK_MFMA")) c->pt.tok_mfma = !(te[0] == '0');
+  if (const char *te = getenv("MIND_TOK_SMALL_MAX")) c->pt.tok_small_max = atoi(te);
+  if (const char *te = getenv("MIND_TOK_MERGE")) c->pt.tok_merge = !(te[0] == '0');
+  if (const char *te = getenv("MIND_DEC_MW")) c->pt.dec_mw = !(te[0] == '0');
+  if (const char *te = getenv("MIND_DEC_CLS_SIDE")) c->pt.dec_cls_side = !(te[0] == '0');
+  if (const char *te = getenv("MIND_TOK_BF_MIN_N")) c->pt.tok_bf_min_n = atoi(te);
+  if (const char *te = getenv("MIND_TOK_LW_MIN_N")) c->pt.tok_lw_min_n = atoi(te);
+  if (const char *te = getenv("MIND_TOK_LW_MIN")) c->pt.tok_lw_min = atoi(te);
+  if (const char *te = getenv("MIND_TGT_SIDE")) c->pt.tgt_side = !(te[0] == '0');
   if (const char *te = getenv("MIND_PL_TAB_SIDE")) c->pl_tab_side = !(te[0] == '0');
   (void)hipFuncSetAttribute((const void *)k_token_mfma<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_token_mfma_lds_bytes());
   (void)hipFuncSetAttribute((const void *)k_token_mfma<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_token_mfma_lds_bytes());
@@ -492,28 +460,8 @@ extern "C" int mind_ctx_synchronize(mind_ctx *c) {
 extern "C" int mind_set_tuning(mind_ctx *c, const char *name, int value) {
   if (!c || !name) return MIND_EINVAL;
   const std::string n = name;
-  if (n == "dec_mfma_min") c->dec_mfma_min = value;
-  else if (n == "enc_mfma") c->enc_mfma = value != 0;
-  else if (n == "actor_f32") c->actor_f32 = value != 0;
-  else if (n == "actor_f32_min") c->actor_f32_min = value;
-  else if (n == "actor_f32_pair_min") c->actor_f32_pair_min = value;
-  else if (n == "actor_lw_min") c->actor_lw_min = value;
-  else if (n == "actor_lw_chunk") c->actor_lw_chunk = value < 0 ? 0 : value;
-  else if (n == "actor_split") c->actor_np = value == 3 ? 3 : 6;
-  else if (n == "xcd_order") c->xcd_order = value != 0;
-  else if (n == "pair_tile") c->pair_tile = value != 0;
-  else if (n == "plan_chunk_mb") c->plan_chunk_mb = value < 1 ? 1 : value;
-  else if (n == "dec_overlap") c->dec_overlap = value != 0;
-  else if (n == "tok_mfma") c->tok_mfma = value != 0;
-  else if (n == "tok_small_max") c->tok_small_max = (int)value;
-  else if (n == "tok_merge") c->tok_merge = value != 0;
-  else if (n == "dec_mw") c->dec_mw = value != 0;
-  else if (n == "dec_cls_side") c->dec_cls_side = value != 0;
-  else if (n == "tok_bf_min_n") c->tok_bf_min_n = (int)value;
-  else if (n == "tok_lw_min_n") c->tok_lw_min_n = value;
-  else if (n == "tok_lw_min") c->tok_lw_min = value;
-  else if (n == "tok_lw_chunk") c->tok_lw_chunk = value < 0 ? 0 : value;
-  else if (n == "tgt_side") c->tgt_side = value != 0;
+  if (pred_tuning_set(c->pt, name, value)) return MIND_OK;      // the predictor's knobs (pred_choice.h)
+  if (n == "plan_chunk_mb") c->plan_chunk_mb = value < 1 ? 1 : value;
   else if (n == "pl_tab_side") c->pl_tab_side = value != 0;
   else if (n == "ilqr_chunk") c->ilqr_chunk = value < 0 ? 0 : (int)value;
   else if (n == "ilqr_wgs") c->ilqr_wgs = value < 1 ? 1 : (value > 32 ? 32 : value);
@@ -565,44 +513,6 @@ extern "C" int mind_debug_pack_bfrag(const float *w, int row_stride, uint32_t *o
   const std::vector<float> t = pack_bfrag(v, row_stride);
   memcpy(out, t.data(), 16384 * sizeof(uint32_t));
   return MIND_OK;
-}
-
-// the pair kernels' job lists as mind_predict_batch builds them (same helpers of pair_jobs.h), for a host-side check of the schedule
-extern "C" int mind_debug_pair_schedule(const int *scene_tokens, const int *scene_actors, int n_scenes, int n_cu, int last_layer, int *out_jobs, int cap,
-                                        int *out_info) {
-  if (!scene_tokens || !scene_actors || n_scenes <= 0 || n_cu <= 0 || !out_jobs || !out_info) return MIND_EINVAL;
-  std::vector<PairJob> jl;
-  int slot = 0;
-  for (int b = 0; b < n_scenes; ++b) {
-    const int N = scene_tokens[b], a = scene_actors[b];
-    if (N <= 0 || a < 0 || a >= N) return MIND_EINVAL;
-    const int tiles = (N + 15) / 16, ns = pair_column_splits(N);
-    for (int j = 0; j < N; ++j)
-      for (int s_ = 0; s_ < ns; ++s_) {
-        PairJob J;
-        memset(&J, 0, sizeof(J));
-        J.N = N; J.j = j; J.scene = b; J.slot = slot++;
-        pair_job_range(tiles, ns, s_, &J.t0, &J.t1);
-        J.flags = (j < a || j == N - 1) ? 1 : 0;
-        if (!last_layer || (J.flags & 1)) jl.push_back(J);
-      }
-  }
-  const int njobs = (int)jl.size();
-  const int grid = njobs < n_cu ? njobs : n_cu;
-  pair_jobs_deal(jl, grid, PAIR_WAVES, (n_scenes >= 8 && grid % 8 == 0) ? 8 : 1);
-  const int stride = grid * PAIR_WAVES;
-  int n = 0;
-  for (size_t i = 0; i < jl.size(); ++i) {
-    const PairJob &J = jl[i];
-    if (J.t1 <= J.t0) continue;
-    if (n < cap) {
-      int *o = out_jobs + (size_t)6 * n;
-      o[0] = J.scene; o[1] = J.j; o[2] = J.t0; o[3] = J.t1; o[4] = J.slot; o[5] = (int)(i % stride);
-    }
-    ++n;
-  }
-  out_info[0] = pair_column_splits(scene_tokens[0]); out_info[1] = grid; out_info[2] = (int)jl.size(); out_info[3] = n;
-  return n;
 }
 
 extern "C" int mind_set_profiling(mind_ctx *c, int enable) {
@@ -1332,509 +1242,7 @@ extern "C" int mind_weights_load(mind_ctx *c, const mind_tensor_desc *tensors, i
 // -------------------------------------------------------------------------------------------------
 // predictor forward
 // -------------------------------------------------------------------------------------------------
-__global__ void k_tokpos(const TokMeta *__restrict__ meta, int n_tok, const float *__restrict__ actr,
-                         const float *__restrict__ avec, const float *__restrict__ lctr,
-                         const float *__restrict__ lvec, float *__restrict__ tokpos) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n_tok) return;
-  const TokMeta m = meta[t];
-  float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (m.type == 0 && actr) o = make_float4(actr[m.src * 2], actr[m.src * 2 + 1], avec[m.src * 2], avec[m.src * 2 + 1]);
-  if (m.type == 1 && lctr) o = make_float4(lctr[m.src * 2], lctr[m.src * 2 + 1], lvec[m.src * 2], lvec[m.src * 2 + 1]);
-  ((float4 *)tokpos)[t] = o;
-}
-
-extern "C" int mind_predict_batch(mind_ctx *c, const mind_scene_batch *in, mind_pred_out *out) {
-  if (!c || !in || !out) return MIND_EINVAL;
-  if (!c->have_weights) return fail(c, MIND_ESTATE, "weights not loaded");
-  const int Bn = in->n_scenes;
-  if (Bn <= 0 || !in->actor_off || !in->lane_off || !in->actors || !in->tgt_nodes || !in->tgt_rpe || !out->cls ||
-      !out->reg || !out->vel)
-    return fail(c, MIND_EINVAL, "null input/output pointer");
-  if (!in->lanes && !in->lane_feat) return fail(c, MIND_EINVAL, "need lanes or lane_feat");
-  if (!in->rpe && !(in->actor_ctrs && in->actor_vecs && in->lane_ctrs && in->lane_vecs))
-    return fail(c, MIND_EINVAL, "need rpe or ctrs/vecs");
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t st = c->stream;
-  const int A = in->actor_off[Bn], Ltot = in->lane_off[Bn];
-  if (A <= 0 || Ltot < 0) return fail(c, MIND_EINVAL, "empty batch");
-
-  // ---- host tables: tokens, jobs (cached by the batch's scene sizes)
-  std::vector<int> key;
-  key.reserve(2 * Bn + 3);
-  key.push_back(Bn);
-  for (int b = 0; b <= Bn; ++b) key.push_back(in->actor_off[b]);
-  for (int b = 0; b <= Bn; ++b) key.push_back(in->lane_off[b]);
-  TableSet *ts = nullptr;
-  for (TableSet &t : c->tabs)
-    if (t.key == key) ts = &t;
-  const bool tab_hit = ts != nullptr;
-  if (!ts) {
-    ts = &c->tabs[0];
-    for (TableSet &t : c->tabs)
-      if (t.stamp < ts->stamp) ts = &t;         // least recently used (empty sets have stamp 0)
-  }
-  ts->stamp = ++c->tab_clock;
-  int rc;
-  if (!tab_hit) {
-    std::vector<TokMeta> meta;
-    std::vector<PairJob> jobs;
-    std::vector<int> actor_row(A), actor_scene(A), cls_row(Bn), scene_n(Bn);
-    long long edge_pairs = 0, edge_pairs_t = 0;
-    int ntok = 0;
-    for (int b = 0; b < Bn; ++b) {
-      const int a = in->actor_off[b + 1] - in->actor_off[b], l = in->lane_off[b + 1] - in->lane_off[b];
-      if (a <= 0 || l < 0) return fail(c, MIND_EINVAL, "scene %d has %d agents, %d lanes", b, a, l);
-    }
-    int slot = 0;
-    double pairs_full = 0, pairs_l5 = 0;
-    for (int b = 0; b < Bn; ++b) {
-      const int a = in->actor_off[b + 1] - in->actor_off[b], l = in->lane_off[b + 1] - in->lane_off[b];
-      const int N = a + l + 1;
-      const int tiles = (N + 15) / 16;
-      const int ns = pair_column_splits(N);      // (a function of the scene's own size only: pair_jobs.h)
-      for (int j = 0; j < N; ++j) {
-        TokMeta m;
-        memset(&m, 0, sizeof(m));
-        m.type = j < a ? 0 : (j < a + l ? 1 : 2);
-        m.src = j < a ? in->actor_off[b] + j : (j < a + l ? in->lane_off[b] + (j - a) : 0);
-        m.slot0 = slot;
-        m.nsplit = ns;
-        m.flags = (j < a || j == N - 1) ? 1 : 0;
-        meta.push_back(m);
-        for (int s_ = 0; s_ < ns; ++s_) {
-          PairJob J;
-          memset(&J, 0, sizeof(J));
-          J.edge_base = edge_pairs;
-          J.edge_base_t = edge_pairs_t;
-          J.N = N;
-          J.j = j;
-          pair_job_range(tiles, ns, s_, &J.t0, &J.t1);
-          J.tok_base = ntok;
-          J.slot = slot++;
-          J.flags = m.flags;
-          J.scene = b;
-          jobs.push_back(J);
-        }
-        if (j < a) { actor_row[in->actor_off[b] + j] = ntok + j; actor_scene[in->actor_off[b] + j] = b; }
-      }
-      cls_row[b] = ntok + N - 1;
-      scene_n[b] = N;
-      ntok += N;
-      edge_pairs += (long long)N * N;
-      edge_pairs_t += (long long)N * tiles * 16;
-      pairs_full += (double)N * N;
-      pairs_l5 += (double)N * (a + 1);
-    }
-    // The order of a job list is its schedule (pair_jobs.h): equal work per wave slot, and for batches of eight scenes or more all column
-    // jobs of a scene on one XCD.  The last fusion layer runs the consumed columns only (actors + cls): k_pair_t walks a list of its own
-    // instead of skipping the other jobs after a dependent load each.
-    std::vector<PairJob> jobs5;
-    for (const PairJob &J : jobs)
-      if (J.flags & 1) jobs5.push_back(J);
-    auto deal = [&](std::vector<PairJob> &jl) {
-      const int grid_ = (int)jl.size() < c->n_cu ? (int)jl.size() : c->n_cu;
-      pair_jobs_deal(jl, grid_, PAIR_WAVES, (c->xcd_order && Bn >= 8 && grid_ % 8 == 0) ? 8 : 1);
-    };
-    deal(jobs);
-    deal(jobs5);
-    ts->key.clear();                    // invalid until the upload below has completed
-    if ((rc = ensure(c, ts->meta, meta.size() * sizeof(TokMeta)))) return rc;
-    if ((rc = ensure(c, ts->jobs, jobs.size() * sizeof(PairJob)))) return rc;
-    if ((rc = ensure(c, ts->jobs5, jobs5.size() * sizeof(PairJob)))) return rc;
-    if ((rc = ensure(c, ts->rows, (size_t)(2 * A + Bn) * sizeof(int)))) return rc;
-    HIPCHK(c, hipMemcpyAsync(ts->meta.p, meta.data(), meta.size() * sizeof(TokMeta), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(ts->jobs.p, jobs.data(), jobs.size() * sizeof(PairJob), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(ts->jobs5.p, jobs5.data(), jobs5.size() * sizeof(PairJob), hipMemcpyHostToDevice, st));
-    std::vector<int> rows(2 * A + Bn);
-    memcpy(rows.data(), actor_row.data(), A * sizeof(int));
-    memcpy(rows.data() + A, actor_scene.data(), A * sizeof(int));
-    memcpy(rows.data() + 2 * A, cls_row.data(), Bn * sizeof(int));
-    HIPCHK(c, hipMemcpyAsync(ts->rows.p, rows.data(), rows.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    // the host vectors above must outlive the async copies
-    HIPCHK(c, hipStreamSynchronize(st));
-    ts->actor_row.swap(actor_row);
-    ts->cls_row.swap(cls_row);
-    ts->scene_n.swap(scene_n);
-    ts->edge_pairs = edge_pairs; ts->edge_pairs_t = edge_pairs_t; ts->ntok = ntok; ts->slot = slot; ts->njobs = (int)jobs.size();
-    ts->njobs5 = (int)jobs5.size();
-    ts->pairs_full = pairs_full; ts->pairs_l5 = pairs_l5;
-    ts->key.swap(key);
-  } else {
-    c->n_table_hits++;
-  }
-  const std::vector<int> &actor_row = ts->actor_row, &cls_row = ts->cls_row;
-  const long long edge_pairs = ts->edge_pairs;
-  const int ntok = ts->ntok, slot = ts->slot, njobs = ts->njobs;
-  const bool tiled = c->pair_prec == 3 || (c->pair_prec != 0 && c->pair_tile);      // k_pair_t / k_pair_t6: the edge tensor in its tile-native layout
-  const double pairs_full = ts->pairs_full, pairs_l5 = ts->pairs_l5;
-
-  // ---- workspaces
-  // (k_pair_t<*, 1> keeps the tensor in bf16: the fp32-sized buffer is simply half used)
-  if ((rc = ensure(c, c->edge, (size_t)(tiled ? ts->edge_pairs_t : edge_pairs) * 128 * sizeof(float)))) return rc;
-  if ((rc = ensure(c, c->x, (size_t)ntok * 128 * sizeof(float)))) return rc;
-  if ((rc = ensure(c, c->ST, (size_t)ntok * 256 * sizeof(float)))) return rc;
-  const size_t qk_stride = c->pair_prec == 3 ? P6_QK_STRIDE : 1024;      // dwords of folded query per token (three parts under bf16x6)
-  if ((rc = ensure(c, c->QK, (size_t)(ntok + 1) * qk_stride * sizeof(float)))) return rc;      // (+ 1: k_pair_t6's padding rows read past the last record)
-  if ((rc = ensure(c, c->part, (size_t)slot * PART_STRIDE * sizeof(float)))) return rc;
-  if ((rc = ensure(c, c->tokpos, (size_t)ntok * 4 * sizeof(float)))) return rc;
-  if ((rc = ensure(c, c->actor_feat, (size_t)A * 128 * sizeof(float)))) return rc;
-  if ((rc = ensure(c, c->lane_feat, (size_t)(Ltot > 0 ? Ltot : 1) * 128 * sizeof(float)))) return rc;
-  if ((rc = ensure(c, c->tgt_feat, (size_t)Bn * 128 * sizeof(float)))) return rc;
-  if ((rc = ensure(c, c->cmode, (size_t)Bn * 768 * sizeof(float)))) return rc;
-  if ((rc = ensure(c, c->tgt_emb, (size_t)Bn * 128 * sizeof(float)))) return rc;
-  const float *const *rpe_dev = nullptr;
-  if (in->rpe) {
-    if ((rc = ensure(c, c->rpe_ptrs, (size_t)Bn * sizeof(float *)))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->rpe_ptrs.p, in->rpe, (size_t)Bn * sizeof(float *), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipStreamSynchronize(st));          // in->rpe is the caller's host array
-    rpe_dev = (const float *const *)c->rpe_ptrs.p;
-  }
-
-  const TokMeta *dmeta = (const TokMeta *)ts->meta.p;
-  const PairJob *djobs = (const PairJob *)ts->jobs.p;
-  float *x = (float *)c->x.p, *ST = (float *)c->ST.p, *QK = (float *)c->QK.p, *part = (float *)c->part.p;
-  float *edge = (float *)c->edge.p, *tokpos = (float *)c->tokpos.p;
-  float *actor_feat = (float *)c->actor_feat.p;
-  const float *lane_feat = in->lane_feat;
-
-  // ---- encoders: ActorNet on the context stream, the (independent) lane encoders and token positions beside it on
-  //      the side stream (everything they read was complete at the synchronisation point above)
-  hipStream_t ss = c->side ? c->side : st;
-  if (c->side) {
-    // the side stream reads inputs the caller produced on the context stream (uploads, mind_aime_rebase outputs): it starts
-    // behind everything queued there so far (a table-cache hit no longer synchronises the stream on the way in)
-    HIPCHK(c, hipEventRecord(c->ev_main, st));
-    HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_main, 0));
-  }
-  // ActorNet: fp32 VALU kernel under MIND_PAIR_F32, the bf16-split / bf16 MFMA kernel otherwise (the precision setting covers
-  // every MFMA contraction of the predictor)
-  // ... and the fp32-MFMA kernel (plain fp32 operands on the matrix core: the reference's arithmetic class): the ActorNet of the exact-fp32
-  // setting, and -- two actors per workgroup -- of every setting on full-tree rounds (thousands of actors per call)
-  const bool f32_pair = c->actor_f32 && A >= (c->pair_prec == 0 ? c->actor_f32_pair_min : c->actor_f32_min);
-  const bool act_timed = c->profiling && !c->ev_defer;      // (inside a plan nothing drains the stream per call: no ActorNet time there)
-  if (act_timed && !c->ev_act0) {
-    HIPCHK(c, hipEventCreate(&c->ev_act0));
-    HIPCHK(c, hipEventCreate(&c->ev_act1));
-  }
-  c->last_actor_lw = 0; c->last_actor_launches = 1; c->last_actor_chunks = 1; c->actor_ms = 0.f;
-  if (act_timed) HIPCHK(c, hipEventRecord(c->ev_act0, st));
-  if (f32_pair)
-    hipLaunchKernelGGL(k_actor_f32<2>, dim3((A + 1) / 2), dim3(AF_T), mind_actor_f32_lds_bytes(2), st, in->actors, A, actor_feat, c->actorFW);
-  else if (c->pair_prec == 0 && c->actor_f32 && c->enc_mfma)
-    hipLaunchKernelGGL(k_actor_f32<1>, dim3(A), dim3(AF_T), mind_actor_f32_lds_bytes(1), st, in->actors, A, actor_feat, c->actorFW);
-  else if (c->pair_prec == 0 || !c->enc_mfma)
-    hipLaunchKernelGGL(k_actor_net, dim3(A), dim3(AT), mind_actor_lds_bytes(), st, in->actors, A, actor_feat, c->actorW);
-  else if (A >= c->actor_lw_min) {
-    // rounds of thousands of actors: the same arithmetic layer by layer over chunks of actors, the weight fragments stationary
-    // (actor_lw_kernels.hip; bit-identical to k_actor_mfma<NP>)
-    const int chunk = c->actor_lw_chunk > 0 ? c->actor_lw_chunk : LW_CHUNK;
-    const size_t need = lw_arena_bytes(chunk);
-    if (c->actor_lw_arena.cap < need) {
-      HIPCHK(c, hipStreamSynchronize(st));
-      if (c->actor_lw_arena.p) (void)hipFree(c->actor_lw_arena.p);
-      c->actor_lw_arena.p = nullptr; c->actor_lw_arena.cap = 0;
-      if (hipMalloc(&c->actor_lw_arena.p, need) != hipSuccess) return fail(c, MIND_ENOMEM, "hipMalloc(%zu) for the layer-wise ActorNet's arena failed", need);
-      c->actor_lw_arena.cap = need;
-    }
-    lw_build_plan(A, chunk, c->actor_lw_plan);
-    const int np = (c->pair_prec == 3 || (c->pair_prec == 1 && c->actor_np == 6)) ? 6 : (c->pair_prec == 1 ? 3 : 1);
-    u32 *arena = (u32 *)c->actor_lw_arena.p;
-    const int nl = np == 6 ? lw_run<6>(c->actor_lw_plan, st, arena, in->actors, actor_feat, c->actorBW)
-                 : np == 3 ? lw_run<3>(c->actor_lw_plan, st, arena, in->actors, actor_feat, c->actorBW)
-                           : lw_run<1>(c->actor_lw_plan, st, arena, in->actors, actor_feat, c->actorBW);
-    if (nl < 0) return fail(c, MIND_ESTATE, "layer-wise ActorNet: a stage has no kernel");
-    c->last_actor_lw = 1; c->last_actor_launches = nl; c->last_actor_chunks = (A + chunk - 1) / chunk;
-  }
-  else if (c->pair_prec == 3 || (c->pair_prec == 1 && c->actor_np == 6))
-    hipLaunchKernelGGL(k_actor_mfma<6>, dim3(A), dim3(AM_T), mind_actor_mfma_lds_bytes(), st, in->actors, A, actor_feat, c->actorBW);
-  else if (c->pair_prec == 1)
-    hipLaunchKernelGGL(k_actor_mfma<3>, dim3(A), dim3(AM_T), mind_actor_mfma_lds_bytes(), st, in->actors, A, actor_feat, c->actorBW);
-  else
-    hipLaunchKernelGGL(k_actor_mfma<1>, dim3(A), dim3(AM_T), mind_actor_mfma_lds_bytes(), st, in->actors, A, actor_feat, c->actorBW);
-  if (act_timed) HIPCHK(c, hipEventRecord(c->ev_act1, st));
-  if (!lane_feat) {
-    float *lf = out->lane_feat ? out->lane_feat : (float *)c->lane_feat.p;
-    if (Ltot > 0)
-      hipLaunchKernelGGL(k_lane_net, dim3((Ltot + PL - 1) / PL), dim3(DT), 0, ss, in->lanes, Ltot, lf, c->laneW);
-    lane_feat = lf;
-  } else if (out->lane_feat && out->lane_feat != in->lane_feat && Ltot > 0) {
-    HIPCHK(c, hipMemcpyAsync(out->lane_feat, in->lane_feat, (size_t)Ltot * 128 * sizeof(float), hipMemcpyDeviceToDevice, ss));
-  }
-  hipLaunchKernelGGL(k_tokpos, dim3((ntok + 255) / 256), dim3(256), 0, ss, dmeta, ntok, in->actor_ctrs, in->actor_vecs,
-                     in->lane_ctrs, in->lane_vecs, tokpos);
-  if (c->side) {
-    HIPCHK(c, hipEventRecord(c->ev_side, c->side));
-    HIPCHK(c, hipStreamWaitEvent(st, c->ev_side, 0));
-  }
-  // the target polyline's encoder + embedding feed the decoder only: they stay on the side stream while the fusion layers run
-  hipLaunchKernelGGL(k_lane_net, dim3((Bn + PL - 1) / PL), dim3(DT), 0, ss, in->tgt_nodes, Bn, (float *)c->tgt_feat.p, c->laneW);
-  hipLaunchKernelGGL(k_dec_tgt, dim3(Bn), dim3(DT), mind_dec_scene_lds_bytes(), ss, (const float *)c->tgt_feat.p, in->tgt_rpe, (float *)c->tgt_emb.p,
-                     c->decW);
-  if (c->side) HIPCHK(c, hipEventRecord(c->ev_tgt, c->side));
-  if (c->side && !c->tgt_side) HIPCHK(c, hipStreamWaitEvent(st, c->ev_tgt, 0));
-
-  // ---- fusion: init tokens + 6 x (pair kernel, token kernel)
-  // The token kernel by SCENE (a scene's result must not depend on what else is in its batch): scenes of at least tok_bf_min_n tokens
-  // under the bf16 pair-kernel arithmetics run k_token_mfma<1> (bf16 hi + lo split operands on the MFMA, 16 tokens per workgroup: the
-  // VALU kernel is LDS-bound at those sizes), every other scene the VALU kernel -- consecutive scenes of one class share a launch, small
-  // launches take four tokens per workgroup (more workgroups, half the LDS operand traffic each; bit-identical to eight)
-  const int qsplit = c->pair_prec == 3 ? 48 : c->pair_prec != 0 ? 16 : 0;      // the bf16 pair kernels read the folded query as hi / lo (bf16x6: hi / mid / lo) fragments
-  const size_t tokm_lds = mind_token_mfma_lds_bytes();
-  // ... and scenes of at least tok_lw_min_n tokens the fp32-MFMA class (kind 1; tok_bf_min_n keeps its precedence under bf16x3 / bf16): a run
-  // of them with at least tok_lw_min tokens runs layer-wise (token_lw_kernels.hip), a shorter run k_token_mfma<0> -- the same bits
-  struct TokRun { int t0, n, kind; };                  // kind 0: VALU, 1: fp32 MFMA (opt-in), 2: bf16 split MFMA
-  std::vector<TokRun> tok_runs;
-  {
-    int t0 = 0;
-    for (int b = 0; b < Bn; ++b) {
-      const int N = (in->actor_off[b + 1] - in->actor_off[b]) + (in->lane_off[b + 1] - in->lane_off[b]) + 1;
-      // (the two-way-split token kernel is not an fp32-class arithmetic: never under bf16x6)
-      const int kind = c->tok_mfma ? 1 : (c->pair_prec != 0 && c->pair_prec != 3 && c->tok_bf_min_n > 0 && N >= c->tok_bf_min_n) ? 2
-                       : N >= c->tok_lw_min_n ? 1 : 0;
-      if (!tok_runs.empty() && tok_runs.back().kind == kind) tok_runs.back().n += N;
-      else tok_runs.push_back({t0, N, kind});
-      t0 += N;
-    }
-  }
-  const int tl_chunk = c->tok_lw_chunk > 0 ? c->tok_lw_chunk : TL_CHUNK;
-  c->last_tok_lw = 0; c->last_tok_launches = 0; c->last_tok_chunks = 0; c->tok_ms = 0.f;
-  for (float &v : c->tok_stage_ms) v = 0.f;
-  for (const TokRun &r : tok_runs)
-    if (r.kind == 1 && r.n >= c->tok_lw_min) {
-      c->last_tok_lw = 1;
-      c->last_tok_chunks += (r.n + tl_chunk - 1) / tl_chunk;
-    }
-  if (c->last_tok_lw && c->tok_lw_arena.cap < tl_arena_bytes(tl_chunk)) {
-    const size_t need = tl_arena_bytes(tl_chunk);
-    HIPCHK(c, hipStreamSynchronize(st));
-    if (c->tok_lw_arena.p) (void)hipFree(c->tok_lw_arena.p);
-    c->tok_lw_arena.p = nullptr; c->tok_lw_arena.cap = 0;
-    if (hipMalloc(&c->tok_lw_arena.p, need) != hipSuccess) return fail(c, MIND_ENOMEM, "hipMalloc(%zu) for the layer-wise token stage's arena failed", need);
-    c->tok_lw_arena.cap = need;
-  }
-  // (HIP events around every token launch with profiling on, outside a plan: mind_last_token_stats / mind_last_token_stage_ms)
-  const bool tok_timed = c->profiling && !c->ev_defer;
-  size_t ev_tok_used = 0;
-  auto tok_mark = [&](int tag) -> hipError_t {
-    if (!tok_timed) return hipSuccess;
-    if (ev_tok_used == c->ev_tok.size()) {
-      hipEvent_t e;
-      const hipError_t rc_ = hipEventCreate(&e);
-      if (rc_ != hipSuccess) return rc_;
-      c->ev_tok.push_back(e);
-      c->ev_tok_tag.push_back(0);
-    }
-    c->ev_tok_tag[ev_tok_used] = tag;
-    return hipEventRecord(c->ev_tok[ev_tok_used++], st);
-  };
-  auto launch_tokens = [&](int mode, int Lw) -> int {
-    HIPCHK(c, tok_mark(-1));
-    for (const TokRun &r : tok_runs) {
-      const TokMeta *m_ = dmeta + r.t0;
-      float *x_ = x + (size_t)r.t0 * 128, *ST_ = ST + (size_t)r.t0 * 256, *QK_ = QK + (size_t)r.t0 * qk_stride;
-      if (r.kind == 1 && r.n >= c->tok_lw_min) {
-        tl_build_plan(r.n, mode, tl_chunk, c->n_cu, c->tok_lw_plan);
-        for (const TlLaunch &L : c->tok_lw_plan) {
-          if (tl_launch(L, st, mode, m_, actor_feat, lane_feat, x_, part, ST_, QK_, qk_stride, c->tokW[Lw], c->tokWM[Lw], (float *)c->tok_lw_arena.p, tl_chunk))
-            return fail(c, MIND_ESTATE, "layer-wise token stage: a stage has no kernel");
-          HIPCHK(c, tok_mark(L.stage));
-        }
-        c->last_tok_launches += (int)c->tok_lw_plan.size();
-        continue;
-      }
-      c->last_tok_launches++;
-      if (r.kind == 0) {
-        const bool small = r.n <= c->tok_small_max;
-        const int tpw = small ? TOK_TPW_SMALL : TOK_TPW_BIG;
-        // (small launches: independent projections merged, k_token_m -- bit-identical; "tok_merge" 0 keeps the plain form for A/B)
-        hipLaunchKernelGGL(small ? (c->tok_merge ? k_token_m : k_token<TOK_TPW_SMALL>) : k_token<TOK_TPW_BIG>, dim3((r.n + tpw - 1) / tpw), dim3(TT_THREADS), 0,
-                           st, m_, r.n, mode, actor_feat, lane_feat, x_, part, ST_, QK_, c->tokW[Lw]);
-      } else if (r.kind == 1) {
-        hipLaunchKernelGGL(k_token_mfma<0>, dim3((r.n + TM_TOK - 1) / TM_TOK), dim3(TM_THREADS), tokm_lds, st, m_, r.n, mode, actor_feat, lane_feat, x_,
-                           part, ST_, QK_, c->tokW[Lw], c->tokWM[Lw]);
-      } else {
-        hipLaunchKernelGGL(k_token_mfma<1>, dim3((r.n + TM_TOK - 1) / TM_TOK), dim3(TM_THREADS), tokm_lds, st, m_, r.n, mode, actor_feat, lane_feat, x_,
-                           part, ST_, QK_, c->tokW[Lw], c->tokWB[Lw]);
-      }
-      HIPCHK(c, tok_mark(TL_NSTAGE));
-    }
-    return MIND_OK;
-  };
-  if ((rc = launch_tokens(1 | 4 | qsplit, 0))) return rc;
-  int grid = njobs < c->n_cu ? njobs : c->n_cu;      // jobs are dealt wave-major over the workgroups
-  const size_t lds = mind_pair_lds_bytes();
-  c->n_pair_launch = 0;
-  c->pairs_done = 0;
-  if (c->profiling && c->ev.size() < 12) {
-    while (c->ev.size() < 12) {
-      hipEvent_t e;
-      HIPCHK(c, hipEventCreate(&e));
-      c->ev.push_back(e);
-    }
-  }
-  hipEvent_t *evs = c->ev.data();
-  if (c->profiling && c->ev_defer) {
-    while (c->ev_pool.size() < c->ev_pool_used + 12) {
-      hipEvent_t e;
-      HIPCHK(c, hipEventCreate(&e));
-      c->ev_pool.push_back(e);
-    }
-    evs = c->ev_pool.data() + c->ev_pool_used;
-    c->ev_pending.push_back(c->ev_pool_used);
-    c->ev_pool_used += 12;
-  }
-  c->last_ntok = ntok; c->last_edge_pairs = edge_pairs; c->last_slots = slot; c->last_A = A; c->last_B = Bn;
-  c->last_scene_n = ts->scene_n; c->last_edge_tiled = tiled; c->last_edge_bf16 = tiled && c->pair_prec == 2;
-  for (int L = 0; L < c->debug_layers; ++L) {
-    const int um = L < 4 ? 0 : (L == 4 ? 1 : 2);
-    if (c->profiling) HIPCHK(c, hipEventRecord(evs[2 * L], st));
-    if (c->pair_prec == 0) {
-      if (L == 0)
-        hipLaunchKernelGGL(k_pair<0>, dim3(grid), dim3(PAIR_THREADS), lds, st, djobs, njobs, edge, ST, QK, part, c->WAe[L], c->WAp[L],
-                           c->vtab[L], c->rtab, tokpos, rpe_dev, um);
-      else
-        hipLaunchKernelGGL(k_pair<1>, dim3(grid), dim3(PAIR_THREADS), lds, st, djobs, njobs, edge, ST, QK, part, c->WAe[L],
-                           L == 5 ? c->WAe[L] : c->WAp[L], c->vtab[L], c->rtab, tokpos, rpe_dev, um);
-    } else if (tiled) {
-      const size_t ldsb = mind_pair_bf_lds_bytes();
-      const u32 *we = c->WBe[L], *wp = L == 5 ? c->WBe[L] : c->WBp[L];
-      const PairJob *jl = L == 5 ? (const PairJob *)ts->jobs5.p : djobs;
-      const int nj = L == 5 ? ts->njobs5 : njobs;
-      const int grid_t = nj < c->n_cu ? nj : c->n_cu;
-#define LAUNCH_T(M, NPV)                                                                                                       \
-  hipLaunchKernelGGL((k_pair_t<M, NPV>), dim3(grid_t), dim3(PAIR_THREADS), ldsb, st, jl, nj, edge, ST, QK, part, we, wp,       \
-                     c->vtab[L], c->rtab, tokpos, rpe_dev, um)
-      if (c->pair_prec == 3) {
-        const u32 *wle = c->WLe[L], *wlp = L == 5 ? c->WLe[L] : c->WLp[L];
-        if (L == 0)
-          hipLaunchKernelGGL(k_pair_t6<0>, dim3(grid_t), dim3(PAIR_THREADS), ldsb, st, jl, nj, edge, ST, QK, part, we, wp, wle, wlp, c->vtab[L], c->rtab,
-                             tokpos, rpe_dev, um);
-        else
-          hipLaunchKernelGGL(k_pair_t6<1>, dim3(grid_t), dim3(PAIR_THREADS), ldsb, st, jl, nj, edge, ST, QK, part, we, wp, wle, wlp, c->vtab[L], c->rtab,
-                             tokpos, rpe_dev, um);
-      } else if (c->pair_prec == 1) { if (L == 0) LAUNCH_T(0, 3); else LAUNCH_T(1, 3); }
-      else { if (L == 0) LAUNCH_T(0, 1); else LAUNCH_T(1, 1); }
-#undef LAUNCH_T
-    } else {
-      const size_t ldsb = mind_pair_bf_lds_bytes();
-      const u32 *we = c->WBe[L], *wp = L == 5 ? c->WBe[L] : c->WBp[L];
-#define LAUNCH_BF(M, NPV)                                                                                                       \
-  hipLaunchKernelGGL((k_pair_bf<M, NPV>), dim3(grid), dim3(PAIR_THREADS), ldsb, st, djobs, njobs, edge, ST, QK, part, we, wp, \
-                     c->vtab[L], c->rtab, tokpos, rpe_dev, um)
-      if (c->pair_prec == 1) { if (L == 0) LAUNCH_BF(0, 3); else LAUNCH_BF(1, 3); }
-      else { if (L == 0) LAUNCH_BF(0, 1); else LAUNCH_BF(1, 1); }
-#undef LAUNCH_BF
-    }
-    if (c->profiling) HIPCHK(c, hipEventRecord(evs[2 * L + 1], st));
-    c->n_pair_launch++;
-    c->pairs_done += (L == 5) ? pairs_l5 : pairs_full;
-    const int mode = 2 | (L < 5 ? 4 : 8) | qsplit;
-    if ((rc = launch_tokens(mode, L + 1))) return rc;
-  }
-  // ---- decoder
-  const int *d_actor_row = (const int *)ts->rows.p;
-  const int *d_actor_scene = d_actor_row + A;
-  const int *d_cls_row = d_actor_row + 2 * A;
-  // the actor part's first half (actor_proj: 85 % of its weights) needs only the fused actor tokens: it runs on the side stream
-  // beside k_dec_scene, the head follows both on the context stream (bit-identical to the one-kernel form)
-  const bool fp32_dec = c->pair_prec == 0 || !c->enc_mfma || A < c->dec_mfma_min;
-  const bool split_dec = fp32_dec && c->side && c->dec_overlap;
-  if (split_dec) {
-    if ((rc = ensure(c, c->dec_h2, (size_t)A * 768 * sizeof(float)))) return rc;
-    HIPCHK(c, hipEventRecord(c->ev_main, st));
-    HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_main, 0));
-    hipLaunchKernelGGL(k_dec_actor<1>, dim3((A + RA - 1) / RA), dim3(DT), mind_dec_actor_lds_bytes(), c->side, x, d_actor_row, d_actor_scene, A,
-                       (const float *)nullptr, (const float *)nullptr, (float *)nullptr, (float *)nullptr, c->decW, (float *)c->dec_h2.p);
-    HIPCHK(c, hipEventRecord(c->ev_side, c->side));
-  }
-  // the scene part: eight workgroups per scene while the whole launch is resident (one workgroup per CU: 158 KB of LDS), else one per scene --
-  // the two kernels give the same bits, so a scene's result does not depend on the size of its batch
-  bool cls_on_side = false;
-  const int mw_blocks = ((Bn + 7) / 8) * 8 * DEC_MW_G;
-  bool mw = c->dec_mw && mw_blocks <= c->n_cu;
-  if (mw) {
-    if (c->dec_abort && *(volatile unsigned *)c->dec_abort) return fail(c, MIND_EHIP, "k_dec_scene_mw: a barrier of an earlier launch timed out (launch not resident)");
-    if (!c->dec_abort) {
-      if (hipHostMalloc((void **)&c->dec_abort, 64, hipHostMallocMapped) != hipSuccess) { c->dec_abort = nullptr; mw = false; }
-      else *c->dec_abort = 0u;
-    }
-    const size_t need_x = (size_t)(c->n_cu / DEC_MW_G) * 2 * 6 * 1536 * sizeof(float), need_b = (size_t)(c->n_cu / DEC_MW_G) * 4 * sizeof(unsigned);
-    if (mw && c->dec_xbuf.cap < need_x) {
-      if ((rc = ensure(c, c->dec_xbuf, need_x))) return rc;
-    }
-    if (mw && c->dec_bars.cap < need_b) {
-      if ((rc = ensure(c, c->dec_bars, need_b))) return rc;
-      HIPCHK(c, hipMemsetAsync(c->dec_bars.p, 0, c->dec_bars.cap, st));        // (once: the barrier resets its arrival count itself)
-    }
-  }
-  if (mw)
-    hipLaunchKernelGGL(k_dec_scene_mw, dim3(mw_blocks), dim3(DT), mind_dec_scene_lds_bytes(), st, x, d_cls_row, (float *)c->cmode.p, out->cls, c->decW, Bn,
-                       (float *)c->dec_xbuf.p, (unsigned *)c->dec_bars.p, c->dec_abort);
-  else if (split_dec && c->dec_cls_side) {
-    // the mode tokens on the context stream, the mode probabilities (the cls head: ~10 us a launch) on the side stream beside the actor part's
-    // head, which needs the tokens only; the caller's next work on the context stream follows both
-    hipLaunchKernelGGL(k_dec_scene_c, dim3(Bn), dim3(DT), mind_dec_scene_lds_bytes(), st, x, d_cls_row, (float *)c->cmode.p, c->decW);
-    HIPCHK(c, hipEventRecord(c->ev_main, st));
-    HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_main, 0));
-    hipLaunchKernelGGL(k_dec_cls, dim3(Bn), dim3(DT), mind_dec_scene_lds_bytes(), c->side, (float *)c->cmode.p, out->cls, c->decW);
-    if (!c->ev_cls) HIPCHK(c, hipEventCreateWithFlags(&c->ev_cls, hipEventDisableTiming));
-    HIPCHK(c, hipEventRecord(c->ev_cls, c->side));
-    cls_on_side = true;
-  } else
-    hipLaunchKernelGGL(k_dec_scene, dim3(Bn), dim3(DT), mind_dec_scene_lds_bytes(), st, x, d_cls_row, (float *)c->cmode.p, out->cls, c->decW);
-  if (c->side) HIPCHK(c, hipStreamWaitEvent(st, c->ev_tgt, 0));      // the decoder's actor part reads the target embedding
-  // actor part of the decoder: the K-split fp32 kernel (a handful of workgroups, bound by the latency of one pass over the weights:
-  // 62 us at 40 agents), or -- opt-in, mind_set_tuning("dec_mfma_min") -- the MFMA kernel (16 agents per workgroup: 104 us at 40
-  // agents, 209 vs 277 us at 13.8 k).  Off by default: a plan's result must not depend on what else is in the batch.
-  if (split_dec) {
-    HIPCHK(c, hipStreamWaitEvent(st, c->ev_side, 0));
-    hipLaunchKernelGGL(k_dec_actor<2>, dim3((A + RA - 1) / RA), dim3(DT), mind_dec_actor_lds_bytes(), st, x, d_actor_row, d_actor_scene, A,
-                       (const float *)c->cmode.p, (const float *)c->tgt_emb.p, out->reg, out->vel, c->decW, (float *)c->dec_h2.p);
-  } else if (fp32_dec)
-    hipLaunchKernelGGL(k_dec_actor<0>, dim3((A + RA - 1) / RA), dim3(DT), mind_dec_actor_lds_bytes(), st, x, d_actor_row, d_actor_scene, A,
-                       (const float *)c->cmode.p, (const float *)c->tgt_emb.p, out->reg, out->vel, c->decW, (float *)nullptr);
-  else if (c->pair_prec == 3 || (c->pair_prec == 1 && c->actor_np == 6))
-    hipLaunchKernelGGL(k_dec_actor_mfma<6>, dim3((A + DM_RA - 1) / DM_RA), dim3(DM_T), mind_dec_actor_mfma_lds_bytes(), st, x, d_actor_row,
-                       d_actor_scene, A, (const float *)c->cmode.p, (const float *)c->tgt_emb.p, out->reg, out->vel, c->decBW);
-  else if (c->pair_prec == 1)
-    hipLaunchKernelGGL(k_dec_actor_mfma<3>, dim3((A + DM_RA - 1) / DM_RA), dim3(DM_T), mind_dec_actor_mfma_lds_bytes(), st, x, d_actor_row,
-                       d_actor_scene, A, (const float *)c->cmode.p, (const float *)c->tgt_emb.p, out->reg, out->vel, c->decBW);
-  else
-    hipLaunchKernelGGL(k_dec_actor_mfma<1>, dim3((A + DM_RA - 1) / DM_RA), dim3(DM_T), mind_dec_actor_mfma_lds_bytes(), st, x, d_actor_row,
-                       d_actor_scene, A, (const float *)c->cmode.p, (const float *)c->tgt_emb.p, out->reg, out->vel, c->decBW);
-  if (cls_on_side) HIPCHK(c, hipStreamWaitEvent(st, c->ev_cls, 0));      // whatever follows on the context stream sees the mode probabilities too
-  if (out->actor_emb || out->cls_emb) {
-    // debug taps: gather fused tokens
-    for (int a = 0; a < A && out->actor_emb; ++a)
-      HIPCHK(c, hipMemcpyAsync(out->actor_emb + (size_t)a * 128, x + (size_t)actor_row[a] * 128, 128 * sizeof(float),
-                               hipMemcpyDeviceToDevice, st));
-    for (int b = 0; b < Bn && out->cls_emb; ++b)
-      HIPCHK(c, hipMemcpyAsync(out->cls_emb + (size_t)b * 128, x + (size_t)cls_row[b] * 128, 128 * sizeof(float),
-                               hipMemcpyDeviceToDevice, st));
-  }
-  HIPCHK(c, hipGetLastError());
-  if (c->profiling && c->ev_defer) {
-    c->pair_ms = 0.f;         // (read by mind_pair_events_resolve behind the plan's last synchronisation)
-  } else if (c->profiling) {
-    HIPCHK(c, hipStreamSynchronize(st));
-    c->pair_ms = 0.f;
-    for (int L = 0; L < c->debug_layers; ++L) {
-      float ms = 0.f;
-      HIPCHK(c, hipEventElapsedTime(&ms, c->ev[2 * L], c->ev[2 * L + 1]));
-      c->pair_ms += ms;
-    }
-    if (c->ev_act0) HIPCHK(c, hipEventElapsedTime(&c->actor_ms, c->ev_act0, c->ev_act1));
-    for (size_t i = 1; i < ev_tok_used; ++i) {
-      if (c->ev_tok_tag[i] < 0) continue;
-      float ms = 0.f;
-      HIPCHK(c, hipEventElapsedTime(&ms, c->ev_tok[i - 1], c->ev_tok[i]));
-      c->tok_stage_ms[c->ev_tok_tag[i]] += ms;
-      c->tok_ms += ms;
-    }
-  }
-  return MIND_OK;
-}
+#include "predict.hip"
 
 // -------------------------------------------------------------------------------------------------
 // tree-iLQR host side

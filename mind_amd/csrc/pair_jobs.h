@@ -42,6 +42,12 @@ static inline void pair_job_range(int tiles, int ns, int s, int *t0, int *t1) {
   *t1 = (int)((long long)tiles * (s + 1) / ns);
 }
 
+// workgroups of a pair-kernel launch over a list of njobs jobs (jobs are dealt wave-major over the workgroups)
+static inline int pair_grid(long long njobs, int n_cu) { return njobs < n_cu ? (int)njobs : n_cu; }
+
+// `lanes` of the deal: batches of eight scenes or more keep all column jobs of a scene on one XCD
+static inline int pair_xcd_lanes(bool xcd_order, int n_scenes, int grid) { return (xcd_order && n_scenes >= 8 && grid % 8 == 0) ? 8 : 1; }
+
 template <class Job>
 static void pair_jobs_deal(std::vector<Job> &jl, int grid, int waves, int lanes) {
   const int slots = grid * waves;

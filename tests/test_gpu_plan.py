@@ -360,7 +360,7 @@ def test_recorded_demo_scenes_branching_weights_whole_run(scene, prec):
     or if the candidate whose cost disagrees is one where this solver's OWN answer moves by more than the parity tolerance
     when its inputs are perturbed by their rounding resolution (the criterion of the plain-weights whole-run test).  The cycles of
     either kind are pinned (tests/golden/waived_cycles.json): none can silently join or leave them.
-    Both arithmetics of the predictor: the default (bf16x3) and fp32 throughout, the reference's own precision."""
+    Three arithmetics of the predictor: the default (bf16x6), the opt-in bf16x3, and fp32 throughout, the reference's own precision."""
     sys.path.insert(0, ROOT)
     from bench import WORKLOADS, make_closed_loop
     pl, sim, w = make_closed_loop(dict(WORKLOADS[scene]), scripted=False, ckpt="formula_branching:20240121")

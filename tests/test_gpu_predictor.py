@@ -456,3 +456,31 @@ def test_tile_native_edge_tensor_equals_the_oracles(a, l, B, seed, hip_predictor
                 assert d.max() < 2e-4, (k, b, d.max())
     finally:
         hip_predictor.debug_set_layers(6)
+
+
+@pytest.mark.parametrize("knobs,restore", [({}, {}), ({"tok_mfma": 1}, {"tok_mfma": 0}), ({"actor_f32_min": 0}, {"actor_f32_min": 1 << 30})])
+@pytest.mark.parametrize("prec", ["f32", "bf16x3", "bf16", "bf16x6"])
+@pytest.mark.parametrize("a,l,B", [(3, 4, 1), (17, 30, 3)])
+def test_launches_are_the_ones_pred_choose_records(a, l, B, prec, knobs, restore, hip_predictor):
+    """What a call launched (mind_last_actor_stats, mind_last_token_stats, mind_last_fusion_stats) against the record of pred_choose for the
+    same knobs, arithmetic and scene sizes on this device's CU count (mind_debug_predict_choice: the function mind_predict_batch decides with)."""
+    from mind_amd._lib import predict_choice
+    n_cu = torch.cuda.get_device_properties(0).multi_processor_count
+    d = predict_choice(knobs, prec, [(a, l)] * B, n_cu=n_cu)
+    before = hip_predictor.pair_precision()
+    try:
+        hip_predictor.set_pair_precision(prec)
+        for k, v in knobs.items():
+            hip_predictor.set_tuning(k, v)
+        out = hip_predictor.predict_numpy_batch(predictor_batch(a, l, B, seed=4))
+        actor, tok, fusion = hip_predictor.last_actor_stats(), hip_predictor.last_token_stats(), hip_predictor.fusion_stats()
+    finally:
+        for k, v in restore.items():
+            hip_predictor.set_tuning(k, v)
+        hip_predictor.set_pair_precision(before)
+    assert torch.isfinite(out["reg"]).all()
+    assert (actor["layerwise"], actor["launches"], actor["chunks"]) == (int(d["actor_form"] == 3), d["actor_launches"], d["actor_chunks"]) == (0, 1, 1)
+    assert d["actor_form"] == (1 if prec == "f32" or "actor_f32_min" in knobs else 2)
+    assert (tok["layerwise"], tok["launches"], tok["chunks"]) == (d["tok_lw"], 7 * d["n_runs"], d["tok_chunks"]) == (0, 7, 0)
+    assert d["runs"] == [(0, B * (a + l + 1), int("tok_mfma" in knobs), 0, int("tok_mfma" not in knobs), int("tok_mfma" not in knobs))]
+    assert fusion[0] == 6
