@@ -203,6 +203,26 @@ int mind_debug_pair_schedule(const int *scene_tokens, const int *scene_actors, i
 int mind_debug_predict_choice(const char *const *knob_names, const int *knob_values, int n_knobs, int pair_prec, int n_cu, int have_side,
                               const int *scene_actors, const int *scene_lanes, int n_scenes, long long *out, int cap);
 
+/* host-only helper (tests): how a tree-iLQR call launches and what index tables it uploads -- the records of il_choose and il_tree_tables
+ * (mind_amd/csrc/ilqr_choice.h), the two functions the solver itself decides with -- for a fresh context's knobs with the n_knobs (name,
+ * value) pairs of mind_set_tuning applied ("ilqr_*" only), a device of n_cu compute units, the call's mode (bit 0: generic mode of
+ * mind_ilqr_solve_fields, bit 1: mind_cost_eval, bit 2: two fits in one launch -- no decision depends on it today) and n_trees cost trees of
+ * n_nodes[t] nodes whose parent arrays lie one behind the other in `parents`.  out receives up to cap long long of the record: a header
+ *   [0] header length (16)  [1] trees  [2] kernel form (0 one workgroup per tree, 1 wide trees: G workgroups share a tree, 2 narrow trees: a
+ *   master + followers take a tree's Levenberg-Marquardt slots)  [3] G (1 outside form 1)  [4] GS (workgroups per tree that take slots)
+ *   [5] derivative speculators per tree (0, 1)  [6] sets of per-slot arrays in the arena  [7] workgroups of the launch
+ *   [8] workgroups_per_tree as mind_last_ilqr_stats reports it  [9] the kernel writes its results to the host staging itself
+ *   [10] ... and marks each tree when it is complete  [11] "ilqr_test_starve" lets the followers of form 2 leave at once  [12]..[15] 0
+ * and per tree {nodes, levels nl, segments nseg, segment levels nsl, widest segment level maxls, forward steps nfs}, the lengths of its
+ * fourteen tables and then the tables themselves: level starts, level nodes, child starts, child list, segment starts, segment nodes,
+ * segment-level starts, segment-level segments, segment records (16 ints each: s0, s1, last node, first node, node before the last, the last
+ * node's child count, its child-list start, 0, its first six children, 0, 0), step starts, step items (8 ints each: q0, q1, first node, second
+ * node, the first node's parent, 0, 0, 0), the items' q1, step node starts, step nodes.  Returns the length of the full record, or
+ * MIND_EINVAL for an unknown knob, a tree without nodes, a null pointer, or a node whose parent is not below it (node 0: not -1); bad (two
+ * ints, may be null) then names that tree and node, and is {-1, -1} otherwise.  Needs no GPU and no context. */
+int mind_debug_ilqr_plan(const char *const *knob_names, const int *knob_values, int n_knobs, int n_cu, int mode, int n_trees, const int *n_nodes,
+                         const int32_t *parents, long long *out, int cap, int *bad);
+
 /* host-only helper (tests): the launch list of the layer-wise batched ActorNet for a call of n_actors actors in the arithmetic np (6, 3, 1 =
  * bf16x6, bf16x3, bf16; anything else: MIND_EINVAL) with `chunk` actors per chunk (0 = the default) -- exactly what mind_predict_batch issues.
  * out_launches receives up to cap records of 16 long long in issue order: {stage 0..25 (-1: the input split), kind (0 input split, 1 conv,

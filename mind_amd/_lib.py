@@ -161,7 +161,7 @@ class PlannerOut(C.Structure):     # mind_planner_out
 EXPORTS = ["mind_ctx_create", "mind_ctx_destroy", "mind_last_error_string", "mind_ctx_synchronize",
            "mind_weights_load", "mind_predict_batch", "mind_last_fusion_stats", "mind_last_actor_stats", "mind_debug_actor_lw_plan", "mind_last_token_stats", "mind_last_token_stage_ms", "mind_debug_token_lw_plan", "mind_set_profiling",
            "mind_ilqr_solve_trees", "mind_ilqr_contingency", "mind_ilqr_solve_fields", "mind_cost_eval", "mind_lane_dist_field", "mind_aime_world", "mind_aime_rebase", "mind_debug_set_layers",
-           "mind_debug_read", "mind_set_pair_precision", "mind_get_pair_precision", "mind_debug_pack_bfrag", "mind_debug_pack_conv_frag", "mind_debug_pair_schedule", "mind_debug_predict_choice", "mind_set_tuning", "mind_last_ilqr_stats", "mind_aime_plan", "mind_last_ilqr_profile", "mind_eval_traj_trees", "mind_last_ilqr_trace", "mind_ilqr_contingency_begin", "mind_ilqr_finish", "mind_fill_tracks", "mind_ilqr_contingency_begin_plan", "mind_debug_trig", "mind_aime_plan_begin", "mind_aime_plan_poll", "mind_aime_plan_finish", "mind_ctx_busy", "mind_ilqr_finish_plan",
+           "mind_debug_read", "mind_set_pair_precision", "mind_get_pair_precision", "mind_debug_pack_bfrag", "mind_debug_pack_conv_frag", "mind_debug_pair_schedule", "mind_debug_predict_choice", "mind_debug_ilqr_plan", "mind_set_tuning", "mind_last_ilqr_stats", "mind_aime_plan", "mind_last_ilqr_profile", "mind_eval_traj_trees", "mind_last_ilqr_trace", "mind_ilqr_contingency_begin", "mind_ilqr_finish", "mind_fill_tracks", "mind_ilqr_contingency_begin_plan", "mind_debug_trig", "mind_aime_plan_begin", "mind_aime_plan_poll", "mind_aime_plan_finish", "mind_ctx_busy", "mind_ilqr_finish_plan",
            "mind_set_exchange", "mind_last_exchange_stats",
            "mind_loop_create", "mind_loop_destroy", "mind_loop_reset", "mind_loop_advance", "mind_loop_state", "mind_loop_last_plan", "mind_loop_export",
            "mind_planner_create", "mind_planner_destroy", "mind_planner_reset", "mind_planner_observe", "mind_planner_set_lanes", "mind_planner_set_target_lane",
@@ -239,6 +239,8 @@ def load():
     lib.mind_debug_pair_schedule.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]
     lib.mind_debug_predict_choice.argtypes = [C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                               C.c_int, C.POINTER(C.c_longlong), C.c_int]
+    lib.mind_debug_ilqr_plan.argtypes = [C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int32),
+                                         C.POINTER(C.c_longlong), C.c_int, C.POINTER(C.c_int)]
     lib.mind_debug_trig.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double)]
     lib.mind_debug_pack_conv_frag.argtypes = [C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_size_t]
     lib.mind_debug_set_layers.argtypes = [C.c_void_p, C.c_int]
@@ -296,6 +298,42 @@ def predict_choice(knobs, prec, scenes, n_cu=256, have_side=True):
     assert 0 < n <= cap and out[0] == 32 and n == 32 + 6 * out[1], n
     d = dict(zip(PRED_CHOICE_FIELDS, out[:30]))
     d["runs"] = [tuple(out[32 + 6 * i:38 + 6 * i]) for i in range(out[1])]
+    return d
+
+
+# header and per-tree tables of mind_debug_ilqr_plan's record (include/mind_hip.h)
+ILQR_PLAN_FIELDS = ("header", "n_trees", "form", "G", "GS", "spec", "nslot", "grid", "workgroups_per_tree", "host_out", "early", "starve_followers")
+ILQR_TREE_FIELDS = ("M", "nl", "nseg", "nsl", "maxls", "nfs")
+ILQR_TREE_TABLES = ("level_start", "level_nodes", "child_start", "child_list", "seg_start", "seg_nodes", "slevel_start", "slevel_segs", "seg_rec",
+                    "fstep_start", "fstep_items", "fstep_q1", "fstep_nstart", "fstep_nodes")
+
+
+def ilqr_plan(knobs, parents, n_cu=256, generic=False, evaluate=False, two_fits=False):
+    """il_choose's record and il_tree_tables' tables (mind_debug_ilqr_plan; no GPU) for mind_set_tuning pairs `knobs` and the cost trees whose
+    parent arrays are `parents`: dict of ILQR_PLAN_FIELDS + "trees" = [dict of ILQR_TREE_FIELDS and ILQR_TREE_TABLES (lists of ints), ...];
+    {"bad": (tree, node)} for a node whose parent is not below it; None when rejected otherwise"""
+    lib = load()
+    names = (C.c_char_p * max(1, len(knobs)))(*[k.encode() for k in knobs])
+    vals = (C.c_int * max(1, len(knobs)))(*[int(v) for v in knobs.values()])
+    nn = (C.c_int * len(parents))(*[len(p) for p in parents])
+    flat = [int(v) for p in parents for v in p]
+    par = (C.c_int32 * max(1, len(flat)))(*flat)
+    bad = (C.c_int * 2)()
+    mode = int(generic) | int(evaluate) << 1 | int(two_fits) << 2
+    n = lib.mind_debug_ilqr_plan(names, vals, len(knobs), n_cu, mode, len(parents), nn, par, None, 0, bad)
+    if n == MIND_EINVAL:
+        return {"bad": (bad[0], bad[1])} if bad[0] >= 0 else None
+    out = (C.c_longlong * n)()
+    assert lib.mind_debug_ilqr_plan(names, vals, len(knobs), n_cu, mode, len(parents), nn, par, out, n, bad) == n and out[0] == 16
+    d = dict(zip(ILQR_PLAN_FIELDS, out[:12]))
+    d["trees"], o = [], 16
+    for _ in parents:
+        tr = dict(zip(ILQR_TREE_FIELDS, out[o:o + 6]))
+        lens, o = out[o + 6:o + 20], o + 20
+        for name, ln in zip(ILQR_TREE_TABLES, lens):
+            tr[name], o = list(out[o:o + ln]), o + ln
+        d["trees"].append(tr)
+    assert o == n
     return d
 
 

@@ -35,7 +35,7 @@ struct PlNode {
   float tgt[22];
 };
 
-int pl_pin(mind_ctx *c, int which, size_t bytes) {      // (declared ahead of ilqr_impl in mind_hip.hip)
+int pl_pin(mind_ctx *c, int which, size_t bytes) {      // (declared ahead of il_solve in ilqr_host.hip)
   if (bytes <= c->pl_pin_cap[which]) return MIND_OK;
   if (c->pl_pin[which]) (void)hipHostFree(c->pl_pin[which]);
   c->pl_pin[which] = nullptr; c->pl_pin_cap[which] = 0;
@@ -216,7 +216,7 @@ extern "C" int mind_aime_plan(mind_ctx *c, const mind_aime_plan_in *in, mind_aim
   }
   const float *droot = (const float *)c->pl_root.p;
   if ((rc = ensure(c, c->pl_lf, (size_t)l * 128 * sizeof(float)))) return rc;
-  // the lane-distance field of the contingency solves this plan will begin: everything it depends on is known now (ilqr_impl adopts it)
+  // the lane-distance field of the contingency solves this plan will begin: everything it depends on is known now (il_solve adopts it)
   if (in->solve_cfg_full && in->solve_x0 && in->solve_lane && in->solve_n_lane_pts >= 2 && !(c->xfn && (c->xw > 1 || c->xforce)) &&
       (rc = il_field_prepare(c, in->solve_cfg_full, in->solve_x0, in->solve_lane, in->solve_n_lane_pts, c->pl_copy)))
     return rc;
@@ -818,7 +818,7 @@ extern "C" int mind_aime_plan(mind_ctx *c, const mind_aime_plan_in *in, mind_aim
     if ((rc = pl_pin(c, 2, n_res * sizeof(float)))) return rc;
     float *hp = (float *)c->pl_pin[2];
     if (want_solves) {
-      // k_ilqr right behind k_aime_flat: the cost trees' agent arrays stay where that kernel wrote them (ilqr_impl reads them on the device)
+      // k_ilqr right behind k_aime_flat: the cost trees' agent arrays stay where that kernel wrote them (il_solve reads them on the device)
       // and the host builds the solver's tables while it runs.  What only the CALLER wants -- the finished branches' rows (k_aime_gather) and the
       // plan's read-back (rows | flat means | sigmas: the tree objects, the candidate evaluation) -- is queued on the copy stream AFTER the
       // solves have been launched: beside k_ilqr on the device, and behind its launch on the host (the five calls stood 10 us in front of it).

@@ -314,10 +314,11 @@ int cycle_speculate(mind_cycle *L, const double *x0) {
     T.n_agents = 1; T.agent_mean = L->zero_mean.data(); T.agent_cov = L->zero_cov.data();
   }
   L->spec_xs.resize(M * 6); L->spec_us.resize(M * 2); L->spec_st.resize(n);
-  sc->il_begin_only = true;
-  const int rc = ilqr_impl(sc, &L->cfg_warm, nullptr, trees.data(), n, x0, L->solve_lane.data(), d.solve_n_lane_pts, d.target_vel, 0, nullptr,
-                           L->spec_xs.data(), L->spec_us.data(), L->spec_st.data(), nullptr);
-  sc->il_begin_only = false;
+  IlqrCall q;
+  q.cfg = &L->cfg_warm; q.trees = trees.data(); q.n_trees = n; q.x0 = x0; q.lane = L->solve_lane.data(); q.n_lane_pts = d.solve_n_lane_pts;
+  q.target_vel = d.target_vel; q.xs = L->spec_xs.data(); q.us = L->spec_us.data(); q.stats = L->spec_st.data();
+  q.begin_only = true;
+  const int rc = il_solve(sc, q);
   if (rc != MIND_OK) return MIND_OK;                 // (the in-line path then computes -- or reports -- the same thing)
   L->spec_pending = true;
   L->warm_speculated += n;
@@ -375,7 +376,7 @@ int cycle_solve_speculated(mind_cycle *L, const double *x0) {
   if (!misses.empty()) {          // both fits, as without speculation: beside the hits' full fits when there are any
     L->miss_xs.resize(Mm * 6); L->miss_us.resize(Mm * 2); L->miss_stw.resize(misses.size()); L->miss_stf.resize(misses.size());
     if (!hits.empty()) {
-      (void)mind_set_tuning(sc, "ilqr_wgs", c->ilqr_wgs);
+      (void)mind_set_tuning(sc, "ilqr_wgs", c->it.ilqr_wgs);
       rc = mind_ilqr_contingency_begin(sc, &L->cfg_warm, &L->cfg_full, misses.data(), (int)misses.size(), x0, L->solve_lane.data(), d.solve_n_lane_pts, d.target_vel,
                                        L->miss_xs.data(), L->miss_us.data(), L->miss_stw.data(), L->miss_stf.data());
       if (rc) return fail(c, rc, "%s: %s", L->who, sc->err.c_str());

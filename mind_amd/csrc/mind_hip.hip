@@ -30,6 +30,7 @@
 #include "ilqr_kernels.hip"
 #include "pair_jobs.h"
 #include "pred_choice.h"
+#include "ilqr_choice.h"
 #include "aime_kernels.hip"
 
 namespace {
@@ -107,27 +108,10 @@ struct mind_ctx {
   TableSet tabs[MIND_TABLE_SETS];
   long long tab_clock = 0;
   long long n_table_hits = 0;
-  // nodes per forward step of a narrow tree's line search ("ilqr_chunk"; 0: whole segments, the default).  Measured on the recorded
-  // demo_1 loop: chunks of 6 / 8 / 12 nodes cost 2.10 / 2.05 / 2.04 ms per launch against 1.99 for whole segments (round 3: the cost
-  // waves shared the SIMDs' float64 pipe with five state-chain waves); with the chains of a level packed into ONE wave and the cost
-  // chunks kept off its SIMD (round 4) still 2.12 / 2.00 / 2.02 against 1.89: every extra forward step pays a rollout prologue (parent
-  // state, first operands: two dependent round trips) and a barrier, more than the shorter cost tail saves (profiles/r04x_*)
-  int ilqr_chunk = 0;
-  // wide cost trees: workgroups per tree (halved until every workgroup of the launch is resident; cfg4 full tree, six trees per launch:
-  // 8.33 / 7.40 / 7.37 / 7.63 ms per plan with 8 / 16 / 24 / 32, profiles/r03an), node count from which they are used (mind_set_tuning)
-  int ilqr_wgs = 16, ilqr_multi_min = 192, ilqr_wgs_big = 32, ilqr_big_min = 12288;
-  // narrow cost trees (below ilqr_multi_min nodes): workgroups per tree that take the fit's Levenberg-Marquardt slots (k_ilqr<GEN, 2>: a master +
-  // ilqr_slots - 1 followers, one slot each; 1 = everything in one workgroup).  "ilqr_slots" / MIND_ILQR_SLOTS
-  int ilqr_slots = 10;
-  // ... and one more workgroup per tree that differentiates a pass's first candidate while the master prices the candidates (il_speculate; the
-  // master swaps derivative sets instead of running its derivative pass when that candidate is the accepted one).  "ilqr_spec_deriv" / MIND_ILQR_SPEC_DERIV
-  bool ilqr_spec_deriv = true;
+  IlqrTuning it;       // the tree-iLQR solver's launch knobs (ilqr_choice.h)
   // uploads of at most this many bytes from the context's page-locked staging run as a kernel on the consumer's queue (pl_upload; 0 = always
   // hipMemcpyAsync).  "upload_kernel_max" / MIND_UPLOAD_KERNEL_MAX
   int upload_kernel_max = 1 << 20;
-  // tree-iLQR launches of at most this many nodes in all write their results (xs, us, statistics) to the host staging themselves at the kernel's
-  // end instead of two copies behind it (0 = always copies).  "ilqr_host_out_max" / MIND_ILQR_HOST_OUT_MAX
-  long ilqr_host_out_max = 4096;
   // mind_aime_plan, unsharded: k_aime_branch writes a round's decisions to the host staging itself (no copy behind it).  "dec_mirror" / MIND_DEC_MIRROR
   bool dec_mirror = true;
   // ... and its pruning decisions + branch-time bits come from one launch (k_aime_select_branch) instead of two.  "glue_fused" / MIND_GLUE_FUSED
@@ -140,10 +124,12 @@ struct mind_ctx {
   // ... and the scene tables of a round of at most AIME_SMALL scenes per chunk travel in the glue kernels' arguments (no upload between the
   // predictor and k_aime_world).  "tab_small" / MIND_TAB_SMALL
   bool tab_small = true;
-  // host tables of a tree-iLQR call (ilqr_impl): kept between calls so that a planning cycle does not allocate a hundred small vectors
-  struct IlScratch { std::vector<std::vector<int>> vv[14]; std::vector<int> tmp[6]; std::vector<double> hD; std::vector<float> hF; std::vector<int> hI; } il_scr;
+  // host side of a tree-iLQR call (ilqr_host.hip), kept between calls so that a planning cycle does not allocate a hundred small vectors: the
+  // trees' index tables and the image of the arena's uploaded doubles / floats / ints
+  std::vector<IlTables> il_tab;
+  struct IlImage { std::vector<double> hD; std::vector<float> hF; std::vector<int> hI; } il_img;
   std::vector<std::vector<int>> pl_scr_kids; std::vector<float> pl_scr_pr; std::vector<int> pl_scr_i[3];      // mind_aime_plan's flattening scratch
-  // the pending tree-iLQR launch writes its results to the host itself and marks every tree when it is complete (ilqr_impl `early`): where, and
+  // the pending tree-iLQR launch writes its results to the host itself and marks every tree when it is complete (IlqrChoice::early): where, and
   // the word's value that means "complete" for THIS launch.  Valid between the launch and its mind_ilqr_finish.
   struct IlEarly { const double *xs = nullptr, *us = nullptr; volatile unsigned *done = nullptr; unsigned gen = 0; int n_trees = 0; long nodes = 0; } il_early;
   unsigned il_gen = 0;
@@ -175,7 +161,7 @@ struct mind_ctx {
   hipEvent_t ev_pl = nullptr, ev_tab = nullptr, ev_root = nullptr;
   // the lane-distance field of a plan's contingency solves (gen_dist_field: a function of the ego position, the grid and the target lane --
   // all known when the plan starts), computed on the side stream beside the plan's first round instead of between its last decisions and
-  // k_ilqr (il_field_prepare; adopted by ilqr_impl when grid and lane are the ones it was made for)
+  // k_ilqr (il_field_prepare; adopted by il_solve when grid and lane are the ones it was made for)
   DevBuf il_field;
   void *il_field_pin = nullptr;
   size_t il_field_pin_cap = 0;
@@ -218,16 +204,13 @@ struct mind_ctx {
   hipEvent_t ev_il0 = nullptr, ev_il1 = nullptr;   // around the tree-iLQR launch of the last call (profiling on)
   float ilqr_ms = 0.f;
   int ilqr_multi = 0, ilqr_trees = 0;
-  bool ilqr_test_starve = false;
   // per-iteration traces of the last tree-iLQR call (mind_last_ilqr_trace): device address per tree, rows per phase, iterations run
   std::function<int()> il_finish;     // the pending half of a call begun with mind_ilqr_contingency_begin
   bool il_finish_owned = false;       // ... whose outputs are library buffers (the solves a plan began itself): may be drained and dropped
   // the cost trees' agent means / sigmas of the context's last plan where k_aime_flat wrote them (device): a tree-iLQR call on the plan's own
   // trees (mind_ilqr_contingency_begin_plan) reads them there instead of taking them through the host
   const float *pl_dev_fmean = nullptr, *pl_dev_fcov = nullptr;
-  bool il_use_dev_flat = false;
   hipEvent_t ev_rows = nullptr;
-  bool il_begin_only = false;
   std::vector<const double *> il_trace_dev;
   std::vector<int> il_trace_its;      // [tree][phase 2]
   int il_trace_cap = 0, il_trace_phases = 0;
@@ -374,18 +357,18 @@ extern "C" int mind_ctx_create(int device, void *stream, mind_ctx **out) {
   if (const char *te = getenv("MIND_PL_TAB_SIDE")) c->pl_tab_side = !(te[0] == '0');
   (void)hipFuncSetAttribute((const void *)k_token_mfma<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_token_mfma_lds_bytes());
   (void)hipFuncSetAttribute((const void *)k_token_mfma<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_token_mfma_lds_bytes());
-  if (const char *we = getenv("MIND_ILQR_CHUNK")) c->ilqr_chunk = atoi(we) < 0 ? 0 : atoi(we);
   if (const char *ce = getenv("MIND_PLAN_CHUNK_MB")) { const long v = atol(ce); if (v > 0) c->plan_chunk_mb = v; }
-  if (const char *we = getenv("MIND_ILQR_WGS")) { const int v = atoi(we); c->ilqr_wgs = v < 1 ? 1 : (v > 32 ? 32 : v); }
-  if (const char *we = getenv("MIND_ILQR_SPEC_DERIV")) c->ilqr_spec_deriv = atoi(we) != 0;
   if (const char *we = getenv("MIND_TAB_SMALL")) c->tab_small = atoi(we) != 0;
   if (const char *we = getenv("MIND_TAB_HOST_MAX")) c->tab_host_max = std::max(0, atoi(we));
   if (const char *we = getenv("MIND_EARLY_EVAL")) c->early_eval = atoi(we) != 0;
   if (const char *we = getenv("MIND_GLUE_FUSED")) c->glue_fused = atoi(we) != 0;
   if (const char *we = getenv("MIND_DEC_MIRROR")) c->dec_mirror = atoi(we) != 0;
-  if (const char *we = getenv("MIND_ILQR_HOST_OUT_MAX")) c->ilqr_host_out_max = std::max(0, atoi(we));
   if (const char *we = getenv("MIND_UPLOAD_KERNEL_MAX")) c->upload_kernel_max = std::max(0, atoi(we));
-  if (const char *we = getenv("MIND_ILQR_SLOTS")) { const int v = atoi(we); c->ilqr_slots = v < 1 ? 1 : (v > IL_SLOTS ? IL_SLOTS : v); }
+  // (the same clamps as mind_set_tuning: one function sets a knob)
+  const char *const il_env[][2] = {{"MIND_ILQR_CHUNK", "ilqr_chunk"}, {"MIND_ILQR_WGS", "ilqr_wgs"}, {"MIND_ILQR_SPEC_DERIV", "ilqr_spec_deriv"},
+                                   {"MIND_ILQR_HOST_OUT_MAX", "ilqr_host_out_max"}, {"MIND_ILQR_SLOTS", "ilqr_slots"}};
+  for (const auto &e : il_env)
+    if (const char *we = getenv(e[0])) (void)ilqr_tuning_set(c->it, e[1], atoi(we));
   (void)hipFuncSetAttribute((const void *)k_dec_scene, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_dec_scene_lds_bytes());
   (void)hipFuncSetAttribute((const void *)k_dec_scene_mw, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_dec_scene_lds_bytes());
   (void)hipFuncSetAttribute((const void *)k_dec_scene_c, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_dec_scene_lds_bytes());
@@ -461,23 +444,15 @@ extern "C" int mind_set_tuning(mind_ctx *c, const char *name, int value) {
   if (!c || !name) return MIND_EINVAL;
   const std::string n = name;
   if (pred_tuning_set(c->pt, name, value)) return MIND_OK;      // the predictor's knobs (pred_choice.h)
+  if (ilqr_tuning_set(c->it, name, value)) return MIND_OK;      // the tree-iLQR solver's (ilqr_choice.h)
   if (n == "plan_chunk_mb") c->plan_chunk_mb = value < 1 ? 1 : value;
   else if (n == "pl_tab_side") c->pl_tab_side = value != 0;
-  else if (n == "ilqr_chunk") c->ilqr_chunk = value < 0 ? 0 : (int)value;
-  else if (n == "ilqr_wgs") c->ilqr_wgs = value < 1 ? 1 : (value > 32 ? 32 : value);
-  else if (n == "ilqr_multi_min") c->ilqr_multi_min = value;
-  else if (n == "ilqr_wgs_big") c->ilqr_wgs_big = value < 1 ? 1 : (value > 32 ? 32 : value);
-  else if (n == "ilqr_big_min") c->ilqr_big_min = value;
-  else if (n == "ilqr_spec_deriv") c->ilqr_spec_deriv = value != 0;
   else if (n == "tab_small") c->tab_small = value != 0;
   else if (n == "tab_host_max") c->tab_host_max = value < 0 ? 0 : value;
   else if (n == "early_eval") c->early_eval = value != 0;
   else if (n == "glue_fused") c->glue_fused = value != 0;
   else if (n == "dec_mirror") c->dec_mirror = value != 0;
-  else if (n == "ilqr_host_out_max") c->ilqr_host_out_max = value < 0 ? 0 : value;
   else if (n == "upload_kernel_max") c->upload_kernel_max = value < 0 ? 0 : value;
-  else if (n == "ilqr_slots") c->ilqr_slots = value < 1 ? 1 : (value > IL_SLOTS ? IL_SLOTS : value);
-  else if (n == "ilqr_test_starve") c->ilqr_test_starve = value != 0;   // tests: launch a wide tree without its last workgroups
   else return fail(c, MIND_EINVAL, "mind_set_tuning: unknown knob '%s'", name);
   return MIND_OK;
 }
@@ -1247,694 +1222,7 @@ extern "C" int mind_weights_load(mind_ctx *c, const mind_tensor_desc *tensors, i
 // -------------------------------------------------------------------------------------------------
 // tree-iLQR host side
 // -------------------------------------------------------------------------------------------------
-// grid coordinates exactly as numpy builds them (ilqr/utils.py:7-13): linspace(0, size, n) + offset
-static void il_make_grid(int W, int H, double res, const double *ego_xy, double *gx, double *gy, double &offx, double &offy) {
-  const double fsx = (double)(W - 1) * res, fsy = (double)(H - 1) * res;
-  offx = ego_xy[0] - 0.5 * fsx; offy = ego_xy[1] - 0.5 * fsy;
-  const double sx = fsx / (double)(W - 1), sy = fsy / (double)(H - 1);
-  for (int i = 0; i < W; ++i) gx[i] = (double)i * sx + 0.0;
-  gx[W - 1] = fsx;
-  for (int i = 0; i < H; ++i) gy[i] = (double)i * sy + 0.0;
-  gy[H - 1] = fsy;
-  for (int i = 0; i < W; ++i) gx[i] += offx;
-  for (int i = 0; i < H; ++i) gy[i] += offy;
-}
-
-// gen_dist_field (ilqr/utils.py:5-22): distance of every grid centroid to the polyline
-extern "C" int mind_lane_dist_field(mind_ctx *c, const double *ego_xy, const double *lane, int n_pts, int W, int H,
-                                    double res, double *offset, double *gx, double *gy, double *dist) {
-  if (!c || !ego_xy || !lane || n_pts < 2 || W < 2 || H < 2 || !(res > 0) || !offset || !gx || !gy || !dist)
-    return fail(c, MIND_EINVAL, "mind_lane_dist_field: bad argument");
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t st = c->stream;
-  il_make_grid(W, H, res, ego_xy, gx, gy, offset[0], offset[1]);
-  const size_t nd = (size_t)W + H + 2 * (size_t)n_pts + (size_t)W * H;
-  int rc;
-  if ((rc = ensure(c, c->ilqr_dev, nd * sizeof(double)))) return rc;
-  double *d = (double *)c->ilqr_dev.p;
-  HIPCHK(c, hipMemcpyAsync(d, gx, W * sizeof(double), hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(d + W, gy, H * sizeof(double), hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(d + W + H, lane, 2 * (size_t)n_pts * sizeof(double), hipMemcpyHostToDevice, st));
-  double *out = d + W + H + 2 * (size_t)n_pts;
-  hipLaunchKernelGGL(k_lane_field, dim3((W * H + 255) / 256), dim3(256), 0, st, d, d + W, W, H, d + W + H, n_pts, out, 0);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(dist, out, (size_t)W * H * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  return MIND_OK;
-}
-
-struct IlqrEvalReq { int nq; const int32_t *node; const double *x, *u; double *out; };
-namespace { int pl_pin(mind_ctx *c, int which, size_t bytes); }     // page-locked staging buffers of the context (aime_plan.hip)
-
-// Upload of a few ten KB from the context's page-locked staging (hipHostMalloc: mapped into the device's address space) as a KERNEL on the
-// consumer's own queue: the device reads the host buffer over PCIe (a few us) and the consumer follows back to back.  hipMemcpyAsync sends
-// copies above its blit threshold to the SDMA engine, whose hand-over to the compute queue stood 10-15 us on either side of the copy in the
-// plan's timeline (root scene: 60 KB, the solver's tables: 40 KB; profiles/r06az_timeline.txt).  16-byte words; large uploads stay copies.
-typedef unsigned up_u4 __attribute__((ext_vector_type(4)));
-__global__ __launch_bounds__(256) void k_upload(const up_u4 *__restrict__ src, up_u4 *__restrict__ dst, size_t n16) {
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) dst[i] = __builtin_nontemporal_load(src + i);
-}
-static int pl_upload(mind_ctx *c, void *dst, const void *pinned_src, size_t bytes, hipStream_t s) {
-  if (!bytes) return MIND_OK;
-  if (c->upload_kernel_max > 0 && bytes <= (size_t)c->upload_kernel_max && bytes % 16 == 0 && (uintptr_t)dst % 16 == 0 && (uintptr_t)pinned_src % 16 == 0) {
-    const size_t n16 = bytes / 16;
-    hipLaunchKernelGGL(k_upload, dim3((unsigned)std::min<size_t>((n16 + 255) / 256, 256)), dim3(256), 0, s, (const up_u4 *)pinned_src, (up_u4 *)dst, n16);
-    HIPCHK(c, hipGetLastError());
-    return MIND_OK;
-  }
-  HIPCHK(c, hipMemcpyAsync(dst, pinned_src, bytes, hipMemcpyHostToDevice, s));
-  return MIND_OK;
-}
-
-// Shared host side of mind_ilqr_solve_trees / mind_ilqr_solve_fields / mind_cost_eval: build the device
-// arena, then either run the solver (ev == nullptr) or evaluate node costs at the requested points.
-// grid != nullptr selects the generic mode (materialised per-node fields + per-node weights).
-// the field of the NEXT tree-iLQR call on this context, ahead of it: grid + lane up, k_lane_field on `s`, an event behind it
-static int il_field_prepare(mind_ctx *c, const mind_ilqr_cfg *cfg, const double *x0, const double *lane, int n_lane_pts, hipStream_t s) {
-  c->il_field_valid = false;
-  const int W = cfg->grid_w, H = cfg->grid_h;
-  if (W < 3 || H < 3 || n_lane_pts < 2 || !(cfg->grid_res > 0)) return MIND_OK;        // (the call itself reports bad arguments)
-  const size_t nin = (size_t)W + H + 2 * (size_t)n_lane_pts, nd = nin + (size_t)W * H;
-  int rc;
-  if ((rc = ensure(c, c->il_field, nd * sizeof(double)))) return rc;
-  if (c->il_field_pin_cap < nin * sizeof(double)) {
-    if (c->il_field_pin) (void)hipHostFree(c->il_field_pin);
-    c->il_field_pin = nullptr; c->il_field_pin_cap = 0;
-    if (hipHostMalloc(&c->il_field_pin, 2 * nin * sizeof(double), hipHostMallocDefault) != hipSuccess) { c->il_field_pin = nullptr; return MIND_OK; }
-    c->il_field_pin_cap = 2 * nin * sizeof(double);
-  }
-  if (!c->ev_field) HIPCHK(c, hipEventCreateWithFlags(&c->ev_field, hipEventDisableTiming));
-  double *h = (double *)c->il_field_pin, ox, oy;
-  il_make_grid(W, H, cfg->grid_res, x0, h, h + W, ox, oy);
-  memcpy(h + W + H, lane, 2 * (size_t)n_lane_pts * sizeof(double));
-  double *d = (double *)c->il_field.p;
-  HIPCHK(c, hipMemcpyAsync(d, h, nin * sizeof(double), hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(k_lane_field, dim3((W * H + 255) / 256), dim3(256), 0, s, d, d + W, W, H, d + W + H, n_lane_pts, d + nin);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(c->ev_field, s));
-  c->il_field_key[0] = x0[0]; c->il_field_key[1] = x0[1]; c->il_field_key[2] = W; c->il_field_key[3] = H; c->il_field_key[4] = cfg->grid_res;
-  c->il_field_lane.assign(lane, lane + 2 * (size_t)n_lane_pts);
-  c->il_field_valid = true;
-  return MIND_OK;
-}
-
-static int ilqr_impl(mind_ctx *c, const mind_ilqr_cfg *cfg, const mind_field_grid *grid, const mind_cost_tree *trees, int n_trees,
-                     const double *x0, const double *target_lane, int n_lane_pts, double target_vel,
-                     int use_exo, const double *us_init, double *xs, double *us,
-                     mind_ilqr_stats *stats, const IlqrEvalReq *ev,
-                     const mind_ilqr_cfg *cfg2 = nullptr, mind_ilqr_stats *stats2 = nullptr) {
-  // cfg2 != nullptr: two fits in one launch -- (cfg, lane term only) then, from its controls, (cfg2, full cost)
-  const bool gen = grid != nullptr;
-  const int n_phases = cfg2 ? 2 : 1;
-  const int use_exo_first = cfg2 ? 0 : use_exo;
-  if (cfg2) use_exo = 1;
-  if (!c || !cfg || !trees || n_trees <= 0 || !x0) return fail(c, MIND_EINVAL, "iLQR: bad argument");
-  if (c->il_finish) return fail(c, MIND_ESTATE, "a tree-iLQR call begun with mind_ilqr_contingency_begin has not been finished (mind_ilqr_finish)");
-  if (!ev && (!xs || !us)) return fail(c, MIND_EINVAL, "iLQR: null output");
-  if (!gen && (!target_lane || n_lane_pts < 2)) return fail(c, MIND_EINVAL, "iLQR: target lane needs >= 2 points");
-  if (gen) { use_exo = 0; n_lane_pts = 0; }
-  const int W = gen ? grid->W : cfg->grid_w, H = gen ? grid->H : cfg->grid_h;
-  if (W < 3 || H < 3 || cfg->max_iter < 0) return fail(c, MIND_EINVAL, "bad grid / max_iter");
-  if (gen && (!grid->gx || !grid->gy || !(grid->res > 0))) return fail(c, MIND_EINVAL, "bad field grid");
-  for (int t = 0; t < n_trees; ++t)
-    if (gen != (trees[t].field != nullptr) || gen != (trees[t].node_w != nullptr))
-      return fail(c, MIND_EINVAL, "tree %d: field / node_w must be given exactly in the generic (grid) mode", t);
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t st = c->stream;
-  // MIND_PLAN_TRACE=1: host time stamps of this call's sections on stderr (as in mind_aime_plan)
-  static const bool il_trace = getenv("MIND_PLAN_TRACE") != nullptr;
-  const auto il_t0 = std::chrono::steady_clock::now();
-  auto ITR = [&](const char *what) {
-    if (il_trace) fprintf(stderr, "[ilqr] %8.1f us  %s\n", std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - il_t0).count(), what);
-  };
-  const double grid_res = gen ? grid->res : cfg->grid_res;
-  // ---- grid coordinates exactly as numpy builds them (ilqr/utils.py:7-13)
-  std::vector<double> gx(W), gy(H);
-  const double fsx = (double)(W - 1) * grid_res, fsy = (double)(H - 1) * grid_res;
-  const double offx = gen ? grid->off_x : x0[0] - 0.5 * fsx, offy = gen ? grid->off_y : x0[1] - 0.5 * fsy;
-  if (gen) {
-    memcpy(gx.data(), grid->gx, W * sizeof(double));
-    memcpy(gy.data(), grid->gy, H * sizeof(double));
-  } else {
-    double ox, oy;
-    il_make_grid(W, H, grid_res, x0, gx.data(), gy.data(), ox, oy);
-  }
-  // (mind_ilqr_contingency_begin_plan: the trees' agent arrays are the plan's own device buffers, tree t at node offset pl_tree_off[t])
-  const bool dev_flat = c->il_use_dev_flat && !gen && !ev && c->pl_dev_fmean && c->pl_dev_fcov;
-  c->il_use_dev_flat = false;
-  // ---- launch mode: one workgroup per tree | wide trees: G workgroups share a tree's items | narrow trees: G workgroups take a tree's LM slots
-  int maxM = 0;
-  for (int t = 0; t < n_trees; ++t) maxM = trees[t].n_nodes > maxM ? trees[t].n_nodes : maxM;
-  int G = c->ilqr_wgs;
-  // trees of tens of thousands of nodes (the deep stress trees: 29.5 k) keep twice the workgroups busy: 55 -> 35 ms per launch at 32 per tree,
-  // while the cfg4 trees (6.5 k nodes) are best at 16-24 (profiles/r03an_*)
-  if (G > 1 && G < c->ilqr_wgs_big && maxM >= c->ilqr_big_min) G = c->ilqr_wgs_big;
-  while (G > 1 && ((n_trees + 7) / 8) * 8 * G > c->n_cu) G >>= 1;     // every workgroup of the launch must be resident (1 per CU)
-  const bool multi = !gen && !ev && G > 1 && maxM >= c->ilqr_multi_min;
-  int GS = multi ? 1 : c->ilqr_slots;
-  // (c->ilqr_wgs == 1 is the caller's "stay on few CUs": the speculative warm start beside the predictor)
-  if (gen || ev || c->ilqr_wgs <= 1) GS = 1;
-  while (GS > 1 && ((n_trees + 7) / 8) * 8 * GS > c->n_cu) --GS;
-  const bool slots = GS > 1;
-  // the derivative speculator: one more workgroup per tree, only where the whole launch stays resident with it
-  const int spec = slots && c->ilqr_spec_deriv && GS < 31 && ((n_trees + 7) / 8) * 8 * (GS + 1) <= c->n_cu ? 1 : 0;
-  // sets of per-slot arrays (gains, value functions, candidates: ~146 doubles per node and slot): what this launch can use -- the followers' slots
-  // (GS, after the residency loop above) or the master's own speculation (IL_SPEC), not IL_SLOTS for every narrow-tree launch
-  const size_t nslot = slots ? (size_t)(GS > IL_SPEC ? GS : IL_SPEC) : IL_SPEC;
-  // ---- layout of one device arena: [doubles | floats | ints | tree structs]
-  size_t nd = 0, nf = 0, ni = 0;
-  auto takeD = [&](size_t n) { size_t o = nd; nd += (n + 1) & ~(size_t)1; return o; };
-  auto takeF = [&](size_t n) { size_t o = nf; nf += (n + 3) & ~(size_t)3; return o; };
-  auto takeI = [&](size_t n) { size_t o = ni; ni += (n + 3) & ~(size_t)3; return o; };
-  // the doubles region starts with everything the host uploads (grid, lane, queries, initial controls, per-node
-  // weights); the workspace behind `nd_in` is produced by the kernels and never copied from the host
-  const size_t o_gx = takeD(W), o_gy = takeD(H), o_lane = takeD((size_t)n_lane_pts * 2 + 2);
-  const size_t o_evx = takeD(ev ? (size_t)ev->nq * 6 : 0), o_evu = takeD(ev ? (size_t)ev->nq * 2 : 0);
-  const size_t o_evn = takeI(ev ? ev->nq : 0);
-  const size_t o_bars = takeI(4 * (size_t)n_trees + 4);   // barrier words of the multi-workgroup launch + its abort word (zero at upload)
-  const size_t ctl_ints = (sizeof(IlSlotCtl) + 15) / 16 * 4;
-  const size_t o_ctl = takeI(slots ? ctl_ints * (size_t)n_trees : 0);      // slot control blocks (zero at upload; 16-byte aligned: the ints region is)
-  const int trace_cap = std::min(256, std::max(cfg->max_iter, cfg2 ? cfg2->max_iter : 0));      // rows of the per-iteration trace, per phase
-  struct TL { size_t nodew, field, relag, relag2, Fx2, L2, Lx2, Lxx2, rel2; size_t xs, us, Fx, L, Lx, Lxx, k, K, Vx, Vxx, xsn, usn, Ln, stats, prob, mean, cov, parent, lstart, lnodes, cstart, clist, sstart, snodes, slstart, slsegs, segrec, rel, fsstart, fsq0, fsq1, fsnstart, fsnodes, trace; int M, a, nl, nseg, nsl, maxls, nfs; };
-  std::vector<TL> tl(n_trees);
-  long Mtot = 0;
-  for (int t = 0; t < n_trees; ++t) tl[t].us = takeD(2 * (size_t)(trees[t].n_nodes > 0 ? trees[t].n_nodes : 0));
-  for (int t = 0; t < n_trees; ++t) tl[t].nodew = takeD(gen ? (size_t)(trees[t].n_nodes > 0 ? trees[t].n_nodes : 0) * IL_NW : 0);
-  const size_t nd_in = nd;
-  const size_t o_quad = takeD(gen ? 2 : (size_t)W * H), o_evo = takeD(ev ? (size_t)ev->nq * IL_EVAL_OUT : 0);
-  // results of all trees are contiguous (us already is: it lives in the upload region), so they come back in three copies
-  for (int t = 0; t < n_trees; ++t) tl[t].xs = takeD(6 * (size_t)(trees[t].n_nodes > 0 ? trees[t].n_nodes : 0));
-  for (int t = 0; t < n_trees; ++t) tl[t].stats = takeD(2 * IL_NSTAT);
-  for (int t = 0; t < n_trees; ++t) {
-    const mind_cost_tree &tr = trees[t];
-    if (tr.n_nodes <= 0 || !tr.parent || (!gen && (!tr.prob || tr.n_agents <= 0)) || (use_exo && !dev_flat && (!tr.agent_mean || !tr.agent_cov)))
-      return fail(c, MIND_EINVAL, "tree %d: bad arrays", t);
-    if (tr.n_agents > IL_MAXA) return fail(c, MIND_EINVAL, "tree %d: %d agents > %d supported", t, tr.n_agents, IL_MAXA);
-    const size_t M = tr.n_nodes;
-    TL &L = tl[t];
-    L.M = (int)M; L.a = gen ? 1 : tr.n_agents;
-    L.trace = takeD((size_t)2 * trace_cap * IL_TRACE_W);
-    // what the derivative pass writes, and (derivative speculator) a second set laid out alike right behind it
-    L.relag = takeD(use_exo ? M * IL_RA : 0); L.Fx = takeD(36 * M); L.L = takeD(M); L.Lx = takeD(6 * M); L.Lxx = takeD(36 * M);
-    L.relag2 = takeD(spec && use_exo ? M * IL_RA : 0); L.Fx2 = takeD(spec ? 36 * M : 0); L.L2 = takeD(spec ? M : 0); L.Lx2 = takeD(spec ? 6 * M : 0);
-    L.Lxx2 = takeD(spec ? 36 * M : 0);
-    L.k = takeD(nslot * 2 * M); L.K = takeD(nslot * 12 * M); L.Vx = takeD(nslot * 6 * M); L.Vxx = takeD(nslot * 36 * M);
-    L.xsn = takeD(nslot * 60 * M); L.usn = takeD(nslot * 20 * M); L.Ln = takeD(nslot * 10 * M);
-    L.prob = takeF(M); L.mean = takeF(dev_flat ? 0 : M * L.a * 2); L.cov = takeF(dev_flat ? 0 : M * L.a);
-    L.parent = takeI(M); L.lnodes = takeI(M); L.cstart = takeI(M + 1); L.clist = takeI(M); L.rel = takeI(M); L.rel2 = takeI(spec ? M : 0);
-    Mtot += (long)M;
-  }
-  // levels need the depth first
-  // (the vectors live in the context: their capacity survives the call)
-  for (auto &v : c->il_scr.vv) if ((int)v.size() < n_trees) v.resize(n_trees);
-  auto &lvl_start = c->il_scr.vv[0], &lvl_nodes = c->il_scr.vv[1], &cst = c->il_scr.vv[2], &cls = c->il_scr.vv[3];
-  auto &sg_start = c->il_scr.vv[4], &sg_nodes = c->il_scr.vv[5], &sl_start = c->il_scr.vv[6], &sl_segs = c->il_scr.vv[7];
-  auto &seg_rec = c->il_scr.vv[8], &fs_start = c->il_scr.vv[9], &fs_q0 = c->il_scr.vv[10], &fs_q1 = c->il_scr.vv[11], &fs_nstart = c->il_scr.vv[12], &fs_nodes = c->il_scr.vv[13];
-  auto &depth = c->il_scr.tmp[0], &fill = c->il_scr.tmp[1], &cf = c->il_scr.tmp[2], &seg_of = c->il_scr.tmp[3], &seg_depth = c->il_scr.tmp[4], &sf = c->il_scr.tmp[5];
-  for (int t = 0; t < n_trees; ++t) {
-    const mind_cost_tree &tr = trees[t];
-    const int M = tr.n_nodes;
-    depth.assign(M, 0);
-    int maxd = 0;
-    for (int i = 0; i < M; ++i) {
-      const int p = tr.parent[i];
-      if (i == 0 ? p != -1 : (p < 0 || p >= i)) return fail(c, MIND_EINVAL, "tree %d: node %d has parent %d", t, i, p);
-      depth[i] = i == 0 ? 0 : depth[p] + 1;
-      maxd = depth[i] > maxd ? depth[i] : maxd;
-    }
-    tl[t].nl = maxd + 1;
-    lvl_start[t].assign(maxd + 2, 0);
-    for (int i = 0; i < M; ++i) lvl_start[t][depth[i] + 1]++;
-    for (int d = 0; d <= maxd; ++d) lvl_start[t][d + 1] += lvl_start[t][d];
-    lvl_nodes[t].resize(M);
-    fill.assign(maxd + 1, 0);
-    for (int i = 0; i < M; ++i) lvl_nodes[t][lvl_start[t][depth[i]] + fill[depth[i]]++] = i;
-    cst[t].assign(M + 1, 0);
-    for (int i = 1; i < M; ++i) cst[t][tr.parent[i] + 1]++;
-    for (int i = 0; i < M; ++i) cst[t][i + 1] += cst[t][i];
-    cls[t].assign(M > 1 ? M : 1, 0);
-    cf.assign(M, 0);
-    for (int i = 1; i < M; ++i) cls[t][cst[t][tr.parent[i]] + cf[tr.parent[i]]++] = i;
-    tl[t].lstart = takeI(maxd + 2);
-    // chain segments: a node starts a segment if it is node 0 or its parent has >= 2 children
-    seg_of.assign(M, -1); seg_depth.clear();
-    auto nchild = [&](int i) { return cst[t][i + 1] - cst[t][i]; };
-    sg_start[t].clear(); sg_nodes[t].clear();
-    for (int i = 0; i < M; ++i) {
-      if (!(i == 0 || nchild(tr.parent[i]) >= 2)) continue;
-      const int sidx = (int)sg_start[t].size();
-      sg_start[t].push_back((int)sg_nodes[t].size());
-      seg_depth.push_back(i == 0 ? 0 : seg_depth[seg_of[tr.parent[i]]] + 1);
-      int c = i;
-      while (true) {
-        seg_of[c] = sidx;
-        sg_nodes[t].push_back(c);
-        if (nchild(c) != 1) break;
-        c = cls[t][cst[t][c]];
-      }
-    }
-    sg_start[t].push_back((int)sg_nodes[t].size());
-    const int nseg = (int)seg_depth.size();
-    int maxsd = 0;
-    for (int d : seg_depth) maxsd = d > maxsd ? d : maxsd;
-    sl_start[t].assign(maxsd + 2, 0);
-    for (int d : seg_depth) sl_start[t][d + 1]++;
-    for (int d = 0; d <= maxsd; ++d) sl_start[t][d + 1] += sl_start[t][d];
-    sl_segs[t].resize(nseg);
-    sf.assign(maxsd + 1, 0);
-    for (int sgi = 0; sgi < nseg; ++sgi) sl_segs[t][sl_start[t][seg_depth[sgi]] + sf[seg_depth[sgi]]++] = sgi;
-    tl[t].nseg = nseg; tl[t].nsl = maxsd + 1;
-    tl[t].maxls = 1;
-    for (int d = 0; d <= maxsd; ++d) tl[t].maxls = std::max(tl[t].maxls, sl_start[t][d + 1] - sl_start[t][d]);
-    tl[t].sstart = takeI(nseg + 1); tl[t].snodes = takeI(M); tl[t].slstart = takeI(maxsd + 2); tl[t].slsegs = takeI(nseg);
-    // segment record of the backward sweep (16 ints): positions [s0, s1) of seg_nodes, last / first node, the node before the last, the
-    // last node's child count, where its children start in child_list and the first six of them -- one round trip instead of the walk
-    // segment -> positions -> node -> child range -> children
-    seg_rec[t].assign((size_t)nseg * 16, 0);
-    for (int sgi = 0; sgi < nseg; ++sgi) {
-      int *r = seg_rec[t].data() + (size_t)sgi * 16;
-      const int s0 = sg_start[t][sgi], s1 = sg_start[t][sgi + 1], cl = sg_nodes[t][s1 - 1];
-      r[0] = s0; r[1] = s1; r[2] = cl; r[3] = sg_nodes[t][s0]; r[4] = sg_nodes[t][s1 - 2 >= s0 ? s1 - 2 : s1 - 1];
-      r[5] = nchild(cl); r[6] = cst[t][cl];
-      for (int e = 0; e < 6 && e < r[5]; ++e) r[8 + e] = cls[t][cst[t][cl] + e];
-    }
-    tl[t].segrec = takeI((size_t)nseg * 16);
-    // forward steps of the line search: the segments of a level, cut into chunks of ilqr_chunk nodes when only a few chains run
-    // side by side (the other waves then price the nodes the previous step reached); wide levels stay whole
-    const int chunk = (c->ilqr_chunk > 0 && tl[t].maxls <= 6) ? c->ilqr_chunk : M;
-    fs_start[t].assign(1, 0); fs_nstart[t].assign(1, 0);
-    fs_q0[t].clear(); fs_q1[t].clear(); fs_nodes[t].clear();
-    for (int d = 0; d <= maxsd; ++d) {
-      int maxlen = 0;
-      for (int e = sl_start[t][d]; e < sl_start[t][d + 1]; ++e) { const int sgi = sl_segs[t][e]; maxlen = std::max(maxlen, sg_start[t][sgi + 1] - sg_start[t][sgi]); }
-      for (int k0 = 0; k0 < maxlen; k0 += chunk) {
-        for (int e = sl_start[t][d]; e < sl_start[t][d + 1]; ++e) {
-          const int sgi = sl_segs[t][e], q0 = sg_start[t][sgi] + k0, q1 = std::min(sg_start[t][sgi + 1], q0 + chunk);
-          if (q0 >= q1) continue;
-          // item record: positions [q0, q1) of seg_nodes, its first two nodes and the first node's parent (the rollout's prologue
-          // would otherwise walk q0 -> node -> parent -> state through four dependent loads)
-          const int c0 = sg_nodes[t][q0], c1 = sg_nodes[t][q0 + 1 < q1 ? q0 + 1 : q1 - 1];
-          for (int v : {q0, q1, c0, c1, c0 == 0 ? -1 : tr.parent[c0], 0, 0, 0}) fs_q0[t].push_back(v);
-          fs_q1[t].push_back(q1);
-          for (int q = q0; q < q1; ++q) fs_nodes[t].push_back(sg_nodes[t][q]);
-        }
-        fs_start[t].push_back((int)fs_q1[t].size()); fs_nstart[t].push_back((int)fs_nodes[t].size());
-      }
-    }
-    tl[t].nfs = (int)fs_start[t].size() - 1;
-    tl[t].fsstart = takeI(fs_start[t].size()); tl[t].fsq0 = takeI(fs_q0[t].size()); tl[t].fsq1 = takeI(fs_q1[t].size());
-    tl[t].fsnstart = takeI(fs_nstart[t].size()); tl[t].fsnodes = takeI(M);
-  }
-  ITR("tables built");
-  // arena: [uploaded doubles (nd_in) | floats | ints | tree structs | constants] = ONE host->device copy, then the doubles the
-  // kernels produce (workspace + results), then (generic mode) the materialised fields
-  const size_t bytesIn = nd_in * sizeof(double), bytesF = nf * sizeof(float), bytesI = ni * sizeof(int);
-  const size_t o_structs = bytesIn + bytesF + bytesI;
-  const size_t o_consts = (o_structs + (size_t)n_trees * sizeof(IlqrTreeDev) + 15) & ~(size_t)15;
-  const size_t o_work = (o_consts + 2 * sizeof(IlqrConst) + 15) & ~(size_t)15;
-  size_t total = (o_work + (nd - nd_in) * sizeof(double) + 15) & ~(size_t)15;
-  for (int t = 0; t < n_trees && gen; ++t) { tl[t].field = total; total += (size_t)tl[t].M * W * H * sizeof(double); }
-  int rc;
-  if ((rc = ensure(c, c->ilqr_dev, total))) return rc;
-  char *base = (char *)c->ilqr_dev.p;
-  double *dD = (double *)base;                 // uploaded doubles: offsets < nd_in
-  double *dW = (double *)(base + o_work);      // produced doubles: offsets >= nd_in
-  auto Dp = [=](size_t o) -> double * { return o < nd_in ? dD + o : dW + (o - nd_in); };
-  float *dF = (float *)(base + bytesIn);
-  int *dI = (int *)(base + bytesIn + bytesF);
-  // host staging of the read-only part
-  auto &hD = c->il_scr.hD; auto &hF = c->il_scr.hF; auto &hI = c->il_scr.hI;
-  hD.assign(nd_in, 0.0); hF.assign(nf, 0.f); hI.assign(ni, 0);
-  memcpy(hD.data() + o_gx, gx.data(), W * sizeof(double));
-  memcpy(hD.data() + o_gy, gy.data(), H * sizeof(double));
-  if (n_lane_pts) memcpy(hD.data() + o_lane, target_lane, (size_t)n_lane_pts * 2 * sizeof(double));
-  if (ev) {
-    memcpy(hD.data() + o_evx, ev->x, (size_t)ev->nq * 6 * sizeof(double));
-    memcpy(hD.data() + o_evu, ev->u, (size_t)ev->nq * 2 * sizeof(double));
-    memcpy(hI.data() + o_evn, ev->node, (size_t)ev->nq * sizeof(int));
-    for (int q = 0; q < ev->nq; ++q)
-      if (ev->node[q] < 0 || ev->node[q] >= trees[0].n_nodes) return fail(c, MIND_EINVAL, "mind_cost_eval: node %d out of range", ev->node[q]);
-  }
-  // where the results land on the host: xs of all trees and, right behind them, the stats of all trees; us (it lives in the uploaded region).
-  // A launch of small trees writes them there ITSELF at its end (k_ilqr: the staging is page-locked and mapped), instead of two copies behind it
-  const size_t n_hs = (size_t)2 * IL_NSTAT * n_trees;
-  const size_t n_xs = (size_t)(tl[0].stats - tl[0].xs);
-  const size_t n_hx = n_xs + n_hs, n_us = (size_t)Mtot * 2;
-  if ((rc = pl_pin(c, 5, (n_hx + n_us + 2) * sizeof(double) + (size_t)n_trees * sizeof(unsigned)))) return rc;
-  double *hx = (double *)c->pl_pin[5], *hus = hx + n_hx;
-  unsigned *h_abort = (unsigned *)(hus + n_us);
-  unsigned *h_done = h_abort + 4;               // (behind the two doubles kept for the abort word)
-  const bool host_out = !ev && c->ilqr_host_out_max > 0 && Mtot <= c->ilqr_host_out_max;
-  // per-tree completion words (a launch that cannot abort): the caller may look at a tree's results before the launch has ended (mind_loop)
-  const bool early = host_out && !multi && !gen;
-  c->il_early = mind_ctx::IlEarly();
-  if (early) {
-    c->il_gen += 1u;
-    if (c->il_gen == 0u) c->il_gen = 1u;
-    for (int t = 0; t < n_trees; ++t) h_done[t] = 0u;
-    c->il_early.xs = hx; c->il_early.us = hus; c->il_early.done = h_done; c->il_early.gen = c->il_gen; c->il_early.n_trees = n_trees; c->il_early.nodes = Mtot;
-  }
-  std::vector<IlqrTreeDev> hT(n_trees);
-  long moff = 0;
-  for (int t = 0; t < n_trees; ++t) {
-    const mind_cost_tree &tr = trees[t];
-    const TL &L = tl[t];
-    const size_t M = L.M;
-    if (us_init) memcpy(hD.data() + L.us, us_init + moff * 2, 2 * M * sizeof(double));
-    if (tr.prob) memcpy(hF.data() + L.prob, tr.prob, M * sizeof(float));
-    if (gen) memcpy(hD.data() + L.nodew, tr.node_w, M * IL_NW * sizeof(double));
-    if (tr.agent_mean && !gen && !dev_flat) memcpy(hF.data() + L.mean, tr.agent_mean, M * L.a * 2 * sizeof(float));
-    if (tr.agent_cov && !gen && !dev_flat) memcpy(hF.data() + L.cov, tr.agent_cov, M * L.a * sizeof(float));
-    memcpy(hI.data() + L.parent, tr.parent, M * sizeof(int));
-    memcpy(hI.data() + L.lstart, lvl_start[t].data(), lvl_start[t].size() * sizeof(int));
-    memcpy(hI.data() + L.lnodes, lvl_nodes[t].data(), M * sizeof(int));
-    memcpy(hI.data() + L.cstart, cst[t].data(), (M + 1) * sizeof(int));
-    memcpy(hI.data() + L.clist, cls[t].data(), cls[t].size() * sizeof(int));
-    memcpy(hI.data() + L.sstart, sg_start[t].data(), sg_start[t].size() * sizeof(int));
-    memcpy(hI.data() + L.snodes, sg_nodes[t].data(), sg_nodes[t].size() * sizeof(int));
-    memcpy(hI.data() + L.slstart, sl_start[t].data(), sl_start[t].size() * sizeof(int));
-    memcpy(hI.data() + L.slsegs, sl_segs[t].data(), sl_segs[t].size() * sizeof(int));
-    memcpy(hI.data() + L.segrec, seg_rec[t].data(), seg_rec[t].size() * sizeof(int));
-    memcpy(hI.data() + L.fsstart, fs_start[t].data(), fs_start[t].size() * sizeof(int));
-    memcpy(hI.data() + L.fsq0, fs_q0[t].data(), fs_q0[t].size() * sizeof(int));
-    memcpy(hI.data() + L.fsq1, fs_q1[t].data(), fs_q1[t].size() * sizeof(int));
-    memcpy(hI.data() + L.fsnstart, fs_nstart[t].data(), fs_nstart[t].size() * sizeof(int));
-    memcpy(hI.data() + L.fsnodes, fs_nodes[t].data(), fs_nodes[t].size() * sizeof(int));
-    IlqrTreeDev &D = hT[t];
-    D.M = L.M; D.n_agents = L.a; D.n_levels = L.nl; D.pad = 0;
-    D.parent = dI + L.parent; D.level_start = dI + L.lstart; D.level_nodes = dI + L.lnodes;
-    D.child_start = dI + L.cstart; D.child_list = dI + L.clist;
-    D.rel = dI + L.rel;
-    D.relag = Dp(L.relag);
-    D.field = gen ? (const double *)(base + L.field) : nullptr;
-    D.node_w = gen ? Dp(L.nodew) : nullptr;
-    D.n_segs = L.nseg; D.n_slevels = L.nsl; D.max_level_segs = L.maxls; D.pad2 = 0;
-    D.seg_start = dI + L.sstart; D.seg_nodes = dI + L.snodes; D.slevel_start = dI + L.slstart; D.slevel_segs = dI + L.slsegs; D.seg_rec = dI + L.segrec;
-    D.n_fsteps = L.nfs; D.padf = 0;
-    D.trace = trace_cap > 0 ? Dp(L.trace) : nullptr; D.trace_cap = trace_cap; D.padt = 0;
-    D.fstep_start = dI + L.fsstart; D.fstep_q0 = dI + L.fsq0; D.fstep_q1 = dI + L.fsq1; D.fstep_nstart = dI + L.fsnstart; D.fstep_nodes = dI + L.fsnodes;
-    D.prob = dF + L.prob; D.mean = dF + L.mean; D.cov = dF + L.cov;
-    if (dev_flat) { D.mean = c->pl_dev_fmean + (size_t)moff * L.a * 2; D.cov = c->pl_dev_fcov + (size_t)moff * L.a; }
-    D.xs = Dp(L.xs); D.us = Dp(L.us); D.Fx = Dp(L.Fx); D.L = Dp(L.L); D.Lx = Dp(L.Lx); D.Lxx = Dp(L.Lxx);
-    D.k = Dp(L.k); D.K = Dp(L.K); D.Vx = Dp(L.Vx); D.Vxx = Dp(L.Vxx);
-    D.xs_new = Dp(L.xsn); D.us_new = Dp(L.usn); D.L_new = Dp(L.Ln); D.stats = Dp(L.stats);
-    D.ctl = slots ? (IlSlotCtl *)(dI + o_ctl + ctl_ints * (size_t)t) : nullptr;
-    D.h_xs = host_out ? hx + (L.xs - tl[0].xs) : nullptr; D.h_us = host_out ? hus + (L.us - tl[0].us) : nullptr;
-    D.h_stats = host_out ? hx + (L.stats - tl[0].xs) : nullptr;
-    D.h_done = early ? h_done + t : nullptr; D.h_gen = c->il_gen; D.pad_h = 0;
-    if (early && ((L.xs - tl[0].xs) != (size_t)moff * 6 || (L.us - tl[0].us) != (size_t)moff * 2)) return fail(c, MIND_EINVAL, "tree-iLQR arena: results are not contiguous");
-    D.dset = spec ? (long long)L.Fx2 - (long long)L.Fx : 0; D.drel = spec ? (long long)L.rel2 - (long long)L.rel : 0;
-    if (spec && (L.L2 - L.L != L.Fx2 - L.Fx || L.Lx2 - L.Lx != L.Fx2 - L.Fx || L.Lxx2 - L.Lxx != L.Fx2 - L.Fx || (use_exo && L.relag2 - L.relag != L.Fx2 - L.Fx)))
-      return fail(c, MIND_EINVAL, "tree-iLQR arena: the two derivative sets are laid out differently");
-    moff += (long)M;
-  }
-  for (int t = 0; t < n_trees && gen; ++t)
-    HIPCHK(c, hipMemcpyAsync(base + tl[t].field, trees[t].field, (size_t)tl[t].M * W * H * sizeof(double), hipMemcpyHostToDevice, st));
-  IlqrConst K;
-  memset(&K, 0, sizeof(K));
-  K.dt = cfg->dt; K.wb = cfg->wheelbase;
-  for (int i = 0; i < 6; ++i) { K.w_des[i] = cfg->w_des_state[i]; K.w_con[i] = cfg->w_state_con[i]; K.lb[i] = cfg->state_lower[i]; K.ub[i] = cfg->state_upper[i]; K.x0[i] = x0[i]; }
-  K.w_ctrl[0] = cfg->w_ctrl[0]; K.w_ctrl[1] = cfg->w_ctrl[1];
-  K.w_tgt = cfg->w_tgt; K.w_ego = cfg->w_ego; K.w_ego_off = cfg->w_ego_cov_offset; K.w_exo = cfg->w_exo;
-  K.w_exo_off = cfg->w_exo_cov_offset; K.w_exo_cost = cfg->w_exo_cost_offset;
-  K.res = grid_res; K.off_x = offx; K.off_y = offy; K.target_vel = target_vel;
-  K.W = W; K.H = H; K.max_iter = cfg->max_iter; K.use_exo = use_exo_first;
-  for (int j = 0; j < IL_NA; ++j) K.alphas[j] = std::pow(1.1, -(double)(j * j));
-  K.gx = Dp(o_gx); K.gy = Dp(o_gy); K.quad = Dp(o_quad);
-  // a field prepared ahead for exactly this grid and lane (il_field_prepare): the kernels read it where it is
-  const bool field_ahead = !gen && !ev && c->il_field_valid && c->il_field_key[0] == x0[0] && c->il_field_key[1] == x0[1] && c->il_field_key[2] == (double)W &&
-                           c->il_field_key[3] == (double)H && c->il_field_key[4] == grid_res && c->il_field_lane.size() == 2 * (size_t)n_lane_pts &&
-                           memcmp(c->il_field_lane.data(), target_lane, c->il_field_lane.size() * sizeof(double)) == 0;
-  c->il_field_valid = false;         // (one call's worth: the next call makes its own or prepares again)
-  if (field_ahead) K.quad = (double *)c->il_field.p + (size_t)W + H + 2 * (size_t)n_lane_pts;
-  // cell centres are computed in the kernels when the grid is the numpy linspace (always in the planner mode)
-  K.stepx = fsx / (double)(W - 1); K.stepy = fsy / (double)(H - 1); K.fsx = fsx; K.fsy = fsy;
-  K.lin = 1;
-  for (int i = 0; i < W && K.lin; ++i) K.lin = gx[i] == ((i == W - 1 ? K.fsx : (double)i * K.stepx) + offx);
-  for (int i = 0; i < H && K.lin; ++i) K.lin = gy[i] == ((i == H - 1 ? K.fsy : (double)i * K.stepy) + offy);
-  K.in_x0 = offx + 1.5 * grid_res; K.in_x1 = offx + ((double)W - 2.5) * grid_res;
-  K.in_y0 = offy + 1.5 * grid_res; K.in_y1 = offy + ((double)H - 2.5) * grid_res;
-  IlqrConst K2[2];
-  K2[0] = K;
-  K2[1] = K;
-  if (cfg2) {      // the full-cost fit: same grid / state / lane field, its own weights
-    IlqrConst &F = K2[1];
-    for (int i = 0; i < 6; ++i) { F.w_des[i] = cfg2->w_des_state[i]; F.w_con[i] = cfg2->w_state_con[i]; F.lb[i] = cfg2->state_lower[i]; F.ub[i] = cfg2->state_upper[i]; }
-    F.w_ctrl[0] = cfg2->w_ctrl[0]; F.w_ctrl[1] = cfg2->w_ctrl[1];
-    F.w_tgt = cfg2->w_tgt; F.w_ego = cfg2->w_ego; F.w_ego_off = cfg2->w_ego_cov_offset; F.w_exo = cfg2->w_exo;
-    F.w_exo_off = cfg2->w_exo_cov_offset; F.w_exo_cost = cfg2->w_exo_cost_offset;
-    F.max_iter = cfg2->max_iter; F.use_exo = 1;
-    if (cfg2->dt != cfg->dt || cfg2->wheelbase != cfg->wheelbase || cfg2->grid_res != cfg->grid_res || cfg2->grid_w != cfg->grid_w ||
-        cfg2->grid_h != cfg->grid_h)
-      return fail(c, MIND_EINVAL, "mind_ilqr_contingency: both configurations must share dt / wheelbase / grid");
-  }
-  // one staged copy of everything the host provides (`up` lives until the stream has been synchronised below)
-  // (page-locked staging: a pageable source makes hipMemcpyAsync a blocking staged copy that also stalls the other contexts of the
-  // process -- several planner threads on one GPU then run slower together than one alone)
-  ITR("staged in vectors");
-  if ((rc = pl_pin(c, 4, o_work))) return rc;
-  char *up = (char *)c->pl_pin[4];
-  {
-    memset(up, 0, o_work);
-    memcpy(up, hD.data(), bytesIn);
-    if (bytesF) memcpy(up + bytesIn, hF.data(), bytesF);
-    if (bytesI) memcpy(up + bytesIn + bytesF, hI.data(), bytesI);
-    // (tests: "ilqr_test_starve" with slots on follower workgroups = the followers leave at once, as if they were never scheduled)
-    if (slots && c->ilqr_test_starve) ((unsigned *)(up + bytesIn + bytesF))[o_bars + 4 * (size_t)n_trees + 1] = 1u;
-    memcpy(up + o_structs, hT.data(), (size_t)n_trees * sizeof(IlqrTreeDev));
-    memcpy(up + o_consts, K2, 2 * sizeof(IlqrConst));
-    if ((rc = pl_upload(c, base, up, o_work, st))) return rc;
-  }
-  ITR("upload queued");
-  const IlqrConst *dK = (const IlqrConst *)(base + o_consts);
-  if (field_ahead) HIPCHK(c, hipStreamWaitEvent(st, c->ev_field, 0));
-  else if (!gen) hipLaunchKernelGGL(k_lane_field, dim3((W * H + 255) / 256), dim3(256), 0, st, K.gx.p, K.gy.p, W, H, Dp(o_lane), n_lane_pts, Dp(o_quad));
-  int amax = 1;
-  for (int t = 0; t < n_trees; ++t) amax = tl[t].a > amax ? tl[t].a : amax;
-  const IlqrTreeDev *dT = (const IlqrTreeDev *)(base + o_structs);
-  {
-    auto off = [&](size_t o) { return (size_t)((const char *)Dp(o) - base); };
-    c->il_dbg[0] = off(tl[0].L); c->il_dbg[1] = off(tl[0].Lx); c->il_dbg[2] = off(tl[0].Lxx); c->il_dbg[3] = off(tl[0].Fx); c->il_dbg[4] = off(tl[0].xs);
-  }
-  c->il_dbg[5] = (size_t)tl[0].M;
-  if (ev) {
-    const size_t lds = (IL_SCR + (size_t)4 * amax) * sizeof(double);
-    if (gen) hipLaunchKernelGGL(k_cost_eval<true>, dim3(ev->nq), dim3(64), lds, st, dT, K, ev->nq, dI + o_evn, Dp(o_evx), Dp(o_evu), Dp(o_evo));
-    else hipLaunchKernelGGL(k_cost_eval<false>, dim3(ev->nq), dim3(64), lds, st, dT, K, ev->nq, dI + o_evn, Dp(o_evx), Dp(o_evu), Dp(o_evo));
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(ev->out, Dp(o_evo), (size_t)ev->nq * IL_EVAL_OUT * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    return MIND_OK;
-  }
-  const size_t il_lds = il_lds_bytes(amax);
-  // wide trees (hundreds of nodes, dozens of chain segments per level): several workgroups per tree (ilqr_kernels.hip il_fit<.., true>)
-  unsigned *dBars = (unsigned *)(dI + o_bars);
-  if (c->profiling) {
-    if (!c->ev_il0) { HIPCHK(c, hipEventCreate(&c->ev_il0)); HIPCHK(c, hipEventCreate(&c->ev_il1)); }
-    HIPCHK(c, hipEventRecord(c->ev_il0, st));
-  }
-  c->ilqr_trees = n_trees; c->ilqr_multi = multi ? G : (slots ? GS + spec : 1); c->ilqr_ms = 0.f;
-  auto launch = [=](bool multi_) {
-    if (gen) {
-      hipLaunchKernelGGL((k_ilqr<true, 0>), dim3(n_trees), dim3(IL_THREADS), il_lds, st, dT, dK, n_phases, n_trees, 1, dBars, 0);
-    } else if (slots) {
-      // a master + GS - 1 followers per tree; a follower that is not resident yet is simply not used (IlSlotCtl.alive): no co-residency needed
-      // (+ the derivative speculator, the last workgroup of a tree)
-      hipLaunchKernelGGL((k_ilqr<false, 2>), dim3(((n_trees + 7) / 8) * 8 * (GS + spec)), dim3(IL_THREADS), il_lds, st, dT, dK, n_phases, n_trees, GS, dBars, spec);
-    } else if (multi_) {
-      // (ilqr_test_starve: the last eight workgroups are withheld, as if the device could not hold the whole launch: their peers wait
-      // at the first barrier, raise the abort word and the call falls back to the one-workgroup kernel below)
-      hipLaunchKernelGGL((k_ilqr<false, 1>), dim3(((n_trees + 7) / 8) * 8 * G - (c->ilqr_test_starve ? 8 : 0)), dim3(IL_THREADS), il_lds, st, dT, dK,
-                         n_phases, n_trees, G, dBars, 0);
-    } else {
-      hipLaunchKernelGGL((k_ilqr<false, 0>), dim3(n_trees), dim3(IL_THREADS), il_lds, st, dT, dK, n_phases, n_trees, 1, dBars, 0);
-    }
-  };
-  launch(multi);
-  ITR("kernel launched");
-  HIPCHK(c, hipGetLastError());
-  if (c->profiling) HIPCHK(c, hipEventRecord(c->ev_il1, st));
-  if (!host_out) {
-    HIPCHK(c, hipMemcpyAsync(hx, Dp(tl[0].xs), n_hx * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(hus, Dp(tl[0].us), n_us * sizeof(double), hipMemcpyDeviceToHost, st));
-  }
-  if (multi) HIPCHK(c, hipMemcpyAsync(h_abort, dBars + 4 * (size_t)n_trees, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-  // everything behind the launch -- the wait, the fallback of a launch that was not resident, the outputs -- as one closure over values:
-  // run at once, or kept in the context by mind_ilqr_contingency_begin and run by mind_ilqr_finish (the caller's thread is free meanwhile)
-  const size_t hs_size = n_hs;
-  std::function<int()> fin = [=]() -> int {
-  std::vector<double> hs(hs_size);
-  HIPCHK(c, hipStreamSynchronize(st));
-  if (c->profiling) HIPCHK(c, hipEventElapsedTime(&c->ilqr_ms, c->ev_il0, c->ev_il1));
-  if (multi) {
-    const unsigned aborted = *h_abort;
-    if (aborted) {
-      // the workgroups of a wide tree did not meet at a barrier within ~2 s: the launch was not fully resident (another context or
-      // stream held CUs -- several planners on one GPU).  The one-workgroup-per-tree kernel needs no co-residency: the upload (initial
-      // controls, zeroed barrier words) is repeated and the call solved with it -- same arithmetic, same results, just slower.
-      c->n_ilqr_fallbacks++;
-      HIPCHK(c, hipMemcpyAsync(base, up, o_work, hipMemcpyHostToDevice, st));
-      launch(false);
-      HIPCHK(c, hipGetLastError());
-      c->ilqr_multi = 1;
-      if (!host_out) {
-        HIPCHK(c, hipMemcpyAsync(hx, Dp(tl[0].xs), n_hx * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemcpyAsync(hus, Dp(tl[0].us), n_us * sizeof(double), hipMemcpyDeviceToHost, st));
-      }
-      HIPCHK(c, hipStreamSynchronize(st));
-    }
-  }
-  memcpy(xs, hx, (size_t)Mtot * 6 * sizeof(double));
-  memcpy(us, hus, n_us * sizeof(double));
-  memcpy(hs.data(), hx + n_xs, hs.size() * sizeof(double));
-  c->il_trace_dev.assign(n_trees, nullptr);
-  c->il_trace_its.assign((size_t)2 * n_trees, 0);
-  c->il_trace_cap = trace_cap; c->il_trace_phases = n_phases;
-  for (int t = 0; t < n_trees; ++t) {
-    c->il_trace_dev[t] = trace_cap > 0 ? Dp(tl[t].trace) : nullptr;
-    for (int ph = 0; ph < n_phases; ++ph) c->il_trace_its[2 * t + ph] = (int)hs[(size_t)2 * IL_NSTAT * t + (size_t)ph * IL_NSTAT];
-  }
-  c->il_spec_req = 0; c->il_spec_hit = 0;
-#ifndef IL_PROFILE
-  for (int t = 0; t < n_trees; ++t)
-    for (int ph = 0; ph < n_phases; ++ph) {
-      const double *h = hs.data() + (size_t)2 * IL_NSTAT * t + (size_t)ph * IL_NSTAT;
-      c->il_spec_req += (long long)h[9]; c->il_spec_hit += (long long)h[10];
-    }
-#endif
-  {
-    // phase cycles of the launch's critical tree (the one with the most cycles over all its fits): what bounds the launch
-    double best = -1.0;
-    for (int t = 0; t < n_trees; ++t) {
-      double tot = 0.0, ph_c[5] = {0, 0, 0, 0, 0}, passes = 0.0;
-      for (int ph = 0; ph < n_phases; ++ph) {
-        const double *h = hs.data() + (size_t)2 * IL_NSTAT * t + (size_t)ph * IL_NSTAT;
-        ph_c[0] += h[4]; ph_c[1] += h[5]; ph_c[2] += h[8]; ph_c[3] += h[6]; ph_c[4] += h[7];
-        passes += h[IL_NSTAT - 1];
-      }
-      for (double v : ph_c) tot += v;
-      if (tot > best) {
-        best = tot;
-        double *o = c->il_prof;
-        o[0] = tl[t].M; o[1] = tl[t].nl; o[2] = passes;
-        for (int q = 0; q < 5; ++q) o[3 + q] = ph_c[q];       // derivatives, backward, state chain, cost pass, selection
-        o[8] = (double)n_trees;
-      }
-    }
-  }
-  for (int ph = 0; ph < n_phases; ++ph) {
-    mind_ilqr_stats *so = ph == 0 ? stats : stats2;
-    if (!so) continue;
-    for (int t = 0; t < n_trees; ++t) {
-      const double *h = hs.data() + (size_t)2 * IL_NSTAT * t + (size_t)ph * IL_NSTAT;
-      mind_ilqr_stats *stats = so;      // (shadows the parameter inside this loop body)
-      stats[t].iterations = (int)h[0]; stats[t].converged = (int)h[1];
-      stats[t].J = h[2]; stats[t].mu = h[3];
-      if (getenv("MIND_ILQR_TRACE"))
-        fprintf(stderr, "[k_ilqr] tree %d exo %d M %d segs %d seg-levels %d widest %d agents %d it %d passes %.0f: cycles derivatives %.0f backward %.0f state chain %.0f cost pass %.0f select %.0f\n", t,
-                n_phases == 2 ? ph : use_exo, tl[t].M, tl[t].nseg, tl[t].nsl, tl[t].maxls, tl[t].a, stats[t].iterations, h[IL_NSTAT - 1], h[4], h[5], h[8], h[6], h[7]);
-#ifdef IL_PROFILE
-      if (getenv("MIND_ILQR_TRACE")) {
-        fprintf(stderr, "[k_ilqr prof] wave0: chain node (n=%.0f): stage %.0f u+dyn+store %.0f | cost chunk (n=%.0f): stage+loads %.0f field %.0f cost+store %.0f | riccati node (n=%.0f): products %.0f Qxx %.0f solve %.0f update %.0f | deriv block (n=%.0f): setup %.0f tasks %.0f assemble %.0f\n",
-                h[13], h[8] / fmax(h[13], 1), h[9] / fmax(h[13], 1),
-                h[23], h[10] / fmax(h[23], 1), h[11] / fmax(h[23], 1), h[12] / fmax(h[23], 1),
-                h[18], h[14] / fmax(h[18], 1), h[15] / fmax(h[18], 1), h[16] / fmax(h[18], 1), h[17] / fmax(h[18], 1),
-                h[22], h[19] / fmax(h[22], 1), h[20] / fmax(h[22], 1), h[21] / fmax(h[22], 1));
-      }
-#endif
-    }
-  }
-  return MIND_OK;
-  };
-  if (c->il_begin_only) {
-    c->il_begin_only = false;
-    c->il_finish = std::move(fin);
-    return MIND_OK;
-  }
-  return fin();
-}
-
-extern "C" int mind_ilqr_contingency_begin(mind_ctx *c, const mind_ilqr_cfg *cfg_warm, const mind_ilqr_cfg *cfg_full,
-                                           const mind_cost_tree *trees, int n_trees, const double *x0, const double *target_lane,
-                                           int n_lane_pts, double target_vel, double *xs, double *us,
-                                           mind_ilqr_stats *stats_warm, mind_ilqr_stats *stats_full) {
-  if (!c || !cfg_full) return fail(c, MIND_EINVAL, "mind_ilqr_contingency_begin: null configuration");
-  c->il_begin_only = true;
-  const int rc = ilqr_impl(c, cfg_warm, nullptr, trees, n_trees, x0, target_lane, n_lane_pts, target_vel, 0, nullptr, xs, us, stats_warm, nullptr,
-                           cfg_full, stats_full);
-  c->il_begin_only = false;
-  return rc;
-}
-
-// mind_ilqr_contingency_begin on the cost trees the last mind_aime_plan of this context flattened (its library-owned tables: no tree
-// arrays cross the boundary again)
-extern "C" int mind_ilqr_contingency_begin_plan(mind_ctx *c, const mind_ilqr_cfg *cfg_warm, const mind_ilqr_cfg *cfg_full, const double *x0,
-                                                const double *target_lane, int n_lane_pts, double target_vel, double *xs, double *us,
-                                                mind_ilqr_stats *stats_warm, mind_ilqr_stats *stats_full) {
-  if (!c || !cfg_full) return fail(c, MIND_EINVAL, "mind_ilqr_contingency_begin_plan: null configuration");
-  const int nt = (int)c->pl_tree_top.size();
-  if (nt <= 0 || c->pl_plan_agents <= 0) return fail(c, MIND_ESTATE, "mind_ilqr_contingency_begin_plan: the context holds no planned cost trees");
-  const int a = c->pl_plan_agents;
-  std::vector<mind_cost_tree> trees(nt);
-  for (int t = 0; t < nt; ++t) {
-    const size_t lo = (size_t)c->pl_tree_off[t];
-    mind_cost_tree &T = trees[t];
-    memset(&T, 0, sizeof(T));
-    T.n_nodes = c->pl_tree_off[t + 1] - c->pl_tree_off[t];
-    T.parent = c->pl_flat_parent.data() + lo; T.prob = c->pl_flat_prob.data() + lo;
-    T.n_agents = a;
-    // (host copies when the plan has read them back already; the call itself reads the device buffers k_aime_flat filled)
-    T.agent_mean = c->pl_fmean_p ? c->pl_fmean_p + lo * a * 2 : nullptr; T.agent_cov = c->pl_fcov_p ? c->pl_fcov_p + lo * a : nullptr;
-  }
-  c->il_begin_only = true;
-  c->il_use_dev_flat = c->pl_dev_fmean != nullptr && c->pl_dev_fcov != nullptr;
-  const int rc = ilqr_impl(c, cfg_warm, nullptr, trees.data(), nt, x0, target_lane, n_lane_pts, target_vel, 0, nullptr, xs, us, stats_warm, nullptr,
-                           cfg_full, stats_full);
-  c->il_begin_only = false;
-  c->il_use_dev_flat = false;
-  return rc;
-}
-
-extern "C" int mind_ilqr_finish(mind_ctx *c) {
-  if (!c) return MIND_EINVAL;
-  if (!c->il_finish) return fail(c, MIND_ESTATE, "mind_ilqr_finish: no tree-iLQR call was begun on this context");
-  std::function<int()> fin = std::move(c->il_finish);
-  c->il_finish = nullptr;
-  c->il_finish_owned = false;
-  c->il_early = mind_ctx::IlEarly();
-  return fin();
-}
-
-extern "C" int mind_ilqr_contingency(mind_ctx *c, const mind_ilqr_cfg *cfg_warm, const mind_ilqr_cfg *cfg_full,
-                                     const mind_cost_tree *trees, int n_trees, const double *x0, const double *target_lane,
-                                     int n_lane_pts, double target_vel, double *xs, double *us,
-                                     mind_ilqr_stats *stats_warm, mind_ilqr_stats *stats_full) {
-  if (!cfg_full) return fail(c, MIND_EINVAL, "mind_ilqr_contingency: null configuration");
-  return ilqr_impl(c, cfg_warm, nullptr, trees, n_trees, x0, target_lane, n_lane_pts, target_vel, 0, nullptr, xs, us, stats_warm, nullptr,
-                   cfg_full, stats_full);
-}
-
-extern "C" int mind_ilqr_solve_trees(mind_ctx *c, const mind_ilqr_cfg *cfg, const mind_cost_tree *trees, int n_trees,
-                                     const double *x0, const double *target_lane, int n_lane_pts, double target_vel,
-                                     int use_exo, const double *us_init, double *xs, double *us,
-                                     mind_ilqr_stats *stats) {
-  return ilqr_impl(c, cfg, nullptr, trees, n_trees, x0, target_lane, n_lane_pts, target_vel, use_exo, us_init, xs, us, stats, nullptr);
-}
-
-extern "C" int mind_ilqr_solve_fields(mind_ctx *c, const mind_ilqr_cfg *cfg, const mind_field_grid *grid,
-                                      const mind_cost_tree *trees, int n_trees, const double *x0,
-                                      const double *us_init, double *xs, double *us, mind_ilqr_stats *stats) {
-  if (!grid) return fail(c, MIND_EINVAL, "mind_ilqr_solve_fields: null grid");
-  return ilqr_impl(c, cfg, grid, trees, n_trees, x0, nullptr, 0, 0.0, 0, us_init, xs, us, stats, nullptr);
-}
-
-extern "C" int mind_cost_eval(mind_ctx *c, const mind_ilqr_cfg *cfg, const mind_field_grid *grid, const mind_cost_tree *tree,
-                              const double *x0, const double *target_lane, int n_lane_pts, double target_vel, int use_exo,
-                              int n_query, const int32_t *node, const double *x, const double *u, double *out) {
-  if (n_query <= 0 || !node || !x || !u || !out) return fail(c, MIND_EINVAL, "mind_cost_eval: bad argument");
-  IlqrEvalReq ev{n_query, node, x, u, out};
-  return ilqr_impl(c, cfg, grid, tree, 1, x0, target_lane, n_lane_pts, target_vel, use_exo, nullptr, nullptr, nullptr, nullptr, &ev);
-}
+#include "ilqr_host.hip"
 
 // -------------------------------------------------------------------------------------------------
 // AIME glue (k7): world-frame modes + topology signatures of a round's scenes

@@ -20,13 +20,14 @@ rt.ilqr_contingency = capture
 state_in, ctrl_in, ctrl_out, xs_all = D[scene + "_state_in"], D[scene + "_ctrl_in"], D[scene + "_ctrl_out"], D[scene + "_traj_xs"]
 if os.environ.get("TRACE_FROM"):
     lo = int(os.environ["TRACE_FROM"])
+    os.environ["MIND_ILQR_TRACE"] = "1"      # (the library reads it once per process, at its first solve: every cycle is traced, marked from `lo` on)
 for pi in range(len(state_in)):
     while True:
         will = sim.sim_time >= sim.enable_time and (sim.last_trigger is None or sim.sim_time - sim.last_trigger >= sim.PLAN_STEP)
         if will and pi > 0:
             sim.state, sim.ctrl = state_in[pi].copy(), ctrl_in[pi].copy()
         if will and os.environ.get("TRACE_FROM") and pi >= lo:
-            os.environ["MIND_ILQR_TRACE"] = "1"
+            print("[k_ilqr] ---- cycle %d ----" % pi, file=sys.stderr, flush=True)
         if sim.step():
             break
     st, tt = sim.last_result[0][0], sim.last_result[1][0]

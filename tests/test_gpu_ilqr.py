@@ -469,3 +469,81 @@ def test_cost_tree_beyond_the_lds_sums_matches_oracle(hip_predictor):
             assert stt[0]["iterations"] == ref["iterations"] and stt[0]["mu"] == ref["mu"] and stt[0]["J"] == ref["J"], wgs
     finally:
         hip_predictor.set_tuning("ilqr_wgs", 16)
+
+
+def test_workgroups_per_tree_is_what_il_choose_records(hip_predictor):
+    """What a call launched (mind_last_ilqr_stats) against the record of il_choose for the same knobs, tree sizes and this device's CU count
+    (mind_debug_ilqr_plan: the function the solver decides with): a narrow tree on slots + speculator, a bigger narrow tree, a wide launch."""
+    import torch
+    from mind_amd._lib import ilqr_plan
+    n_cu = torch.cuda.get_device_properties(0).multi_processor_count
+    cfg = oi.default_cfg(max_iter=3)
+    try:
+        for kind, a, knobs in (("lead", 4, {}), ("branch3", 40, {}), ("branch3", 6, {"ilqr_multi_min": 8, "ilqr_wgs": 4})):
+            sst = scripted_scenario_tree(kind, a)
+            flat = oi.flatten(sst["nodes"])
+            x0 = oi.init_state(sst["state"], sst["ctrl"])
+            for k, v in knobs.items():
+                hip_predictor.set_tuning(k, v)
+            hip_predictor.ilqr_solve(cfg, [flat, flat], x0, sst["target_lane"], sst["target_vel"], 1)
+            d = ilqr_plan(knobs, [flat["parent"]] * 2, n_cu=n_cu)
+            assert hip_predictor.ilqr_stats()[1:] == (2, d["workgroups_per_tree"]), (kind, a, knobs, d)
+            assert d["form"] == (1 if knobs else 2) and d["trees"][0]["M"] == len(flat["parent"])
+    finally:
+        hip_predictor.set_tuning("ilqr_multi_min", 192)
+        hip_predictor.set_tuning("ilqr_wgs", 16)
+
+
+def test_rejected_call_leaves_nothing_behind_for_the_next(hip_predictor):
+    """A two-halves contingency call that fails its validation (the two configurations differ in dt) and then a plain solve on the same
+    context: the solve runs to its end in the call (no begin-only request left over) and returns the golden result."""
+    from mind_amd import _lib
+    from mind_amd.predictor import IlqrCall
+    sst = scripted_scenario_tree("lead", 4)
+    flat = oi.flatten(sst["nodes"])
+    x0 = oi.init_state(sst["state"], sst["ctrl"])
+    cfg, cfg_bad = oi.default_cfg(max_iter=100), oi.default_cfg(max_iter=100)
+    cfg_bad.dt = cfg.dt * 2
+    for call in (IlqrCall(hip_predictor.lib, cfg, [flat], x0, sst["target_lane"], sst["target_vel"], cfg_full=cfg_bad).begin(hip_predictor),
+                 IlqrCall(hip_predictor.lib, cfg, [flat], x0, sst["target_lane"], sst["target_vel"], cfg_full=cfg_bad).run(hip_predictor)):
+        assert call.rc == _lib.MIND_EINVAL
+        with pytest.raises(_lib.MindError, match="both configurations must share dt / wheelbase / grid"):
+            call.finish()
+    assert hip_predictor.lib.mind_ilqr_finish(hip_predictor.ctx) == _lib.MIND_ESTATE          # nothing was begun
+    xs_w, us_w, st_w = hip_predictor.ilqr_solve(cfg, [flat], x0, sst["target_lane"], sst["target_vel"], 0)
+    xs_f, us_f, st_f = hip_predictor.ilqr_solve(cfg, [flat], x0, sst["target_lane"], sst["target_vel"], 1, us_init=us_w)
+    assert np.abs(xs_w[0] - G["lead_a4_it100_xs_w"]).max() < 1e-8
+    assert np.abs(xs_f[0] - G["lead_a4_it100_xs_f"]).max() < 1e-7 and np.abs(us_f[0] - G["lead_a4_it100_us_f"]).max() < 1e-7
+    assert st_f[0]["mu"] == G["lead_a4_it100_Jf"][1]
+    assert hip_predictor.lib.mind_ilqr_finish(hip_predictor.ctx) == _lib.MIND_ESTATE
+
+
+@pytest.mark.parametrize("env,tuning,knobs", [
+    ({"MIND_ILQR_SLOTS": "99"}, {}, {"ilqr_slots": 99}),                              # clamped to IL_SLOTS
+    ({"MIND_ILQR_WGS": "-3"}, {}, {"ilqr_wgs": -3}),                                  # clamped to 1: one workgroup per tree
+    ({"MIND_ILQR_SPEC_DERIV": "0", "MIND_ILQR_CHUNK": "-4", "MIND_ILQR_HOST_OUT_MAX": "-1"}, {}, {"ilqr_spec_deriv": 0}),
+    ({}, {"ilqr_slots": 0, "ilqr_spec_deriv": 5}, {"ilqr_slots": 0}),
+    ({"MIND_ILQR_SLOTS": "3"}, {"ilqr_slots": 99, "ilqr_wgs": 99, "ilqr_wgs_big": 0, "ilqr_chunk": -1, "ilqr_host_out_max": -1},
+     {"ilqr_slots": 99, "ilqr_wgs": 99, "ilqr_wgs_big": 0, "ilqr_chunk": -1, "ilqr_host_out_max": -1})])
+def test_context_knobs_reach_the_launch_choice(env, tuning, knobs):
+    """A fresh process per case: the MIND_ILQR_* variables at context creation and mind_set_tuning go through the one clamping function
+    (ilqr_tuning_set), so the launch is what mind_debug_ilqr_plan records for the same values; every value gives the same bits; an unknown
+    name is still rejected."""
+    import json
+    import subprocess
+    import sys
+    import torch
+    from mind_amd._lib import ilqr_plan
+    n_cu = torch.cuda.get_device_properties(0).multi_processor_count
+    child_env = {k: v for k, v in os.environ.items() if not k.startswith("MIND_ILQR_")}
+    child_env.update(env)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "ilqr_knob_worker.py"), json.dumps(tuning)], env=child_env, capture_output=True,
+                         text=True, timeout=120)
+    assert out.returncode == 0, out.stderr[-2000:]
+    got = json.loads(out.stdout.strip().splitlines()[-1])
+    sst = scripted_scenario_tree("lead", 4)
+    flat = oi.flatten(sst["nodes"])
+    d = ilqr_plan(knobs, [flat["parent"]], n_cu=n_cu)
+    assert got["workgroups_per_tree"] == d["workgroups_per_tree"], (got, d)
+    assert got["unknown_rc"] == -1 and "unknown knob 'ilqr_no_such_knob'" in got["unknown_msg"]
+    assert got["max_abs_err_xs_w"] < 1e-8
