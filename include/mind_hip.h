@@ -223,6 +223,26 @@ int mind_debug_predict_choice(const char *const *knob_names, const int *knob_val
 int mind_debug_ilqr_plan(const char *const *knob_names, const int *knob_values, int n_knobs, int n_cu, int mode, int n_trees, const int *n_nodes,
                          const int32_t *parents, long long *out, int cap, int *bad);
 
+/* host-only helper (tests): the bookkeeping of mind_aime_plan -- AimeBook, pl_route and pl_chunk (mind_amd/csrc/aime_book.h), the functions the
+ * plan itself calls -- replayed over the decision words of n_rounds rounds, on rank `rank` of `world` (force: a one-rank group exchanges too,
+ * as with mind_set_exchange).  dec holds the rounds one behind the other, dec_len[r] floats each: per rank of the group (one rank when no
+ * exchange runs) sel [Bmax,6] (kept mode or -1, visiting order) | sel_prob [Bmax,6] | hit [Bmax,6,2] (branch-time bits, two 32-bit words),
+ * Bmax = the largest block of the round's scenes; a length that does not fit the round is MIND_EINVAL.  The plan stops at the first empty
+ * branch set; this replay goes on while rounds are given.  n_tokens > 0: the chunk size of every round for that many tokens per scene,
+ * bytes_per_pair and plan_chunk_mb; per_scene: floats per scene in the all-to-all's byte table.  The record `out` (as much of it as `cap`
+ * holds) is a header of 16,
+ *   [0] header length  [1] which "unsupported" exit was taken (0 none; msg then holds the plan's error string), [2], [3] the numbers it names
+ *   [4] rounds consumed  [5] nodes  [6] cost trees  [7] their trajectory nodes  [8] floats of rows  [9] root flags  [10] exchanges run  [11] world
+ * per consumed round {scenes B, this rank's block lo, hi, Bmax, chunk size, branch set S, this rank's children s0, Sm, scenes the all-to-all
+ * moves on any rank} and todo [S], cnt_r [world], s0_r [world + 1], k_aime_windows' ints [3 Sm], the byte table [2][world], the scene ranges
+ * sent to / received from every rank [world][2] each; and without an exit: per node {round, scene, mode, parent, prob (float32 bits), cur_t,
+ * end_t, flags, dur, row_off, owner rank, scene in the owner's block}; the gather and then the flat job table, each {jobs, workgroups, bytes of
+ * the device image} + per job {row0, n, dst, a, round of its world buffer} + job of workgroup + agent of workgroup; tree_top, tree_off
+ * [trees + 1], flat_parent, flat_prob (float32 bits).  Returns the length of the full record or MIND_EINVAL.  Needs no GPU and no context. */
+int mind_debug_aime_book(int pred_len, int max_depth, int max_rounds, int n_agents, int world, int rank, int force, int n_rounds, const int *dec_len,
+                         const float *dec, int n_tokens, int bytes_per_pair, int plan_chunk_mb, int per_scene, long long *out, int cap, char *msg,
+                         int msg_cap);
+
 /* host-only helper (tests): the launch list of the layer-wise batched ActorNet for a call of n_actors actors in the arithmetic np (6, 3, 1 =
  * bf16x6, bf16x3, bf16; anything else: MIND_EINVAL) with `chunk` actors per chunk (0 = the default) -- exactly what mind_predict_batch issues.
  * out_launches receives up to cap records of 16 long long in issue order: {stage 0..25 (-1: the input split), kind (0 input split, 1 conv,

@@ -161,7 +161,7 @@ class PlannerOut(C.Structure):     # mind_planner_out
 EXPORTS = ["mind_ctx_create", "mind_ctx_destroy", "mind_last_error_string", "mind_ctx_synchronize",
            "mind_weights_load", "mind_predict_batch", "mind_last_fusion_stats", "mind_last_actor_stats", "mind_debug_actor_lw_plan", "mind_last_token_stats", "mind_last_token_stage_ms", "mind_debug_token_lw_plan", "mind_set_profiling",
            "mind_ilqr_solve_trees", "mind_ilqr_contingency", "mind_ilqr_solve_fields", "mind_cost_eval", "mind_lane_dist_field", "mind_aime_world", "mind_aime_rebase", "mind_debug_set_layers",
-           "mind_debug_read", "mind_set_pair_precision", "mind_get_pair_precision", "mind_debug_pack_bfrag", "mind_debug_pack_conv_frag", "mind_debug_pair_schedule", "mind_debug_predict_choice", "mind_debug_ilqr_plan", "mind_set_tuning", "mind_last_ilqr_stats", "mind_aime_plan", "mind_last_ilqr_profile", "mind_eval_traj_trees", "mind_last_ilqr_trace", "mind_ilqr_contingency_begin", "mind_ilqr_finish", "mind_fill_tracks", "mind_ilqr_contingency_begin_plan", "mind_debug_trig", "mind_aime_plan_begin", "mind_aime_plan_poll", "mind_aime_plan_finish", "mind_ctx_busy", "mind_ilqr_finish_plan",
+           "mind_debug_read", "mind_set_pair_precision", "mind_get_pair_precision", "mind_debug_pack_bfrag", "mind_debug_pack_conv_frag", "mind_debug_pair_schedule", "mind_debug_predict_choice", "mind_debug_ilqr_plan", "mind_debug_aime_book", "mind_set_tuning", "mind_last_ilqr_stats", "mind_aime_plan", "mind_last_ilqr_profile", "mind_eval_traj_trees", "mind_last_ilqr_trace", "mind_ilqr_contingency_begin", "mind_ilqr_finish", "mind_fill_tracks", "mind_ilqr_contingency_begin_plan", "mind_debug_trig", "mind_aime_plan_begin", "mind_aime_plan_poll", "mind_aime_plan_finish", "mind_ctx_busy", "mind_ilqr_finish_plan",
            "mind_set_exchange", "mind_last_exchange_stats",
            "mind_loop_create", "mind_loop_destroy", "mind_loop_reset", "mind_loop_advance", "mind_loop_state", "mind_loop_last_plan", "mind_loop_export",
            "mind_planner_create", "mind_planner_destroy", "mind_planner_reset", "mind_planner_observe", "mind_planner_set_lanes", "mind_planner_set_target_lane",
@@ -241,6 +241,7 @@ def load():
                                               C.c_int, C.POINTER(C.c_longlong), C.c_int]
     lib.mind_debug_ilqr_plan.argtypes = [C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int32),
                                          C.POINTER(C.c_longlong), C.c_int, C.POINTER(C.c_int)]
+    lib.mind_debug_aime_book.argtypes = [C.c_int] * 8 + [C.POINTER(C.c_int), C.POINTER(C.c_float)] + [C.c_int] * 4 + [C.POINTER(C.c_longlong), C.c_int, C.c_char_p, C.c_int]
     lib.mind_debug_trig.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double)]
     lib.mind_debug_pack_conv_frag.argtypes = [C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_size_t]
     lib.mind_debug_set_layers.argtypes = [C.c_void_p, C.c_int]
@@ -334,6 +335,47 @@ def ilqr_plan(knobs, parents, n_cu=256, generic=False, evaluate=False, two_fits=
             tr[name], o = list(out[o:o + ln]), o + ln
         d["trees"].append(tr)
     assert o == n
+    return d
+
+
+AIME_ROUND_FIELDS = ("B", "lo", "hi", "Bmax", "chunk", "S", "s0", "Sm", "any")
+AIME_NODE_FIELDS = ("round", "scene", "mode", "parent", "prob", "cur_t", "end_t", "flags", "dur", "row_off", "owner", "lscene")
+
+
+def aime_book(pred_len, max_depth, n_agents, rounds, world=1, rank=0, force=False, max_rounds=32, n_tokens=0, bytes_per_pair=512, plan_chunk_mb=96 * 1024,
+              per_scene=1):
+    """mind_aime_plan's bookkeeping (mind_debug_aime_book; no GPU) replayed over `rounds`, one float32 array of decision words per round
+    ([ranks, 24 * Bmax]: sel | sel_prob | hit, include/mind_hip.h).  -> dict: "error" (None or the plan's message), "code", "rounds" = [dict of
+    AIME_ROUND_FIELDS + todo, cnt_r, s0_r, win, tab, snd, rcv], and without an error "nodes" (dicts of AIME_NODE_FIELDS, prob as float32 bits),
+    "gather" / "flat" (jobs [(row0, n, dst, a, round)], job_of_block, agent_of_block, bytes), tree_top, tree_off, flat_parent, flat_prob
+    (float32 bits), n_rows, root_flags; None when the arguments are rejected"""
+    import numpy as np
+    lib = load()
+    arrs = [np.ascontiguousarray(r, np.float32).ravel() for r in rounds]
+    lens = (C.c_int * max(1, len(arrs)))(*[a.size for a in arrs])
+    dec = np.concatenate(arrs + [np.zeros(1, np.float32)])
+    msg = C.create_string_buffer(256)
+    args = [pred_len, max_depth, max_rounds, n_agents, world, rank, int(force), len(arrs), lens, dec.ctypes.data_as(C.POINTER(C.c_float)), n_tokens,
+            bytes_per_pair, plan_chunk_mb, per_scene]
+    n = lib.mind_debug_aime_book(*args, None, 0, msg, 256)
+    if n == MIND_EINVAL:
+        return None
+    out = (C.c_longlong * n)()
+    assert lib.mind_debug_aime_book(*args, out, n, msg, 256) == n and out[0] == 16
+    o, take = [16], lambda k: (list(out[o[0]:o[0] + k]), o.__setitem__(0, o[0] + k))[0]
+    d = dict(code=out[1], error=msg.value.decode() if out[1] else None, args=(out[2], out[3]), n_rows=out[8], root_flags=out[9], rounds=[])
+    for _ in range(out[4]):
+        r = dict(zip(AIME_ROUND_FIELDS, take(9)))
+        for k, ln in (("todo", r["S"]), ("cnt_r", world), ("s0_r", world + 1), ("win", 3 * r["Sm"]), ("tab", 2 * world), ("snd", 2 * world), ("rcv", 2 * world)):
+            r[k] = take(ln)
+        d["rounds"].append(r)
+    if not out[1]:
+        d["nodes"] = [dict(zip(AIME_NODE_FIELDS, take(12))) for _ in range(out[5])]
+        for name in ("gather", "flat"):
+            nj, nb, nbytes = take(3)
+            d[name] = dict(jobs=[tuple(take(5)) for _ in range(nj)], job_of_block=take(nb), agent_of_block=take(nb), bytes=nbytes)
+        d["tree_top"], d["tree_off"], d["flat_parent"], d["flat_prob"] = take(out[6]), take(out[6] + 1), take(out[7]), take(out[7])
+    assert o[0] == n
     return d
 
 

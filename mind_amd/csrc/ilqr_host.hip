@@ -110,7 +110,7 @@ struct IlqrCall {
   mind_ilqr_stats *stats = nullptr, *stats2 = nullptr;      // of the first / the second fit
   const IlqrEvalReq *ev = nullptr;
   bool begin_only = false;      // return behind the launch: the other half stays in c->il_finish (mind_ilqr_finish)
-  bool dev_flat = false;        // the trees are the context's last plan's: read their agent arrays where k_aime_flat wrote them (tree t at node offset pl_tree_off[t])
+  bool dev_flat = false;        // the trees are the context's last plan's: read their agent arrays where k_aime_flat wrote them (tree t at node offset plan.book.tree_off[t])
 };
 
 // what the steps of one call share
@@ -167,7 +167,7 @@ static int il_check(mind_ctx *c, const IlqrCall &q, IlRun &R) {
   if (cfg2 && (cfg2->dt != cfg->dt || cfg2->wheelbase != cfg->wheelbase || cfg2->grid_res != cfg->grid_res || cfg2->grid_w != cfg->grid_w ||
                cfg2->grid_h != cfg->grid_h))
     return fail(c, MIND_EINVAL, "mind_ilqr_contingency: both configurations must share dt / wheelbase / grid");
-  R.dev_flat = q.dev_flat && !gen && !ev && c->pl_dev_fmean && c->pl_dev_fcov;
+  R.dev_flat = q.dev_flat && !gen && !ev && c->plan.dev_fmean && c->plan.dev_fcov;
   R.n_agents.resize(q.n_trees);
   for (int t = 0; t < q.n_trees; ++t) {
     const mind_cost_tree &tr = q.trees[t];
@@ -307,7 +307,7 @@ static int il_stage(mind_ctx *c, IlRun &R) {
     D.trace = R.trace_cap > 0 ? R.Dp(L.trace) : nullptr; D.trace_cap = R.trace_cap; D.padt = 0;
     D.fstep_start = dI + L.fsstart; D.fstep_q0 = dI + L.fsitems; D.fstep_q1 = dI + L.fsq1; D.fstep_nstart = dI + L.fsnstart; D.fstep_nodes = dI + L.fsnodes;
     D.prob = dF + L.prob; D.mean = dF + L.mean; D.cov = dF + L.cov;
-    if (R.dev_flat) { D.mean = c->pl_dev_fmean + (size_t)moff * a * 2; D.cov = c->pl_dev_fcov + (size_t)moff * a; }
+    if (R.dev_flat) { D.mean = c->plan.dev_fmean + (size_t)moff * a * 2; D.cov = c->plan.dev_fcov + (size_t)moff * a; }
     D.xs = R.Dp(L.xs); D.us = R.Dp(L.us); D.Fx = R.Dp(L.Fx); D.L = R.Dp(L.L); D.Lx = R.Dp(L.Lx); D.Lxx = R.Dp(L.Lxx);
     D.k = R.Dp(L.k); D.K = R.Dp(L.K); D.Vx = R.Dp(L.Vx); D.Vxx = R.Dp(L.Vxx);
     D.xs_new = R.Dp(L.xsn); D.us_new = R.Dp(L.usn); D.L_new = R.Dp(L.Ln); D.stats = R.Dp(L.stats);
@@ -584,19 +584,19 @@ extern "C" int mind_ilqr_contingency_begin_plan(mind_ctx *c, const mind_ilqr_cfg
                                                 const double *target_lane, int n_lane_pts, double target_vel, double *xs, double *us,
                                                 mind_ilqr_stats *stats_warm, mind_ilqr_stats *stats_full) {
   if (!c || !cfg_full) return fail(c, MIND_EINVAL, "mind_ilqr_contingency_begin_plan: null configuration");
-  const int nt = (int)c->pl_tree_top.size();
-  if (nt <= 0 || c->pl_plan_agents <= 0) return fail(c, MIND_ESTATE, "mind_ilqr_contingency_begin_plan: the context holds no planned cost trees");
-  const int a = c->pl_plan_agents;
+  const int nt = (int)c->plan.book.tree_top.size();
+  if (nt <= 0 || c->plan.agents <= 0) return fail(c, MIND_ESTATE, "mind_ilqr_contingency_begin_plan: the context holds no planned cost trees");
+  const int a = c->plan.agents;
   std::vector<mind_cost_tree> trees(nt);
   for (int t = 0; t < nt; ++t) {
-    const size_t lo = (size_t)c->pl_tree_off[t];
+    const size_t lo = (size_t)c->plan.book.tree_off[t];
     mind_cost_tree &T = trees[t];
     memset(&T, 0, sizeof(T));
-    T.n_nodes = c->pl_tree_off[t + 1] - c->pl_tree_off[t];
-    T.parent = c->pl_flat_parent.data() + lo; T.prob = c->pl_flat_prob.data() + lo;
+    T.n_nodes = c->plan.book.tree_off[t + 1] - c->plan.book.tree_off[t];
+    T.parent = c->plan.book.flat_parent.data() + lo; T.prob = c->plan.book.flat_prob.data() + lo;
     T.n_agents = a;
     // (host copies when the plan has read them back already; the call itself reads the device buffers k_aime_flat filled)
-    T.agent_mean = c->pl_fmean_p ? c->pl_fmean_p + lo * a * 2 : nullptr; T.agent_cov = c->pl_fcov_p ? c->pl_fcov_p + lo * a : nullptr;
+    T.agent_mean = c->plan.fmean_p ? c->plan.fmean_p + lo * a * 2 : nullptr; T.agent_cov = c->plan.fcov_p ? c->plan.fcov_p + lo * a : nullptr;
   }
   IlqrCall q = il_contingency_call(cfg_warm, cfg_full, trees.data(), nt, x0, target_lane, n_lane_pts, target_vel, xs, us, stats_warm, stats_full);
   q.begin_only = true;

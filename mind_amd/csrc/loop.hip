@@ -69,7 +69,7 @@ struct mind_cycle {
   std::vector<long long> kept_keys;
   mind_aime_plan_out po;
   bool have_plan = false;
-  long long plan_gen = -1;          // mind_ctx::pl_gen of the last plan
+  long long plan_gen = -1;          // mind_ctx::plan.gen of the last plan
   std::chrono::steady_clock::time_point t_plan_end;
   // speculative warm start (TrajectoryTreeOptimizer.speculate_warm / _take_speculation, this repo's trajectory_tree.py): the warm-start fits of the
   // PREVIOUS plan's tree shapes run on a second context beside the AIME rounds; a tree whose shape recurs takes its warm-start controls from there
@@ -166,7 +166,7 @@ template <class Seen> void cycle_repeat_unseen(mind_cycle *L, size_t known_befor
 template <class Id> int cycle_last_plan(mind_cycle *L, const std::vector<Id> &idents, mind_aime_plan_out *plan, const double **xs, const double **us,
                                         const mind_ilqr_stats **stats_warm, const mind_ilqr_stats **stats_full, const Id **agents, const float **types, double *x0) {
   if (!L->have_plan) return fail(L->c, MIND_ESTATE, "%s_last_plan: no plan is held", L->who);
-  if (L->plan_gen != L->c->pl_gen) return fail(L->c, MIND_ESTATE, "%s_last_plan: the context has planned again since (another planner shares it): the plan's tables are gone", L->who);
+  if (L->plan_gen != L->c->plan.gen) return fail(L->c, MIND_ESTATE, "%s_last_plan: the context has planned again since (another planner shares it): the plan's tables are gone", L->who);
   *plan = L->po;
   if (xs) *xs = L->sol_owned ? L->sol_xs.data() : L->c->pl_sol_xs.data();
   if (us) *us = L->sol_owned ? L->sol_us.data() : L->c->pl_sol_us.data();
@@ -572,7 +572,7 @@ int cycle_plan(mind_cycle *L) {
     if (L->po.flat_parent[k] == -1) { first = k; break; }
   if (first < 0) return fail(c, MIND_ESTATE, "%s: the chosen tree has no root child", L->who);
   L->ctrl[0] = xs[(size_t)first * 6 + 4]; L->ctrl[1] = xs[(size_t)first * 6 + 5];
-  L->best = best; L->last_agents = a; L->last_nodes = M; L->have_plan = true; L->plan_gen = c->pl_gen;
+  L->best = best; L->last_agents = a; L->last_nodes = M; L->have_plan = true; L->plan_gen = c->plan.gen;
   // accounting (TrajectoryTreeOptimizer.counters, MINDPlanner.timing_sum; bench.py's live kernel durations when profiling is on)
   mind_loop_totals &S = L->tot;
   for (int t = 0; t < nt; ++t) {

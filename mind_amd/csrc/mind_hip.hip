@@ -31,6 +31,7 @@
 #include "pair_jobs.h"
 #include "pred_choice.h"
 #include "ilqr_choice.h"
+#include "aime_book.h"
 #include "aime_kernels.hip"
 
 namespace {
@@ -128,7 +129,6 @@ struct mind_ctx {
   // trees' index tables and the image of the arena's uploaded doubles / floats / ints
   std::vector<IlTables> il_tab;
   struct IlImage { std::vector<double> hD; std::vector<float> hF; std::vector<int> hI; } il_img;
-  std::vector<std::vector<int>> pl_scr_kids; std::vector<float> pl_scr_pr; std::vector<int> pl_scr_i[3];      // mind_aime_plan's flattening scratch
   // the pending tree-iLQR launch writes its results to the host itself and marks every tree when it is complete (IlqrChoice::early): where, and
   // the word's value that means "complete" for THIS launch.  Valid between the launch and its mind_ilqr_finish.
   struct IlEarly { const double *xs = nullptr, *us = nullptr; volatile unsigned *done = nullptr; unsigned gen = 0; int n_trees = 0; long nodes = 0; } il_early;
@@ -180,8 +180,6 @@ struct mind_ctx {
   // on the context stream.  Measured on the recorded demo_1 loop: no difference (AIME 2.00 vs 2.01 ms per plan, profiles/r03ag) -- off.
   hipStream_t pl_copy = nullptr;
   bool pl_tab_side = false;
-  std::vector<mind_aime_node> pl_nodes;
-  std::vector<float> pl_flat_prob;
   std::vector<double> pl_sol_xs, pl_sol_us;          // results of the solves a plan began itself (mind_ilqr_finish_plan)
   std::vector<mind_ilqr_stats> pl_sol_stw, pl_sol_stf;
   // mind_aime_plan_begin / _finish: the plan on a thread of the library (state 0 idle, 1 running, 2 done)
@@ -190,10 +188,17 @@ struct mind_ctx {
   mind_aime_plan_in pa_in;
   mind_aime_plan_out pa_out;
   int pa_rc = 0;
-  const float *pl_rows_p = nullptr, *pl_fmean_p = nullptr, *pl_fcov_p = nullptr;      // into page-locked slot 2, valid until the next plan
-  std::vector<int32_t> pl_tree_top, pl_tree_off, pl_flat_parent;
-  int pl_plan_agents = 0;       // agents per scene of the plan those tables belong to
-  long long pl_gen = 0;         // plans begun on this context so far: whoever holds a plan's library-owned tables (mind_loop) checks they are still that plan's
+  // the context's last plan: its bookkeeping and host result tables (aime_book.h: node table, tree_top / tree_off / flat_parent / flat_prob) and
+  // where its rows and flattened cost trees lie
+  struct Plan {
+    AimeBook book;
+    int agents = 0;             // agents per scene of the plan those tables belong to
+    long long gen = 0;          // plans begun on this context so far: whoever holds a plan's library-owned tables (mind_loop) checks they are still that plan's
+    const float *rows_p = nullptr, *fmean_p = nullptr, *fcov_p = nullptr;      // into page-locked slot 2, valid until the next plan
+    // the cost trees' agent means / sigmas where k_aime_flat wrote them (device): a tree-iLQR call on the plan's own trees
+    // (mind_ilqr_contingency_begin_plan) reads them there instead of taking them through the host
+    const float *dev_fmean = nullptr, *dev_fcov = nullptr;
+  } plan;
   DevBuf pl_flat;
   DevBuf dec_xbuf, dec_bars;
   unsigned *dec_abort = nullptr;      // host-visible abort word of its barriers (page-locked, mapped)
@@ -207,9 +212,6 @@ struct mind_ctx {
   // per-iteration traces of the last tree-iLQR call (mind_last_ilqr_trace): device address per tree, rows per phase, iterations run
   std::function<int()> il_finish;     // the pending half of a call begun with mind_ilqr_contingency_begin
   bool il_finish_owned = false;       // ... whose outputs are library buffers (the solves a plan began itself): may be drained and dropped
-  // the cost trees' agent means / sigmas of the context's last plan where k_aime_flat wrote them (device): a tree-iLQR call on the plan's own
-  // trees (mind_ilqr_contingency_begin_plan) reads them there instead of taking them through the host
-  const float *pl_dev_fmean = nullptr, *pl_dev_fcov = nullptr;
   hipEvent_t ev_rows = nullptr;
   std::vector<const double *> il_trace_dev;
   std::vector<int> il_trace_its;      // [tree][phase 2]

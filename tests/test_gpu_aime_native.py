@@ -155,3 +155,58 @@ def test_lazy_scenario_tree_read_after_the_next_plan_is_still_its_own_plans():
         assert len(a) == len(b) > 0
         for x, y in zip(a, b):
             assert x[0] == y[0] and x[1] == y[1] and all(np.array_equal(p, q) for p, q in zip(x[2:], y[2:]))
+
+
+def test_chunked_rounds_of_a_small_world_plan_what_whole_rounds_plan():
+    """mind_aime_plan's chunked rounds ("plan_chunk_mb") away from the cfg4 size: the 16-agent world under the scripted full tree (rounds of
+    1 / 6 / 36 / ~216 scenes), planned whole, in chunks, and in chunks with the small-table shortcuts off ("tab_small", "dec_mirror",
+    "tab_host_max", "glue_fused"): node table, rows, flattened cost trees, chosen tree and solve results must be bit-identical.
+    The budget is 8 MB, not the smallest one.  At 512 B per pair 1 MB leaves a 36-scene round a shorter last chunk only for scenes of 5, 6, 8, 9,
+    11, 12, 15 or 16 tokens (pl_chunk), and no such world grows a 36-scene round under these scripted modes: the six ego speeds must pass
+    different neighbours or their modes merge, and over the host path's scan of 3-14 agents on 1-4 lanes of 15-160 m every world of at most 16
+    tokens merged the root scene's six modes into three or four.  The smallest worlds with a 36-scene round have three 160 m lanes (30 lane pieces) and 11 agents:
+    42 tokens, more than 1 MB of edges per scene, so 1 MB puts every scene in a chunk of its own (asserted below for this world).  The
+    chunk size comes from the plan's own rule through mind_debug_aime_book."""
+    sys.path.insert(0, ROOT)
+    from bench import make_closed_loop
+    from mind_amd._lib import aime_book, predict_choice
+    # what the context was created with: the library's defaults or their MIND_* overrides (mind_hip.hip: mind_ctx_create)
+    defaults = {k: int(os.environ.get("MIND_" + k.upper(), v)) for k, v in dict(plan_chunk_mb=96 * 1024, tab_small=1, dec_mirror=1, tab_host_max=4096, glue_fused=1).items()}
+    budget = 8
+    outs = []
+    for knobs in ({}, dict(plan_chunk_mb=budget), dict(plan_chunk_mb=budget, tab_small=0, dec_mirror=0, tab_host_max=0, glue_fused=0)):
+        pl, sim, w = make_closed_loop(dict(n_agents=16, n_lanes=4, n_segs=8, seed=4), full_tree=True, speculative=False)
+        rt = pl.network.rt
+        plans, plan = [], rt.aime_plan
+        rt.aime_plan = lambda *a, **k: plans.append(plan(*a, **k)) or plans[-1]
+        try:
+            for k, v in knobs.items():
+                rt.set_tuning(k, v)
+            sim.run_plans(1)
+        finally:
+            del rt.aime_plan
+            for k, v in defaults.items():
+                rt.set_tuning(k, v)
+        (nodes, rows, info), (scen, traj) = plans[-1], sim.last_result
+        outs.append(dict(info=info, nodes=nodes.tobytes(), rows=rows.copy(), best=pl.timing["best_traj_idx"], costs=np.array(pl.timing["tree_costs"]),
+                         xs=[np.array([n.data[0] for k, n in t.nodes.items() if k != -1]) for t in traj]))
+        assert len(plans) == 1 and pl.scen_tree_gen.n_native_plans == 1
+    whole = outs[0]
+    a, l = whole["info"]["a"], whole["info"]["l"]
+    assert whole["info"]["round_scenes"][:3] == [1, 6, 36] and whole["info"]["n_expanded"] >= 250          # 1 + 6 + 36 + 216 when no mode is pruned
+    # the chunk size of the 36-scene round: the plan's own rule, over the decision words of a full tree's first three rounds
+    words = []
+    for B in (1, 6, 36):
+        hit = np.zeros((B, 6, 2), np.uint32)
+        hit[:, :, 0] = 1 << (4 + 6 * len(words))
+        words.append(np.concatenate([np.tile(np.arange(6, dtype=np.float32), B), np.full(6 * B, .1, np.float32), hit.ravel().view(np.float32)]))
+    bpp = predict_choice({}, rt.pair_precision(), [(a, l)])["edge_pair_bytes"]
+    chunk, at_1mb = (aime_book(50, 4, a, words, n_tokens=a + l + 1, bytes_per_pair=bpp, plan_chunk_mb=mb)["rounds"][2]["chunk"] for mb in (budget, 1))
+    assert chunk < 36 and 36 % chunk != 0 and at_1mb == 1, (chunk, at_1mb)
+    for o in outs[1:]:
+        assert o["nodes"] == whole["nodes"] and np.array_equal(o["rows"], whole["rows"]) and o["info"]["round_scenes"] == whole["info"]["round_scenes"]
+        assert len(o["info"]["flats"]) == len(whole["info"]["flats"]) == 6
+        for (ta, fa), (tb, fb) in zip(o["info"]["flats"], whole["info"]["flats"]):
+            assert ta == tb and all(np.array_equal(fa[k], fb[k]) and fa[k].dtype == fb[k].dtype for k in ("parent", "prob", "mean", "cov"))
+        assert o["best"] == whole["best"] and np.array_equal(o["costs"], whole["costs"])
+        assert len(o["xs"]) == len(whole["xs"]) > 0 and all(np.array_equal(x, y) for x, y in zip(o["xs"], whole["xs"]))
