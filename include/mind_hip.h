@@ -142,6 +142,8 @@ int mind_set_pair_precision(mind_ctx *ctx, int mode);
  * "ilqr_spec_deriv" (1, default: with slots on follower workgroups one more workgroup per tree runs the derivative pass of a pass's first
  * candidate beside the master's pricing of the candidates, and the master swaps derivative sets instead of differentiating when that
  * candidate is the accepted one; same bits; mind_last_ilqr_stats counts it among the workgroups per tree; MIND_ILQR_SPEC_DERIV),
+ * "ilqr_score_block" (mind_ilqr_score_trees: candidates per workgroup, rounded down to a power of two 1 .. 64; 0, default: 64 while that keeps
+ * two workgroups per CU, halved otherwise down to 4; same bits for every value),
  * copies off the planning cycle's critical path (all of them leave every result bit for bit): "upload_kernel_max" (uploads of at most this many
  * bytes from the context's page-locked staging -- the root scene, the solver's tables -- run as a kernel on the consumer's queue that reads the
  * host buffer, instead of a copy the SDMA engine hands over; default 1 MB, 0 = always copies), "ilqr_host_out_max" (tree-iLQR launches of at
@@ -784,6 +786,16 @@ int mind_cost_eval(mind_ctx *ctx, const mind_ilqr_cfg *cfg, const mind_field_gri
                    const mind_cost_tree *tree, const double *x0, const double *target_lane,
                    int n_lane_pts, double target_vel, int use_exo, int n_query,
                    const int32_t *node, const double *x, const double *u, double *out);
+
+/* Rollout + TreeCost of n_cand candidate control trees per cost tree, no optimisation (solver.py:255-330
+ * without the derivatives).  grid == NULL: planner mode, arguments as mind_ilqr_solve_trees; grid != NULL:
+ * generic mode as mind_ilqr_solve_fields (lane arguments ignored).  us_cand HOST [n_cand, sum M, 2];
+ * outputs HOST xs [n_cand, sum M, 6] (NULL = not wanted), L [n_cand, sum M] (NULL = not wanted),
+ * J [n_cand, n_trees] = numpy-order sum of the tree's L. */
+int mind_ilqr_score_trees(mind_ctx *ctx, const mind_ilqr_cfg *cfg, const mind_field_grid *grid,
+                          const mind_cost_tree *trees, int n_trees, const double *x0,
+                          const double *target_lane, int n_lane_pts, double target_vel, int use_exo,
+                          int n_cand, const double *us_cand, double *xs, double *L, double *J);
 
 #ifdef __cplusplus
 }

@@ -27,6 +27,9 @@ struct IlqrTuning {
   // tree-iLQR launches of at most this many nodes in all write their results (xs, us, statistics) to the host staging themselves at the kernel's
   // end instead of two copies behind it (0 = always copies).  "ilqr_host_out_max" / MIND_ILQR_HOST_OUT_MAX
   long ilqr_host_out_max = 4096;
+  // candidates per workgroup of a scoring launch (k_ilqr_score; a power of two 1 .. 64, 0 = il_score_block decides).  Same bits for every
+  // value.  "ilqr_score_block"
+  int ilqr_score_block = 0;
   // tests: launch a wide tree without its last workgroups / let the followers of a narrow tree leave at once
   bool ilqr_test_starve = false;
 };
@@ -42,6 +45,7 @@ static bool ilqr_tuning_set(IlqrTuning &t, const char *name, int value) {
   else if (is("ilqr_slots")) t.ilqr_slots = value < 1 ? 1 : (value > IL_SLOTS ? IL_SLOTS : value);
   else if (is("ilqr_spec_deriv")) t.ilqr_spec_deriv = value != 0;
   else if (is("ilqr_host_out_max")) t.ilqr_host_out_max = value < 0 ? 0 : value;
+  else if (is("ilqr_score_block")) { t.ilqr_score_block = 0; for (int b = 1; b <= 64 && value > 0; b <<= 1) if (b <= value) t.ilqr_score_block = b; }
   else if (is("ilqr_test_starve")) t.ilqr_test_starve = value != 0;
   else return false;
   return true;
@@ -92,6 +96,16 @@ static IlqrChoice il_choose(const IlqrTuning &t, int n_cu, int n_trees, int max_
   // per-tree completion words only for a launch that cannot abort
   ch.early = ch.host_out && !multi && !gen;
   return ch;
+}
+
+// Candidates per workgroup of a scoring launch (k_ilqr_score: one workgroup per cost tree and block of candidates, a lane per candidate in its
+// state recursion).  A full wave of 64 while that still leaves two workgroups per CU; halved otherwise, down to 4 -- a block's waves price
+// nodes x candidates items, so smaller blocks spread a small call over more CUs
+static int il_score_block(const IlqrTuning &t, int n_cu, int n_trees, int n_cand) {
+  if (t.ilqr_score_block > 0) return t.ilqr_score_block;
+  int cb = 64;
+  while (cb > 4 && (long)n_trees * ((n_cand + cb - 1) / cb) < 2L * n_cu) cb >>= 1;
+  return cb;
 }
 
 // Index tables of one cost tree, as the kernels read them (IlqrTreeDev), + the scratch they are built with: kept in the context, so that a
@@ -212,6 +226,7 @@ struct IlTreeOff {
 struct IlArena {
   size_t nd = 0, nf = 0, ni = 0, nd_in = 0;
   size_t o_gx, o_gy, o_lane, o_evx, o_evu, o_quad, o_evo;        // doubles
+  size_t o_scu, o_scx, o_scl, o_scj;                             // doubles of a scoring call: candidate controls (uploaded) | states, node costs, sums (produced)
   size_t o_evn, o_bars, o_ctl, ctl_ints;                         // ints: queries' nodes, barrier + abort words, slot control blocks (ints per tree)
   size_t bytesIn, bytesF, bytesI, o_structs, o_consts, o_work, total;      // bytes
   std::vector<IlTreeOff> tree;
@@ -226,6 +241,7 @@ struct IlShape {
   const int *n_agents;                  // [n_trees] (1 in the generic mode)
   bool gen, use_exo, dev_flat;          // dev_flat: the agent arrays are read where a plan left them on the device, not uploaded
   int trace_cap;
+  int n_cand = 0;                       // candidate control trees of a scoring call, 0 otherwise
 };
 
 static void il_layout(const IlShape &s, const IlqrChoice &ch, const IlTables *tab, IlArena &A) {
@@ -245,6 +261,10 @@ static void il_layout(const IlShape &s, const IlqrChoice &ch, const IlTables *ta
   A.o_ctl = A.takeI(ch.form == 2 ? A.ctl_ints * (size_t)n_trees : 0);      // (zero at upload; 16-byte aligned: the ints region is)
   for (int t = 0; t < n_trees; ++t) A.tree[t].us = A.takeD(2 * nodes(t));
   for (int t = 0; t < n_trees; ++t) A.tree[t].nodew = A.takeD(s.gen ? nodes(t) * IL_NW : 0);
+  size_t Mtot = 0;
+  for (int t = 0; t < n_trees; ++t) Mtot += nodes(t);
+  const size_t n_sc = (size_t)s.n_cand * Mtot;      // (candidate, node) rows of a scoring call; 0 otherwise: nothing below moves
+  A.o_scu = A.takeD(2 * n_sc);
   A.nd_in = A.nd;
   A.o_quad = A.takeD(s.gen ? 2 : (size_t)s.W * s.H); A.o_evo = A.takeD((size_t)s.nq * IL_EVAL_OUT);
   // results of all trees are contiguous (us already is: it lives in the upload region), so they come back in three copies
@@ -271,6 +291,7 @@ static void il_layout(const IlShape &s, const IlqrChoice &ch, const IlTables *ta
     L.fsstart = A.takeI(T.fs_start.size()); L.fsitems = A.takeI(T.fs_items.size()); L.fsq1 = A.takeI(T.fs_q1.size());
     L.fsnstart = A.takeI(T.fs_nstart.size()); L.fsnodes = A.takeI(nodes(t));
   }
+  A.o_scx = A.takeD(6 * n_sc); A.o_scl = A.takeD(n_sc); A.o_scj = A.takeD((size_t)s.n_cand * n_trees);
   A.bytesIn = A.nd_in * sizeof(double); A.bytesF = A.nf * sizeof(float); A.bytesI = A.ni * sizeof(int);
   A.o_structs = A.bytesIn + A.bytesF + A.bytesI;
   A.o_consts = (A.o_structs + (size_t)n_trees * sizeof(IlqrTreeDev) + 15) & ~(size_t)15;

@@ -92,10 +92,14 @@ static int il_field_prepare(mind_ctx *c, const mind_ilqr_cfg *cfg, const double 
 // one tree-iLQR call
 // -------------------------------------------------------------------------------------------------
 struct IlqrEvalReq { int nq; const int32_t *node; const double *x, *u; double *out; };
+// rollout + node costs + their sum of n_cand candidate control trees per cost tree: us_cand [n_cand, sum M, 2] -> xs [n_cand, sum M, 6] (or null),
+// L [n_cand, sum M] (or null), J [n_cand, n_trees]
+struct IlqrScoreReq { int n_cand; const double *us_cand; double *xs, *L, *J; };
+#define IL_SCORE_MAX_ROWS (1L << 20)      // n_cand x sum M a scoring call admits (48 MB of states)
 
 // What a caller asks of il_solve.  cfg2 != nullptr: two fits in one launch -- (cfg, lane term only) then, from its controls, (cfg2, full
 // cost); grid != nullptr: the generic mode (materialised per-node fields + per-node weights); ev != nullptr: node costs at the requested
-// points instead of a solve
+// points instead of a solve; sc != nullptr: candidate control trees priced instead of a solve (any number of trees)
 struct IlqrCall {
   const mind_ilqr_cfg *cfg = nullptr, *cfg2 = nullptr;
   const mind_field_grid *grid = nullptr;
@@ -109,6 +113,7 @@ struct IlqrCall {
   double *xs = nullptr, *us = nullptr;
   mind_ilqr_stats *stats = nullptr, *stats2 = nullptr;      // of the first / the second fit
   const IlqrEvalReq *ev = nullptr;
+  const IlqrScoreReq *sc = nullptr;
   bool begin_only = false;      // return behind the launch: the other half stays in c->il_finish (mind_ilqr_finish)
   bool dev_flat = false;        // the trees are the context's last plan's: read their agent arrays where k_aime_flat wrote them (tree t at node offset plan.book.tree_off[t])
 };
@@ -154,7 +159,10 @@ static int il_check(mind_ctx *c, const IlqrCall &q, IlRun &R) {
   const IlqrEvalReq *ev = q.ev;
   if (!c || !cfg || !q.trees || q.n_trees <= 0 || !q.x0) return fail(c, MIND_EINVAL, "iLQR: bad argument");
   if (c->il_finish) return fail(c, MIND_ESTATE, "a tree-iLQR call begun with mind_ilqr_contingency_begin has not been finished (mind_ilqr_finish)");
-  if (!ev && (!q.xs || !q.us)) return fail(c, MIND_EINVAL, "iLQR: null output");
+  const IlqrScoreReq *sc = q.sc;
+  if (!ev && !sc && (!q.xs || !q.us)) return fail(c, MIND_EINVAL, "iLQR: null output");
+  if (sc && sc->n_cand < 1) return fail(c, MIND_EINVAL, "mind_ilqr_score_trees: n_cand = %d, at least one candidate is needed", sc->n_cand);
+  if (sc && (!sc->us_cand || !sc->J)) return fail(c, MIND_EINVAL, "mind_ilqr_score_trees: null us_cand / J");
   const bool gen = R.gen = q.grid != nullptr;
   if (!gen && (!q.lane || q.n_lane_pts < 2)) return fail(c, MIND_EINVAL, "iLQR: target lane needs >= 2 points");
   R.n_phases = cfg2 ? 2 : 1;
@@ -167,7 +175,7 @@ static int il_check(mind_ctx *c, const IlqrCall &q, IlRun &R) {
   if (cfg2 && (cfg2->dt != cfg->dt || cfg2->wheelbase != cfg->wheelbase || cfg2->grid_res != cfg->grid_res || cfg2->grid_w != cfg->grid_w ||
                cfg2->grid_h != cfg->grid_h))
     return fail(c, MIND_EINVAL, "mind_ilqr_contingency: both configurations must share dt / wheelbase / grid");
-  R.dev_flat = q.dev_flat && !gen && !ev && c->plan.dev_fmean && c->plan.dev_fcov;
+  R.dev_flat = q.dev_flat && !gen && !ev && !sc && c->plan.dev_fmean && c->plan.dev_fcov;
   R.n_agents.resize(q.n_trees);
   for (int t = 0; t < q.n_trees; ++t) {
     const mind_cost_tree &tr = q.trees[t];
@@ -186,6 +194,16 @@ static int il_check(mind_ctx *c, const IlqrCall &q, IlRun &R) {
   if (ev)
     for (int i = 0; i < ev->nq; ++i)
       if (ev->node[i] < 0 || ev->node[i] >= q.trees[0].n_nodes) return fail(c, MIND_EINVAL, "mind_cost_eval: node %d out of range", ev->node[i]);
+  if (sc) {
+    if (q.n_trees > 65535) return fail(c, MIND_EINVAL, "mind_ilqr_score_trees: %d cost trees > 65535 supported", q.n_trees);
+    if ((long)sc->n_cand * R.Mtot > IL_SCORE_MAX_ROWS)
+      return fail(c, MIND_EINVAL, "mind_ilqr_score_trees: %d candidates x %ld nodes > %ld rows supported", sc->n_cand, R.Mtot, IL_SCORE_MAX_ROWS);
+    const size_t n = (size_t)sc->n_cand * (size_t)R.Mtot * 2;
+    for (size_t i = 0; i < n; ++i)
+      if (!std::isfinite(sc->us_cand[i]))
+        return fail(c, MIND_EINVAL, "mind_ilqr_score_trees: candidate %ld has a non-finite control at node %ld", (long)(i / ((size_t)R.Mtot * 2)),
+                    (long)(i / 2 % (size_t)R.Mtot));
+  }
   R.trace_cap = std::min(256, std::max(cfg->max_iter, cfg2 ? cfg2->max_iter : 0));      // rows of the per-iteration trace, per phase
   return MIND_OK;
 }
@@ -262,6 +280,7 @@ static int il_stage(mind_ctx *c, IlRun &R) {
     memcpy(hD.data() + A.o_evu, ev->u, (size_t)ev->nq * 2 * sizeof(double));
     memcpy(hI.data() + A.o_evn, ev->node, (size_t)ev->nq * sizeof(int));
   }
+  if (q.sc) memcpy(hD.data() + A.o_scu, q.sc->us_cand, (size_t)q.sc->n_cand * (size_t)R.Mtot * 2 * sizeof(double));
   // A launch of small trees writes its results to the host ITSELF at its end (k_ilqr: the staging is page-locked and mapped), instead of two
   // copies behind it
   const IlTreeOff &L0 = A.tree[0];
@@ -322,7 +341,7 @@ static int il_stage(mind_ctx *c, IlRun &R) {
     moff += (long)M;
   }
   // a field prepared ahead for exactly this grid and lane (il_field_prepare): the kernels read it where it is
-  R.field_ahead = !gen && !ev && c->il_field_valid && c->il_field_key[0] == q.x0[0] && c->il_field_key[1] == q.x0[1] && c->il_field_key[2] == (double)R.W &&
+  R.field_ahead = !gen && !ev && !q.sc && c->il_field_valid && c->il_field_key[0] == q.x0[0] && c->il_field_key[1] == q.x0[1] && c->il_field_key[2] == (double)R.W &&
                   c->il_field_key[3] == (double)R.H && c->il_field_key[4] == R.grid_res && c->il_field_lane.size() == 2 * (size_t)R.n_lane_pts &&
                   memcmp(c->il_field_lane.data(), q.lane, c->il_field_lane.size() * sizeof(double)) == 0;
   c->il_field_valid = false;         // (one call's worth: the next call makes its own or prepares again)
@@ -492,6 +511,26 @@ static int il_eval(mind_ctx *c, const IlRun &R, hipStream_t st) {
   return MIND_OK;
 }
 
+// the scoring launch: states, node costs and their sums of every (candidate, tree), read back at once
+static int il_score(mind_ctx *c, const IlRun &R, hipStream_t st) {
+  const IlqrScoreReq *sc = R.q.sc;
+  const IlArena &A = R.A;
+  const int n_trees = R.q.n_trees;
+  const IlqrTreeDev *dT = (const IlqrTreeDev *)(R.base + A.o_structs);
+  const int cb = il_score_block(c->it, c->n_cu, n_trees, sc->n_cand);
+  const dim3 grid((sc->n_cand + cb - 1) / cb, n_trees), block(IL_SC_THREADS);
+  const size_t lds = il_score_lds_bytes(R.amax);
+  const size_t rows = (size_t)sc->n_cand * (size_t)R.Mtot;
+  if (R.gen) hipLaunchKernelGGL(k_ilqr_score<true>, grid, block, lds, st, dT, R.K[0], n_trees, sc->n_cand, cb, R.Mtot, il_ag_doubles(R.amax), R.Dp(A.o_scu), R.Dp(A.o_scx), R.Dp(A.o_scl), R.Dp(A.o_scj));
+  else hipLaunchKernelGGL(k_ilqr_score<false>, grid, block, lds, st, dT, R.K[0], n_trees, sc->n_cand, cb, R.Mtot, il_ag_doubles(R.amax), R.Dp(A.o_scu), R.Dp(A.o_scx), R.Dp(A.o_scl), R.Dp(A.o_scj));
+  HIPCHK(c, hipGetLastError());
+  if (sc->xs) HIPCHK(c, hipMemcpyAsync(sc->xs, R.Dp(A.o_scx), rows * 6 * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (sc->L) HIPCHK(c, hipMemcpyAsync(sc->L, R.Dp(A.o_scl), rows * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(sc->J, R.Dp(A.o_scj), (size_t)sc->n_cand * n_trees * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  return MIND_OK;
+}
+
 // ---- 7. launch: the lane field (unless one was prepared ahead), k_ilqr in the chosen form, the copies behind it; leaves what il_finish_run needs in P
 static int il_launch(mind_ctx *c, const IlRun &R, hipStream_t st, IlPending &P) {
   const IlqrCall &q = R.q;
@@ -501,6 +540,7 @@ static int il_launch(mind_ctx *c, const IlRun &R, hipStream_t st, IlPending &P) 
   if (R.field_ahead) HIPCHK(c, hipStreamWaitEvent(st, c->ev_field, 0));
   else if (!R.gen) hipLaunchKernelGGL(k_lane_field, dim3((R.W * R.H + 255) / 256), dim3(256), 0, st, R.K[0].gx.p, R.K[0].gy.p, R.W, R.H, R.Dp(A.o_lane), R.n_lane_pts, R.Dp(A.o_quad));
   if (q.ev) return il_eval(c, R, st);
+  if (q.sc) return il_score(c, R, st);
   P.st = st; P.gen = R.gen; P.n_trees = n_trees; P.n_phases = R.n_phases; P.use_exo = R.use_exo; P.trace_cap = R.trace_cap; P.Mtot = R.Mtot; P.ch = ch;
   P.dT = (const IlqrTreeDev *)(R.base + A.o_structs); P.dK = (const IlqrConst *)(R.base + A.o_consts);
   P.dBars = (unsigned *)(R.dI() + A.o_bars);
@@ -539,9 +579,9 @@ static int il_solve(mind_ctx *c, const IlqrCall &q) {
   il_grid(R);
   int maxM = 0;
   for (int t = 0; t < q.n_trees; ++t) maxM = std::max(maxM, q.trees[t].n_nodes);
-  R.ch = il_choose(c->it, c->n_cu, q.n_trees, maxM, R.Mtot, R.gen, q.ev != nullptr);
+  R.ch = il_choose(c->it, c->n_cu, q.n_trees, maxM, R.Mtot, R.gen, q.ev != nullptr || q.sc != nullptr);
   if ((rc = il_build_tables(c, q))) return rc;
-  const IlShape shape{R.W, R.H, R.n_lane_pts, q.ev ? q.ev->nq : 0, q.n_trees, R.n_agents.data(), R.gen, R.use_exo != 0, R.dev_flat, R.trace_cap};
+  const IlShape shape{R.W, R.H, R.n_lane_pts, q.ev ? q.ev->nq : 0, q.n_trees, R.n_agents.data(), R.gen, R.use_exo != 0, R.dev_flat, R.trace_cap, q.sc ? q.sc->n_cand : 0};
   il_layout(shape, R.ch, c->il_tab.data(), R.A);
   stamp("tables built");
   if ((rc = il_stage(c, R))) return rc;
@@ -549,7 +589,7 @@ static int il_solve(mind_ctx *c, const IlqrCall &q) {
   if ((rc = il_upload(c, R, st))) return rc;
   stamp("upload queued");
   IlPending P;
-  if ((rc = il_launch(c, R, st, P)) || q.ev) return rc;
+  if ((rc = il_launch(c, R, st, P)) || q.ev || q.sc) return rc;
   stamp("kernel launched");
   if (!q.begin_only) return il_finish_run(c, P);
   c->il_finish = [c, P = std::move(P)]() { return il_finish_run(c, P); };
@@ -649,6 +689,16 @@ extern "C" int mind_cost_eval(mind_ctx *c, const mind_ilqr_cfg *cfg, const mind_
   IlqrCall q;
   q.cfg = cfg; q.grid = grid; q.trees = tree; q.n_trees = 1; q.x0 = x0; q.lane = target_lane; q.n_lane_pts = n_lane_pts; q.target_vel = target_vel;
   q.use_exo = use_exo; q.ev = &ev;
+  return il_solve(c, q);
+}
+
+extern "C" int mind_ilqr_score_trees(mind_ctx *c, const mind_ilqr_cfg *cfg, const mind_field_grid *grid, const mind_cost_tree *trees, int n_trees,
+                                     const double *x0, const double *target_lane, int n_lane_pts, double target_vel, int use_exo, int n_cand,
+                                     const double *us_cand, double *xs, double *L, double *J) {
+  const IlqrScoreReq sc{n_cand, us_cand, xs, L, J};
+  IlqrCall q;
+  q.cfg = cfg; q.grid = grid; q.trees = trees; q.n_trees = n_trees; q.x0 = x0; q.lane = target_lane; q.n_lane_pts = n_lane_pts; q.target_vel = target_vel;
+  q.use_exo = use_exo; q.sc = &sc;
   return il_solve(c, q);
 }
 

@@ -28,6 +28,7 @@
 #include "actor_f32_kernels.hip"
 #include "dec_mfma_kernels.hip"
 #include "ilqr_kernels.hip"
+#include "ilqr_score_kernels.hip"
 #include "pair_jobs.h"
 #include "pred_choice.h"
 #include "ilqr_choice.h"

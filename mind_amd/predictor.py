@@ -436,6 +436,53 @@ class HipPredictor:
         luu[:, 0, 0], luu[:, 1, 1] = out[:, 45], out[:, 46]
         return dict(l=out[:, 0].copy(), l_x=out[:, 1:7].copy(), l_u=out[:, 7:9].copy(), l_xx=out[:, 9:45].reshape(-1, 6, 6).copy(), l_uu=luu)
 
+    def ilqr_score(self, cfg, flats, x0, lane, target_vel, use_exo, us_cand, grid=None, want_xs=True, want_L=True):
+        """Rollout + TreeCost of C candidate control trees on every cost tree of ``flats`` in one launch, no optimisation
+        (mind_ilqr_score_trees).  grid None: planner-mode flat dicts as ``ilqr_solve`` takes them; grid given: generic tree dicts
+        (parent, field, node_w) as ``ilqr_solve_fields`` takes one, ``lane`` / ``use_exo`` ignored.  ``us_cand``: [C, sum M, 2], or one
+        array [C, M_t, 2] per tree.  Returns (xs list[[C, M_t, 6]], L list[[C, M_t]], J [C, n_trees]); J[c, t] is the J a fit of one
+        iteration from candidate c reports.  want_xs / want_L False: that output is not read back (None in its place)."""
+        n = len(flats)
+        keep = []
+        trees = (_lib.CostTree * max(n, 1))()
+        Ms = []
+        for i, f in enumerate(flats):
+            if grid is not None:
+                trees[i] = self._generic_tree(f, keep)
+            else:
+                par = np.ascontiguousarray(f["parent"], np.int32)
+                prob = np.ascontiguousarray(f["prob"], np.float32)
+                mean = np.ascontiguousarray(f["mean"], np.float32)
+                cov = np.ascontiguousarray(f["cov"], np.float32)
+                keep += [par, prob, mean, cov]
+                t = trees[i]
+                t.n_nodes, t.n_agents = len(par), mean.shape[1]
+                t.parent = par.ctypes.data_as(C.POINTER(C.c_int32))
+                t.prob = prob.ctypes.data_as(C.POINTER(C.c_float))
+                t.agent_mean = mean.ctypes.data_as(C.POINTER(C.c_float))
+                t.agent_cov = cov.ctypes.data_as(C.POINTER(C.c_float))
+            Ms.append(int(trees[i].n_nodes))
+        Mt = int(sum(Ms))
+        if isinstance(us_cand, (list, tuple)):
+            us_cand = np.concatenate([np.asarray(u, np.float64) for u in us_cand], axis=1)
+        uc = np.ascontiguousarray(us_cand, np.float64)
+        if uc.ndim != 3 or uc.shape[1:] != (Mt, 2):
+            raise ValueError(f"us_cand must be [C, {Mt}, 2] for these cost trees, got {uc.shape}")
+        nc = uc.shape[0]
+        g = C.byref(self._grid(grid, keep)) if grid is not None else None
+        x0 = np.ascontiguousarray(x0, np.float64)
+        lane_a = None if lane is None or grid is not None else np.ascontiguousarray(lane, np.float64)
+        xs = np.zeros((nc, Mt, 6)) if want_xs else None
+        L = np.zeros((nc, Mt)) if want_L else None
+        J = np.zeros((nc, n))
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double)) if a is not None else None
+        rc = self.lib.mind_ilqr_score_trees(self.ctx, C.byref(cfg), g, trees, n, dp(x0), dp(lane_a), 0 if lane_a is None else len(lane_a),
+                                            C.c_double(float(target_vel)), int(use_exo), nc, dp(uc), dp(xs), dp(L), dp(J))
+        _lib.check(self.lib, self.ctx, rc, "mind_ilqr_score_trees")
+        offs = np.cumsum([0] + Ms)
+        split = lambda a: None if a is None else [a[:, offs[i]:offs[i + 1]].copy() for i in range(n)]
+        return split(xs), split(L), J
+
     def aime_world(self, reg, vel, actor_ctrs, actor_vecs, a_off, rots, origs, cov_last, last, target_lane=None, cls=None,
                    scen_prob=None, dist_thres=None):
         """k7 on the device (mind_aime_world): reg [A,6,60,5] / vel [A,6,60,2] / actor_ctrs, actor_vecs [A,2] device
