@@ -4,8 +4,9 @@ CPU restatement of the reference scene predictor forward, written from the
 formulas, as plain torch tensor ops in fp32 (or fp64 with ``dtype``).  Only
 tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import it.
 
-Pinned against the imported reference (tests/test_oracle_vs_reference.py, build
-container only) and against tests/golden/predictor_*.npz (everywhere).
+Pinned by tests/test_oracle_predictor.py against recorded values of the imported
+reference (tests/golden/ref_live/) and against tests/golden/predictor.npz, and by
+tests/test_oracle_regimes.py against the reference under stressed weights.
 
 Follows, function by function:
   rpe()            planners/mind/utils.py:193-242          (get_rpe/get_cos/get_sin)

@@ -192,7 +192,8 @@ def test_recorded_demo_scenes_match_reference_closed_loop(scene, prec):
     CPU, formula weights -- its trained checkpoint is not in the tree) was run to the first four planning cycles
     (tests/golden/gen_golden.py demo_plans); the same closed loop here must pick the same AIME branch every cycle and
     reproduce agent / ego trajectories within 1e-3 m (+ float32 resolution of the ~6.5 km map coordinates) -- in the default
-    arithmetic of the predictor (bf16x3) AND with every contraction in fp32, the reference's own precision."""
+    arithmetic of the predictor (bf16x6), in the opt-in two-way split (bf16x3) AND with every contraction in fp32, the reference's
+    own precision."""
     sys.path.insert(0, ROOT)
     from bench import WORKLOADS, make_closed_loop
     pl, sim, w = make_closed_loop(dict(WORKLOADS[scene]), scripted=False)
@@ -576,8 +577,8 @@ def test_four_recorded_scenes_pipelined_from_one_thread_equal_separate_runs():
 @pytest.mark.parametrize("scene", ["demo_1", "demo_4"])
 def test_aime_tree_does_not_depend_on_the_pair_kernel_arithmetic(scene):
     """The discrete AIME result (node ids, branch times, chosen tree) of a branching closed loop is the same whether the pair
-    kernel runs on the fp32 MFMA or in its default bf16x3 arithmetic, and the trajectories agree to 1e-4 m: the decisions do
-    not sit on the rounding difference between the two fp32-class modes."""
+    kernel runs on the fp32 MFMA or in its opt-in bf16x3 arithmetic (the default is bf16x6), and the trajectories agree to 1e-4 m: the
+    decisions do not sit on the rounding difference between the two modes."""
     sys.path.insert(0, ROOT)
     from bench import WORKLOADS, make_closed_loop
     runs = {}
