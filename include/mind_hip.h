@@ -797,6 +797,41 @@ int mind_ilqr_score_trees(mind_ctx *ctx, const mind_ilqr_cfg *cfg, const mind_fi
                           const double *target_lane, int n_lane_pts, double target_vel, int use_exo,
                           int n_cand, const double *us_cand, double *xs, double *L, double *J);
 
+/* The gains of ONE backward pass (solver.py:332-373; the rule they feed: solver.py:202-253) about the controls
+ * us HOST [sum M, 2], with the regularisation mu HOST [n_trees] (>= 0), on every cost tree; no optimisation.
+ * grid selects the planner or the generic mode as in mind_ilqr_score_trees.  Outputs HOST, rows in key order, tree
+ * after tree: k [sum M, 2], K [sum M, 2, 6], dV [sum M], V_x [sum M, 6], V_xx [sum M, 6, 6] (the values after the
+ * node's own update), the nominal xs [sum M, 6] = rollout of us, L [sum M], J [n_trees] = numpy-order sum of L,
+ * bad_node [n_trees].  k, K and bad_node are required, the others may be NULL.  The reference's root key -1
+ * aliases numpy row -1, so ITS V_x / V_xx row M-1 also holds node 0's value; here row M-1 is that node's own.
+ * A singular Q_uu is no error: bad_node[t] = the lowest key among the nodes whose own Q_uu was singular while all
+ * their descendants were fine (-1: none); that tree's k, K, dV, V_x, V_xx are zeros, its xs / L / J are valid.
+ * One workgroup per tree: meant for planner-size trees (a 12 288-node tree is served, but slowly). */
+typedef struct {
+  double *k, *K, *dV, *V_x, *V_xx, *xs, *L, *J;
+  int32_t *bad_node;
+} mind_ilqr_gains_out;
+int mind_ilqr_gains(mind_ctx *ctx, const mind_ilqr_cfg *cfg, const mind_field_grid *grid,
+                    const mind_cost_tree *trees, int n_trees, const double *x0, const double *target_lane,
+                    int n_lane_pts, double target_vel, int use_exo, const double *us, const double *mu,
+                    const mind_ilqr_gains_out *out);
+
+/* Closed-loop rollouts under given gains (the line search's rule, solver.py:202-253, with the gains of
+ * solver.py:332-373): candidate c, with the step size alpha[c] and the start offset dx0[c] (HOST [n_cand, 6];
+ * NULL = zeros), applies at node i with parent p
+ *   u_new[i] = us[i] + alpha[c] k[i] + K[i] (x_new[p] - xs[p]),   x_new[i] = f(x_new[p], u_new[i]),
+ * xs = the nominal states, recomputed from us by the call; for node 0 the pair is (x0 + dx0[c], x0) -- the one
+ * extension over the reference, whose node 0 has no feedback term.  us HOST [sum M, 2], k [sum M, 2], K [sum M, 2, 6],
+ * alpha [n_cand].  Outputs HOST xs [n_cand, sum M, 6], us_out [n_cand, sum M, 2], L [n_cand, sum M] (each may be
+ * NULL), J [n_cand, n_trees] = the LINE SEARCH's sum of the tree's L: sequential from 0.0 in key order (python's
+ * sum()), not the numpy-order sum mind_ilqr_score_trees reports.  Modes, limits and MIND_ESTATE as
+ * mind_ilqr_score_trees. */
+int mind_ilqr_policy_rollouts(mind_ctx *ctx, const mind_ilqr_cfg *cfg, const mind_field_grid *grid,
+                              const mind_cost_tree *trees, int n_trees, const double *x0, const double *target_lane,
+                              int n_lane_pts, double target_vel, int use_exo, const double *us, const double *k,
+                              const double *K, int n_cand, const double *alpha, const double *dx0, double *xs,
+                              double *us_out, double *L, double *J);
+
 #ifdef __cplusplus
 }
 #endif

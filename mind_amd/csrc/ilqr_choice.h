@@ -227,6 +227,10 @@ struct IlArena {
   size_t nd = 0, nf = 0, ni = 0, nd_in = 0;
   size_t o_gx, o_gy, o_lane, o_evx, o_evu, o_quad, o_evo;        // doubles
   size_t o_scu, o_scx, o_scl, o_scj;                             // doubles of a scoring call: candidate controls (uploaded) | states, node costs, sums (produced)
+  // doubles of a gains call: mu (uploaded) | k, K, dV, V_x, V_xx, nominal xs, L of all trees, J, bad_node (produced, back to back: one read-back)
+  size_t o_gmu, o_gk, o_gK, o_gdv, o_gvx, o_gvxx, o_gxs, o_gl, o_gj, o_gbad;
+  // doubles of a policy-rollout call: k, K, alpha, dx0 (uploaded) | nominal states per candidate block, states, controls, node costs, sums (produced)
+  size_t o_pk, o_pK, o_pal, o_pdx, o_pxn, o_pxs, o_pus, o_pl, o_pj;
   size_t o_evn, o_bars, o_ctl, ctl_ints;                         // ints: queries' nodes, barrier + abort words, slot control blocks (ints per tree)
   size_t bytesIn, bytesF, bytesI, o_structs, o_consts, o_work, total;      // bytes
   std::vector<IlTreeOff> tree;
@@ -242,6 +246,8 @@ struct IlShape {
   bool gen, use_exo, dev_flat;          // dev_flat: the agent arrays are read where a plan left them on the device, not uploaded
   int trace_cap;
   int n_cand = 0;                       // candidate control trees of a scoring call, 0 otherwise
+  bool gains = false;                   // a gains call (k_ilqr_gains)
+  int n_pol = 0, n_pol_blk = 0;         // candidates of a policy-rollout call and the workgroups they are dealt to (k_ilqr_policy), 0 otherwise
 };
 
 static void il_layout(const IlShape &s, const IlqrChoice &ch, const IlTables *tab, IlArena &A) {
@@ -265,6 +271,10 @@ static void il_layout(const IlShape &s, const IlqrChoice &ch, const IlTables *ta
   for (int t = 0; t < n_trees; ++t) Mtot += nodes(t);
   const size_t n_sc = (size_t)s.n_cand * Mtot;      // (candidate, node) rows of a scoring call; 0 otherwise: nothing below moves
   A.o_scu = A.takeD(2 * n_sc);
+  // the gains and policy requests' uploads; without them every region below is empty and nothing moves
+  const size_t n_g = s.gains ? Mtot : 0, n_gt = s.gains ? (size_t)n_trees : 0, n_pm = s.n_pol > 0 ? Mtot : 0, n_po = (size_t)s.n_pol * Mtot;
+  A.o_gmu = A.takeD(n_gt);
+  A.o_pk = A.takeD(2 * n_pm); A.o_pK = A.takeD(12 * n_pm); A.o_pal = A.takeD((size_t)s.n_pol); A.o_pdx = A.takeD(6 * (size_t)s.n_pol);
   A.nd_in = A.nd;
   A.o_quad = A.takeD(s.gen ? 2 : (size_t)s.W * s.H); A.o_evo = A.takeD((size_t)s.nq * IL_EVAL_OUT);
   // results of all trees are contiguous (us already is: it lives in the upload region), so they come back in three copies
@@ -292,6 +302,10 @@ static void il_layout(const IlShape &s, const IlqrChoice &ch, const IlTables *ta
     L.fsnstart = A.takeI(T.fs_nstart.size()); L.fsnodes = A.takeI(nodes(t));
   }
   A.o_scx = A.takeD(6 * n_sc); A.o_scl = A.takeD(n_sc); A.o_scj = A.takeD((size_t)s.n_cand * n_trees);
+  A.o_gk = A.takeD(2 * n_g); A.o_gK = A.takeD(12 * n_g); A.o_gdv = A.takeD(n_g); A.o_gvx = A.takeD(6 * n_g); A.o_gvxx = A.takeD(36 * n_g);
+  A.o_gxs = A.takeD(6 * n_g); A.o_gl = A.takeD(n_g); A.o_gj = A.takeD(n_gt); A.o_gbad = A.takeD(n_gt);
+  A.o_pxn = A.takeD(6 * (size_t)s.n_pol_blk * n_pm); A.o_pxs = A.takeD(6 * n_po); A.o_pus = A.takeD(2 * n_po); A.o_pl = A.takeD(n_po);
+  A.o_pj = A.takeD((size_t)s.n_pol * (s.n_pol > 0 ? n_trees : 0));
   A.bytesIn = A.nd_in * sizeof(double); A.bytesF = A.nf * sizeof(float); A.bytesI = A.ni * sizeof(int);
   A.o_structs = A.bytesIn + A.bytesF + A.bytesI;
   A.o_consts = (A.o_structs + (size_t)n_trees * sizeof(IlqrTreeDev) + 15) & ~(size_t)15;

@@ -96,10 +96,17 @@ struct IlqrEvalReq { int nq; const int32_t *node; const double *x, *u; double *o
 // L [n_cand, sum M] (or null), J [n_cand, n_trees]
 struct IlqrScoreReq { int n_cand; const double *us_cand; double *xs, *L, *J; };
 #define IL_SCORE_MAX_ROWS (1L << 20)      // n_cand x sum M a scoring call admits (48 MB of states)
+// the gains of one backward pass about the controls us [sum M, 2] with regularisation mu [n_trees] (k_ilqr_gains): per-node k, K, dV, V_x, V_xx,
+// the nominal xs and L, per-tree J and bad_node
+struct IlqrGainsReq { const double *us, *mu; const mind_ilqr_gains_out *out; };
+// closed-loop rollouts of n_cand (alpha [n_cand], dx0 [n_cand, 6] or null) under the gains k [sum M, 2], K [sum M, 12] about us (k_ilqr_policy):
+// -> xs [n_cand, sum M, 6], us_out [n_cand, sum M, 2], L [n_cand, sum M] (each or null), J [n_cand, n_trees]
+struct IlqrPolicyReq { int n_cand; const double *us, *k, *K, *alpha, *dx0; double *xs, *us_out, *L, *J; };
 
 // What a caller asks of il_solve.  cfg2 != nullptr: two fits in one launch -- (cfg, lane term only) then, from its controls, (cfg2, full
 // cost); grid != nullptr: the generic mode (materialised per-node fields + per-node weights); ev != nullptr: node costs at the requested
-// points instead of a solve; sc != nullptr: candidate control trees priced instead of a solve (any number of trees)
+// points instead of a solve; sc != nullptr: candidate control trees priced instead of a solve (any number of trees); ga / po != nullptr: the
+// gains about us_init / policy rollouts under given gains instead of a solve (any number of trees; us_init = the request's us)
 struct IlqrCall {
   const mind_ilqr_cfg *cfg = nullptr, *cfg2 = nullptr;
   const mind_field_grid *grid = nullptr;
@@ -114,6 +121,8 @@ struct IlqrCall {
   mind_ilqr_stats *stats = nullptr, *stats2 = nullptr;      // of the first / the second fit
   const IlqrEvalReq *ev = nullptr;
   const IlqrScoreReq *sc = nullptr;
+  const IlqrGainsReq *ga = nullptr;
+  const IlqrPolicyReq *po = nullptr;
   bool begin_only = false;      // return behind the launch: the other half stays in c->il_finish (mind_ilqr_finish)
   bool dev_flat = false;        // the trees are the context's last plan's: read their agent arrays where k_aime_flat wrote them (tree t at node offset plan.book.tree_off[t])
 };
@@ -123,6 +132,7 @@ struct IlRun {
   const IlqrCall &q;
   bool gen = false, dev_flat = false, field_ahead = false;
   int n_phases = 1, use_exo = 0, use_exo_first = 0, n_lane_pts = 0, W = 0, H = 0, trace_cap = 0, amax = 1;
+  int pol_cb = 0;                       // candidates per workgroup of a policy-rollout call (il_score_block)
   long Mtot = 0;
   double grid_res = 0, fsx = 0, fsy = 0, offx = 0, offy = 0;
   std::vector<double> gx, gy;
@@ -160,7 +170,13 @@ static int il_check(mind_ctx *c, const IlqrCall &q, IlRun &R) {
   if (!c || !cfg || !q.trees || q.n_trees <= 0 || !q.x0) return fail(c, MIND_EINVAL, "iLQR: bad argument");
   if (c->il_finish) return fail(c, MIND_ESTATE, "a tree-iLQR call begun with mind_ilqr_contingency_begin has not been finished (mind_ilqr_finish)");
   const IlqrScoreReq *sc = q.sc;
-  if (!ev && !sc && (!q.xs || !q.us)) return fail(c, MIND_EINVAL, "iLQR: null output");
+  const IlqrGainsReq *ga = q.ga;
+  const IlqrPolicyReq *po = q.po;
+  if (!ev && !sc && !ga && !po && (!q.xs || !q.us)) return fail(c, MIND_EINVAL, "iLQR: null output");
+  if (ga && (!ga->us || !ga->mu || !ga->out || !ga->out->k || !ga->out->K || !ga->out->bad_node))
+    return fail(c, MIND_EINVAL, "mind_ilqr_gains: null us / mu / out / out->k / out->K / out->bad_node");
+  if (po && po->n_cand < 1) return fail(c, MIND_EINVAL, "mind_ilqr_policy_rollouts: n_cand = %d, at least one candidate is needed", po->n_cand);
+  if (po && (!po->us || !po->k || !po->K || !po->alpha || !po->J)) return fail(c, MIND_EINVAL, "mind_ilqr_policy_rollouts: null us / k / K / alpha / J");
   if (sc && sc->n_cand < 1) return fail(c, MIND_EINVAL, "mind_ilqr_score_trees: n_cand = %d, at least one candidate is needed", sc->n_cand);
   if (sc && (!sc->us_cand || !sc->J)) return fail(c, MIND_EINVAL, "mind_ilqr_score_trees: null us_cand / J");
   const bool gen = R.gen = q.grid != nullptr;
@@ -203,6 +219,28 @@ static int il_check(mind_ctx *c, const IlqrCall &q, IlRun &R) {
       if (!std::isfinite(sc->us_cand[i]))
         return fail(c, MIND_EINVAL, "mind_ilqr_score_trees: candidate %ld has a non-finite control at node %ld", (long)(i / ((size_t)R.Mtot * 2)),
                     (long)(i / 2 % (size_t)R.Mtot));
+  }
+  // index of the first non-finite entry of a[0..n), -1 when there is none
+  const auto first_bad = [](const double *a, size_t n) { for (size_t i = 0; i < n; ++i) if (!std::isfinite(a[i])) return (long)i; return -1L; };
+  if (ga) {
+    if (q.n_trees > 65535) return fail(c, MIND_EINVAL, "mind_ilqr_gains: %d cost trees > 65535 supported", q.n_trees);
+    long b;
+    if ((b = first_bad(ga->us, (size_t)R.Mtot * 2)) >= 0) return fail(c, MIND_EINVAL, "mind_ilqr_gains: non-finite control at node %ld", b / 2);
+    if ((b = first_bad(ga->mu, (size_t)q.n_trees)) >= 0) return fail(c, MIND_EINVAL, "mind_ilqr_gains: non-finite mu of tree %ld", b);
+    for (int t = 0; t < q.n_trees; ++t)
+      if (ga->mu[t] < 0.0) return fail(c, MIND_EINVAL, "mind_ilqr_gains: negative mu of tree %d", t);
+  }
+  if (po) {
+    if (q.n_trees > 65535) return fail(c, MIND_EINVAL, "mind_ilqr_policy_rollouts: %d cost trees > 65535 supported", q.n_trees);
+    if ((long)po->n_cand * R.Mtot > IL_SCORE_MAX_ROWS)
+      return fail(c, MIND_EINVAL, "mind_ilqr_policy_rollouts: %d candidates x %ld nodes > %ld rows supported", po->n_cand, R.Mtot, IL_SCORE_MAX_ROWS);
+    long b;
+    if ((b = first_bad(po->us, (size_t)R.Mtot * 2)) >= 0) return fail(c, MIND_EINVAL, "mind_ilqr_policy_rollouts: non-finite control at node %ld", b / 2);
+    if ((b = first_bad(po->k, (size_t)R.Mtot * 2)) >= 0) return fail(c, MIND_EINVAL, "mind_ilqr_policy_rollouts: non-finite k at node %ld", b / 2);
+    if ((b = first_bad(po->K, (size_t)R.Mtot * 12)) >= 0) return fail(c, MIND_EINVAL, "mind_ilqr_policy_rollouts: non-finite K at node %ld", b / 12);
+    if ((b = first_bad(po->alpha, (size_t)po->n_cand)) >= 0) return fail(c, MIND_EINVAL, "mind_ilqr_policy_rollouts: non-finite alpha of candidate %ld", b);
+    if (po->dx0 && (b = first_bad(po->dx0, (size_t)po->n_cand * 6)) >= 0)
+      return fail(c, MIND_EINVAL, "mind_ilqr_policy_rollouts: non-finite dx0 of candidate %ld", b / 6);
   }
   R.trace_cap = std::min(256, std::max(cfg->max_iter, cfg2 ? cfg2->max_iter : 0));      // rows of the per-iteration trace, per phase
   return MIND_OK;
@@ -281,6 +319,14 @@ static int il_stage(mind_ctx *c, IlRun &R) {
     memcpy(hI.data() + A.o_evn, ev->node, (size_t)ev->nq * sizeof(int));
   }
   if (q.sc) memcpy(hD.data() + A.o_scu, q.sc->us_cand, (size_t)q.sc->n_cand * (size_t)R.Mtot * 2 * sizeof(double));
+  if (q.ga) memcpy(hD.data() + A.o_gmu, q.ga->mu, (size_t)n_trees * sizeof(double));
+  if (q.po) {
+    const IlqrPolicyReq *po = q.po;
+    memcpy(hD.data() + A.o_pk, po->k, (size_t)R.Mtot * 2 * sizeof(double));
+    memcpy(hD.data() + A.o_pK, po->K, (size_t)R.Mtot * 12 * sizeof(double));
+    memcpy(hD.data() + A.o_pal, po->alpha, (size_t)po->n_cand * sizeof(double));
+    if (po->dx0) memcpy(hD.data() + A.o_pdx, po->dx0, (size_t)po->n_cand * 6 * sizeof(double));      // (null: the zeros of the image)
+  }
   // A launch of small trees writes its results to the host ITSELF at its end (k_ilqr: the staging is page-locked and mapped), instead of two
   // copies behind it
   const IlTreeOff &L0 = A.tree[0];
@@ -341,7 +387,7 @@ static int il_stage(mind_ctx *c, IlRun &R) {
     moff += (long)M;
   }
   // a field prepared ahead for exactly this grid and lane (il_field_prepare): the kernels read it where it is
-  R.field_ahead = !gen && !ev && !q.sc && c->il_field_valid && c->il_field_key[0] == q.x0[0] && c->il_field_key[1] == q.x0[1] && c->il_field_key[2] == (double)R.W &&
+  R.field_ahead = !gen && !ev && !q.sc && !q.ga && !q.po && c->il_field_valid && c->il_field_key[0] == q.x0[0] && c->il_field_key[1] == q.x0[1] && c->il_field_key[2] == (double)R.W &&
                   c->il_field_key[3] == (double)R.H && c->il_field_key[4] == R.grid_res && c->il_field_lane.size() == 2 * (size_t)R.n_lane_pts &&
                   memcmp(c->il_field_lane.data(), q.lane, c->il_field_lane.size() * sizeof(double)) == 0;
   c->il_field_valid = false;         // (one call's worth: the next call makes its own or prepares again)
@@ -531,6 +577,51 @@ static int il_score(mind_ctx *c, const IlRun &R, hipStream_t st) {
   return MIND_OK;
 }
 
+// the gains launch: one workgroup per tree; the outputs lie back to back in the arena (il_layout) and come back in ONE copy into the
+// page-locked read-back staging, from where the wanted ones are handed out
+static int il_gains(mind_ctx *c, const IlRun &R, hipStream_t st) {
+  const mind_ilqr_gains_out *o = R.q.ga->out;
+  const IlArena &A = R.A;
+  const int n_trees = R.q.n_trees;
+  const IlqrTreeDev *dT = (const IlqrTreeDev *)(R.base + A.o_structs);
+  const size_t lds = il_gains_lds_bytes(R.amax), M = (size_t)R.Mtot;
+  if (R.gen) hipLaunchKernelGGL(k_ilqr_gains<true>, dim3(n_trees), dim3(IL_PG_THREADS), lds, st, dT, R.K[0], n_trees, il_ag_doubles(R.amax), R.Dp(A.o_gmu), R.Dp(A.o_gk), R.Dp(A.o_gK), R.Dp(A.o_gdv), R.Dp(A.o_gvx), R.Dp(A.o_gvxx), R.Dp(A.o_gxs), R.Dp(A.o_gl), R.Dp(A.o_gj), R.Dp(A.o_gbad));
+  else hipLaunchKernelGGL(k_ilqr_gains<false>, dim3(n_trees), dim3(IL_PG_THREADS), lds, st, dT, R.K[0], n_trees, il_ag_doubles(R.amax), R.Dp(A.o_gmu), R.Dp(A.o_gk), R.Dp(A.o_gK), R.Dp(A.o_gdv), R.Dp(A.o_gvx), R.Dp(A.o_gvxx), R.Dp(A.o_gxs), R.Dp(A.o_gl), R.Dp(A.o_gj), R.Dp(A.o_gbad));
+  HIPCHK(c, hipGetLastError());
+  const size_t span = A.o_gbad + (size_t)n_trees - A.o_gk;
+  int rc;
+  if ((rc = pl_pin(c, 5, span * sizeof(double)))) return rc;      // (grows the staging il_stage sized for a solve; this call uses none of that)
+  const double *h = (const double *)c->pl_pin[5];
+  HIPCHK(c, hipMemcpyAsync(c->pl_pin[5], R.Dp(A.o_gk), span * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  const struct { double *dst; size_t src, n; } outs[8] = {{o->k, A.o_gk, 2 * M}, {o->K, A.o_gK, 12 * M}, {o->dV, A.o_gdv, M}, {o->V_x, A.o_gvx, 6 * M},
+                                                          {o->V_xx, A.o_gvxx, 36 * M}, {o->xs, A.o_gxs, 6 * M}, {o->L, A.o_gl, M}, {o->J, A.o_gj, (size_t)n_trees}};
+  for (const auto &e : outs)
+    if (e.dst) memcpy(e.dst, h + (e.src - A.o_gk), e.n * sizeof(double));
+  for (int t = 0; t < n_trees; ++t) o->bad_node[t] = (int32_t)h[A.o_gbad - A.o_gk + t];
+  return MIND_OK;
+}
+
+// the policy-rollout launch: states, controls, node costs and their sums of every (candidate, tree), read back at once
+static int il_policy(mind_ctx *c, const IlRun &R, hipStream_t st, int cb) {
+  const IlqrPolicyReq *po = R.q.po;
+  const IlArena &A = R.A;
+  const int n_trees = R.q.n_trees;
+  const IlqrTreeDev *dT = (const IlqrTreeDev *)(R.base + A.o_structs);
+  const dim3 grid((po->n_cand + cb - 1) / cb, n_trees), block(IL_SC_THREADS);
+  const size_t lds = il_score_lds_bytes(R.amax);
+  const size_t rows = (size_t)po->n_cand * (size_t)R.Mtot;
+  if (R.gen) hipLaunchKernelGGL(k_ilqr_policy<true>, grid, block, lds, st, dT, R.K[0], n_trees, po->n_cand, cb, R.Mtot, il_ag_doubles(R.amax), R.Dp(A.o_pk), R.Dp(A.o_pK), R.Dp(A.o_pal), R.Dp(A.o_pdx), R.Dp(A.o_pxn), R.Dp(A.o_pxs), R.Dp(A.o_pus), R.Dp(A.o_pl), R.Dp(A.o_pj));
+  else hipLaunchKernelGGL(k_ilqr_policy<false>, grid, block, lds, st, dT, R.K[0], n_trees, po->n_cand, cb, R.Mtot, il_ag_doubles(R.amax), R.Dp(A.o_pk), R.Dp(A.o_pK), R.Dp(A.o_pal), R.Dp(A.o_pdx), R.Dp(A.o_pxn), R.Dp(A.o_pxs), R.Dp(A.o_pus), R.Dp(A.o_pl), R.Dp(A.o_pj));
+  HIPCHK(c, hipGetLastError());
+  if (po->xs) HIPCHK(c, hipMemcpyAsync(po->xs, R.Dp(A.o_pxs), rows * 6 * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (po->us_out) HIPCHK(c, hipMemcpyAsync(po->us_out, R.Dp(A.o_pus), rows * 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (po->L) HIPCHK(c, hipMemcpyAsync(po->L, R.Dp(A.o_pl), rows * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(po->J, R.Dp(A.o_pj), (size_t)po->n_cand * n_trees * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  return MIND_OK;
+}
+
 // ---- 7. launch: the lane field (unless one was prepared ahead), k_ilqr in the chosen form, the copies behind it; leaves what il_finish_run needs in P
 static int il_launch(mind_ctx *c, const IlRun &R, hipStream_t st, IlPending &P) {
   const IlqrCall &q = R.q;
@@ -541,6 +632,8 @@ static int il_launch(mind_ctx *c, const IlRun &R, hipStream_t st, IlPending &P) 
   else if (!R.gen) hipLaunchKernelGGL(k_lane_field, dim3((R.W * R.H + 255) / 256), dim3(256), 0, st, R.K[0].gx.p, R.K[0].gy.p, R.W, R.H, R.Dp(A.o_lane), R.n_lane_pts, R.Dp(A.o_quad));
   if (q.ev) return il_eval(c, R, st);
   if (q.sc) return il_score(c, R, st);
+  if (q.ga) return il_gains(c, R, st);
+  if (q.po) return il_policy(c, R, st, R.pol_cb);
   P.st = st; P.gen = R.gen; P.n_trees = n_trees; P.n_phases = R.n_phases; P.use_exo = R.use_exo; P.trace_cap = R.trace_cap; P.Mtot = R.Mtot; P.ch = ch;
   P.dT = (const IlqrTreeDev *)(R.base + A.o_structs); P.dK = (const IlqrConst *)(R.base + A.o_consts);
   P.dBars = (unsigned *)(R.dI() + A.o_bars);
@@ -579,9 +672,15 @@ static int il_solve(mind_ctx *c, const IlqrCall &q) {
   il_grid(R);
   int maxM = 0;
   for (int t = 0; t < q.n_trees; ++t) maxM = std::max(maxM, q.trees[t].n_nodes);
-  R.ch = il_choose(c->it, c->n_cu, q.n_trees, maxM, R.Mtot, R.gen, q.ev != nullptr || q.sc != nullptr);
+  const bool other = q.ev || q.sc || q.ga || q.po;      // a request served instead of a solve
+  R.ch = il_choose(c->it, c->n_cu, q.n_trees, maxM, R.Mtot, R.gen, other);
   if ((rc = il_build_tables(c, q))) return rc;
-  const IlShape shape{R.W, R.H, R.n_lane_pts, q.ev ? q.ev->nq : 0, q.n_trees, R.n_agents.data(), R.gen, R.use_exo != 0, R.dev_flat, R.trace_cap, q.sc ? q.sc->n_cand : 0};
+  IlShape shape{R.W, R.H, R.n_lane_pts, q.ev ? q.ev->nq : 0, q.n_trees, R.n_agents.data(), R.gen, R.use_exo != 0, R.dev_flat, R.trace_cap, q.sc ? q.sc->n_cand : 0};
+  shape.gains = q.ga != nullptr;
+  if (q.po) {
+    R.pol_cb = il_score_block(c->it, c->n_cu, q.n_trees, q.po->n_cand);
+    shape.n_pol = q.po->n_cand; shape.n_pol_blk = (q.po->n_cand + R.pol_cb - 1) / R.pol_cb;
+  }
   il_layout(shape, R.ch, c->il_tab.data(), R.A);
   stamp("tables built");
   if ((rc = il_stage(c, R))) return rc;
@@ -589,7 +688,7 @@ static int il_solve(mind_ctx *c, const IlqrCall &q) {
   if ((rc = il_upload(c, R, st))) return rc;
   stamp("upload queued");
   IlPending P;
-  if ((rc = il_launch(c, R, st, P)) || q.ev || q.sc) return rc;
+  if ((rc = il_launch(c, R, st, P)) || other) return rc;
   stamp("kernel launched");
   if (!q.begin_only) return il_finish_run(c, P);
   c->il_finish = [c, P = std::move(P)]() { return il_finish_run(c, P); };
@@ -699,6 +798,27 @@ extern "C" int mind_ilqr_score_trees(mind_ctx *c, const mind_ilqr_cfg *cfg, cons
   IlqrCall q;
   q.cfg = cfg; q.grid = grid; q.trees = trees; q.n_trees = n_trees; q.x0 = x0; q.lane = target_lane; q.n_lane_pts = n_lane_pts; q.target_vel = target_vel;
   q.use_exo = use_exo; q.sc = &sc;
+  return il_solve(c, q);
+}
+
+extern "C" int mind_ilqr_gains(mind_ctx *c, const mind_ilqr_cfg *cfg, const mind_field_grid *grid, const mind_cost_tree *trees, int n_trees,
+                               const double *x0, const double *target_lane, int n_lane_pts, double target_vel, int use_exo, const double *us,
+                               const double *mu, const mind_ilqr_gains_out *out) {
+  const IlqrGainsReq ga{us, mu, out};
+  IlqrCall q;
+  q.cfg = cfg; q.grid = grid; q.trees = trees; q.n_trees = n_trees; q.x0 = x0; q.lane = target_lane; q.n_lane_pts = n_lane_pts; q.target_vel = target_vel;
+  q.use_exo = use_exo; q.us_init = us; q.ga = &ga;
+  return il_solve(c, q);
+}
+
+extern "C" int mind_ilqr_policy_rollouts(mind_ctx *c, const mind_ilqr_cfg *cfg, const mind_field_grid *grid, const mind_cost_tree *trees, int n_trees,
+                                         const double *x0, const double *target_lane, int n_lane_pts, double target_vel, int use_exo,
+                                         const double *us, const double *k, const double *K, int n_cand, const double *alpha, const double *dx0,
+                                         double *xs, double *us_out, double *L, double *J) {
+  const IlqrPolicyReq po{n_cand, us, k, K, alpha, dx0, xs, us_out, L, J};
+  IlqrCall q;
+  q.cfg = cfg; q.grid = grid; q.trees = trees; q.n_trees = n_trees; q.x0 = x0; q.lane = target_lane; q.n_lane_pts = n_lane_pts; q.target_vel = target_vel;
+  q.use_exo = use_exo; q.us_init = us; q.po = &po;
   return il_solve(c, q);
 }
 

@@ -106,6 +106,8 @@ struct IlqrTreeDev {
   GP<double> k, K, Vx, Vxx;                                   // [IL_SPEC][M,*]  (one set per speculative mu)
   GP<double> xs_new, us_new, L_new;                            // [IL_SPEC][NA,M,*]
   GP<int> rel;                 // [M] number of exo agents near the nominal state (<= IL_REL), or -1 = overflow
+                            //   (k_ilqr_gains, which runs no derivative pass, keeps its per-node "no value function" flag here: il_layout
+                            //   allocates rel [M] for every call)
   GP<double> relag;            // [M, IL_RA] compact staged records {mean_x, mean_y, sigma+offset, threshold}: entry 0 =
                             //   ego, entries 1..rel[c] = the relevant exo agents in ascending agent order
   // generic mode (planners/ilqr surface: arbitrary materialised fields + per-node diagonal weights)

@@ -29,6 +29,7 @@
 #include "dec_mfma_kernels.hip"
 #include "ilqr_kernels.hip"
 #include "ilqr_score_kernels.hip"
+#include "ilqr_policy_kernels.hip"
 #include "pair_jobs.h"
 #include "pred_choice.h"
 #include "ilqr_choice.h"

@@ -170,6 +170,7 @@ class TrajectoryTreeOptimizer:
         self.cost_tree = None
         self.debug = None
         self._job = None
+        self._last_fit = None     # what policy() linearises about: the job, returned controls and final mu of the last solve / warm_start_solve
         # speculative warm start (see speculate_warm)
         self.speculative = os.environ.get("MIND_SPECULATIVE_WARM_START", "1") != "0"
         self._worker = None
@@ -208,7 +209,27 @@ class TrajectoryTreeOptimizer:
         xs, us, st = self._runtime().ilqr_solve(cfg, [j["flat"]], j["x0"], j["lane"], j["tv"], 0 if j["warm"] else 1,
                                                 None if us_init is None else [np.asarray(us_init, np.float64)])
         self.debug = st[0]
+        self._last_fit = dict(job=j, us=us[0], mu=st[0]["mu"])
         return xs[0], us[0]
+
+    def policy(self, mu=None):
+        """The feedback policy about the trajectory the last ``solve`` / ``warm_start_solve`` returned: one backward pass on the device
+        (mind_ilqr_gains) with ``mu`` (default: the fit's final mu), on that fit's cost.  Same dict as ``iLQR.policy``; raises
+        numpy.linalg.LinAlgError when a Q_uu is singular."""
+        last = self._last_fit
+        if last is None:
+            raise RuntimeError("TrajectoryTreeOptimizer.policy: no solve() / warm_start_solve() has run yet")
+        j = last["job"]
+        m = float(last["mu"] if mu is None else mu)
+        if not np.isfinite(m) or m < 0.0:
+            raise ValueError(f"TrajectoryTreeOptimizer.policy: mu must be finite and >= 0, got {m}")
+        cfg = ilqr_cfg_from(self.config, "w_opt_cfg" if j["warm"] else "opt_cfg")
+        g = self._runtime().ilqr_gains(cfg, [j["flat"]], j["x0"], j["lane"], j["tv"], 0 if j["warm"] else 1, last["us"], m)
+        if g["bad_node"][0] >= 0:
+            raise np.linalg.LinAlgError(f"Singular matrix: Q_uu of node {int(g['bad_node'][0])}")
+        res = {name: g[name][0] for name in ("k", "K", "dV", "V_x", "V_xx", "xs", "L")}
+        res["J"], res["mu"] = float(g["J"][0]), m
+        return res
 
     def warm_start_solve(self, us_init=None):
         return self._solve(us_init)

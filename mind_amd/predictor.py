@@ -444,24 +444,7 @@ class HipPredictor:
         iteration from candidate c reports.  want_xs / want_L False: that output is not read back (None in its place)."""
         n = len(flats)
         keep = []
-        trees = (_lib.CostTree * max(n, 1))()
-        Ms = []
-        for i, f in enumerate(flats):
-            if grid is not None:
-                trees[i] = self._generic_tree(f, keep)
-            else:
-                par = np.ascontiguousarray(f["parent"], np.int32)
-                prob = np.ascontiguousarray(f["prob"], np.float32)
-                mean = np.ascontiguousarray(f["mean"], np.float32)
-                cov = np.ascontiguousarray(f["cov"], np.float32)
-                keep += [par, prob, mean, cov]
-                t = trees[i]
-                t.n_nodes, t.n_agents = len(par), mean.shape[1]
-                t.parent = par.ctypes.data_as(C.POINTER(C.c_int32))
-                t.prob = prob.ctypes.data_as(C.POINTER(C.c_float))
-                t.agent_mean = mean.ctypes.data_as(C.POINTER(C.c_float))
-                t.agent_cov = cov.ctypes.data_as(C.POINTER(C.c_float))
-            Ms.append(int(trees[i].n_nodes))
+        trees, Ms = self._cost_trees(flats, grid, keep)
         Mt = int(sum(Ms))
         if isinstance(us_cand, (list, tuple)):
             us_cand = np.concatenate([np.asarray(u, np.float64) for u in us_cand], axis=1)
@@ -482,6 +465,104 @@ class HipPredictor:
         offs = np.cumsum([0] + Ms)
         split = lambda a: None if a is None else [a[:, offs[i]:offs[i + 1]].copy() for i in range(n)]
         return split(xs), split(L), J
+
+    def _cost_trees(self, flats, grid, keep):
+        """flats -> (CostTree array, node counts): planner-mode flat dicts (grid None) or generic tree dicts, as ``ilqr_score`` takes them"""
+        trees = (_lib.CostTree * max(len(flats), 1))()
+        Ms = []
+        for i, f in enumerate(flats):
+            if grid is not None:
+                trees[i] = self._generic_tree(f, keep)
+            else:
+                par = np.ascontiguousarray(f["parent"], np.int32)
+                prob = np.ascontiguousarray(f["prob"], np.float32)
+                mean = np.ascontiguousarray(f["mean"], np.float32)
+                cov = np.ascontiguousarray(f["cov"], np.float32)
+                keep += [par, prob, mean, cov]
+                t = trees[i]
+                t.n_nodes, t.n_agents = len(par), mean.shape[1]
+                t.parent = par.ctypes.data_as(C.POINTER(C.c_int32))
+                t.prob = prob.ctypes.data_as(C.POINTER(C.c_float))
+                t.agent_mean = mean.ctypes.data_as(C.POINTER(C.c_float))
+                t.agent_cov = cov.ctypes.data_as(C.POINTER(C.c_float))
+            Ms.append(int(trees[i].n_nodes))
+        return trees, Ms
+
+    @staticmethod
+    def _per_node(a, Mt, tail, name):
+        """one [sum M, *tail] array from one array or one array per tree"""
+        if isinstance(a, (list, tuple)):
+            a = np.concatenate([np.asarray(v, np.float64).reshape((-1,) + tail) for v in a], axis=0)
+        a = np.ascontiguousarray(a, np.float64)
+        if a.shape != (Mt,) + tail:
+            raise ValueError(f"{name} must be {[Mt] + list(tail)} for these cost trees, got {list(a.shape)}")
+        return a
+
+    def ilqr_gains(self, cfg, flats, x0, lane, target_vel, use_exo, us, mu, grid=None):
+        """The gains of one backward pass about the controls ``us`` ([sum M, 2], or one [M_t, 2] per tree) with the regularisation ``mu``
+        (a number or one per tree) on every cost tree of ``flats`` in one launch (mind_ilqr_gains, k_ilqr_gains); flats / grid as
+        ``ilqr_score``.  Returns a dict of per-tree lists k [M_t,2], K [M_t,2,6], dV [M_t], V_x [M_t,6], V_xx [M_t,6,6] (after the node's own
+        update; no alias row), xs [M_t,6], L [M_t], plus J [n_trees] and bad_node int32 [n_trees] (-1: fine; else the tree's gains are zeros)."""
+        n = len(flats)
+        keep = []
+        trees, Ms = self._cost_trees(flats, grid, keep)
+        Mt = int(sum(Ms))
+        u = self._per_node(us, Mt, (2,), "us")
+        mu_a = np.ascontiguousarray(np.broadcast_to(np.asarray(mu, np.float64), (n,)))
+        g = C.byref(self._grid(grid, keep)) if grid is not None else None
+        x0 = np.ascontiguousarray(x0, np.float64)
+        lane_a = None if lane is None or grid is not None else np.ascontiguousarray(lane, np.float64)
+        shapes = dict(k=(Mt, 2), K=(Mt, 2, 6), dV=(Mt,), V_x=(Mt, 6), V_xx=(Mt, 6, 6), xs=(Mt, 6), L=(Mt,), J=(n,))
+        res = {name: np.zeros(s) for name, s in shapes.items()}
+        bad = np.full(n, -1, np.int32)
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double)) if a is not None else None
+        out = _lib.IlqrGainsOut()
+        for name, a in res.items():
+            setattr(out, name, dp(a))
+        out.bad_node = bad.ctypes.data_as(C.POINTER(C.c_int32))
+        rc = self.lib.mind_ilqr_gains(self.ctx, C.byref(cfg), g, trees, n, dp(x0), dp(lane_a), 0 if lane_a is None else len(lane_a),
+                                      C.c_double(float(target_vel)), int(use_exo), dp(u), dp(mu_a), C.byref(out))
+        _lib.check(self.lib, self.ctx, rc, "mind_ilqr_gains")
+        offs = np.cumsum([0] + Ms)
+        ret = {name: [a[offs[i]:offs[i + 1]].copy() for i in range(n)] for name, a in res.items() if name != "J"}
+        ret["J"], ret["bad_node"] = res["J"], bad
+        return ret
+
+    def ilqr_policy_rollouts(self, cfg, flats, x0, lane, target_vel, use_exo, us, k, K, alpha, dx0=None, grid=None, want_xs=True,
+                             want_us=True, want_L=True):
+        """Closed-loop rollouts under the gains (k, K) about ``us`` on every cost tree of ``flats`` in one launch (mind_ilqr_policy_rollouts,
+        k_ilqr_policy): candidate c applies u = us + alpha[c] k + K (x - xs_nominal) from the start state x0 + dx0[c].  us / k / K: [sum M, ..]
+        or one array per tree; alpha [C]; dx0 [C, 6] or None (zeros).  Returns (xs list[[C, M_t, 6]], us list[[C, M_t, 2]], L list[[C, M_t]],
+        J [C, n_trees]); J is the line search's sequential sum of L.  want_* False: that output is not read back (None in its place)."""
+        n = len(flats)
+        keep = []
+        trees, Ms = self._cost_trees(flats, grid, keep)
+        Mt = int(sum(Ms))
+        u = self._per_node(us, Mt, (2,), "us")
+        k_a = self._per_node(k, Mt, (2,), "k")
+        K_a = self._per_node(K, Mt, (2, 6), "K")
+        al = np.ascontiguousarray(alpha, np.float64)
+        if al.ndim != 1:
+            raise ValueError(f"alpha must be [C], got {list(al.shape)}")
+        nc = len(al)
+        d0 = None if dx0 is None else np.ascontiguousarray(dx0, np.float64)
+        if d0 is not None and d0.shape != (nc, 6):
+            raise ValueError(f"dx0 must be [{nc}, 6], got {list(d0.shape)}")
+        g = C.byref(self._grid(grid, keep)) if grid is not None else None
+        x0 = np.ascontiguousarray(x0, np.float64)
+        lane_a = None if lane is None or grid is not None else np.ascontiguousarray(lane, np.float64)
+        xs = np.zeros((nc, Mt, 6)) if want_xs else None
+        uo = np.zeros((nc, Mt, 2)) if want_us else None
+        L = np.zeros((nc, Mt)) if want_L else None
+        J = np.zeros((nc, n))
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double)) if a is not None else None
+        rc = self.lib.mind_ilqr_policy_rollouts(self.ctx, C.byref(cfg), g, trees, n, dp(x0), dp(lane_a), 0 if lane_a is None else len(lane_a),
+                                                C.c_double(float(target_vel)), int(use_exo), dp(u), dp(k_a), dp(K_a), nc, dp(al), dp(d0),
+                                                dp(xs), dp(uo), dp(L), dp(J))
+        _lib.check(self.lib, self.ctx, rc, "mind_ilqr_policy_rollouts")
+        offs = np.cumsum([0] + Ms)
+        split = lambda a: None if a is None else [a[:, offs[i]:offs[i + 1]].copy() for i in range(n)]
+        return split(xs), split(uo), split(L), J
 
     def aime_world(self, reg, vel, actor_ctrs, actor_vecs, a_off, rots, origs, cov_last, last, target_lane=None, cls=None,
                    scen_prob=None, dist_thres=None):

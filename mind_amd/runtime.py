@@ -41,6 +41,18 @@ def new_runtime(device=None):
     return rt
 
 
+def ilqr_gains(cfg, flats, x0, lane, target_vel, use_exo, us, mu, grid=None):
+    """``HipPredictor.ilqr_gains`` on this thread's runtime: the gains of one backward pass about ``us`` on every cost tree."""
+    return get_runtime().ilqr_gains(cfg, flats, x0, lane, target_vel, use_exo, us, mu, grid=grid)
+
+
+def ilqr_policy_rollouts(cfg, flats, x0, lane, target_vel, use_exo, us, k, K, alpha, dx0=None, grid=None, want_xs=True, want_us=True,
+                         want_L=True):
+    """``HipPredictor.ilqr_policy_rollouts`` on this thread's runtime: closed-loop rollouts under the gains (k, K) about ``us``."""
+    return get_runtime().ilqr_policy_rollouts(cfg, flats, x0, lane, target_vel, use_exo, us, k, K, alpha, dx0=dx0, grid=grid, want_xs=want_xs,
+                                              want_us=want_us, want_L=want_L)
+
+
 def reset_runtime():
     rt = getattr(_local, "rt", None)
     if rt is not None:
