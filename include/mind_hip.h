@@ -266,6 +266,26 @@ int mind_debug_token_lw_plan(int n_tokens, int mode, int chunk, long long *out_l
  * (ci_pad = ci rounded up to a power of two >= 16).  Returns the number of dwords written (<= cap) or a negative error. */
 int mind_debug_pack_conv_frag(const float *w, int co, int ci, int ksz, uint32_t *out, size_t cap);
 
+/* host-only helpers (tests) over mind_amd/csrc/weight_pack.h, the packer and the binder mind_weights_load itself runs.  None needs a GPU or a
+ * context.
+ *
+ * mind_debug_pack: one packer by name -- "afrag" (a = row stride), "wk_frag", "tok_bfrag" (a = row stride), "bfrag_lo3" (a = row stride),
+ * "conv_f32" (a, b, c = co, ci, ksz of a torch-layout Conv1d weight), "center_outputs" (W [a][b] followed by the bias [a], in and out).  The
+ * fragment packers read a [128][128] block of w with the given row stride.  Returns the number of floats (or dwords as float bit patterns)
+ * written (<= cap) or MIND_EINVAL.
+ *
+ * mind_debug_weight_image: the packed blob of a state_dict.  out_info[3] = {entries, floats of the blob, bytes of the name list with its
+ * terminator}; blob, names (the entry keys in blob order, each followed by '\n') and entries ({offset, length} in floats per entry) are each
+ * filled when non-null and large enough (blob_cap in floats, names_cap in bytes, entries_cap in entries).  MIND_ENOTFOUND with the
+ * tensor's name in msg when a tensor is missing or has the wrong size.
+ *
+ * mind_debug_weight_bind: packs the state_dict, forgets the blob entry `drop` (may be null; MIND_EINVAL when there is no such entry) and binds
+ * the pointer tables against the host image.  MIND_OK, or MIND_ENOTFOUND with msg = the missing tensor (packing) or blob key (binding). */
+int mind_debug_pack(const char *what, const float *w, int a, int b, int c, float *out, size_t cap);
+int mind_debug_weight_image(const mind_tensor_desc *tensors, int n_tensors, float *blob, size_t blob_cap, char *names, size_t names_cap,
+                            long long *entries, int entries_cap, long long *out_info, char *msg, int msg_cap);
+int mind_debug_weight_bind(const mind_tensor_desc *tensors, int n_tensors, const char *drop, char *msg, int msg_cap);
+
 /* Debug tap (tests): the tree-iLQR kernel's sin / cos / tan (mind_amd/csrc/mind_trig.h, the routine oracle/ilqr_ref.c shares) of n host
  * doubles, evaluated on the device one wave of 64 arguments at a time -- out[4 n] = sin, cos, tan, the cosine that comes with the
  * tangent.  The oracle's oracle_sincos / oracle_tan_cos must give the same bits (tests/test_gpu_ilqr.py). */

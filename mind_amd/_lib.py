@@ -165,7 +165,7 @@ class PlannerOut(C.Structure):     # mind_planner_out
 EXPORTS = ["mind_ctx_create", "mind_ctx_destroy", "mind_last_error_string", "mind_ctx_synchronize",
            "mind_weights_load", "mind_predict_batch", "mind_last_fusion_stats", "mind_last_actor_stats", "mind_debug_actor_lw_plan", "mind_last_token_stats", "mind_last_token_stage_ms", "mind_debug_token_lw_plan", "mind_set_profiling",
            "mind_ilqr_solve_trees", "mind_ilqr_contingency", "mind_ilqr_solve_fields", "mind_cost_eval", "mind_ilqr_score_trees", "mind_ilqr_gains", "mind_ilqr_policy_rollouts", "mind_lane_dist_field", "mind_aime_world", "mind_aime_rebase", "mind_debug_set_layers",
-           "mind_debug_read", "mind_set_pair_precision", "mind_get_pair_precision", "mind_debug_pack_bfrag", "mind_debug_pack_conv_frag", "mind_debug_pair_schedule", "mind_debug_predict_choice", "mind_debug_ilqr_plan", "mind_debug_aime_book", "mind_set_tuning", "mind_last_ilqr_stats", "mind_aime_plan", "mind_last_ilqr_profile", "mind_eval_traj_trees", "mind_last_ilqr_trace", "mind_ilqr_contingency_begin", "mind_ilqr_finish", "mind_fill_tracks", "mind_ilqr_contingency_begin_plan", "mind_debug_trig", "mind_aime_plan_begin", "mind_aime_plan_poll", "mind_aime_plan_finish", "mind_ctx_busy", "mind_ilqr_finish_plan",
+           "mind_debug_read", "mind_set_pair_precision", "mind_get_pair_precision", "mind_debug_pack_bfrag", "mind_debug_pack_conv_frag", "mind_debug_pack", "mind_debug_weight_image", "mind_debug_weight_bind", "mind_debug_pair_schedule", "mind_debug_predict_choice", "mind_debug_ilqr_plan", "mind_debug_aime_book", "mind_set_tuning", "mind_last_ilqr_stats", "mind_aime_plan", "mind_last_ilqr_profile", "mind_eval_traj_trees", "mind_last_ilqr_trace", "mind_ilqr_contingency_begin", "mind_ilqr_finish", "mind_fill_tracks", "mind_ilqr_contingency_begin_plan", "mind_debug_trig", "mind_aime_plan_begin", "mind_aime_plan_poll", "mind_aime_plan_finish", "mind_ctx_busy", "mind_ilqr_finish_plan",
            "mind_set_exchange", "mind_last_exchange_stats",
            "mind_loop_create", "mind_loop_destroy", "mind_loop_reset", "mind_loop_advance", "mind_loop_state", "mind_loop_last_plan", "mind_loop_export",
            "mind_planner_create", "mind_planner_destroy", "mind_planner_reset", "mind_planner_observe", "mind_planner_set_lanes", "mind_planner_set_target_lane",
@@ -259,6 +259,10 @@ def load():
     lib.mind_debug_aime_book.argtypes = [C.c_int] * 8 + [C.POINTER(C.c_int), C.POINTER(C.c_float)] + [C.c_int] * 4 + [C.POINTER(C.c_longlong), C.c_int, C.c_char_p, C.c_int]
     lib.mind_debug_trig.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double)]
     lib.mind_debug_pack_conv_frag.argtypes = [C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_size_t]
+    lib.mind_debug_pack.argtypes = [C.c_char_p, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_size_t]
+    lib.mind_debug_weight_image.argtypes = [C.POINTER(TensorDesc), C.c_int, C.POINTER(C.c_float), C.c_size_t, C.c_char_p, C.c_size_t,
+                                            C.POINTER(C.c_longlong), C.c_int, C.POINTER(C.c_longlong), C.c_char_p, C.c_int]
+    lib.mind_debug_weight_bind.argtypes = [C.POINTER(TensorDesc), C.c_int, C.c_char_p, C.c_char_p, C.c_int]
     lib.mind_debug_set_layers.argtypes = [C.c_void_p, C.c_int]
     lib.mind_debug_read.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_float), C.c_int64]
     lib.mind_set_exchange.argtypes = [C.c_void_p, C.c_int, C.c_int, EXCHANGE_FN, C.c_void_p, C.c_int]
@@ -392,6 +396,62 @@ def aime_book(pred_len, max_depth, n_agents, rounds, world=1, rank=0, force=Fals
         d["tree_top"], d["tree_off"], d["flat_parent"], d["flat_prob"] = take(out[6]), take(out[6] + 1), take(out[7]), take(out[7])
     assert o[0] == n
     return d
+
+
+def tensor_descs(sd):
+    """(TensorDesc array, the float32 arrays it points into -- keep them alive while it is used) of a state_dict of arrays or torch tensors"""
+    import numpy as np
+    descs = (TensorDesc * max(1, len(sd)))()
+    keep = []
+    for i, (k, v) in enumerate(sd.items()):
+        a = np.ascontiguousarray(v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v), dtype=np.float32)
+        keep.append(a)
+        descs[i].name = k.encode()
+        descs[i].data = a.ctypes.data_as(C.POINTER(C.c_float))
+        descs[i].numel = a.size
+    return descs, keep
+
+
+def weight_image(sd):
+    """wp_pack's blob of a state_dict (mind_debug_weight_image; no GPU) -> (float32 blob, [(entry key, offset, length in floats), ...] in blob
+    order); raises KeyError naming the tensor that is missing or has the wrong size"""
+    import numpy as np
+    lib = load()
+    descs, keep = tensor_descs(sd)
+    msg = C.create_string_buffer(256)
+    info = (C.c_longlong * 3)()
+    rc = lib.mind_debug_weight_image(descs, len(sd), None, 0, None, 0, None, 0, info, msg, 256)        # the sizes
+    if rc == MIND_ENOTFOUND:
+        raise KeyError(msg.value.decode())
+    assert rc == MIND_OK, rc
+    ne, nf, nb = info
+    blob, names, ents = np.zeros(nf, np.float32), C.create_string_buffer(nb), (C.c_longlong * (2 * ne))()
+    assert lib.mind_debug_weight_image(descs, len(sd), blob.ctypes.data_as(C.POINTER(C.c_float)), nf, names, nb, ents, ne, info, msg, 256) == MIND_OK
+    keys = names.value.decode().split("\n")[:-1]
+    assert len(keys) == ne
+    return blob, [(k, ents[2 * i], ents[2 * i + 1]) for i, k in enumerate(keys)]
+
+
+def weight_bind(sd, drop=None):
+    """wp_pack + wp_bind against the host image (mind_debug_weight_bind; no GPU) with the blob entry `drop` forgotten in between -> None when
+    every required entry is bound, else the name of the first missing one (a state_dict tensor when packing fails, a blob key when binding does)"""
+    lib = load()
+    descs, keep = tensor_descs(sd)
+    msg = C.create_string_buffer(256)
+    rc = lib.mind_debug_weight_bind(descs, len(sd), drop.encode() if drop else None, msg, 256)
+    assert rc in (MIND_OK, MIND_ENOTFOUND), rc
+    return None if rc == MIND_OK else msg.value.decode()
+
+
+def pack(what, w, a=0, b=0, c=0, cap=1 << 20):
+    """one packer of weight_pack.h by name (mind_debug_pack; no GPU): float32 array in -> float32 array out (bf16 fragments: view as uint32)"""
+    import numpy as np
+    lib = load()
+    w = np.ascontiguousarray(w, np.float32)
+    out = np.zeros(cap, np.float32)
+    n = lib.mind_debug_pack(what.encode(), w.ctypes.data_as(C.POINTER(C.c_float)), a, b, c, out.ctypes.data_as(C.POINTER(C.c_float)), cap)
+    assert n > 0, (what, n)
+    return out[:n].copy()
 
 
 class MindError(RuntimeError):

@@ -36,12 +36,7 @@
 #define AF_ACT (AF_FA + 48 * AF_RS(128))    // floats per actor: 19 392 (77.6 KB)
 #define AF_LDS_FLOATS(NACT) ((NACT) * AF_ACT + 128)
 
-struct AfRes { const float *c1, *c2, *ds; const float *g1, *b1, *g2, *b2, *gd, *bd; };
-struct AfLat { const float *w; const float *g, *b; };
-struct AfW {                                // packed conv fragments + GroupNorm affine, same order as ActorW / AmW
-  AfRes res[9];
-  AfLat lat[4];
-};
+#include "weight_tables.h"   // AfW
 
 // sums of NACT values over the workgroup (one per actor); `flip` alternates the scratch so that two reductions need no barrier in between
 template <int NACT>

@@ -4,7 +4,7 @@
 //
 // Every Conv1d is the same GEMM  out[co][col] = sum_k Wm[co][k] X[k][col]  with the columns running over (actor, t) of a chunk:
 //   * k_lw_conv<NP, LGC, KSZ, STRIDE, MT>: WEIGHT-STATIONARY.  Workgroup (x, y) copies the fragments of the MT m-tiles MT y .. MT y + MT - 1
-//     (mind_ctx::actorBW, the pack_conv_frag layout, untouched: [m-tile][k-step][hi / mid / lo][lane][4]) into LDS once and its 16 waves
+//     (WeightTables::actorB, the pack_conv_frag layout, untouched: [m-tile][k-step][hi / mid / lo][lane][4]) into LDS once and its 16 waves
 //     sweep 16-column tiles past them.  MT = 4 where the layer has >= 128 output channels and 4 .. 12 k-steps (four m-tiles fit: 4 x 12 x
 //     3 KB = 144 KB; below four k-steps the k loop is fully unrolled and the fragments of four m-tiles, hoisted out of the tile loop, would
 //     spill), MT = 2 otherwise (the 256-input-channel layers: 2 x 24 x 3 KB = 144 KB): a column block is fetched Cout / (16 MT)

@@ -39,12 +39,7 @@ __device__ int am_trn_;
 #define AM_RED (AM_FA + 48 * AM_RSD(128))
 #define AM_LDS_DWORDS (AM_RED + 64)
 
-struct AmRes { const u32 *c1, *c2, *ds; const float *g1, *b1, *g2, *b2, *gd, *bd; };
-struct AmLat { const u32 *w; const float *g, *b; };
-struct AmW {                                // packed conv fragments + GroupNorm affine, same order as ActorW
-  AmRes res[9];
-  AmLat lat[4];
-};
+#include "weight_tables.h"   // AmW
 typedef u32 u32x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ float am_block_sum(float v, float *red, int flip) {

@@ -20,11 +20,7 @@
 #define DM_R2 (DM_ROWS * AM_RSD(128))             // fp32 rows: h1 raw [16][388], h2 [16][772], t1 raw [96][132], prm [96][40]
 #define DM_LDS_DWORDS (DM_R2 + DM_ROWS * 132)
 
-struct DmW {
-  const u32 *a0, *a3, *r0, *r3, *r6;              // packed fragments
-  const float *a0b, *a0g, *a0be, *a3b, *a3g, *a3be, *r0b, *r0g, *r0be, *r3b, *r3g, *r3be, *r6b;
-  const float *T, *Tp;                            // Bezier bases [60][8], [60][7]
-};
+#include "weight_tables.h"   // DmW
 
 // out[row][f] = bias[f] + sum_k W[f][k] in[row][k] for `rows` rows, f < n_out (m-tiles past n_out are zero rows of the packing)
 template <int NP, int CP>

@@ -12,6 +12,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "weight_tables.h"   // LaneW, ActorW, DecW
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #define NT 256
@@ -397,16 +399,6 @@ __device__ __forceinline__ void ln_rows(float *buf, int ld, int R, int n, const 
 // =================================================================================================
 // LaneNet: PL polylines (10 points each) per workgroup.
 // =================================================================================================
-struct LaneW {
-  const float *pW, *pb, *pg, *pbe;  // proj 16->128 (+LN)
-  // aggre blocks 0/1: fc1.0, fc1.3, fc2.0 (256->128), fc2.3, norm
-  const float *f10W[2], *f10b[2], *f10g[2], *f10be[2];
-  const float *f13W[2], *f13b[2], *f13g[2], *f13be[2];
-  const float *f20W[2], *f20b[2], *f20g[2], *f20be[2];
-  const float *f23W[2], *f23b[2], *f23g[2], *f23be[2];
-  const float *ng[2], *nbe[2];
-};
-
 #define PL 2
 #define LR (PL * 10)
 
@@ -477,12 +469,6 @@ __global__ __launch_bounds__(DT) void k_lane_net(const float *__restrict__ feats
 // ActorNet: one agent per workgroup; the whole 4-scale pyramid lives in LDS.
 // Conv weights are stored [ci][dk][co] (transposed) so that thread <-> co reads are coalesced.
 // =================================================================================================
-struct ResW { const float *c1, *g1, *b1, *c2, *g2, *b2, *ds, *gd, *bd; };
-struct ActorW {
-  ResW res[9];                 // groups.{0..3}.{0,1}, output
-  const float *latW[4], *latG[4], *latB[4];
-};
-
 #ifndef AT
 #define AT 1024   // threads of k_actor_net
 #endif
@@ -731,18 +717,6 @@ extern "C" size_t mind_actor_lds_bytes() { return (size_t)ACT_LDS_FLOATS * sizeo
 // SceneDecoder, scene part: target embedding (k_dec_tgt), 6 mode tokens through ctx_proj + 2 encoder layers,
 // mode probabilities (k_dec_scene).  One workgroup per scene.
 // =================================================================================================
-struct DecW {
-  const float *rpeW, *rpeb, *rpeg, *rpebe;                       // proj_rpe 20(->pad 20)->128
-  const float *t0W, *t0b, *t0g, *t0be, *t3W, *t3b, *t3g, *t3be;  // proj_tgt
-  const float *c0W, *c0b, *c0g, *c0be, *c3W, *c3b, *c3g, *c3be;  // ctx_proj 128->384->768
-  const float *a0W, *a0b, *a0g, *a0be, *a3W, *a3b, *a3g, *a3be;  // actor_proj
-  const float *inW[2], *inb[2], *outW[2], *outb[2], *l1W[2], *l1b[2], *l2W[2], *l2b[2];
-  const float *n1g[2], *n1b[2], *n2g[2], *n2b[2];
-  const float *k0W, *k0b, *k0g, *k0be, *k3W, *k3b, *k3g, *k3be, *k6W, *k6b;  // cls head
-  const float *r0W, *r0b, *r0g, *r0be, *r3W, *r3b, *r3g, *r3be, *r6W, *r6b;  // reg head
-  const float *T, *Tp;                                                           // [60][8], [60][7]
-};
-
 #define DEC_SCENE_PART 24576
 #define DEC_SCENE_LDS_FLOATS (256 + 768 + 768 + 2304 + 768 + 9216 + 768 + 144 + DEC_SCENE_PART)
 // target embedding (network.py:491-495): needs only the target polyline's LaneNet feature and its RPE, so it runs on the side stream

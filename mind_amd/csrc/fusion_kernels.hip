@@ -22,7 +22,8 @@
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-typedef unsigned int u32;
+#include "weight_tables.h"   // u32, VT_*, TokWeights
+
 typedef u32 u32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
@@ -49,17 +50,6 @@ struct PairJob {
   int scene;
   long long edge_base_t;  // the same for the tile-native layout of k_pair_t (pair_tile_kernels.hip): columns padded to whole 16-row tiles
 };
-
-// per-layer small vectors, staged in LDS (floats): 7 x 128
-//  0: gamma_m 1: beta_m 2: b_p 3: gamma_p 4: beta_p 5: gamma_e 6: beta_e
-#define VT_GM 0
-#define VT_BM 128
-#define VT_BP 256
-#define VT_GP 384
-#define VT_BEP 512
-#define VT_GE 640
-#define VT_BE 768
-#define VT_SIZE 896
 
 // Eight waves (two per SIMD) share the two weight matrices: while one wave of a SIMD is in its LayerNorm / softmax /
 // staging phases the other one keeps the MFMA busy.  Everything per-wave is sized so that the workgroup fits
@@ -545,15 +535,6 @@ struct TokMeta {
   int nsplit;    // number of partial slots
   int flags;     // bit0: actor or cls (needed by the last layer)
   int pad0, pad1, pad2;
-};
-
-struct TokWeights {
-  // epilogue of layer L (may be null when init)
-  const float *WvT, *bv, *WoT, *bo, *g2, *b2, *W1T, *b1, *W2T, *bb2, *g3, *b3;
-  // prologue of layer L+1 (may be null for the last layer)
-  const float *WsT, *WtT, *bm, *WqT, *bq, *Wk;
-  // init projections
-  const float *WpaT, *bpa, *gpa, *bepa, *WplT, *bpl, *gpl, *bepl;
 };
 
 // ---- k_token building blocks.  512 threads = 4 k-groups x 128 output features: a projection's reduction

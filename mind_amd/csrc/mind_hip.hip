@@ -34,6 +34,7 @@
 #include "pred_choice.h"
 #include "ilqr_choice.h"
 #include "aime_book.h"
+#include "weight_pack.h"
 #include "aime_kernels.hip"
 
 namespace {
@@ -41,18 +42,6 @@ namespace {
 struct DevBuf {
   void *p = nullptr;
   size_t cap = 0;
-};
-
-struct WeightBlob {
-  std::vector<float> host;
-  std::map<std::string, size_t> off;
-  size_t add(const std::string &key, const std::vector<float> &v) {
-    while (host.size() % 64) host.push_back(0.f);  // 256-byte alignment
-    size_t o = host.size();
-    host.insert(host.end(), v.begin(), v.end());
-    off[key] = o;
-    return o;
-  }
 };
 
 }  // namespace
@@ -79,20 +68,11 @@ struct mind_ctx {
   std::vector<char> aime_stage;   // host staging of mind_aime_world's small tables (guarded by ev_stage)
   bool aime_stage_busy = false;
   std::string err;
-  // weights
+  // weights: the packed device blob and the kernels' pointer tables into it (weight_pack.h, weight_tables.h); valid while have_weights
   float *wdev = nullptr;
   bool have_weights = false;
-  WeightBlob blob;
-  LaneW laneW;
-  ActorW actorW;
-  DmW decBW;     // actor part of the decoder, same packing (dec_mfma_kernels.hip)
-  AmW actorBW;   // the same convolutions as bf16 hi / lo MFMA fragments (actor_mfma_kernels.hip)
-  AfW actorFW;   // ... and as fp32 MFMA A fragments (actor_f32_kernels.hip)
-  DecW decW;
-  TokWeights tokW[7];  // [L]: epilogue of layer L-1 (L>=1) + prologue of layer L (L<=5); [0] = init
-  TokWeightsM tokWM[7]; // the same matrices as fp32 MFMA A fragments (k_token_mfma<0>)
-  TokWeightsM tokWB[7]; // ... and as bf16 hi / lo A fragments (k_token_mfma<1>: scenes of >= tok_bf_min_n tokens)
-  PredTuning pt;       // the predictor's kernel-selection knobs (pred_choice.h)
+  WeightTables W = {};
+  PredTuning pt;      // the predictor's kernel-selection knobs (pred_choice.h)
   // layer-wise token stage (token_lw_kernels.hip): its scratch arena holds one chunk and is allocated at first use
   DevBuf tok_lw_arena;
   std::vector<TlLaunch> tok_lw_plan;
@@ -102,9 +82,6 @@ struct mind_ctx {
   float tok_ms = 0.f, tok_stage_ms[TL_NSTAGE + 1] = {};
   std::vector<hipEvent_t> ev_tok;
   std::vector<int> ev_tok_tag;
-  const float *WAe[6], *WAp[6], *vtab[6], *rtab = nullptr;
-  const u32 *WBe[6], *WBp[6];   // bf16 hi / lo fragments of the same matrices (pair_bf16_kernels.hip)
-  const u32 *WLe[6], *WLp[6];   // the third part of the exact three-way split (hi + mid + lo; mid = the two-way split's lo): k_pair_t6
   // job / token tables of recent mind_predict_batch calls (least-recently-used of MIND_TABLE_SETS): a call whose scene sizes
   // were seen before rebuilds, uploads and synchronises nothing -- the closed loop's rounds recur every cycle, a full tree's
   // rounds (1 / 6 / 36 / 216 scenes) every plan
@@ -484,7 +461,6 @@ extern "C" int mind_set_pair_precision(mind_ctx *c, int mode) {
 
 extern "C" int mind_get_pair_precision(mind_ctx *c) { return c ? c->pair_prec : MIND_EINVAL; }
 
-namespace { std::vector<float> pack_bfrag(const std::vector<float> &w, int row_stride); }
 extern "C" int mind_debug_pack_bfrag(const float *w, int row_stride, uint32_t *out) {
   if (!w || !out || row_stride < 128) return MIND_EINVAL;
   std::vector<float> v(w, w + (size_t)127 * row_stride + 128);
@@ -623,233 +599,6 @@ extern "C" int mind_debug_actor_lw_plan(int n_actors, int np, int chunk, long lo
 // -------------------------------------------------------------------------------------------------
 // weight packing
 // -------------------------------------------------------------------------------------------------
-namespace {
-
-struct SD {
-  std::map<std::string, std::pair<const float *, int64_t>> m;
-  std::string missing;
-  const float *get(const std::string &k, int64_t numel) {
-    auto it = m.find(k);
-    if (it == m.end() || it->second.second != numel) {
-      if (missing.empty()) missing = k;
-      return nullptr;
-    }
-    return it->second.first;
-  }
-};
-
-std::vector<float> vec(const float *p, size_t n) { return p ? std::vector<float>(p, p + n) : std::vector<float>(n, 0.f); }
-
-// [out][in] -> [in][out]
-std::vector<float> transpose(const float *w, int n_out, int n_in, int row_stride = -1, int col0 = 0) {
-  if (row_stride < 0) row_stride = n_in;
-  std::vector<float> t((size_t)n_out * n_in, 0.f);
-  if (!w) return t;
-  for (int o = 0; o < n_out; ++o)
-    for (int k = 0; k < n_in; ++k) t[(size_t)k * n_out + o] = w[(size_t)o * row_stride + col0 + k];
-  return t;
-}
-
-// MFMA 16x16x4 A-fragment order: [ob 8][s4 8][lane 64][w 4] = W[16 ob + (lane&15)][16 s4 + 4 (lane>>4) + w]
-std::vector<float> pack_afrag(const float *w, int row_stride) {
-  std::vector<float> t(16384, 0.f);
-  if (!w) return t;
-  for (int ob = 0; ob < 8; ++ob)
-    for (int s4 = 0; s4 < 8; ++s4)
-      for (int lane = 0; lane < 64; ++lane)
-        for (int k = 0; k < 4; ++k)
-          t[((size_t)(ob * 8 + s4) * 64 + lane) * 4 + k] =
-              w[(size_t)(16 * ob + (lane & 15)) * row_stride + 16 * s4 + 4 * (lane >> 4) + k];
-  return t;
-}
-
-// folded-K-query fragments of k_token_mfma: per head hd and output block ob the A operand [16 features] x [16 d]:
-// [hd 8][ob 8][lane 64][w 4] = Wk[hd * 16 + 4 (lane >> 4) + w][16 ob + (lane & 15)]   (Wk = rows 128..255 of in_proj_weight)
-std::vector<float> pack_wk_frag(const float *wk) {
-  std::vector<float> t(16384, 0.f);
-  if (!wk) return t;
-  for (int hd = 0; hd < 8; ++hd)
-    for (int ob = 0; ob < 8; ++ob)
-      for (int lane = 0; lane < 64; ++lane)
-        for (int k = 0; k < 4; ++k)
-          t[((size_t)(hd * 8 + ob) * 64 + lane) * 4 + k] = wk[(size_t)(hd * 16 + 4 * (lane >> 4) + k) * 128 + 16 * ob + (lane & 15)];
-  return t;
-}
-
-// round-to-nearest-even bf16 of a float (bits), and the split x = hi + lo
-inline uint16_t bf16_rne(float x) {
-  uint32_t u;
-  memcpy(&u, &x, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);   // NaN
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-inline float bf16_to_f32(uint16_t h) {
-  const uint32_t u = (uint32_t)h << 16;
-  float f;
-  memcpy(&f, &u, 4);
-  return f;
-}
-
-// bf16 MFMA 16x16x32 A-fragment order, hi and lo parts: [part 2][ob 8][g 4][lane 64][dword 4]; dword d of lane
-// (r = lane & 15, q = lane >> 4) packs k-slots 2d, 2d+1; k-slot (q, i) <-> input feature 16 (2g + (i >> 2)) + 4q + (i & 3)
-// (the chained B-operand order of pair_bf16_kernels.hip).  Returned as float bit patterns (16384 dwords).
-// the third part of the exact three-way split x = hi + mid + lo (mid = pack_bfrag's lo part), same fragment order: [ob 8][g 4][lane 64][dword 4]
-std::vector<float> pack_bfrag_lo3(const std::vector<float> &w, int row_stride) {
-  std::vector<uint32_t> t(8192, 0u);
-  for (int ob = 0; ob < 8; ++ob)
-    for (int g = 0; g < 4; ++g)
-      for (int lane = 0; lane < 64; ++lane)
-        for (int d = 0; d < 4; ++d) {
-          uint32_t lo = 0;
-          for (int e = 0; e < 2; ++e) {
-            const int i = 2 * d + e, q = lane >> 4;
-            const int f = 16 * (2 * g + (i >> 2)) + 4 * q + (i & 3);
-            const float x = w[(size_t)(16 * ob + (lane & 15)) * row_stride + f];
-            const float r1 = x - bf16_to_f32(bf16_rne(x));
-            const float r2 = r1 - bf16_to_f32(bf16_rne(r1));
-            lo |= (uint32_t)bf16_rne(r2) << (16 * e);
-          }
-          t[((size_t)(ob * 4 + g) * 64 + lane) * 4 + d] = lo;
-        }
-  std::vector<float> out(8192);
-  memcpy(out.data(), t.data(), 8192 * sizeof(float));
-  return out;
-}
-
-std::vector<float> pack_bfrag(const std::vector<float> &w, int row_stride) {
-  std::vector<uint32_t> t(16384, 0u);
-  for (int ob = 0; ob < 8; ++ob)
-    for (int g = 0; g < 4; ++g)
-      for (int lane = 0; lane < 64; ++lane)
-        for (int d = 0; d < 4; ++d) {
-          uint32_t hi = 0, lo = 0;
-          for (int e = 0; e < 2; ++e) {
-            const int i = 2 * d + e, q = lane >> 4;
-            const int f = 16 * (2 * g + (i >> 2)) + 4 * q + (i & 3);
-            const float x = w[(size_t)(16 * ob + (lane & 15)) * row_stride + f];
-            const uint16_t h = bf16_rne(x);
-            const uint16_t l = bf16_rne(x - bf16_to_f32(h));
-            hi |= (uint32_t)h << (16 * e);
-            lo |= (uint32_t)l << (16 * e);
-          }
-          const size_t o = ((size_t)(ob * 4 + g) * 64 + lane) * 4 + d;
-          t[o] = hi;
-          t[8192 + o] = lo;
-        }
-  std::vector<float> out(16384);
-  memcpy(out.data(), t.data(), 16384 * sizeof(float));
-  return out;
-}
-
-// k_token_mfma<1> (bf16 hi + lo split operands): A fragments of a [128 out] x [128 in] block of w (row stride row_stride) for the bf16 MFMA
-// 16x16x32 in NATURAL k order -- the B operand is read from an fp32 LDS tile, 8 consecutive features per lane --:
-// [ob 8][s 8 = part * 4 + g][lane 64][dword 4]; dword d of lane (r = lane & 15, q = lane >> 4) packs W[16 ob + r][32 g + 8 q + 2 d (+ 1)].
-// Same addressing as pack_afrag's (tm_load reads both), returned as float bit patterns (16384 dwords).
-std::vector<float> pack_tok_bfrag(const float *w, int row_stride) {
-  std::vector<uint32_t> t(16384, 0u);
-  if (w)
-    for (int ob = 0; ob < 8; ++ob)
-      for (int g = 0; g < 4; ++g)
-        for (int lane = 0; lane < 64; ++lane)
-          for (int d = 0; d < 4; ++d) {
-            uint32_t hi = 0, lo = 0;
-            for (int e = 0; e < 2; ++e) {
-              const float x = w[(size_t)(16 * ob + (lane & 15)) * row_stride + 32 * g + 8 * (lane >> 4) + 2 * d + e];
-              const uint16_t h = bf16_rne(x);
-              const uint16_t l = bf16_rne(x - bf16_to_f32(h));
-              hi |= (uint32_t)h << (16 * e);
-              lo |= (uint32_t)l << (16 * e);
-            }
-            t[((size_t)(ob * 8 + g) * 64 + lane) * 4 + d] = hi;
-            t[((size_t)(ob * 8 + 4 + g) * 64 + lane) * 4 + d] = lo;
-          }
-  std::vector<float> f(16384);
-  memcpy(f.data(), t.data(), 16384 * sizeof(float));
-  return f;
-}
-
-// LayerNorm is invariant to a shift along the features: fold the mean subtraction of the LayerNorm that follows a Linear
-// into the Linear ((I - 11^T/n) W, (I - 11^T/n) b).  W is [n_out][n_in] row-major.
-void center_outputs(std::vector<float> &W, std::vector<float> &b, int n_out, int n_in) {
-  for (int k = 0; k < n_in; ++k) {
-    double m = 0;
-    for (int o = 0; o < n_out; ++o) m += W[(size_t)o * n_in + k];
-    m /= n_out;
-    for (int o = 0; o < n_out; ++o) W[(size_t)o * n_in + k] = (float)((double)W[(size_t)o * n_in + k] - m);
-  }
-  double mb = 0;
-  for (int o = 0; o < n_out; ++o) mb += b[o];
-  mb /= n_out;
-  for (int o = 0; o < n_out; ++o) b[o] = (float)((double)b[o] - mb);
-}
-
-// conv weight [co][ci][k] -> [ci][k][co]
-std::vector<float> conv_t(const float *w, int co, int ci, int k) {
-  std::vector<float> t((size_t)co * ci * k, 0.f);
-  if (!w) return t;
-  for (int o = 0; o < co; ++o)
-    for (int i = 0; i < ci; ++i)
-      for (int d = 0; d < k; ++d) t[((size_t)i * k + d) * co + o] = w[((size_t)o * ci + i) * k + d];
-  return t;
-}
-
-// conv weight [co][ci][k] (torch layout) -> A-operand fragments of v_mfma_f32_16x16x32_bf16 for the GEMM of actor_mfma_kernels.hip:
-// [m-tile co/16][k-step][part hi, mid, lo][lane 64][4 dwords] (w = hi + mid + lo exactly, three bf16 parts); lane (r, q) holds row
-// co = 16 mt + r, k-slots 8 q + (0..7) of the step, dword d = slots 2 d, 2 d + 1; GEMM index k = dk * ci_pad + ci (ci_pad = ci
-// rounded up to a power of two >= 16; zeros beyond).
-std::vector<float> pack_conv_frag(const float *w, int co, int ci, int ksz, int cp_force = 0, int co_pad = 0) {
-  int cp = 16;
-  while (cp < ci) cp *= 2;
-  if (cp_force) cp = cp_force;     // Linear layers: ci itself (a multiple of 32); co_pad: output rows rounded up to 16 (zero rows)
-  const int ks = (ksz * cp + 31) / 32, mts = (co_pad > co ? co_pad : co) / 16;
-  std::vector<uint32_t> t((size_t)mts * ks * 768, 0u);
-  if (w)
-    for (int mt = 0; mt < mts; ++mt)
-      for (int s = 0; s < ks; ++s)
-        for (int lane = 0; lane < 64; ++lane)
-          for (int d = 0; d < 4; ++d) {
-            uint32_t part[3] = {0, 0, 0};
-            for (int e = 0; e < 2; ++e) {
-              const int k = s * 32 + 8 * (lane >> 4) + 2 * d + e;
-              const int dk = k / cp, c = k % cp, o = 16 * mt + (lane & 15);
-              float x = (dk < ksz && c < ci && o < co) ? w[((size_t)o * ci + c) * ksz + dk] : 0.f;
-              for (int pi = 0; pi < 3; ++pi) {
-                const uint16_t h = bf16_rne(x);
-                part[pi] |= (uint32_t)h << (16 * e);
-                x -= bf16_to_f32(h);
-              }
-            }
-            const size_t base = ((size_t)(mt * ks + s) * 3) * 256 + (size_t)lane * 4 + d;
-            for (int pi = 0; pi < 3; ++pi) t[base + 256 * pi] = part[pi];
-          }
-  std::vector<float> out(t.size());
-  memcpy(out.data(), t.data(), t.size() * sizeof(float));
-  return out;
-}
-
-// conv weight [co][ci][k] (torch layout) -> A-operand fragments of v_mfma_f32_16x16x4_f32 for the GEMM of actor_f32_kernels.hip:
-// [m-tile co/16][k-group of 16][lane 64][4 floats]; lane (r, q) holds row co = 16 mt + r, GEMM indices k = 16 g + 4 q + (0..3),
-// k = dk * ci_pad + ci (ci_pad = ci rounded up to a power of two >= 16; zeros beyond)
-std::vector<float> pack_conv_f32(const float *w, int co, int ci, int ksz) {
-  int cp = 16;
-  while (cp < ci) cp *= 2;
-  const int G = ksz * cp / 16, mts = co / 16;
-  std::vector<float> t((size_t)mts * G * 256, 0.f);
-  if (w)
-    for (int mt = 0; mt < mts; ++mt)
-      for (int g = 0; g < G; ++g)
-        for (int lane = 0; lane < 64; ++lane)
-          for (int m = 0; m < 4; ++m) {
-            const int k = g * 16 + 4 * (lane >> 4) + m;
-            const int dk = k / cp, cc = k % cp, o = 16 * mt + (lane & 15);
-            t[((size_t)(mt * G + g) * 64 + lane) * 4 + m] = (dk < ksz && cc < ci) ? w[((size_t)o * ci + cc) * ksz + dk] : 0.f;
-          }
-  return t;
-}
-
-}  // namespace
-
 extern "C" int mind_debug_pack_conv_frag(const float *w, int co, int ci, int ksz, uint32_t *out, size_t cap) {
   if (!w || !out || co <= 0 || co % 16 || ci <= 0 || ksz <= 0) return MIND_EINVAL;
   const std::vector<float> t = pack_conv_frag(w, co, ci, ksz);
@@ -858,362 +607,89 @@ extern "C" int mind_debug_pack_conv_frag(const float *w, int co, int ci, int ksz
   return (int)t.size();
 }
 
+// the other packers of weight_pack.h, by name
+extern "C" int mind_debug_pack(const char *what, const float *w, int a, int b, int c, float *out, size_t cap) {
+  if (!what || !w || !out) return MIND_EINVAL;
+  const std::string k = what;
+  std::vector<float> t;
+  if (k == "afrag" && a >= 128) t = pack_afrag(w, a);
+  else if (k == "wk_frag") t = pack_wk_frag(w);
+  else if (k == "tok_bfrag" && a >= 128) t = pack_tok_bfrag(w, a);
+  else if (k == "bfrag_lo3" && a >= 128) {
+    std::vector<float> v(w, w + (size_t)127 * a + 128);
+    v.resize((size_t)128 * a, 0.f);
+    t = pack_bfrag_lo3(v, a);
+  } else if (k == "conv_f32" && a > 0 && a % 16 == 0 && b > 0 && c > 0) t = pack_conv_f32(w, a, b, c);
+  else if (k == "center_outputs" && a > 0 && b > 0) {      // w, out: W [a][b], then the bias [a]
+    std::vector<float> bias(w + (size_t)a * b, w + (size_t)a * b + a);
+    t.assign(w, w + (size_t)a * b);
+    center_outputs(t, bias, a, b);
+    t.insert(t.end(), bias.begin(), bias.end());
+  } else return MIND_EINVAL;
+  if (t.size() > cap) return MIND_EINVAL;
+  memcpy(out, t.data(), t.size() * sizeof(float));
+  return (int)t.size();
+}
+
+static void sd_of(SD &sd, const mind_tensor_desc *tensors, int n) {
+  for (int i = 0; i < n; ++i)
+    if (tensors[i].name && tensors[i].data) sd.m[tensors[i].name] = {tensors[i].data, tensors[i].numel};
+}
+
+static int debug_pack_blob(const mind_tensor_desc *tensors, int n, WeightBlob &B, char *msg, int msg_cap) {
+  if (!tensors || n <= 0 || (msg_cap > 0 && !msg) || msg_cap < 0) return MIND_EINVAL;
+  if (msg_cap > 0) msg[0] = 0;
+  SD sd;
+  sd_of(sd, tensors, n);
+  wp_pack(sd, B);
+  if (sd.missing.empty()) return MIND_OK;
+  if (msg_cap > 0) snprintf(msg, msg_cap, "%s", sd.missing.c_str());
+  return MIND_ENOTFOUND;
+}
+
+extern "C" int mind_debug_weight_image(const mind_tensor_desc *tensors, int n, float *blob, size_t blob_cap, char *names, size_t names_cap,
+                                       long long *entries, int entries_cap, long long *out_info, char *msg, int msg_cap) {
+  if (!out_info) return MIND_EINVAL;
+  WeightBlob B;
+  const int rc = debug_pack_blob(tensors, n, B, msg, msg_cap);
+  if (rc != MIND_OK) return rc;
+  std::string all;
+  for (const WeightBlob::Entry &e : B.entries) all += e.key + "\n";
+  out_info[0] = (long long)B.entries.size(); out_info[1] = (long long)B.host.size(); out_info[2] = (long long)all.size() + 1;
+  if (blob && blob_cap >= B.host.size()) memcpy(blob, B.host.data(), B.host.size() * sizeof(float));
+  if (names && names_cap > all.size()) memcpy(names, all.c_str(), all.size() + 1);
+  if (entries && entries_cap >= (int)B.entries.size())
+    for (size_t i = 0; i < B.entries.size(); ++i) { entries[2 * i] = (long long)B.entries[i].off; entries[2 * i + 1] = (long long)B.entries[i].len; }
+  return MIND_OK;
+}
+
+extern "C" int mind_debug_weight_bind(const mind_tensor_desc *tensors, int n, const char *drop, char *msg, int msg_cap) {
+  WeightBlob B;
+  const int rc = debug_pack_blob(tensors, n, B, msg, msg_cap);
+  if (rc != MIND_OK) return rc;
+  if (drop && !B.off.erase(drop)) return MIND_EINVAL;
+  WeightTables T;
+  std::string missing;
+  if (wp_bind(B, B.host.data(), T, &missing)) return MIND_OK;
+  if (msg_cap > 0) snprintf(msg, msg_cap, "%s", missing.c_str());
+  return MIND_ENOTFOUND;
+}
+
 extern "C" int mind_weights_load(mind_ctx *c, const mind_tensor_desc *tensors, int n) {
   if (!c || !tensors || n <= 0) return MIND_EINVAL;
   HIPCHK(c, hipSetDevice(c->device));
   SD sd;
-  for (int i = 0; i < n; ++i)
-    if (tensors[i].name && tensors[i].data) sd.m[tensors[i].name] = {tensors[i].data, tensors[i].numel};
-  WeightBlob &B = c->blob;
-  B.host.clear();
-  B.off.clear();
-  auto lin_ln = [&](const std::string &key, const std::string &p, int idx, int n_out, int n_in) {
-    // Linear @idx (transposed) + LayerNorm @idx+1
-    B.add(key + ".W", transpose(sd.get(p + "." + std::to_string(idx) + ".weight", (int64_t)n_out * n_in), n_out, n_in));
-    B.add(key + ".b", vec(sd.get(p + "." + std::to_string(idx) + ".bias", n_out), n_out));
-    B.add(key + ".g", vec(sd.get(p + "." + std::to_string(idx + 1) + ".weight", n_out), n_out));
-    B.add(key + ".be", vec(sd.get(p + "." + std::to_string(idx + 1) + ".bias", n_out), n_out));
-  };
-  // ---- lane_net
-  lin_ln("lane.proj", "lane_net.proj", 0, 128, 16);
-  for (int b = 0; b < 2; ++b) {
-    std::string p = "lane_net.aggre" + std::to_string(b + 1), k = "lane.a" + std::to_string(b);
-    lin_ln(k + ".f10", p + ".fc1", 0, 128, 128);
-    lin_ln(k + ".f13", p + ".fc1", 3, 128, 128);
-    lin_ln(k + ".f20", p + ".fc2", 0, 128, 256);
-    lin_ln(k + ".f23", p + ".fc2", 3, 128, 128);
-    B.add(k + ".ng", vec(sd.get(p + ".norm.weight", 128), 128));
-    B.add(k + ".nb", vec(sd.get(p + ".norm.bias", 128), 128));
-  }
-  // ---- actor_net
-  {
-    const int chans[4] = {32, 64, 128, 256};
-    int n_in = 14;
-    int ri = 0;
-    auto res = [&](const std::string &p, int ci, int co, bool ds) {
-      std::string k = "act.r" + std::to_string(ri++);
-      B.add(k + ".c1", conv_t(sd.get(p + ".conv1.weight", (int64_t)co * ci * 3), co, ci, 3));
-      B.add(k + ".c2", conv_t(sd.get(p + ".conv2.weight", (int64_t)co * co * 3), co, co, 3));
-      B.add(k + ".c1B", pack_conv_frag(sd.get(p + ".conv1.weight", (int64_t)co * ci * 3), co, ci, 3));
-      B.add(k + ".c2B", pack_conv_frag(sd.get(p + ".conv2.weight", (int64_t)co * co * 3), co, co, 3));
-      B.add(k + ".c1F", pack_conv_f32(sd.get(p + ".conv1.weight", (int64_t)co * ci * 3), co, ci, 3));
-      B.add(k + ".c2F", pack_conv_f32(sd.get(p + ".conv2.weight", (int64_t)co * co * 3), co, co, 3));
-      B.add(k + ".g1", vec(sd.get(p + ".bn1.weight", co), co));
-      B.add(k + ".b1", vec(sd.get(p + ".bn1.bias", co), co));
-      B.add(k + ".g2", vec(sd.get(p + ".bn2.weight", co), co));
-      B.add(k + ".b2", vec(sd.get(p + ".bn2.bias", co), co));
-      if (ds) {
-        B.add(k + ".ds", conv_t(sd.get(p + ".downsample.0.weight", (int64_t)co * ci), co, ci, 1));
-        B.add(k + ".dsB", pack_conv_frag(sd.get(p + ".downsample.0.weight", (int64_t)co * ci), co, ci, 1));
-        B.add(k + ".dsF", pack_conv_f32(sd.get(p + ".downsample.0.weight", (int64_t)co * ci), co, ci, 1));
-        B.add(k + ".gd", vec(sd.get(p + ".downsample.1.weight", co), co));
-        B.add(k + ".bd", vec(sd.get(p + ".downsample.1.bias", co), co));
-      }
-    };
-    for (int g = 0; g < 4; ++g) {
-      res("actor_net.groups." + std::to_string(g) + ".0", n_in, chans[g], true);
-      res("actor_net.groups." + std::to_string(g) + ".1", chans[g], chans[g], false);
-      n_in = chans[g];
-    }
-    res("actor_net.output", 128, 128, false);
-    for (int g = 0; g < 4; ++g) {
-      std::string p = "actor_net.lateral." + std::to_string(g), k = "act.lat" + std::to_string(g);
-      B.add(k + ".W", conv_t(sd.get(p + ".conv.weight", (int64_t)128 * chans[g] * 3), 128, chans[g], 3));
-      B.add(k + ".WB", pack_conv_frag(sd.get(p + ".conv.weight", (int64_t)128 * chans[g] * 3), 128, chans[g], 3));
-      B.add(k + ".WF", pack_conv_f32(sd.get(p + ".conv.weight", (int64_t)128 * chans[g] * 3), 128, chans[g], 3));
-      B.add(k + ".g", vec(sd.get(p + ".norm.weight", 128), 128));
-      B.add(k + ".b", vec(sd.get(p + ".norm.bias", 128), 128));
-    }
-  }
-  // ---- fusion_net
-  lin_ln("fus.pa", "fusion_net.proj_actor", 0, 128, 128);
-  lin_ln("fus.pl", "fusion_net.proj_lane", 0, 128, 128);
-  B.add("fus.pa.WM", pack_afrag(sd.get("fusion_net.proj_actor.0.weight", 128 * 128), 128));      // the same as fp32 MFMA A fragments (k_token_mfma)
-  B.add("fus.pl.WM", pack_afrag(sd.get("fusion_net.proj_lane.0.weight", 128 * 128), 128));
-  B.add("fus.pa.WB", pack_tok_bfrag(sd.get("fusion_net.proj_actor.0.weight", 128 * 128), 128));     // ... and as bf16 hi / lo fragments (k_token_mfma<1>)
-  B.add("fus.pl.WB", pack_tok_bfrag(sd.get("fusion_net.proj_lane.0.weight", 128 * 128), 128));
-  {
-    // rpe table [32 chunks][8][4]: k<5 W_r[f][k], 5 bias, 6 gamma, 7 beta, f = 4 chunk + w
-    const float *W = sd.get("fusion_net.proj_rpe_scene.0.weight", 128 * 5);
-    const float *b = sd.get("fusion_net.proj_rpe_scene.0.bias", 128);
-    const float *g = sd.get("fusion_net.proj_rpe_scene.1.weight", 128);
-    const float *be = sd.get("fusion_net.proj_rpe_scene.1.bias", 128);
-    std::vector<float> t(1024, 0.f);
-    if (W && b && g && be)
-      for (int ch = 0; ch < 32; ++ch)
-        for (int w = 0; w < 4; ++w) {
-          const int f = 4 * ch + w;
-          for (int k = 0; k < 5; ++k) t[ch * 32 + k * 4 + w] = W[f * 5 + k];
-          t[ch * 32 + 20 + w] = b[f];
-          t[ch * 32 + 24 + w] = g[f];
-          t[ch * 32 + 28 + w] = be[f];
-        }
-    B.add("fus.rtab", t);
-  }
-  for (int L = 0; L < 6; ++L) {
-    std::string p = "fusion_net.fuse_scene.fusion." + std::to_string(L), k = "fus.L" + std::to_string(L);
-    // proj_memory / proj_edge are followed by a LayerNorm: its mean subtraction is folded into the weights (center_outputs)
-    std::vector<float> Wmc = vec(sd.get(p + ".proj_memory.0.weight", 128 * 384), 128 * 384);
-    std::vector<float> bmc = vec(sd.get(p + ".proj_memory.0.bias", 128), 128);
-    center_outputs(Wmc, bmc, 128, 384);
-    const float *Wm = Wmc.data();
-    B.add(k + ".WAe", pack_afrag(Wm, 384));
-    B.add(k + ".WBe", pack_bfrag(Wmc, 384));
-    B.add(k + ".WLe", pack_bfrag_lo3(Wmc, 384));
-    B.add(k + ".WsT", transpose(Wm, 128, 128, 384, 128));
-    B.add(k + ".WtT", transpose(Wm, 128, 128, 384, 256));
-    B.add(k + ".bm", bmc);
-    std::vector<float> vt(VT_SIZE, 0.f);
-    auto put = [&](int off, const float *src) {
-      if (src) memcpy(vt.data() + off, src, 128 * sizeof(float));
-    };
-    put(VT_GM, sd.get(p + ".proj_memory.1.weight", 128));
-    put(VT_BM, sd.get(p + ".proj_memory.1.bias", 128));
-    if (L != 5) {
-      std::vector<float> Wpc = vec(sd.get(p + ".proj_edge.0.weight", 128 * 128), 128 * 128);
-      std::vector<float> bpc = vec(sd.get(p + ".proj_edge.0.bias", 128), 128);
-      center_outputs(Wpc, bpc, 128, 128);
-      B.add(k + ".WAp", pack_afrag(Wpc.data(), 128));
-      B.add(k + ".WBp", pack_bfrag(Wpc, 128));
-      B.add(k + ".WLp", pack_bfrag_lo3(Wpc, 128));
-      put(VT_BP, bpc.data());
-      put(VT_GP, sd.get(p + ".proj_edge.1.weight", 128));
-      put(VT_BEP, sd.get(p + ".proj_edge.1.bias", 128));
-      put(VT_GE, sd.get(p + ".norm_edge.weight", 128));
-      put(VT_BE, sd.get(p + ".norm_edge.bias", 128));
-    }
-    B.add(k + ".vtab", vt);
-    const float *Win = sd.get(p + ".multihead_attn.in_proj_weight", 384 * 128);
-    const float *bin = sd.get(p + ".multihead_attn.in_proj_bias", 384);
-    {
-      // the token kernel's projections as fp32 MFMA A fragments (k_token_mfma)
-      const float *Wo_ = sd.get(p + ".multihead_attn.out_proj.weight", 128 * 128);
-      const float *W1_ = sd.get(p + ".linear1.weight", 256 * 128), *W2_ = sd.get(p + ".linear2.weight", 128 * 256);
-      B.add(k + ".WsM", pack_afrag(Wm + 128, 384));
-      B.add(k + ".WtM", pack_afrag(Wm + 256, 384));
-      B.add(k + ".WqM", pack_afrag(Win, 128));
-      B.add(k + ".WkM", pack_wk_frag(Win ? Win + 128 * 128 : nullptr));
-      B.add(k + ".WvM", pack_afrag(Win ? Win + 2 * 128 * 128 : nullptr, 128));
-      B.add(k + ".WoM", pack_afrag(Wo_, 128));
-      B.add(k + ".W1aM", pack_afrag(W1_, 128));
-      B.add(k + ".W1bM", pack_afrag(W1_ ? W1_ + 128 * 128 : nullptr, 128));
-      B.add(k + ".W2aM", pack_afrag(W2_, 256));
-      B.add(k + ".W2bM", pack_afrag(W2_ ? W2_ + 128 : nullptr, 256));
-      // ... and as bf16 hi / lo A fragments (k_token_mfma<1>; the folded K query keeps the fp32 fragments)
-      B.add(k + ".WsB", pack_tok_bfrag(Wm + 128, 384));
-      B.add(k + ".WtB", pack_tok_bfrag(Wm + 256, 384));
-      B.add(k + ".WqB", pack_tok_bfrag(Win, 128));
-      B.add(k + ".WvB", pack_tok_bfrag(Win ? Win + 2 * 128 * 128 : nullptr, 128));
-      B.add(k + ".WoB", pack_tok_bfrag(Wo_, 128));
-      B.add(k + ".W1aB", pack_tok_bfrag(W1_, 128));
-      B.add(k + ".W1bB", pack_tok_bfrag(W1_ ? W1_ + 128 * 128 : nullptr, 128));
-      B.add(k + ".W2aB", pack_tok_bfrag(W2_, 256));
-      B.add(k + ".W2bB", pack_tok_bfrag(W2_ ? W2_ + 128 : nullptr, 256));
-    }
-    B.add(k + ".WqT", transpose(Win, 128, 128));
-    B.add(k + ".Wk", vec(Win ? Win + 128 * 128 : nullptr, 128 * 128));
-    B.add(k + ".WvT", transpose(Win ? Win + 2 * 128 * 128 : nullptr, 128, 128));
-    B.add(k + ".bq", vec(bin, 128));
-    B.add(k + ".bv", vec(bin ? bin + 256 : nullptr, 128));
-    B.add(k + ".WoT", transpose(sd.get(p + ".multihead_attn.out_proj.weight", 128 * 128), 128, 128));
-    B.add(k + ".bo", vec(sd.get(p + ".multihead_attn.out_proj.bias", 128), 128));
-    B.add(k + ".W1T", transpose(sd.get(p + ".linear1.weight", 256 * 128), 256, 128));
-    B.add(k + ".b1", vec(sd.get(p + ".linear1.bias", 256), 256));
-    B.add(k + ".W2T", transpose(sd.get(p + ".linear2.weight", 128 * 256), 128, 256));
-    B.add(k + ".b2", vec(sd.get(p + ".linear2.bias", 128), 128));
-    B.add(k + ".g2", vec(sd.get(p + ".norm2.weight", 128), 128));
-    B.add(k + ".be2", vec(sd.get(p + ".norm2.bias", 128), 128));
-    B.add(k + ".g3", vec(sd.get(p + ".norm3.weight", 128), 128));
-    B.add(k + ".be3", vec(sd.get(p + ".norm3.bias", 128), 128));
-  }
-  // ---- pred_scene
-  lin_ln("dec.rpe", "pred_scene.proj_rpe", 0, 128, 20);
-  lin_ln("dec.t0", "pred_scene.proj_tgt", 0, 128, 256);
-  lin_ln("dec.t3", "pred_scene.proj_tgt", 3, 128, 128);
-  lin_ln("dec.c0", "pred_scene.ctx_proj", 0, 384, 128);
-  lin_ln("dec.c3", "pred_scene.ctx_proj", 3, 768, 384);
-  lin_ln("dec.a0", "pred_scene.actor_proj", 0, 384, 128);
-  lin_ln("dec.a3", "pred_scene.actor_proj", 3, 768, 384);
-  B.add("dec.a0.WB", pack_conv_frag(sd.get("pred_scene.actor_proj.0.weight", 384 * 128), 384, 128, 1, 128));
-  B.add("dec.a3.WB", pack_conv_frag(sd.get("pred_scene.actor_proj.3.weight", 768 * 384), 768, 384, 1, 384));
-  B.add("dec.reg0.WB", pack_conv_frag(sd.get("pred_scene.reg.0.weight", 128 * 128), 128, 128, 1, 128));
-  B.add("dec.reg3.WB", pack_conv_frag(sd.get("pred_scene.reg.3.weight", 128 * 128), 128, 128, 1, 128));
-  B.add("dec.reg6.WB", pack_conv_frag(sd.get("pred_scene.reg.6.weight", 40 * 128), 40, 128, 1, 128, 48));
-  {
-    std::vector<float> b6 = vec(sd.get("pred_scene.reg.6.bias", 40), 40);
-    b6.resize(48, 0.f);
-    B.add("dec.reg6.bB", b6);
-  }
-  for (int L = 0; L < 2; ++L) {
-    std::string p = "pred_scene.ctx_sat.layers." + std::to_string(L), k = "dec.e" + std::to_string(L);
-    B.add(k + ".inW", transpose(sd.get(p + ".self_attn.in_proj_weight", 384 * 128), 384, 128));
-    B.add(k + ".inb", vec(sd.get(p + ".self_attn.in_proj_bias", 384), 384));
-    B.add(k + ".outW", transpose(sd.get(p + ".self_attn.out_proj.weight", 128 * 128), 128, 128));
-    B.add(k + ".outb", vec(sd.get(p + ".self_attn.out_proj.bias", 128), 128));
-    B.add(k + ".l1W", transpose(sd.get(p + ".linear1.weight", 1536 * 128), 1536, 128));
-    B.add(k + ".l1b", vec(sd.get(p + ".linear1.bias", 1536), 1536));
-    B.add(k + ".l2W", transpose(sd.get(p + ".linear2.weight", 128 * 1536), 128, 1536));
-    B.add(k + ".l2b", vec(sd.get(p + ".linear2.bias", 128), 128));
-    B.add(k + ".n1g", vec(sd.get(p + ".norm1.weight", 128), 128));
-    B.add(k + ".n1b", vec(sd.get(p + ".norm1.bias", 128), 128));
-    B.add(k + ".n2g", vec(sd.get(p + ".norm2.weight", 128), 128));
-    B.add(k + ".n2b", vec(sd.get(p + ".norm2.bias", 128), 128));
-  }
-  for (const char *hn : {"cls", "reg"}) {
-    std::string p = std::string("pred_scene.") + hn, k = std::string("dec.") + hn;
-    lin_ln(k + "0", p, 0, 128, 128);
-    lin_ln(k + "3", p, 3, 128, 128);
-    const int nl = strcmp(hn, "cls") == 0 ? 1 : 40;
-    B.add(k + "6.W", transpose(sd.get(p + ".6.weight", (int64_t)nl * 128), nl, 128));
-    B.add(k + "6.b", vec(sd.get(p + ".6.bias", nl), nl));
-  }
-  {
-    // Bezier basis (network.py:449-464): float64 numpy -> fp32 (Q21)
-    std::vector<float> T(60 * 8), Tp(60 * 7);
-    auto comb = [](int n, int k) { double r = 1; for (int i = 1; i <= k; ++i) r = r * (n - k + i) / i; return r; };
-    for (int t = 0; t < 60; ++t) {
-      double ts = (t == 59) ? 1.0 : (double)t * (1.0 / 59.0);
-      // numpy linspace: start + arange * step, step = 1/59; last point exactly 1
-      ts = (t == 59) ? 1.0 : 0.0 + (double)t * (1.0 / 59.0);
-      for (int i = 0; i < 8; ++i) T[t * 8 + i] = (float)(comb(7, i) * std::pow(1.0 - ts, 7 - i) * std::pow(ts, i));
-      for (int i = 0; i < 7; ++i) Tp[t * 7 + i] = (float)(7.0 * comb(6, i) * std::pow(1.0 - ts, 6 - i) * std::pow(ts, i));
-    }
-    B.add("dec.T", T);
-    B.add("dec.Tp", Tp);
-  }
+  sd_of(sd, tensors, n);
+  WeightBlob B;       // local: a load that fails here leaves the weights loaded before it in place
+  wp_pack(sd, B);
   if (!sd.missing.empty()) return fail(c, MIND_ENOTFOUND, "state_dict tensor missing or wrong size: %s", sd.missing.c_str());
-
+  c->have_weights = false;     // from here on the tables point into freed memory until the bind below
   if (c->wdev) (void)hipFree(c->wdev);
   c->wdev = nullptr;
   HIPCHK(c, hipMalloc((void **)&c->wdev, B.host.size() * sizeof(float)));
   HIPCHK(c, hipMemcpy(c->wdev, B.host.data(), B.host.size() * sizeof(float), hipMemcpyHostToDevice));
-  auto P = [&](const std::string &k) -> const float * {
-    auto it = B.off.find(k);
-    return it == B.off.end() ? nullptr : c->wdev + it->second;
-  };
-  // ---- pointer tables
-  LaneW &lw = c->laneW;
-  lw.pW = P("lane.proj.W"); lw.pb = P("lane.proj.b"); lw.pg = P("lane.proj.g"); lw.pbe = P("lane.proj.be");
-  for (int b = 0; b < 2; ++b) {
-    std::string k = "lane.a" + std::to_string(b);
-    lw.f10W[b] = P(k + ".f10.W"); lw.f10b[b] = P(k + ".f10.b"); lw.f10g[b] = P(k + ".f10.g"); lw.f10be[b] = P(k + ".f10.be");
-    lw.f13W[b] = P(k + ".f13.W"); lw.f13b[b] = P(k + ".f13.b"); lw.f13g[b] = P(k + ".f13.g"); lw.f13be[b] = P(k + ".f13.be");
-    lw.f20W[b] = P(k + ".f20.W"); lw.f20b[b] = P(k + ".f20.b"); lw.f20g[b] = P(k + ".f20.g"); lw.f20be[b] = P(k + ".f20.be");
-    lw.f23W[b] = P(k + ".f23.W"); lw.f23b[b] = P(k + ".f23.b"); lw.f23g[b] = P(k + ".f23.g"); lw.f23be[b] = P(k + ".f23.be");
-    lw.ng[b] = P(k + ".ng"); lw.nbe[b] = P(k + ".nb");
-  }
-  ActorW &aw = c->actorW;
-  for (int r = 0; r < 9; ++r) {
-    std::string k = "act.r" + std::to_string(r);
-    aw.res[r].c1 = P(k + ".c1"); aw.res[r].g1 = P(k + ".g1"); aw.res[r].b1 = P(k + ".b1");
-    aw.res[r].c2 = P(k + ".c2"); aw.res[r].g2 = P(k + ".g2"); aw.res[r].b2 = P(k + ".b2");
-    aw.res[r].ds = P(k + ".ds"); aw.res[r].gd = P(k + ".gd"); aw.res[r].bd = P(k + ".bd");
-  }
-  for (int g = 0; g < 4; ++g) {
-    std::string k = "act.lat" + std::to_string(g);
-    aw.latW[g] = P(k + ".W"); aw.latG[g] = P(k + ".g"); aw.latB[g] = P(k + ".b");
-  }
-  AmW &bw = c->actorBW;
-  for (int r = 0; r < 9; ++r) {
-    std::string k = "act.r" + std::to_string(r);
-    AmRes &R = bw.res[r];
-    R.c1 = (const u32 *)P(k + ".c1B"); R.c2 = (const u32 *)P(k + ".c2B"); R.ds = (const u32 *)P(k + ".dsB");
-    R.g1 = aw.res[r].g1; R.b1 = aw.res[r].b1; R.g2 = aw.res[r].g2; R.b2 = aw.res[r].b2;
-    R.gd = aw.res[r].gd; R.bd = aw.res[r].bd;
-  }
-  for (int g = 0; g < 4; ++g) {
-    bw.lat[g].w = (const u32 *)P("act.lat" + std::to_string(g) + ".WB");
-    bw.lat[g].g = aw.latG[g]; bw.lat[g].b = aw.latB[g];
-  }
-  AfW &fw = c->actorFW;
-  for (int r = 0; r < 9; ++r) {
-    std::string k = "act.r" + std::to_string(r);
-    AfRes &R = fw.res[r];
-    R.c1 = P(k + ".c1F"); R.c2 = P(k + ".c2F"); R.ds = P(k + ".dsF");
-    R.g1 = aw.res[r].g1; R.b1 = aw.res[r].b1; R.g2 = aw.res[r].g2; R.b2 = aw.res[r].b2;
-    R.gd = aw.res[r].gd; R.bd = aw.res[r].bd;
-  }
-  for (int g = 0; g < 4; ++g) {
-    fw.lat[g].w = P("act.lat" + std::to_string(g) + ".WF");
-    fw.lat[g].g = aw.latG[g]; fw.lat[g].b = aw.latB[g];
-  }
-  c->rtab = P("fus.rtab");
-  for (int L = 0; L < 6; ++L) {
-    std::string k = "fus.L" + std::to_string(L);
-    c->WAe[L] = P(k + ".WAe");
-    c->WAp[L] = P(k + ".WAp");
-    c->WBe[L] = (const u32 *)P(k + ".WBe");
-    c->WBp[L] = (const u32 *)P(k + ".WBp");
-    c->WLe[L] = (const u32 *)P(k + ".WLe");
-    c->WLp[L] = (const u32 *)P(k + ".WLp");
-    c->vtab[L] = P(k + ".vtab");
-  }
-  for (int L = 0; L <= 6; ++L) {
-    TokWeights &w = c->tokW[L];
-    memset(&w, 0, sizeof(w));
-    if (L >= 1) {
-      std::string k = "fus.L" + std::to_string(L - 1);
-      w.WvT = P(k + ".WvT"); w.bv = P(k + ".bv"); w.WoT = P(k + ".WoT"); w.bo = P(k + ".bo");
-      w.g2 = P(k + ".g2"); w.b2 = P(k + ".be2"); w.W1T = P(k + ".W1T"); w.b1 = P(k + ".b1");
-      w.W2T = P(k + ".W2T"); w.bb2 = P(k + ".b2"); w.g3 = P(k + ".g3"); w.b3 = P(k + ".be3");
-    }
-    if (L <= 5) {
-      std::string k = "fus.L" + std::to_string(L);
-      w.WsT = P(k + ".WsT"); w.WtT = P(k + ".WtT"); w.bm = P(k + ".bm");
-      w.WqT = P(k + ".WqT"); w.bq = P(k + ".bq"); w.Wk = P(k + ".Wk");
-    }
-    w.WpaT = P("fus.pa.W"); w.bpa = P("fus.pa.b"); w.gpa = P("fus.pa.g"); w.bepa = P("fus.pa.be");
-    w.WplT = P("fus.pl.W"); w.bpl = P("fus.pl.b"); w.gpl = P("fus.pl.g"); w.bepl = P("fus.pl.be");
-    TokWeightsM &m = c->tokWM[L];
-    memset(&m, 0, sizeof(m));
-    if (L >= 1) {
-      std::string k = "fus.L" + std::to_string(L - 1);
-      m.Wv = P(k + ".WvM"); m.Wo = P(k + ".WoM"); m.W1a = P(k + ".W1aM"); m.W1b = P(k + ".W1bM"); m.W2a = P(k + ".W2aM"); m.W2b = P(k + ".W2bM");
-    }
-    if (L <= 5) {
-      std::string k = "fus.L" + std::to_string(L);
-      m.Ws = P(k + ".WsM"); m.Wt = P(k + ".WtM"); m.Wq = P(k + ".WqM"); m.Wkf = P(k + ".WkM");
-    }
-    m.Wpa = P("fus.pa.WM"); m.Wpl = P("fus.pl.WM");
-    TokWeightsM &bm = c->tokWB[L];
-    memset(&bm, 0, sizeof(bm));
-    if (L >= 1) {
-      std::string k = "fus.L" + std::to_string(L - 1);
-      bm.Wv = P(k + ".WvB"); bm.Wo = P(k + ".WoB"); bm.W1a = P(k + ".W1aB"); bm.W1b = P(k + ".W1bB"); bm.W2a = P(k + ".W2aB"); bm.W2b = P(k + ".W2bB");
-    }
-    if (L <= 5) {
-      std::string k = "fus.L" + std::to_string(L);
-      bm.Ws = P(k + ".WsB"); bm.Wt = P(k + ".WtB"); bm.Wq = P(k + ".WqB"); bm.Wkf = P(k + ".WkM");
-    }
-    bm.Wpa = P("fus.pa.WB"); bm.Wpl = P("fus.pl.WB");
-  }
-  DecW &d = c->decW;
-  d.rpeW = P("dec.rpe.W"); d.rpeb = P("dec.rpe.b"); d.rpeg = P("dec.rpe.g"); d.rpebe = P("dec.rpe.be");
-  d.t0W = P("dec.t0.W"); d.t0b = P("dec.t0.b"); d.t0g = P("dec.t0.g"); d.t0be = P("dec.t0.be");
-  d.t3W = P("dec.t3.W"); d.t3b = P("dec.t3.b"); d.t3g = P("dec.t3.g"); d.t3be = P("dec.t3.be");
-  d.c0W = P("dec.c0.W"); d.c0b = P("dec.c0.b"); d.c0g = P("dec.c0.g"); d.c0be = P("dec.c0.be");
-  d.c3W = P("dec.c3.W"); d.c3b = P("dec.c3.b"); d.c3g = P("dec.c3.g"); d.c3be = P("dec.c3.be");
-  d.a0W = P("dec.a0.W"); d.a0b = P("dec.a0.b"); d.a0g = P("dec.a0.g"); d.a0be = P("dec.a0.be");
-  d.a3W = P("dec.a3.W"); d.a3b = P("dec.a3.b"); d.a3g = P("dec.a3.g"); d.a3be = P("dec.a3.be");
-  for (int L = 0; L < 2; ++L) {
-    std::string k = "dec.e" + std::to_string(L);
-    d.inW[L] = P(k + ".inW"); d.inb[L] = P(k + ".inb"); d.outW[L] = P(k + ".outW"); d.outb[L] = P(k + ".outb");
-    d.l1W[L] = P(k + ".l1W"); d.l1b[L] = P(k + ".l1b"); d.l2W[L] = P(k + ".l2W"); d.l2b[L] = P(k + ".l2b");
-    d.n1g[L] = P(k + ".n1g"); d.n1b[L] = P(k + ".n1b"); d.n2g[L] = P(k + ".n2g"); d.n2b[L] = P(k + ".n2b");
-  }
-  d.k0W = P("dec.cls0.W"); d.k0b = P("dec.cls0.b"); d.k0g = P("dec.cls0.g"); d.k0be = P("dec.cls0.be");
-  d.k3W = P("dec.cls3.W"); d.k3b = P("dec.cls3.b"); d.k3g = P("dec.cls3.g"); d.k3be = P("dec.cls3.be");
-  d.k6W = P("dec.cls6.W"); d.k6b = P("dec.cls6.b");
-  d.r0W = P("dec.reg0.W"); d.r0b = P("dec.reg0.b"); d.r0g = P("dec.reg0.g"); d.r0be = P("dec.reg0.be");
-  d.r3W = P("dec.reg3.W"); d.r3b = P("dec.reg3.b"); d.r3g = P("dec.reg3.g"); d.r3be = P("dec.reg3.be");
-  d.r6W = P("dec.reg6.W"); d.r6b = P("dec.reg6.b");
-  d.T = P("dec.T"); d.Tp = P("dec.Tp");
-  DmW &m = c->decBW;
-  m.a0 = (const u32 *)P("dec.a0.WB"); m.a3 = (const u32 *)P("dec.a3.WB"); m.r0 = (const u32 *)P("dec.reg0.WB");
-  m.r3 = (const u32 *)P("dec.reg3.WB"); m.r6 = (const u32 *)P("dec.reg6.WB");
-  m.a0b = d.a0b; m.a0g = d.a0g; m.a0be = d.a0be; m.a3b = d.a3b; m.a3g = d.a3g; m.a3be = d.a3be;
-  m.r0b = d.r0b; m.r0g = d.r0g; m.r0be = d.r0be; m.r3b = d.r3b; m.r3g = d.r3g; m.r3be = d.r3be; m.r6b = P("dec.reg6.bB");
-  m.T = d.T; m.Tp = d.Tp;
+  std::string missing;
+  if (!wp_bind(B, c->wdev, c->W, &missing)) return fail(c, MIND_ENOTFOUND, "packed weights hold no entry '%s'", missing.c_str());
   c->have_weights = true;
   return MIND_OK;
 }

@@ -237,11 +237,11 @@ static int pred_actor_net(PredCall &p) {
   const dim3 grid(ch.actor_grid);
   switch (ch.actor_form) {
   case PRED_ACTOR_F32:
-    if (ch.actor_arg == 2) hipLaunchKernelGGL(k_actor_f32<2>, grid, dim3(AF_T), mind_actor_f32_lds_bytes(2), p.st, actors, A, actor_feat, c->actorFW);
-    else hipLaunchKernelGGL(k_actor_f32<1>, grid, dim3(AF_T), mind_actor_f32_lds_bytes(1), p.st, actors, A, actor_feat, c->actorFW);
+    if (ch.actor_arg == 2) hipLaunchKernelGGL(k_actor_f32<2>, grid, dim3(AF_T), mind_actor_f32_lds_bytes(2), p.st, actors, A, actor_feat, c->W.actorF);
+    else hipLaunchKernelGGL(k_actor_f32<1>, grid, dim3(AF_T), mind_actor_f32_lds_bytes(1), p.st, actors, A, actor_feat, c->W.actorF);
     break;
   case PRED_ACTOR_VALU:
-    hipLaunchKernelGGL(k_actor_net, grid, dim3(AT), mind_actor_lds_bytes(), p.st, actors, A, actor_feat, c->actorW);
+    hipLaunchKernelGGL(k_actor_net, grid, dim3(AT), mind_actor_lds_bytes(), p.st, actors, A, actor_feat, c->W.actor);
     break;
   case PRED_ACTOR_LW: {
     // the weight fragments stationary, one arena of one chunk (allocated at first use)
@@ -249,17 +249,17 @@ static int pred_actor_net(PredCall &p) {
     if ((rc = ensure_exact(c, c->actor_lw_arena, lw_arena_bytes(ch.actor_chunk), "the layer-wise ActorNet's arena"))) return rc;
     lw_build_plan(A, ch.actor_chunk, c->actor_lw_plan);
     u32 *arena = (u32 *)c->actor_lw_arena.p;
-    const int nl = ch.np == 6 ? lw_run<6>(c->actor_lw_plan, p.st, arena, actors, actor_feat, c->actorBW)
-                 : ch.np == 3 ? lw_run<3>(c->actor_lw_plan, p.st, arena, actors, actor_feat, c->actorBW)
-                              : lw_run<1>(c->actor_lw_plan, p.st, arena, actors, actor_feat, c->actorBW);
+    const int nl = ch.np == 6 ? lw_run<6>(c->actor_lw_plan, p.st, arena, actors, actor_feat, c->W.actorB)
+                 : ch.np == 3 ? lw_run<3>(c->actor_lw_plan, p.st, arena, actors, actor_feat, c->W.actorB)
+                              : lw_run<1>(c->actor_lw_plan, p.st, arena, actors, actor_feat, c->W.actorB);
     if (nl < 0) return fail(c, MIND_ESTATE, "layer-wise ActorNet: a stage has no kernel");
     c->last_actor_lw = 1; c->last_actor_launches = nl; c->last_actor_chunks = ch.actor_chunks;
     break;
   }
   default:
-    if (ch.np == 6) hipLaunchKernelGGL(k_actor_mfma<6>, grid, dim3(AM_T), mind_actor_mfma_lds_bytes(), p.st, actors, A, actor_feat, c->actorBW);
-    else if (ch.np == 3) hipLaunchKernelGGL(k_actor_mfma<3>, grid, dim3(AM_T), mind_actor_mfma_lds_bytes(), p.st, actors, A, actor_feat, c->actorBW);
-    else hipLaunchKernelGGL(k_actor_mfma<1>, grid, dim3(AM_T), mind_actor_mfma_lds_bytes(), p.st, actors, A, actor_feat, c->actorBW);
+    if (ch.np == 6) hipLaunchKernelGGL(k_actor_mfma<6>, grid, dim3(AM_T), mind_actor_mfma_lds_bytes(), p.st, actors, A, actor_feat, c->W.actorB);
+    else if (ch.np == 3) hipLaunchKernelGGL(k_actor_mfma<3>, grid, dim3(AM_T), mind_actor_mfma_lds_bytes(), p.st, actors, A, actor_feat, c->W.actorB);
+    else hipLaunchKernelGGL(k_actor_mfma<1>, grid, dim3(AM_T), mind_actor_mfma_lds_bytes(), p.st, actors, A, actor_feat, c->W.actorB);
   }
   return MIND_OK;
 }
@@ -291,7 +291,7 @@ static int pred_encoders(PredCall &p) {
   if (!p.lane_feat) {
     float *lf = p.out->lane_feat ? p.out->lane_feat : (float *)c->lane_feat.p;
     if (Ltot > 0)
-      hipLaunchKernelGGL(k_lane_net, dim3((Ltot + PL - 1) / PL), dim3(DT), 0, ss, in->lanes, Ltot, lf, c->laneW);
+      hipLaunchKernelGGL(k_lane_net, dim3((Ltot + PL - 1) / PL), dim3(DT), 0, ss, in->lanes, Ltot, lf, c->W.lane);
     p.lane_feat = lf;
   } else if (p.out->lane_feat && p.out->lane_feat != in->lane_feat && Ltot > 0) {
     HIPCHK(c, hipMemcpyAsync(p.out->lane_feat, in->lane_feat, (size_t)Ltot * 128 * sizeof(float), hipMemcpyDeviceToDevice, ss));
@@ -303,9 +303,9 @@ static int pred_encoders(PredCall &p) {
     HIPCHK(c, hipStreamWaitEvent(st, c->ev_side, 0));
   }
   // the target polyline's encoder + embedding feed the decoder only: they stay on the side stream while the fusion layers run
-  hipLaunchKernelGGL(k_lane_net, dim3((Bn + PL - 1) / PL), dim3(DT), 0, ss, in->tgt_nodes, Bn, (float *)c->tgt_feat.p, c->laneW);
+  hipLaunchKernelGGL(k_lane_net, dim3((Bn + PL - 1) / PL), dim3(DT), 0, ss, in->tgt_nodes, Bn, (float *)c->tgt_feat.p, c->W.lane);
   hipLaunchKernelGGL(k_dec_tgt, dim3(Bn), dim3(DT), mind_dec_scene_lds_bytes(), ss, (const float *)c->tgt_feat.p, in->tgt_rpe, (float *)c->tgt_emb.p,
-                     c->decW);
+                     c->W.dec);
   if (c->side) HIPCHK(c, hipEventRecord(c->ev_tgt, c->side));
   if (p.ch.tgt_wait_first) HIPCHK(c, hipStreamWaitEvent(st, c->ev_tgt, 0));
   return MIND_OK;
@@ -340,7 +340,7 @@ static int pred_token_step(PredCall &p, int mode, int Lw) {
     if (r.layerwise) {
       tl_build_plan(r.n, mode, p.ch.tok_chunk, c->n_cu, c->tok_lw_plan);
       for (const TlLaunch &L : c->tok_lw_plan) {
-        if (tl_launch(L, st, mode, m_, actor_feat, lane_feat, x_, part, ST_, QK_, qk_stride, c->tokW[Lw], c->tokWM[Lw], (float *)c->tok_lw_arena.p, p.ch.tok_chunk))
+        if (tl_launch(L, st, mode, m_, actor_feat, lane_feat, x_, part, ST_, QK_, qk_stride, c->W.tok[Lw], c->W.tokM[Lw], (float *)c->tok_lw_arena.p, p.ch.tok_chunk))
           return fail(c, MIND_ESTATE, "layer-wise token stage: a stage has no kernel");
         HIPCHK(c, pred_tok_mark(p, L.stage));
       }
@@ -351,13 +351,13 @@ static int pred_token_step(PredCall &p, int mode, int Lw) {
     if (r.kind == 0) {
       const int tpw = r.small ? TOK_TPW_SMALL : TOK_TPW_BIG;
       hipLaunchKernelGGL(r.small ? (r.merged ? k_token_m : k_token<TOK_TPW_SMALL>) : k_token<TOK_TPW_BIG>, dim3((r.n + tpw - 1) / tpw), dim3(TT_THREADS), 0,
-                         st, m_, r.n, mode, actor_feat, lane_feat, x_, part, ST_, QK_, c->tokW[Lw]);
+                         st, m_, r.n, mode, actor_feat, lane_feat, x_, part, ST_, QK_, c->W.tok[Lw]);
     } else if (r.kind == 1) {
       hipLaunchKernelGGL(k_token_mfma<0>, dim3((r.n + TM_TOK - 1) / TM_TOK), dim3(TM_THREADS), tokm_lds, st, m_, r.n, mode, actor_feat, lane_feat, x_,
-                         part, ST_, QK_, c->tokW[Lw], c->tokWM[Lw]);
+                         part, ST_, QK_, c->W.tok[Lw], c->W.tokM[Lw]);
     } else {
       hipLaunchKernelGGL(k_token_mfma<1>, dim3((r.n + TM_TOK - 1) / TM_TOK), dim3(TM_THREADS), tokm_lds, st, m_, r.n, mode, actor_feat, lane_feat, x_,
-                         part, ST_, QK_, c->tokW[Lw], c->tokWB[Lw]);
+                         part, ST_, QK_, c->W.tok[Lw], c->W.tokB[Lw]);
     }
     HIPCHK(c, pred_tok_mark(p, TL_NSTAGE));
   }
@@ -376,16 +376,16 @@ static int pred_pair_layer(PredCall &p, int L) {
   const dim3 grid(pair_grid(nj, c->n_cu)), block(PAIR_THREADS);
   float *edge = (float *)c->edge.p, *ST = (float *)c->ST.p, *QK = (float *)c->QK.p, *part = (float *)c->part.p, *tokpos = (float *)c->tokpos.p;
   const size_t ldsb = mind_pair_bf_lds_bytes();
-  const u32 *we = c->WBe[L], *wp = last ? c->WBe[L] : c->WBp[L];
+  const u32 *we = c->W.pair.WBe[L], *wp = last ? c->W.pair.WBe[L] : c->W.pair.WBp[L];
   if (c->profiling) HIPCHK(c, hipEventRecord(p.evs[2 * L], p.st));
 #define PAIR_GO(K0, K1, LDS, ...)                                                                                                             \
   do {                                                                                                                                        \
-    if (L == 0) hipLaunchKernelGGL(K0, grid, block, LDS, p.st, jl, nj, edge, ST, QK, part, __VA_ARGS__, c->vtab[L], c->rtab, tokpos, p.rpe_dev, um); \
-    else hipLaunchKernelGGL(K1, grid, block, LDS, p.st, jl, nj, edge, ST, QK, part, __VA_ARGS__, c->vtab[L], c->rtab, tokpos, p.rpe_dev, um);        \
+    if (L == 0) hipLaunchKernelGGL(K0, grid, block, LDS, p.st, jl, nj, edge, ST, QK, part, __VA_ARGS__, c->W.pair.vtab[L], c->W.pair.rtab, tokpos, p.rpe_dev, um); \
+    else hipLaunchKernelGGL(K1, grid, block, LDS, p.st, jl, nj, edge, ST, QK, part, __VA_ARGS__, c->W.pair.vtab[L], c->W.pair.rtab, tokpos, p.rpe_dev, um);        \
   } while (0)
   switch (ch.pair_family) {
-  case PRED_PAIR_F32: PAIR_GO((k_pair<0>), (k_pair<1>), mind_pair_lds_bytes(), c->WAe[L], last ? c->WAe[L] : c->WAp[L]); break;
-  case PRED_PAIR_T6: PAIR_GO((k_pair_t6<0>), (k_pair_t6<1>), ldsb, we, wp, c->WLe[L], last ? c->WLe[L] : c->WLp[L]); break;
+  case PRED_PAIR_F32: PAIR_GO((k_pair<0>), (k_pair<1>), mind_pair_lds_bytes(), c->W.pair.WAe[L], last ? c->W.pair.WAe[L] : c->W.pair.WAp[L]); break;
+  case PRED_PAIR_T6: PAIR_GO((k_pair_t6<0>), (k_pair_t6<1>), ldsb, we, wp, c->W.pair.WLe[L], last ? c->W.pair.WLe[L] : c->W.pair.WLp[L]); break;
   case PRED_PAIR_T:
     if (ch.pair_np == 3) PAIR_GO((k_pair_t<0, 3>), (k_pair_t<1, 3>), ldsb, we, wp);
     else PAIR_GO((k_pair_t<0, 1>), (k_pair_t<1, 1>), ldsb, we, wp);
@@ -457,7 +457,7 @@ static int pred_decoder(PredCall &p) {
     HIPCHK(c, hipEventRecord(c->ev_main, st));
     HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_main, 0));
     hipLaunchKernelGGL(k_dec_actor<1>, agrid, dim3(DT), mind_dec_actor_lds_bytes(), c->side, x, d_actor_row, d_actor_scene, A,
-                       (const float *)nullptr, (const float *)nullptr, (float *)nullptr, (float *)nullptr, c->decW, (float *)c->dec_h2.p);
+                       (const float *)nullptr, (const float *)nullptr, (float *)nullptr, (float *)nullptr, c->W.dec, (float *)c->dec_h2.p);
     HIPCHK(c, hipEventRecord(c->ev_side, c->side));
   }
   // the scene part
@@ -479,20 +479,20 @@ static int pred_decoder(PredCall &p) {
     }
   }
   if (mw)
-    hipLaunchKernelGGL(k_dec_scene_mw, dim3(ch.mw_blocks), dim3(DT), mind_dec_scene_lds_bytes(), st, x, d_cls_row, (float *)c->cmode.p, out->cls, c->decW, Bn,
+    hipLaunchKernelGGL(k_dec_scene_mw, dim3(ch.mw_blocks), dim3(DT), mind_dec_scene_lds_bytes(), st, x, d_cls_row, (float *)c->cmode.p, out->cls, c->W.dec, Bn,
                        (float *)c->dec_xbuf.p, (unsigned *)c->dec_bars.p, c->dec_abort);
   else if (ch.cls_side) {
     // the mode tokens on the context stream, the mode probabilities (the cls head: ~10 us a launch) on the side stream beside the actor part's
     // head, which needs the tokens only; the caller's next work on the context stream follows both
-    hipLaunchKernelGGL(k_dec_scene_c, dim3(Bn), dim3(DT), mind_dec_scene_lds_bytes(), st, x, d_cls_row, (float *)c->cmode.p, c->decW);
+    hipLaunchKernelGGL(k_dec_scene_c, dim3(Bn), dim3(DT), mind_dec_scene_lds_bytes(), st, x, d_cls_row, (float *)c->cmode.p, c->W.dec);
     HIPCHK(c, hipEventRecord(c->ev_main, st));
     HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_main, 0));
-    hipLaunchKernelGGL(k_dec_cls, dim3(Bn), dim3(DT), mind_dec_scene_lds_bytes(), c->side, (float *)c->cmode.p, out->cls, c->decW);
+    hipLaunchKernelGGL(k_dec_cls, dim3(Bn), dim3(DT), mind_dec_scene_lds_bytes(), c->side, (float *)c->cmode.p, out->cls, c->W.dec);
     if (!c->ev_cls) HIPCHK(c, hipEventCreateWithFlags(&c->ev_cls, hipEventDisableTiming));
     HIPCHK(c, hipEventRecord(c->ev_cls, c->side));
     cls_on_side = true;
   } else
-    hipLaunchKernelGGL(k_dec_scene, dim3(Bn), dim3(DT), mind_dec_scene_lds_bytes(), st, x, d_cls_row, (float *)c->cmode.p, out->cls, c->decW);
+    hipLaunchKernelGGL(k_dec_scene, dim3(Bn), dim3(DT), mind_dec_scene_lds_bytes(), st, x, d_cls_row, (float *)c->cmode.p, out->cls, c->W.dec);
   if (c->side) HIPCHK(c, hipStreamWaitEvent(st, c->ev_tgt, 0));      // the decoder's actor part reads the target embedding
   // the actor part: the K-split fp32 kernel (a handful of workgroups, bound by the latency of one pass over the weights), its head behind the
   // side stream's half in the split form, or the MFMA kernel
@@ -500,16 +500,16 @@ static int pred_decoder(PredCall &p) {
   case PRED_DEC_SPLIT:
     HIPCHK(c, hipStreamWaitEvent(st, c->ev_side, 0));
     hipLaunchKernelGGL(k_dec_actor<2>, agrid, dim3(DT), mind_dec_actor_lds_bytes(), st, x, d_actor_row, d_actor_scene, A, cmode, tgt_emb, out->reg,
-                       out->vel, c->decW, (float *)c->dec_h2.p);
+                       out->vel, c->W.dec, (float *)c->dec_h2.p);
     break;
   case PRED_DEC_ONE:
     hipLaunchKernelGGL(k_dec_actor<0>, agrid, dim3(DT), mind_dec_actor_lds_bytes(), st, x, d_actor_row, d_actor_scene, A, cmode, tgt_emb, out->reg,
-                       out->vel, c->decW, (float *)nullptr);
+                       out->vel, c->W.dec, (float *)nullptr);
     break;
   default: {
 #define DEC_MFMA(NPV)                                                                                                                     \
   hipLaunchKernelGGL(k_dec_actor_mfma<NPV>, mgrid, dim3(DM_T), mind_dec_actor_mfma_lds_bytes(), st, x, d_actor_row, d_actor_scene, A, cmode, \
-                     tgt_emb, out->reg, out->vel, c->decBW)
+                     tgt_emb, out->reg, out->vel, c->W.decB)
     if (ch.np == 6) DEC_MFMA(6);
     else if (ch.np == 3) DEC_MFMA(3);
     else DEC_MFMA(1);

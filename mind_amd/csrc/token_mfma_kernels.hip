@@ -19,11 +19,7 @@
                        // eight: 68 KB of the kernel's 97 KB = one four-wave workgroup per CU; two at a time = 46 KB = three workgroups
                        // per CU measured no faster on the cfg4 tree -- 234 vs 221 us per launch -- so one pass it is)
 
-struct TokWeightsM {   // A-fragment packings (pack_afrag) of the matrices TokWeights holds transposed
-  const float *Wv, *Wo, *W1a, *W1b, *W2a, *W2b;     // epilogue of layer L-1 (W1: output halves; W2: input halves)
-  const float *Ws, *Wt, *Wq, *Wkf;                  // prologue of layer L (Wkf: per head [8][ob 8][lane 64][4], see pack_wk_frag)
-  const float *Wpa, *Wpl;                           // init projections
-};
+#include "weight_tables.h"   // TokWeightsM
 
 typedef float tm_f4 __attribute__((ext_vector_type(4)));
 

@@ -196,15 +196,7 @@ class HipPredictor:
             pass
 
     def load_state_dict(self, sd):
-        descs = (_lib.TensorDesc * len(sd))()
-        keep = []
-        for i, (k, v) in enumerate(sd.items()):
-            a = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
-            a = np.ascontiguousarray(a, dtype=np.float32)
-            keep.append(a)
-            descs[i].name = k.encode()
-            descs[i].data = a.ctypes.data_as(C.POINTER(C.c_float))
-            descs[i].numel = a.size
+        descs, keep = _lib.tensor_descs(sd)
         rc = self.lib.mind_weights_load(self.ctx, descs, len(sd))
         _lib.check(self.lib, self.ctx, rc, "mind_weights_load")
 

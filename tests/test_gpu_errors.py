@@ -56,6 +56,22 @@ def test_predictor_argument_errors(hip_predictor, formula_sd):
     assert np.all(np.isfinite(out["reg"].cpu().numpy()))
 
 
+def test_failed_weight_load_leaves_the_loaded_weights_intact(hip_predictor, formula_sd):
+    """mind_weights_load packs into a local blob and touches the context only once every tensor was found: a state_dict that lacks one is
+    refused by name before any device work, and the weights loaded before it predict the same bits afterwards."""
+    pb = predictor_batch(3, 4, 1, seed=1)
+    out = hip_predictor.predict_numpy_batch(pb)
+    before = {k: out[k].cpu().numpy() for k in ("cls", "reg", "vel")}
+    name = "pred_scene.reg.6.bias"
+    bad = {k: v for k, v in formula_sd.items() if k != name}
+    assert len(bad) == len(formula_sd) - 1
+    with pytest.raises(_lib.MindError, match=name):
+        hip_predictor.load_state_dict(bad)
+    after = hip_predictor.predict_numpy_batch(pb)
+    for k, v in before.items():
+        assert np.array_equal(v, after[k].cpu().numpy()), k
+
+
 def test_context_creation_rejects_bad_device():
     import ctypes as C
     lib = _lib.load()
