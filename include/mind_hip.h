@@ -293,7 +293,8 @@ int mind_debug_trig(mind_ctx *ctx, const double *x, int n, double *out);
 
 /* Debug taps used by the parity tests only: run just the first n (0..6) fusion layers on the next
  * mind_predict_batch calls, and read internal device buffers ("x", "ST", "QK", "edge", "part",
- * "actor_feat", "tokpos") back to the host.  mind_debug_read returns the number of floats copied (or
+ * "actor_feat", "tokpos"; "pl_root": the root scene of the last mind_aime_plan as it lies on the device, laid out as RootLayout,
+ * mind_amd/csrc/aime_book.h, up to the buffer's capacity) back to the host.  mind_debug_read returns the number of floats copied (or
  * the buffer's size when host == NULL) or a negative error. */
 int mind_debug_set_layers(mind_ctx *ctx, int n);
 int64_t mind_debug_read(mind_ctx *ctx, const char *name, float *host, int64_t max_floats);
@@ -399,6 +400,16 @@ typedef struct {
 
 /* asynchronous on the context stream (read the outputs after mind_ctx_synchronize or a stream-ordered copy) */
 int mind_aime_world(mind_ctx *ctx, const mind_world_in *in, const mind_world_out *out);
+
+/* tests: the decision kernels of an AIME round on GIVEN inputs, with the launch shapes of the plan's round -- fused = 0: k_aime_select then
+ * k_aime_branch, fused = 1: k_aime_select_branch; by_value = 0: scene tables in device memory, 1: by value in the kernel arguments (at most 8
+ * scenes, all with the same agent count: MIND_EINVAL otherwise).  actor_off [n+1], cmp [n] (predicted step the branch-time test divides by,
+ * 0..59), scen_prob [n]: HOST.  cls [n,6], topo [A,6], ego_end [n,6,4], world [A,6,60,6] (only record 5, max-sigma, is read): DEVICE.
+ * prob_floor <= 0: 0.001.  Outputs (DEVICE): sel, sel_prob [n,6] as mind_world_out, hit [n,6,2]: bit t of the two 32-bit words of kept slot j is
+ * set when some agent's max-sigma at step t exceeds 9 x its max-sigma at step cmp (get_branch_time, scenario_tree.py:592-611).  Synchronous. */
+int mind_debug_aime_decide(mind_ctx *ctx, int n_scenes, const int32_t *actor_off, const int32_t *cmp, const float *cls, const float *scen_prob,
+                           const float *topo, const float *ego_end, const float *world, int lane_check, float dist_thres, float prob_floor,
+                           int fused, int by_value, float *sel, float *sel_prob, uint32_t *hit);
 
 /* Re-basing of the observation at a branch point for all branching nodes of a round: update_obser
  * (scenario_tree.py:467-567) = get_origin_rotation / normalisation into the AV and agent frames

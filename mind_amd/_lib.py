@@ -164,7 +164,7 @@ class PlannerOut(C.Structure):     # mind_planner_out
 
 EXPORTS = ["mind_ctx_create", "mind_ctx_destroy", "mind_last_error_string", "mind_ctx_synchronize",
            "mind_weights_load", "mind_predict_batch", "mind_last_fusion_stats", "mind_last_actor_stats", "mind_debug_actor_lw_plan", "mind_last_token_stats", "mind_last_token_stage_ms", "mind_debug_token_lw_plan", "mind_set_profiling",
-           "mind_ilqr_solve_trees", "mind_ilqr_contingency", "mind_ilqr_solve_fields", "mind_cost_eval", "mind_ilqr_score_trees", "mind_ilqr_gains", "mind_ilqr_policy_rollouts", "mind_lane_dist_field", "mind_aime_world", "mind_aime_rebase", "mind_debug_set_layers",
+           "mind_ilqr_solve_trees", "mind_ilqr_contingency", "mind_ilqr_solve_fields", "mind_cost_eval", "mind_ilqr_score_trees", "mind_ilqr_gains", "mind_ilqr_policy_rollouts", "mind_lane_dist_field", "mind_aime_world", "mind_aime_rebase", "mind_debug_aime_decide", "mind_debug_set_layers",
            "mind_debug_read", "mind_set_pair_precision", "mind_get_pair_precision", "mind_debug_pack_bfrag", "mind_debug_pack_conv_frag", "mind_debug_pack", "mind_debug_weight_image", "mind_debug_weight_bind", "mind_debug_pair_schedule", "mind_debug_predict_choice", "mind_debug_ilqr_plan", "mind_debug_aime_book", "mind_set_tuning", "mind_last_ilqr_stats", "mind_aime_plan", "mind_last_ilqr_profile", "mind_eval_traj_trees", "mind_last_ilqr_trace", "mind_ilqr_contingency_begin", "mind_ilqr_finish", "mind_fill_tracks", "mind_ilqr_contingency_begin_plan", "mind_debug_trig", "mind_aime_plan_begin", "mind_aime_plan_poll", "mind_aime_plan_finish", "mind_ctx_busy", "mind_ilqr_finish_plan",
            "mind_set_exchange", "mind_last_exchange_stats",
            "mind_loop_create", "mind_loop_destroy", "mind_loop_reset", "mind_loop_advance", "mind_loop_state", "mind_loop_last_plan", "mind_loop_export",
@@ -236,6 +236,8 @@ def load():
                                          C.c_double] + [C.POINTER(C.c_double)] * 4
     lib.mind_aime_world.argtypes = [C.c_void_p, C.POINTER(WorldIn), C.POINTER(WorldOut)]
     lib.mind_aime_rebase.argtypes = [C.c_void_p, C.POINTER(RebaseIn), C.POINTER(RebaseOut)]
+    lib.mind_debug_aime_decide.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_float), C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.mind_aime_plan.argtypes = [C.c_void_p, C.POINTER(AimePlanIn), C.POINTER(AimePlanOut)]
     lib.mind_aime_plan_begin.argtypes = [C.c_void_p, C.POINTER(AimePlanIn)]
     lib.mind_aime_plan_poll.argtypes = [C.c_void_p]

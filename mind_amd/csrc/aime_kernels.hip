@@ -69,20 +69,26 @@ __global__ __launch_bounds__(64) void k_aime_world(const AimeScene *__restrict__
     // ego end point of this mode (step `last`) and its distance to the target lane (min over segments of the
     // distance to the clamped projection, utils.py:486-513), the quantity prune_merge thresholds (:300-306)
     const float px = __shfl(wx, S.last, 64), py = __shfl(wy, S.last, 64), pc = __shfl(cv, S.last, 64);
+    // A zero-length segment (repeated lane point) projects to 0 / 0 = NaN: the reference's running `distance < min_distance` never takes
+    // such a segment, and never leaves it when it is the FIRST one (the whole distance is then NaN and the mode is kept).  The clamp below
+    // keeps a NaN (torch.clamp), fminf drops it, and lane 0 remembers whether segment 0 was one.
     float dmin = INFINITY;
+    bool first_nan = false;
     for (int sgi = t; sgi < n_lane - 1; sgi += 64) {
       const float ax = lane[2 * sgi], ay = lane[2 * sgi + 1];
       const float sx = lane[2 * sgi + 2] - ax, sy = lane[2 * sgi + 3] - ay;
       float tt = ((px - ax) * sx + (py - ay) * sy) / (sx * sx + sy * sy);
-      tt = fminf(fmaxf(tt, 0.f), 1.f);
+      tt = tt < 0.f ? 0.f : (tt > 1.f ? 1.f : tt);
       const float dx = (ax + tt * sx) - px, dy = (ay + tt * sy) - py;
-      dmin = fminf(dmin, sqrtf(dx * dx + dy * dy));
+      const float dd = sqrtf(dx * dx + dy * dy);
+      if (sgi == 0 && dd != dd) first_nan = true;
+      dmin = fminf(dmin, dd);
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) dmin = fminf(dmin, __shfl_xor(dmin, o, 64));
     if (t == 0) {
       float *o = ego_end + ((size_t)b * AIME_K + k) * 4;
-      o[0] = px; o[1] = py; o[2] = pc; o[3] = dmin;
+      o[0] = px; o[1] = py; o[2] = pc; o[3] = first_nan ? NAN : dmin;
     }
   }
   // ---- topology signature against the scene's ego (same mode, same step)

@@ -850,6 +850,75 @@ extern "C" int mind_aime_rebase(mind_ctx *c, const mind_rebase_in *in, const min
   return MIND_OK;
 }
 
+// tests: the decision kernels of a round on GIVEN inputs -- k_aime_select + k_aime_branch (fused = 0) or k_aime_select_branch (fused = 1), with
+// the launch shapes of PlanRun's round (aime_plan.hip), the scene tables in memory (by_value = 0) or by value in the kernel arguments (AimeSmall).
+extern "C" int mind_debug_aime_decide(mind_ctx *c, int n_scenes, const int32_t *actor_off, const int32_t *cmp, const float *cls, const float *scen_prob,
+                                      const float *topo, const float *ego_end, const float *world, int lane_check, float dist_thres,
+                                      float prob_floor, int fused, int by_value, float *sel, float *sel_prob, uint32_t *hit) {
+  if (!c || n_scenes <= 0 || !actor_off || !cmp || !cls || !scen_prob || !topo || !ego_end || !world || !sel || !sel_prob || !hit)
+    return fail(c, MIND_EINVAL, "mind_debug_aime_decide: bad argument");
+  const int B = n_scenes;
+  std::vector<AimeScene> hs(B);
+  for (int b = 0; b < B; ++b) {
+    AimeScene &S = hs[b];
+    memset(&S, 0, sizeof(S));
+    S.a0 = actor_off[b]; S.a1 = actor_off[b + 1]; S.last = AIME_T - 1; S.cmp = cmp[b];
+    S.r00 = S.r11 = 1.f;
+    if (S.a0 < 0 || S.a1 <= S.a0) return fail(c, MIND_EINVAL, "mind_debug_aime_decide: scene %d has no agents", b);
+    if (S.cmp < 0 || S.cmp >= AIME_T) return fail(c, MIND_EINVAL, "mind_debug_aime_decide: scene %d: compare step %d out of range", b, S.cmp);
+  }
+  AimeSmall sm;
+  memset(&sm, 0, sizeof(sm));
+  if (by_value) {
+    const int a = hs[0].a1 - hs[0].a0;
+    if (B > AIME_SMALL) return fail(c, MIND_EINVAL, "mind_debug_aime_decide: tables by value hold at most %d scenes (%d given)", AIME_SMALL, B);
+    for (int b = 0; b < B; ++b)
+      if (hs[b].a1 - hs[b].a0 != a || hs[b].a0 != b * a)
+        return fail(c, MIND_EINVAL, "mind_debug_aime_decide: tables by value need the same agent count in every scene");
+    memcpy(sm.s, hs.data(), (size_t)B * sizeof(AimeScene));
+    memcpy(sm.prob, scen_prob, (size_t)B * sizeof(float));
+    sm.n = B; sm.a = a;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  const size_t bS = ((size_t)B * sizeof(AimeScene) + 15) & ~(size_t)15;
+  std::vector<char> stage(bS + (size_t)B * sizeof(float), 0);
+  memcpy(stage.data(), hs.data(), (size_t)B * sizeof(AimeScene));
+  memcpy(stage.data() + bS, scen_prob, (size_t)B * sizeof(float));
+  if (by_value) {
+    // the tables in memory must not be what the kernels read: they hold other (in-range) contents -- ego-only scenes, another compare step,
+    // probability 0 -- so that a kernel that ignored its by-value tables would answer differently
+    for (int b = 0; b < B; ++b) {
+      AimeScene S = hs[b];
+      S.a1 = S.a0 + 1; S.cmp = (S.cmp + 29) % AIME_T;
+      memcpy(stage.data() + (size_t)b * sizeof(AimeScene), &S, sizeof(S));
+    }
+    memset(stage.data() + bS, 0, (size_t)B * sizeof(float));
+  }
+  char *dtab = nullptr;
+  HIPCHK(c, hipMalloc((void **)&dtab, stage.size()));
+  hipError_t e = hipMemcpyAsync(dtab, stage.data(), stage.size(), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    const AimeScene *t_sc = (const AimeScene *)dtab;
+    const float *t_prob = (const float *)(dtab + bS);
+    const float pf_ = prob_floor > 0.f ? prob_floor : 0.001f;
+    const int lc = lane_check ? 1 : 0;
+    if (fused) {
+      hipLaunchKernelGGL(k_aime_select_branch, dim3(B * AIME_K), dim3(64), 0, st, t_sc, cls, t_prob, topo, ego_end, lc, dist_thres, pf_, world, sel, sel_prob,
+                         hit, (float *)nullptr, (float *)nullptr, (unsigned *)nullptr, sm);
+    } else {
+      hipLaunchKernelGGL(k_aime_select, dim3(B), dim3(64), 0, st, t_sc, cls, t_prob, topo, ego_end, lc, dist_thres, sel, sel_prob, pf_, sm);
+      hipLaunchKernelGGL(k_aime_branch, dim3(B * AIME_K), dim3(64), 0, st, t_sc, (const float *)sel, world, hit, (const float *)sel_prob, (float *)nullptr,
+                         (float *)nullptr, (unsigned *)nullptr, sm);
+    }
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+  }
+  (void)hipFree(dtab);
+  HIPCHK(c, e);
+  return MIND_OK;
+}
+
 #include "aime_plan.hip"
 
 // ---- MINDPlanner.evaluate_traj_tree (planner.py:180-198) for all candidate trajectory trees of a plan: mean over a tree's nodes of
@@ -1054,6 +1123,7 @@ extern "C" int64_t mind_debug_read(mind_ctx *c, const char *name, float *host, i
   else if (k == "cmode") { src = c->cmode.p; n = (int64_t)c->last_B * 768; }
   else if (k == "tgt_emb") { src = c->tgt_emb.p; n = (int64_t)c->last_B * 128; }
   else if (k == "tgt_feat") { src = c->tgt_feat.p; n = (int64_t)c->last_B * 128; }
+  else if (k == "pl_root") { src = c->pl_root.p; n = (int64_t)(c->pl_root.cap / sizeof(float)); }    // the last plan's root scene (RootLayout, aime_book.h)
   else if (k == "il_spec") {        // the derivative speculator in the last tree-iLQR launch: {passes it was asked in, results the master took}
     if (!host) return 2;
     if (max_floats < 2) return MIND_EINVAL;

@@ -276,7 +276,16 @@ def get_distance_to_polyline(polyline, point):
     t = np.clip(t, 0, 1)
     closest = p1 + t[:, None] * seg
     d = closest - point
-    return np.sqrt((d * d).sum(-1)).min()
+    return _running_min(np.sqrt((d * d).sum(-1))[None])[0]
+
+
+def _running_min(dist):
+    """The reference's `distance < min_distance` loop over the segments (:505-511), per row of dist [m, n_seg]: a NaN distance (zero-length
+    segment: 0 / 0 in the projection) is never taken, and never left when it is the first one.  Without NaNs this is .min(axis=1)."""
+    first = dist[:, 0]
+    if first.dtype.kind == "f" and not np.isnan(first).any():
+        return np.fmin.reduce(dist, axis=1)
+    return np.where(np.isnan(first), dist.dtype.type(np.nan), np.fmin.reduce(dist, axis=1))
 
 
 def get_distances_to_polyline(polyline, points):
@@ -288,7 +297,7 @@ def get_distances_to_polyline(polyline, points):
     t = np.clip(t, 0, 1)
     closest = p1[None] + t[..., None] * seg[None]
     d = closest - points[:, None, :]
-    return np.sqrt((d * d).sum(-1)).min(axis=1)
+    return _running_min(np.sqrt((d * d).sum(-1)))
 
 
 # ---------------------------------------------------------------------------------------------

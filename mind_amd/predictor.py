@@ -609,6 +609,31 @@ class HipPredictor:
         _lib.check(self.lib, self.ctx, rc, "mind_aime_world")
         return out
 
+    def aime_decide(self, a_off, cmp, cls, scen_prob, topo, ego_end, world, dist_thres=None, prob_floor=0.001, fused=True, by_value=False):
+        """The decision kernels of an AIME round on given inputs (mind_debug_aime_decide; tests).  a_off [B+1], cmp [B] int, scen_prob [B]:
+        host; cls [B,6], topo [A,6], ego_end [B,6,4], world [A,6,60,6]: device float32 tensors or host arrays (uploaded here).  ``dist_thres``
+        switches the target-lane test on.  Returns host arrays sel [B,6] (kept mode or -1), sel_prob [B,6] float32, hit [B,6,2] uint32."""
+        dev = self.device
+        B, A = len(a_off) - 1, int(a_off[-1])
+        up = lambda x: x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(dev)
+        cls, topo, ego_end, world = up(cls), up(topo), up(ego_end), up(world)
+        for t_, n in ((cls, B * 6), (topo, A * 6), (ego_end, B * 24), (world, A * 6 * 60 * 6)):
+            assert t_.device == dev and t_.dtype == torch.float32 and t_.is_contiguous() and t_.numel() == n
+        ao = np.ascontiguousarray(a_off, np.int32)
+        cm = np.ascontiguousarray(cmp, np.int32).reshape(B)
+        sp = np.ascontiguousarray(scen_prob, np.float32).reshape(B)
+        sel = torch.empty(2, B, 6, device=dev)
+        hit = torch.zeros(B, 6, 2, dtype=torch.int32, device=dev)
+        ip = lambda x: x.ctypes.data_as(C.POINTER(C.c_int32))
+        rc = self.lib.mind_debug_aime_decide(self.ctx, B, ip(ao), ip(cm), C.c_void_p(cls.data_ptr()), sp.ctypes.data_as(C.POINTER(C.c_float)),
+                                             C.c_void_p(topo.data_ptr()), C.c_void_p(ego_end.data_ptr()), C.c_void_p(world.data_ptr()),
+                                             int(dist_thres is not None), float(dist_thres) if dist_thres is not None else 0.0, float(prob_floor),
+                                             int(bool(fused)), int(bool(by_value)), C.c_void_p(sel[0].data_ptr()), C.c_void_p(sel[1].data_ptr()),
+                                             C.c_void_p(hit.data_ptr()))
+        _lib.check(self.lib, self.ctx, rc, "mind_debug_aime_decide")
+        s = sel.cpu().numpy()
+        return s[0].astype(np.int64), s[1], hit.cpu().numpy().view(np.uint32)
+
     def aime_rebase(self, pos, ang, vel, types, lane_ctrs, lane_vecs, target_lane, target_lane_info, pad=None,
                     time_ahead=5.0, min_vel=0.5, dev_src=None):
         """update_obser for S child scenes on the device (mind_aime_rebase).  pos [S,a,50,2], ang [S,a,50], vel [S,a,50,2]
