@@ -19,44 +19,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-#include "weight_tables.h"   // u32, VT_*, TokWeights
-
-typedef u32 u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ u32 pk_bf16(float a, float b) {   // {bf16(a) in bits 0..15, bf16(b) in bits 16..31}, RNE
-  f32x2_t v = {a, b};
-  return __builtin_bit_cast(u32, __builtin_convertvector(v, bf16x2_t));
-}
-__device__ __forceinline__ float bf_lo_f32(u32 pk) { return __builtin_bit_cast(float, pk << 16); }
-__device__ __forceinline__ float bf_hi_f32(u32 pk) { return __builtin_bit_cast(float, pk & 0xffff0000u); }
+#include "pair_common.h"   // types, lane geometry, reductions, ln_pairs, sw_pos, the phases shared with the bf16 pair kernels
 
 #define D_ 128
-#define PART_STRIDE 1040  // 8 (m) + 8 (l) + 8*128 (sum p*mem)
-
-struct PairJob {
-  long long edge_base;  // first pair index of the scene's edge tensor (pairs, not floats); pair (i, j) lives at edge_base + j * N + i
-  int N;                // tokens in scene (a + l + 1)
-  int j;                // column (query token)
-  int t0, t1;           // i-tile range [t0, t1), 32 rows each
-  int tok_base;         // first token of the scene in the flat token arrays
-  int slot;             // partial-result slot
-  int flags;            // bit0: column is an actor or the cls token
-  int scene;
-  long long edge_base_t;  // the same for the tile-native layout of k_pair_t (pair_tile_kernels.hip): columns padded to whole 16-row tiles
-};
-
-// Eight waves (two per SIMD) share the two weight matrices: while one wave of a SIMD is in its LayerNorm / softmax /
-// staging phases the other one keeps the MFMA busy.  Everything per-wave is sized so that the workgroup fits
-// the 160 KB of LDS: the staging buffer holds a QUARTER tile (16 pairs x 32 features).
-#define PAIR_WAVES 8
-#define PAIR_THREADS (PAIR_WAVES * 64)
-#define STAGE_FLOATS 512              // 16 rows x 8 chunks of 16 bytes
 #define LDS_WAE 0
 #define LDS_WAP 16384
 #define LDS_STAGE 32768                               // 8 waves x 512 floats
@@ -67,71 +32,6 @@ struct PairJob {
 #define LDS_TOTAL (LDS_RT + 1024)                     // 40896 floats = 163584 bytes (<= 163840)
 
 #define LDS_FENCE() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-#define SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
-// Hide a value's provenance from the optimiser: address arithmetic derived from it is recomputed
-// where it is used (cheap VALU) instead of being hoisted out of the tile loop as hundreds of
-// loop-invariant VGPRs (LDS offsets > 64 KB do not fit the DS immediate field).
-#define OPAQUE(x) asm volatile("" : "+v"(x))
-
-// Lane geometry (16 pairs per tile, v_mfma_f32_16x16x4_f32):
-//   p = lane & 15 : pair (row i = i0 + p of column j),  q = lane >> 4 : feature quarter
-//   a lane holds 8 x f32x4: chunk blk (0..7) = features 16*blk + 4*q + (0..3)  == the MFMA C/D layout
-//   (col = lane&15, row = 4*(lane>>4) + reg) of output block blk, and == the B operand of k-group
-//   blk (k-slot (s, q) <-> feature 16*(s>>2) + 4*q + (s&3)).
-typedef f32x4 frag8[8];
-
-__device__ __forceinline__ float red_quad(float v) {  // sum over the 4 lanes of a pair
-  v += __shfl_xor(v, 16, 64);
-  v += __shfl_xor(v, 32, 64);
-  return v;
-}
-__device__ __forceinline__ float red_max16(float v) {
-  v = fmaxf(v, __shfl_xor(v, 8, 64));
-  v = fmaxf(v, __shfl_xor(v, 4, 64));
-  v = fmaxf(v, __shfl_xor(v, 2, 64));
-  v = fmaxf(v, __shfl_xor(v, 1, 64));
-  return v;
-}
-__device__ __forceinline__ float red_sum16(float v) {
-  v += __shfl_xor(v, 8, 64);
-  v += __shfl_xor(v, 4, 64);
-  v += __shfl_xor(v, 2, 64);
-  v += __shfl_xor(v, 1, 64);
-  return v;
-}
-
-// LayerNorm over the 128 features of each pair (two-pass, biased variance, eps 1e-5).
-__device__ __forceinline__ void ln_pairs(frag8 &a, const float *vtq, int off_g, int off_b, bool relu) {
-  float s = 0.f;
-#pragma unroll
-  for (int b = 0; b < 8; ++b)
-#pragma unroll
-    for (int w = 0; w < 4; ++w) s += a[b][w];
-  s = red_quad(s);
-  const float mean = s * (1.0f / 128.0f);
-  float v = 0.f;
-#pragma unroll
-  for (int b = 0; b < 8; ++b)
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      const float d = a[b][w] - mean;
-      v = fmaf(d, d, v);
-    }
-  v = red_quad(v);
-  const float rstd = 1.0f / sqrtf(v * (1.0f / 128.0f) + 1e-5f);
-#pragma unroll
-  for (int b = 0; b < 8; ++b) {
-    const f32x4 gm = *(const f32x4 *)(vtq + off_g + 16 * b);
-    const f32x4 bt = *(const f32x4 *)(vtq + off_b + 16 * b);
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      float y = (a[b][w] - mean) * rstd * gm[w] + bt[w];
-      if (relu) y = fmaxf(y, 0.f);
-      a[b][w] = y;
-    }
-    if (b & 1) SCHED_FENCE();
-  }
-}
 
 // acc[ob] += W_frag[ob] x B, B k-group s4 = bsrc[s4].  wa: LDS, packed [ob 8][s4 8][lane 64][4].
 // 32 steps of 8 MFMAs (two output blocks x 4 k-steps, alternating accumulators so that dependent
@@ -165,24 +65,10 @@ __device__ __forceinline__ void gemm128(frag8 &acc, const float *wa, const frag8
   }
 }
 
-// swizzled float offset of 16-byte chunk c (0..7) in a 128-byte staging row r (0..15): the 16 lanes of a
-// ds_read_b128 pass (rows 0..15, one chunk each) and of a ds_write_b128 pass (2 rows x 8 chunks) hit 16
-// distinct 16-byte bank groups
-__device__ __forceinline__ int sw_pos(int r, int c) { return (r * 8 + (c ^ ((r >> 1) & 7))) * 4; }
-
 // MODE 0: layer 0, edge built in-kernel from the relative pose encoding (no edge read)
 // MODE 1: layers 1..5, edge read from HBM
 // update_mode 0: update every edge; 1: update only flagged columns; 2: run only flagged columns,
 // no edge update (last layer).
-#ifdef MIND_PAIR_TRACE
-#define PT_DECL long long pt_[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; long long pt_t = clock64();
-#define PT_DRAIN() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-#define PT(i) do { long long n_ = clock64(); pt_[i] += n_ - pt_t; pt_t = n_; } while (0)
-#else
-#define PT_DECL
-#define PT_DRAIN()
-#define PT(i)
-#endif
 
 template <int MODE>
 __global__ __launch_bounds__(PAIR_THREADS, 1) void k_pair(const PairJob *__restrict__ jobs, int n_jobs,
@@ -199,28 +85,7 @@ __global__ __launch_bounds__(PAIR_THREADS, 1) void k_pair(const PairJob *__restr
   const int p = lane & 15;
   const int q = lane >> 4;
 
-  // ---- stage weights / tables (once per workgroup) ----
-  {
-    // all loads of a matrix in flight before the first LDS write (the load -> wait -> write loop serialised 16 L2 round trips)
-    constexpr int PER = 4096 / PAIR_THREADS;
-    f32x4 te[PER], tp[PER];
-#pragma unroll
-    for (int k = 0; k < PER; ++k) te[k] = ((const f32x4 *)WAe)[tid + k * PAIR_THREADS];
-    if (update_mode != 2) {
-#pragma unroll
-      for (int k = 0; k < PER; ++k) tp[k] = ((const f32x4 *)WAp)[tid + k * PAIR_THREADS];
-    }
-#pragma unroll
-    for (int k = 0; k < PER; ++k) ((f32x4 *)(lds + LDS_WAE))[tid + k * PAIR_THREADS] = te[k];
-    if (update_mode != 2) {
-#pragma unroll
-      for (int k = 0; k < PER; ++k) ((f32x4 *)(lds + LDS_WAP))[tid + k * PAIR_THREADS] = tp[k];
-    }
-  }
-  for (int i = tid; i < VT_SIZE; i += PAIR_THREADS) lds[LDS_VT + i] = vtab[i];
-  if (MODE == 0)
-    for (int i = tid; i < 1024; i += PAIR_THREADS) lds[LDS_RT + i] = rtab[i];
-  __syncthreads();
+  pair_stage_tables<4096 / PAIR_THREADS, MODE>(lds, tid, WAe, WAp, vtab, rtab, update_mode, LDS_WAE, LDS_WAP, LDS_VT, LDS_RT);
 
   float *stage = lds + LDS_STAGE + wave * STAGE_FLOATS;
   float *ptab = lds + LDS_PTAB + wave * 128;
@@ -300,68 +165,7 @@ __global__ __launch_bounds__(PAIR_THREADS, 1) void k_pair(const PairJob *__restr
         }
       } else {
         // ---- layer 0: edge0 = ReLU(LN(W_r rpe + b_r)), zeros on the cls row / column (network.py:326-330)
-        float r5[5];
-        const bool is_cls = (ic == N - 1) || (j == N - 1);
-        if (rpe_ptrs != nullptr) {
-          const float *rp = rpe_ptrs[J.scene];
-          const int n1 = N - 1;
-          const size_t o = is_cls ? 0 : ((size_t)ic * n1 + j);
-#pragma unroll
-          for (int k = 0; k < 5; ++k) r5[k] = rp[(size_t)k * n1 * n1 + o];
-        } else {
-          const f32x4 ti = *(const f32x4 *)(tokpos + (size_t)(J.tok_base + ic) * 4);
-          const float dx = pj[0] - ti[0], dy = pj[1] - ti[1];
-          const float dist = sqrtf(dx * dx + dy * dy);
-          const float nj = sqrtf(pj[2] * pj[2] + pj[3] * pj[3]);
-          const float ni = sqrtf(ti[2] * ti[2] + ti[3] * ti[3]);
-          const float den1 = nj * ni + 1e-10f;
-          const float den2 = nj * dist + 1e-10f;
-          r5[0] = (pj[2] * ti[2] + pj[3] * ti[3]) / den1;
-          r5[1] = (pj[2] * ti[3] - pj[3] * ti[2]) / den1;
-          r5[2] = (pj[2] * dx + pj[3] * dy) / den2;
-          r5[3] = (pj[2] * dy - pj[3] * dx) / den2;
-          r5[4] = dist * 2.0f / 100.0f;
-        }
-        const float *rt = lds + LDS_RT + lq * 32;
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-          const float *c = rt + b * 128;
-          f32x4 acc = *(const f32x4 *)(c + 20);  // bias
-#pragma unroll
-          for (int k = 0; k < 5; ++k) {
-            const f32x4 wk = *(const f32x4 *)(c + 4 * k);
-#pragma unroll
-            for (int w = 0; w < 4; ++w) acc[w] = fmaf(wk[w], r5[k], acc[w]);
-          }
-          ef[b] = acc;
-        }
-        {
-          float s = 0.f;
-#pragma unroll
-          for (int b = 0; b < 8; ++b)
-#pragma unroll
-            for (int w = 0; w < 4; ++w) s += ef[b][w];
-          s = red_quad(s);
-          const float mean = s * (1.0f / 128.0f);
-          float v = 0.f;
-#pragma unroll
-          for (int b = 0; b < 8; ++b)
-#pragma unroll
-            for (int w = 0; w < 4; ++w) { const float d = ef[b][w] - mean; v = fmaf(d, d, v); }
-          v = red_quad(v);
-          const float rstd = 1.0f / sqrtf(v * (1.0f / 128.0f) + 1e-5f);
-#pragma unroll
-          for (int b = 0; b < 8; ++b) {
-            const float *c = rt + b * 128;
-            const f32x4 gm = *(const f32x4 *)(c + 24);
-            const f32x4 bt = *(const f32x4 *)(c + 28);
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-              const float y = fmaxf((ef[b][w] - mean) * rstd * gm[w] + bt[w], 0.f);
-              ef[b][w] = is_cls ? 0.f : y;
-            }
-          }
-        }
+        PAIR_EDGE0(ef, lds + LDS_RT + lq * 32, tokpos, rpe_ptrs, pj, J.scene, J.tok_base, j, N, ic)
       }
 
       PT(0);

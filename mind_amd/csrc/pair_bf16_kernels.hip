@@ -2,7 +2,8 @@
 //
 // Reference semantics: planners/mind/networks/network.py:165-232 (same math as k_pair in fusion_kernels.hip, whose
 // algebraic folds -- rank-decomposed proj_memory, K projection folded into the query, V projection folded out of the
-// sum -- are kept).  What changes is the arithmetic of every contraction:
+// sum -- are kept; the LDS layout LB_*, split_frag, gemm_bf, ln_nomean and the phases shared with the tile-native kernels live in
+// pair_common.h).  What changes is the arithmetic of every contraction:
 //
 //   NP == 3 ("bf16x3"): both operands of a product are split into bf16 hi + lo parts (x = hi + lo + O(2^-17 |x|)) and
 //       the three significant partial products hi.hi + hi.lo + lo.hi are accumulated in fp32 on the bf16 MFMA:
@@ -28,116 +29,16 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pair_common.h"   // LDS layout LB_*, MFMA_BF, split_frag, gemm_bf, ln_nomean, the phases shared with the other pair kernels
+
 // tuning switches (A/B-measured on the MI355X): where the next tile's edge rows and this tile's folded query
 // are requested
 #ifndef PBF_PREFETCH_TOP
 #define PBF_PREFETCH_TOP 0      // 1: next tile's edge rows requested right after this tile's rows left the load registers (measured: no difference)
 #endif
-// the staging buffers are private to a wave and one wave's DS instructions execute in order: no s_waitcnt between the passes
-// over a buffer, only a compiler barrier (draining the LDS queue there measured no difference: DESIGN 4)
-#define PBF_FENCE() asm volatile("" ::: "memory")
 #ifndef PBF_QK_FIRST
 #define PBF_QK_FIRST 1
 #endif
-
-#define LB_WE 0                                       // [part 2][ob 8][g 4][lane 64][4 dwords] = 16384 dwords (64 KB)
-#define LB_WP 16384
-#define LB_STAGE 32768                                // 8 waves x 512 dwords
-#define LB_PTAB (LB_STAGE + PAIR_WAVES * STAGE_FLOATS)   // 8 waves x 128: p[head 8][pair 16]
-#define LB_SVEC (LB_PTAB + PAIR_WAVES * 128)          // 8 waves x 128: S[j]
-#define LB_VT (LB_SVEC + PAIR_WAVES * 128)            // 896
-#define LB_RT (LB_VT + VT_SIZE)                       // 1024 (layer 0)
-#define LB_TOTAL (LB_RT + 1024)                       // 40832 dwords = 163328 bytes
-
-#define MFMA_BF(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0)
-
-// split the lane's 8 chunks into the four k-groups' B operands: hi[g], lo[g] (lo only for NP == 3)
-template <int NP>
-__device__ __forceinline__ void split_frag(const frag8 &x, u32x4 (&hi)[4], u32x4 (&lo)[4]) {
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      const f32x4 v = x[2 * g + c];
-      const u32 h0 = pk_bf16(v[0], v[1]), h1 = pk_bf16(v[2], v[3]);
-      hi[g][2 * c] = h0;
-      hi[g][2 * c + 1] = h1;
-      if (NP == 3) {
-        lo[g][2 * c] = pk_bf16(v[0] - bf_lo_f32(h0), v[1] - bf_hi_f32(h0));
-        lo[g][2 * c + 1] = pk_bf16(v[2] - bf_lo_f32(h1), v[3] - bf_hi_f32(h1));
-      }
-    }
-    SCHED_FENCE();
-  }
-}
-
-// acc[ob] += sum_g W[ob][g] . B[g]   (W = hi + lo fragments in LDS at `wa`: [part][ob][g][lane][4 dwords]).
-// Eight steps (g, output-block quad): per step 4 x NP MFMAs that rotate over four accumulators (dependent MFMAs are
-// four issues apart); the hi fragments are double-buffered in registers, the lo fragments are reloaded for the next
-// step as soon as the lo.hi products of this one are issued.
-template <int NP>
-__device__ __forceinline__ void gemm_bf(frag8 &acc, const u32 *wa, const u32x4 (&bhi)[4], const u32x4 (&blo)[4], int lane) {
-  int lo_ = lane * 4;
-  OPAQUE(lo_);
-  const u32 *wl = wa + lo_;
-  u32x4 ah[2][4], al[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    ah[0][k] = *(const u32x4 *)(wl + ((k * 4 + 0) * 256));
-    if (NP == 3) al[k] = *(const u32x4 *)(wl + 8192 + ((k * 4 + 0) * 256));
-  }
-#pragma unroll
-  for (int st = 0; st < 8; ++st) {
-    const int g = st >> 1, o0 = (st & 1) * 4, cur = st & 1, nxt = cur ^ 1;
-    const int gn = (st + 1) >> 1, on = ((st + 1) & 1) * 4;
-#ifdef MIND_GEMM_NO_RELOAD      // (timing-only build of tools/micro/pair_bench: the weight fragments of the first step serve all eight)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { ah[nxt][k] = ah[cur][k]; asm volatile("" : "+v"(ah[nxt][k])); }
-#else
-    if (st < 7) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) ah[nxt][k] = *(const u32x4 *)(wl + (((on + k) * 4 + gn) * 256));
-    }
-#endif
-    if (NP == 3) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) acc[o0 + k] = MFMA_BF(al[k], bhi[g], acc[o0 + k]);
-      SCHED_FENCE();
-#ifndef MIND_GEMM_NO_RELOAD
-      if (st < 7) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) al[k] = *(const u32x4 *)(wl + 8192 + (((on + k) * 4 + gn) * 256));
-      }
-#endif
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) acc[o0 + k] = MFMA_BF(ah[cur][k], bhi[g], acc[o0 + k]);
-    if (NP == 3) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) acc[o0 + k] = MFMA_BF(ah[cur][k], blo[g], acc[o0 + k]);
-    }
-    SCHED_FENCE();
-  }
-}
-
-// LayerNorm of a shift-free input (the mean was folded into the weights): y = x / sqrt(mean(x^2) + eps) * g + b
-__device__ __forceinline__ void ln_nomean(frag8 &a, const float *vtq, int off_g, int off_b) {
-  float v = 0.f;
-#pragma unroll
-  for (int b = 0; b < 8; ++b)
-#pragma unroll
-    for (int w = 0; w < 4; ++w) v = fmaf(a[b][w], a[b][w], v);
-  v = red_quad(v);
-  const float rstd = 1.0f / sqrtf(v * (1.0f / 128.0f) + 1e-5f);
-#pragma unroll
-  for (int b = 0; b < 8; ++b) {
-    const f32x4 gm = *(const f32x4 *)(vtq + off_g + 16 * b);
-    const f32x4 bt = *(const f32x4 *)(vtq + off_b + 16 * b);
-#pragma unroll
-    for (int w = 0; w < 4; ++w) a[b][w] = fmaxf(fmaf(a[b][w] * rstd, gm[w], bt[w]), 0.f);
-    if (b & 1) SCHED_FENCE();
-  }
-}
 
 // MODE 0: layer 0, edge built in-kernel from the relative pose encoding; MODE 1: layers 1..5, edge read from HBM.
 // update_mode as in k_pair.
@@ -155,44 +56,8 @@ __global__ __launch_bounds__(PAIR_THREADS, 1) void k_pair_bf(const PairJob *__re
   const int p = lane & 15;
   const int q = lane >> 4;
 
-  // ---- stage weights / tables (once per workgroup); the lo halves are only needed by the split arithmetic.  All loads of
-  //      a matrix are requested before the first LDS write (a load -> wait -> write loop costs 16 L2 round trips per
-  //      workgroup, a quarter of a small launch)
-  {
-    constexpr int PER = (NP == 3 ? 4096 : 2048) / PAIR_THREADS;
-    f32x4 te[PER], tp[PER];
-#pragma unroll
-    for (int k = 0; k < PER; ++k) te[k] = ((const f32x4 *)WBe)[tid + k * PAIR_THREADS];
-    if (update_mode != 2) {
-#pragma unroll
-      for (int k = 0; k < PER; ++k) tp[k] = ((const f32x4 *)WBp)[tid + k * PAIR_THREADS];
-    }
-#pragma unroll
-    for (int k = 0; k < PER; ++k) ((f32x4 *)(lds + LB_WE))[tid + k * PAIR_THREADS] = te[k];
-    if (update_mode != 2) {
-#pragma unroll
-      for (int k = 0; k < PER; ++k) ((f32x4 *)(lds + LB_WP))[tid + k * PAIR_THREADS] = tp[k];
-    }
-  }
-  for (int i = tid; i < VT_SIZE; i += PAIR_THREADS) lds[LB_VT + i] = vtab[i];
-  if (MODE == 0)
-    for (int i = tid; i < 1024; i += PAIR_THREADS) lds[LB_RT + i] = rtab[i];
-  __syncthreads();
-
-  float *stage = lds + LB_STAGE + wave * STAGE_FLOATS;
-  float *ptab = lds + LB_PTAB + wave * 128;
-  float *svec = lds + LB_SVEC + wave * 128;
-  const float *vt = lds + LB_VT;
-  const u32 *wbe = (const u32 *)(lds + LB_WE);
-  const u32 *wbp = (const u32 *)(lds + LB_WP);
-  // transposed staging image of a 32-feature quarter of the memory tile: [feature 32][pair 16] dwords (hi | lo << 16),
-  // the four pair-quads of a row XOR-swizzled so that both the ds_write_b32 pass and the ds_read_b128 pass are conflict-free
-  //   write: lane (p, q) owns features 16 b2 + 4 q + r (quad code of those rows = q)
-  //   read : lane (n, q') fetches pairs 4 q' .. 4 q' + 3 of feature 16 b2 + n
-  const int cq_w = (0x1320 >> (4 * q)) & 3;                 // c = [0, 2, 3, 1]
-  const int cq_r = (0x1320 >> (4 * ((p >> 2) & 3))) & 3;
-  const int tw_base = (4 * q) * 16 + (((p >> 2) ^ cq_w) * 4) + (p & 3);
-  const int tr_base = p * 16 + ((q ^ cq_r) * 4);
+  pair_stage_tables<(NP == 3 ? 4096 : 2048) / PAIR_THREADS, MODE>(lds, tid, WBe, WBp, vtab, rtab, update_mode, LB_WE, LB_WP, LB_VT, LB_RT);      // (the lo halves are only needed by the split arithmetic)
+  PAIR_WAVE_LDS(lds, wave, p, q)
   PT_DECL
 
   for (int job = wave * gridDim.x + blockIdx.x; job < n_jobs; job += gridDim.x * PAIR_WAVES) {
@@ -264,68 +129,7 @@ __global__ __launch_bounds__(PAIR_THREADS, 1) void k_pair_bf(const PairJob *__re
         if (PBF_PREFETCH_TOP && tile + 1 < J.t1) { PBF_LOAD_RAW(i0 + 16, ll) }
       } else {
         // ---- layer 0: edge0 = ReLU(LN(W_r rpe + b_r)), zeros on the cls row / column (network.py:326-330)
-        float r5[5];
-        const bool is_cls = (ic == N - 1) || (j == N - 1);
-        if (rpe_ptrs != nullptr) {
-          const float *rp = rpe_ptrs[J.scene];
-          const int n1 = N - 1;
-          const size_t o = is_cls ? 0 : ((size_t)ic * n1 + j);
-#pragma unroll
-          for (int k = 0; k < 5; ++k) r5[k] = rp[(size_t)k * n1 * n1 + o];
-        } else {
-          const f32x4 ti = *(const f32x4 *)(tokpos + (size_t)(J.tok_base + ic) * 4);
-          const float dx = pj[0] - ti[0], dy = pj[1] - ti[1];
-          const float dist = sqrtf(dx * dx + dy * dy);
-          const float nj = sqrtf(pj[2] * pj[2] + pj[3] * pj[3]);
-          const float ni = sqrtf(ti[2] * ti[2] + ti[3] * ti[3]);
-          const float den1 = nj * ni + 1e-10f;
-          const float den2 = nj * dist + 1e-10f;
-          r5[0] = (pj[2] * ti[2] + pj[3] * ti[3]) / den1;
-          r5[1] = (pj[2] * ti[3] - pj[3] * ti[2]) / den1;
-          r5[2] = (pj[2] * dx + pj[3] * dy) / den2;
-          r5[3] = (pj[2] * dy - pj[3] * dx) / den2;
-          r5[4] = dist * 2.0f / 100.0f;
-        }
-        const float *rt = lds + LB_RT + lq * 32;
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-          const float *c = rt + b * 128;
-          f32x4 acc = *(const f32x4 *)(c + 20);  // bias
-#pragma unroll
-          for (int k = 0; k < 5; ++k) {
-            const f32x4 wk = *(const f32x4 *)(c + 4 * k);
-#pragma unroll
-            for (int w = 0; w < 4; ++w) acc[w] = fmaf(wk[w], r5[k], acc[w]);
-          }
-          ef[b] = acc;
-        }
-        {
-          float s = 0.f;
-#pragma unroll
-          for (int b = 0; b < 8; ++b)
-#pragma unroll
-            for (int w = 0; w < 4; ++w) s += ef[b][w];
-          s = red_quad(s);
-          const float mean = s * (1.0f / 128.0f);
-          float v = 0.f;
-#pragma unroll
-          for (int b = 0; b < 8; ++b)
-#pragma unroll
-            for (int w = 0; w < 4; ++w) { const float d = ef[b][w] - mean; v = fmaf(d, d, v); }
-          v = red_quad(v);
-          const float rstd = 1.0f / sqrtf(v * (1.0f / 128.0f) + 1e-5f);
-#pragma unroll
-          for (int b = 0; b < 8; ++b) {
-            const float *c = rt + b * 128;
-            const f32x4 gm = *(const f32x4 *)(c + 24);
-            const f32x4 bt = *(const f32x4 *)(c + 28);
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-              const float y = fmaxf((ef[b][w] - mean) * rstd * gm[w] + bt[w], 0.f);
-              ef[b][w] = is_cls ? 0.f : y;
-            }
-          }
-        }
+        PAIR_EDGE0(ef, lds + LB_RT + lq * 32, tokpos, rpe_ptrs, pj, J.scene, J.tok_base, j, N, ic)
       }
 
       // ---- memory = ReLU(LN(W_e e + S[j] + T[i]))   (network.py:197-199, rank-decomposed, mean folded away)
@@ -420,33 +224,7 @@ __global__ __launch_bounds__(PAIR_THREADS, 1) void k_pair_bf(const PairJob *__re
       }
       if (NP == 3) sa += sb + sc;       // lane (p, q): rows 4q..4q+3 = heads 4q..4q+3 of pair p (q < 2)
       // ---- online softmax over i: lanes of quarter q own heads 4q..4q+3
-      float pr[4], scl[4];
-      bool grew = false;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float sv = valid ? sa[r] : -INFINITY;
-        const float mx = red_max16(sv);
-        const float m_new = fmaxf(m_run[r], mx);
-        grew = grew || (m_new != m_run[r]);
-        scl[r] = __expf(m_run[r] - m_new);
-        pr[r] = valid ? __expf(sv - m_new) : 0.f;
-        l_part[r] = l_part[r] * scl[r] + pr[r];
-        m_run[r] = m_new;
-      }
-      PBF_FENCE();
-      if (lq < 2) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) ptab[(4 * lq + r) * 16 + lp] = pr[r];
-      }
-      // rescale the running sum p.mem of this lane's heads (rows 4q..4q+3 of the accumulator blocks): skipped when no
-      // running maximum of the wave moved (wave-uniform branch)
-      if (__any(grew)) {
-#pragma unroll
-        for (int b = 0; b < 8; ++b)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) mbar[b][r] *= scl[r];
-      }
-      PBF_FENCE();
+      pair_softmax_step(sa, valid, lq, lp, m_run, l_part, mbar, ptab);
       // A operand: p[head = lane & 15][pairs 4q .. 4q+3], each duplicated over the (hi, lo) parts of the memory rows
       PT(5);
       u32x4 pah, pal;
@@ -465,23 +243,10 @@ __global__ __launch_bounds__(PAIR_THREADS, 1) void k_pair_bf(const PairJob *__re
       }
       // ---- mbar[head][f] += sum_pairs p[head][pair] * mem[pair][f] on the MFMA, the memory tile transposed through the
       //      staging buffer one 32-feature quarter (= k-group g) at a time as (hi | lo << 16) dwords
-      const u32 *stu = (const u32 *)stage;
-      u32 *stw = (u32 *)stage;
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
-#pragma unroll
-        for (int b2 = 0; b2 < 2; ++b2)
-#pragma unroll
-          for (int rr = 0; rr < 2; ++rr) {
-            const u32 X = mhi[g][2 * b2 + rr];
-            const u32 Y = NP == 3 ? mlo[g][2 * b2 + rr] : 0u;
-            stw[tw_base + (16 * b2 + 2 * rr) * 16] = (X & 0xffffu) | (Y << 16);
-            stw[tw_base + (16 * b2 + 2 * rr + 1) * 16] = (X >> 16) | (Y & 0xffff0000u);
-          }
-        PBF_FENCE();
-        const u32x4 f0 = *(const u32x4 *)(stu + tr_base);
-        const u32x4 f1 = *(const u32x4 *)(stu + tr_base + 256);
-        PBF_FENCE();
+        u32x4 f0, f1;
+        pair_stage_quarter<NP == 3>(stq_w, stq_r, mhi[g], mlo[g], f0, f1);
         mbar[2 * g] = MFMA_BF(pah, f0, mbar[2 * g]);
         mbar[2 * g + 1] = MFMA_BF(pah, f1, mbar[2 * g + 1]);
         if (NP == 3) {
@@ -494,17 +259,7 @@ __global__ __launch_bounds__(PAIR_THREADS, 1) void k_pair_bf(const PairJob *__re
 
     // ---- column partial: m[8], l[8], mbar[8][128]
     float *po = part + (size_t)J.slot * PART_STRIDE;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float l = red_sum16(l_part[r]);
-      if (p == 0 && q < 2) { po[4 * q + r] = m_run[r]; po[8 + 4 * q + r] = l; }
-    }
-    if (q < 2) {
-#pragma unroll
-      for (int b = 0; b < 8; ++b)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) po[16 + (4 * q + r) * 128 + 16 * b + p] = mbar[b][r];
-    }
+    PAIR_STORE_PARTIAL_DIRECT(po, m_run, l_part, mbar, p, q)
   }
 #ifdef MIND_PAIR_TRACE
   if (blockIdx.x == 0 && tid == 0)

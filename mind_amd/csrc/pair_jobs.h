@@ -1,4 +1,4 @@
-// Host side of the pair kernels' job lists (k_pair, k_pair_bf, k_pair_t): which wave runs which column job.
+// Host side of the pair kernels' job lists (k_pair, k_pair_bf, k_pair_t, k_pair_t6): which wave runs which column job.
 //
 // The kernels walk the list with a fixed rule -- wave w of workgroup b runs jobs[w * grid + b + k * 8 * grid], k = 0, 1, ... -- so the ORDER of the
 // list is the schedule.  pair_jobs_deal() orders it such that

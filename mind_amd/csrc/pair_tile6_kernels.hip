@@ -2,8 +2,9 @@
 //
 // Reference semantics: planners/mind/networks/network.py:165-232 (RelaFusionLayer), :259-268 (six layers, the last one
 // without an edge update).  Data movement, folds, job walk and register layouts are k_pair_t's (pair_tile_kernels.hip:
-// tile-native edge tensor, one wave = one column job, prefetch one tile ahead across job boundaries).  The arithmetic of
-// every contraction is the reference's fp32 class instead of the two-way split's 16 bits:
+// tile-native edge tensor, one wave = one column job, prefetch one tile ahead across job boundaries); the LDS layout and the phases
+// the pair kernels run alike come from pair_common.h.  The arithmetic of every contraction is the reference's fp32 class instead of the
+// two-way split's 16 bits:
 //
 //   * both operands of a product are split THREE ways into bf16 parts, x = hi + mid + lo.  With round-to-nearest at every
 //     step the split of an fp32 number is EXACT (8 + 8 + 8 significand bits; the remainder after hi has at most 16 bits and
@@ -31,6 +32,8 @@
 //     p_hi.(m_hi + m_mid), p_mid.(m_hi + m_mid) and p_hi.m_lo + p_lo.m_hi.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "pair_common.h"   // LDS layout LB_*, MFMA_BF, ln_nomean, the phases shared with the other pair kernels
 
 #ifndef P6_RESID_RELOAD
 // 1: the next tile's chunk is requested behind the FIRST GEMM (a whole attention phase + GEMM ahead instead of LN_e + store) and the residual
@@ -174,41 +177,13 @@ __global__ __launch_bounds__(PAIR_THREADS, 1) void k_pair_t6(const PairJob *__re
   const int p = lane & 15;
   const int q = lane >> 4;
 
-  // ---- stage the hi + mid weight fragments / tables (once per workgroup): all loads of a matrix in flight before the first LDS write
-  {
-    constexpr int PER = 4096 / PAIR_THREADS;
-    f32x4 te[PER], tp[PER];
-#pragma unroll
-    for (int k = 0; k < PER; ++k) te[k] = ((const f32x4 *)WBe)[tid + k * PAIR_THREADS];
-    if (update_mode != 2) {
-#pragma unroll
-      for (int k = 0; k < PER; ++k) tp[k] = ((const f32x4 *)WBp)[tid + k * PAIR_THREADS];
-    }
-#pragma unroll
-    for (int k = 0; k < PER; ++k) ((f32x4 *)(lds + LB_WE))[tid + k * PAIR_THREADS] = te[k];
-    if (update_mode != 2) {
-#pragma unroll
-      for (int k = 0; k < PER; ++k) ((f32x4 *)(lds + LB_WP))[tid + k * PAIR_THREADS] = tp[k];
-    }
-  }
-  for (int i = tid; i < VT_SIZE; i += PAIR_THREADS) lds[LB_VT + i] = vtab[i];
-  if (MODE == 0)
-    for (int i = tid; i < 1024; i += PAIR_THREADS) lds[LB_RT + i] = rtab[i];
-  __syncthreads();
+  // (the hi + mid weight fragments)
+  pair_stage_tables<4096 / PAIR_THREADS, MODE>(lds, tid, WBe, WBp, vtab, rtab, update_mode, LB_WE, LB_WP, LB_VT, LB_RT);
 
   // the lo fragments of the two matrices as buffer resources (32 KB each): wave-uniform base + one VGPR of lane offset for every fragment
   const __amdgpu_buffer_rsrc_t rle = __builtin_amdgcn_make_buffer_rsrc((void *)WLe, 0, 32768, 0x00020000);
   const __amdgpu_buffer_rsrc_t rlp = __builtin_amdgcn_make_buffer_rsrc((void *)WLp, 0, 32768, 0x00020000);
-  float *stage = lds + LB_STAGE + wave * STAGE_FLOATS;      // transposition image of the sum_p_mem pass
-  float *ptab = lds + LB_PTAB + wave * 128;
-  float *svec = lds + LB_SVEC + wave * 128;
-  const float *vt = lds + LB_VT;
-  const u32 *wbe = (const u32 *)(lds + LB_WE);
-  const u32 *wbp = (const u32 *)(lds + LB_WP);
-  const int cq_w = (0x1320 >> (4 * q)) & 3;                 // c = [0, 2, 3, 1] (see k_pair_bf)
-  const int cq_r = (0x1320 >> (4 * ((p >> 2) & 3))) & 3;
-  const int tw_base = (4 * q) * 16 + (((p >> 2) ^ cq_w) * 4) + (p & 3);
-  const int tr_base = p * 16 + ((q ^ cq_r) * 4);
+  PAIR_WAVE_LDS(lds, wave, p, q)
 
 #ifdef MIND_PAIR_ABL
   long long pt_[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, pt_t = clock64();
@@ -234,19 +209,15 @@ __global__ __launch_bounds__(PAIR_THREADS, 1) void k_pair_t6(const PairJob *__re
 
   PairJob Jc = jobs[job < n_jobs ? job : 0];      // this wave's current job record: read one job ahead
   for (; job < n_jobs; job += stride) {
-    const PairJob J = Jc;
-    const int jn = job + stride;
-    const bool in_range = jn < n_jobs;
-    const PairJob Jn = jobs[in_range ? jn : job];
-    Jc = Jn;
-    if (J.t1 <= J.t0) { primed = false; continue; }       // padding job (pair_jobs.h)
-    const bool has_next = in_range && Jn.t1 > Jn.t0;
+    PairJob J, Jn;
+    bool has_next;
+    // Jn = the next job of this wave: its first tile is requested during this job's last one
+    if (!pair_job_next(jobs, n_jobs, job, stride, Jc, J, Jn, has_next)) { primed = false; continue; }       // padding job (pair_jobs.h)
     const bool do_update = (update_mode == 0) || (update_mode == 1 && (J.flags & 1));
     const int N = J.N;
     const int j = J.j;
-    const int ntile = (N + 15) >> 4;
-    float *ecol = edge + (((size_t)J.edge_base_t + (size_t)j * (ntile * 16)) << 7);
-    const float *ecolN = edge + (((size_t)Jn.edge_base_t + (size_t)Jn.j * (((Jn.N + 15) >> 4) * 16)) << 7);
+    float *ecol = pair_tile_col<7>(edge, J.edge_base_t, j, N);
+    const float *ecolN = pair_tile_col<7>(edge, Jn.edge_base_t, Jn.j, Jn.N);
     PBF_FENCE();
     if (!primed) P6_LOAD_S(J)
     if (lane < 32) *(f32x4 *)(svec + lane * 4) = s_nx;
@@ -293,68 +264,7 @@ __global__ __launch_bounds__(PAIR_THREADS, 1) void k_pair_t6(const PairJob *__re
       }
       if (MODE == 0) {
         // ---- layer 0: edge0 = ReLU(LN(W_r rpe + b_r)), zeros on the cls row / column (network.py:326-330)
-        float r5[5];
-        const bool is_cls = (ic == N - 1) || (j == N - 1);
-        if (rpe_ptrs != nullptr) {
-          const float *rp = rpe_ptrs[J.scene];
-          const int n1 = N - 1;
-          const size_t o = is_cls ? 0 : ((size_t)ic * n1 + j);
-#pragma unroll
-          for (int k = 0; k < 5; ++k) r5[k] = rp[(size_t)k * n1 * n1 + o];
-        } else {
-          const f32x4 ti = *(const f32x4 *)(tokpos + (size_t)(J.tok_base + ic) * 4);
-          const float dx = pj[0] - ti[0], dy = pj[1] - ti[1];
-          const float dist = sqrtf(dx * dx + dy * dy);
-          const float nj = sqrtf(pj[2] * pj[2] + pj[3] * pj[3]);
-          const float ni = sqrtf(ti[2] * ti[2] + ti[3] * ti[3]);
-          const float den1 = nj * ni + 1e-10f;
-          const float den2 = nj * dist + 1e-10f;
-          r5[0] = (pj[2] * ti[2] + pj[3] * ti[3]) / den1;
-          r5[1] = (pj[2] * ti[3] - pj[3] * ti[2]) / den1;
-          r5[2] = (pj[2] * dx + pj[3] * dy) / den2;
-          r5[3] = (pj[2] * dy - pj[3] * dx) / den2;
-          r5[4] = dist * 2.0f / 100.0f;
-        }
-        const float *rt = lds + LB_RT + lq * 32;
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-          const float *c = rt + b * 128;
-          f32x4 acc = *(const f32x4 *)(c + 20);  // bias
-#pragma unroll
-          for (int k = 0; k < 5; ++k) {
-            const f32x4 wk = *(const f32x4 *)(c + 4 * k);
-#pragma unroll
-            for (int w = 0; w < 4; ++w) acc[w] = fmaf(wk[w], r5[k], acc[w]);
-          }
-          ef[b] = acc;
-        }
-        {
-          float s = 0.f;
-#pragma unroll
-          for (int b = 0; b < 8; ++b)
-#pragma unroll
-            for (int w = 0; w < 4; ++w) s += ef[b][w];
-          s = red_quad(s);
-          const float mean = s * (1.0f / 128.0f);
-          float v = 0.f;
-#pragma unroll
-          for (int b = 0; b < 8; ++b)
-#pragma unroll
-            for (int w = 0; w < 4; ++w) { const float d = ef[b][w] - mean; v = fmaf(d, d, v); }
-          v = red_quad(v);
-          const float rstd = 1.0f / sqrtf(v * (1.0f / 128.0f) + 1e-5f);
-#pragma unroll
-          for (int b = 0; b < 8; ++b) {
-            const float *c = rt + b * 128;
-            const f32x4 gm = *(const f32x4 *)(c + 24);
-            const f32x4 bt = *(const f32x4 *)(c + 28);
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-              const float y = fmaxf((ef[b][w] - mean) * rstd * gm[w] + bt[w], 0.f);
-              ef[b][w] = is_cls ? 0.f : y;
-            }
-          }
-        }
+        PAIR_EDGE0(ef, lds + LB_RT + lq * 32, tokpos, rpe_ptrs, pj, J.scene, J.tok_base, j, N, ic)
       }
 
       // ---- memory = ReLU(LN(W_e e + S[j] + T[i]))   (network.py:197-199, rank-decomposed, mean folded away)
@@ -424,31 +334,7 @@ __global__ __launch_bounds__(PAIR_THREADS, 1) void k_pair_t6(const PairJob *__re
       }
       SCHED_FENCE();
       // ---- online softmax over i: lanes of quarter q (and q ^ 2) own heads 4 (q & 1) .. + 3
-      float pr[4], scl[4];
-      bool grew = false;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float sv = valid ? sa[r] : -INFINITY;
-        const float mx = red_max16(sv);
-        const float m_new = fmaxf(m_run[r], mx);
-        grew = grew || (m_new != m_run[r]);
-        scl[r] = __expf(m_run[r] - m_new);
-        pr[r] = valid ? __expf(sv - m_new) : 0.f;
-        l_part[r] = l_part[r] * scl[r] + pr[r];
-        m_run[r] = m_new;
-      }
-      PBF_FENCE();
-      if (lq < 2) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) ptab[(4 * lq + r) * 16 + lp] = pr[r];
-      }
-      if (__any(grew)) {
-#pragma unroll
-        for (int b = 0; b < 8; ++b)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) mbar[b][r] *= scl[r];
-      }
-      PBF_FENCE();
+      pair_softmax_step(sa, valid, lq, lp, m_run, l_part, mbar, ptab);
       // A operands: p[head = lane & 15][pairs 4q .. 4q+3], k-slot (q', i) <-> (pair 4 q' + (i >> 1), part i & 1) of the staged image:
       //   pa_hh = (p_hi, p_hi) and pa_mm = (p_mid, p_mid) against the (m_hi | m_mid) image, pa_hl = (p_hi, p_lo) against the (m_lo | m_hi) image
       u32x4 pa_hh, pa_mm, pa_hl;
@@ -472,34 +358,11 @@ __global__ __launch_bounds__(PAIR_THREADS, 1) void k_pair_t6(const PairJob *__re
       if (P6_ABL(16)) {
         asm volatile("" ::"v"(pa_hh), "v"(pa_mm), "v"(pa_hl));
       } else {
-        const u32 *stu = (const u32 *)stage;
-        u32 *stw = (u32 *)stage;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-#pragma unroll
-          for (int b2 = 0; b2 < 2; ++b2)
-#pragma unroll
-            for (int rr = 0; rr < 2; ++rr) {
-              const u32 X = mh[g][2 * b2 + rr], Y = mm[g][2 * b2 + rr];
-              stw[tw_base + (16 * b2 + 2 * rr) * 16] = (X & 0xffffu) | (Y << 16);
-              stw[tw_base + (16 * b2 + 2 * rr + 1) * 16] = (X >> 16) | (Y & 0xffff0000u);
-            }
-          PBF_FENCE();
-          const u32x4 f0 = *(const u32x4 *)(stu + tr_base);
-          const u32x4 f1 = *(const u32x4 *)(stu + tr_base + 256);
-          PBF_FENCE();
-#pragma unroll
-          for (int b2 = 0; b2 < 2; ++b2)
-#pragma unroll
-            for (int rr = 0; rr < 2; ++rr) {
-              const u32 X = ml[g][2 * b2 + rr], Y = mh[g][2 * b2 + rr];
-              stw[tw_base + (16 * b2 + 2 * rr) * 16] = (X & 0xffffu) | (Y << 16);
-              stw[tw_base + (16 * b2 + 2 * rr + 1) * 16] = (X >> 16) | (Y & 0xffff0000u);
-            }
-          PBF_FENCE();
-          const u32x4 f2 = *(const u32x4 *)(stu + tr_base);
-          const u32x4 f3 = *(const u32x4 *)(stu + tr_base + 256);
-          PBF_FENCE();
+          u32x4 f0, f1, f2, f3;
+          pair_stage_quarter<true>(stq_w, stq_r, mh[g], mm[g], f0, f1);
+          pair_stage_quarter<true>(stq_w, stq_r, ml[g], mh[g], f2, f3);
           mbar[2 * g] = MFMA_BF(pa_hl, f2, mbar[2 * g]);
           mbar[2 * g + 1] = MFMA_BF(pa_hl, f3, mbar[2 * g + 1]);
           mbar[2 * g] = MFMA_BF(pa_mm, f0, mbar[2 * g]);
@@ -566,29 +429,7 @@ __global__ __launch_bounds__(PAIR_THREADS, 1) void k_pair_t6(const PairJob *__re
 
     // ---- column partial: m[8], l[8], mbar[8][128], through the wave's idle LDS images as nine coalesced 16-byte stores per lane
     float *po = part + (size_t)J.slot * PART_STRIDE;
-    float lsum[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) lsum[r] = red_sum16(l_part[r]);
-    if (p == 0 && q < 2) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) { ptab[4 * q + r] = m_run[r]; ptab[8 + 4 * q + r] = lsum[r]; }
-    }
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {      // heads 4 h .. 4 h + 3 fill the 512-float transposition image
-      if (q == h) {
-#pragma unroll
-        for (int b = 0; b < 8; ++b)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) stage[r * 128 + 16 * b + p] = mbar[b][r];
-      }
-      PBF_FENCE();
-      const f32x4 v0 = *(const f32x4 *)(stage + lane * 4), v1 = *(const f32x4 *)(stage + 256 + lane * 4);
-      *(f32x4 *)(po + 16 + h * 512 + lane * 4) = v0;
-      *(f32x4 *)(po + 16 + h * 512 + 256 + lane * 4) = v1;
-      PBF_FENCE();
-    }
-    if (lane < 4) *(f32x4 *)(po + lane * 4) = *(const f32x4 *)(ptab + lane * 4);
-    PBF_FENCE();
+    pair_store_partial(po, stage, ptab, m_run, l_part, mbar, lane, p, q);
   }
 #ifdef MIND_PAIR_ABL
   if (P6_ABL(128) && blockIdx.x == 0 && (tid & 63) == 0 && wave < 2)

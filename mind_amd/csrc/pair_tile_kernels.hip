@@ -2,8 +2,8 @@
 //
 // Reference semantics: planners/mind/networks/network.py:165-232 (RelaFusionLayer), :259-268 (six layers, the last one
 // without an edge update).  Arithmetic, algebraic folds and the chained register layouts are those of k_pair_bf
-// (pair_bf16_kernels.hip: bf16 hi + lo split operands on v_mfma_f32_16x16x32_bf16, fp32 accumulate).  What changes is how a
-// wave gets at its data:
+// (pair_bf16_kernels.hip: bf16 hi + lo split operands on v_mfma_f32_16x16x32_bf16, fp32 accumulate); the LDS layout, the operand
+// split, the GEMM and the phases the two kernels run alike come from pair_common.h.  What changes is how a wave gets at its data:
 //
 //   * the edge tensor lives in HBM in the kernel's own register layout.  A 16-pair tile of column j is one contiguous 8 KB
 //     chunk [chunk b 8][lane 64][4 floats]: element (row 16 t + p, feature 16 b + 4 q + r) at ((b 64 + 16 q + p) 4 + r), so
@@ -23,7 +23,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define PT_TILE_FLOATS 2048                           // 16 pairs x 128 features
+#include "pair_common.h"   // LDS layout LB_*, MFMA_BF, split_frag, gemm_bf, ln_nomean, the phases shared with the other pair kernels
+
 // Plain bf16 arithmetic (NP == 1, BASELINE config 5) keeps the edge tensor in bf16 as well: a tile chunk is the first GEMM's B operand
 // as is -- [k-group g 4][lane 64][4 dwords], dword 2 c + h of group g = features 16 (2 g + c) + 4 q + 2 h, + 1 as a bf16 pair -- 4 KB per
 // tile, four loads and four stores, no operand conversion on the way in (the mode's operands are rounded to bf16 anyway; half the HBM bytes)
@@ -72,38 +73,8 @@ __global__ __launch_bounds__(PAIR_THREADS, 1) void k_pair_t(const PairJob *__res
   const int p = lane & 15;
   const int q = lane >> 4;
 
-  // ---- stage weights / tables (once per workgroup): all loads of a matrix in flight before the first LDS write
-  {
-    constexpr int PER = (NP == 3 ? 4096 : 2048) / PAIR_THREADS;
-    f32x4 te[PER], tp[PER];
-#pragma unroll
-    for (int k = 0; k < PER; ++k) te[k] = ((const f32x4 *)WBe)[tid + k * PAIR_THREADS];
-    if (update_mode != 2) {
-#pragma unroll
-      for (int k = 0; k < PER; ++k) tp[k] = ((const f32x4 *)WBp)[tid + k * PAIR_THREADS];
-    }
-#pragma unroll
-    for (int k = 0; k < PER; ++k) ((f32x4 *)(lds + LB_WE))[tid + k * PAIR_THREADS] = te[k];
-    if (update_mode != 2) {
-#pragma unroll
-      for (int k = 0; k < PER; ++k) ((f32x4 *)(lds + LB_WP))[tid + k * PAIR_THREADS] = tp[k];
-    }
-  }
-  for (int i = tid; i < VT_SIZE; i += PAIR_THREADS) lds[LB_VT + i] = vtab[i];
-  if (MODE == 0)
-    for (int i = tid; i < 1024; i += PAIR_THREADS) lds[LB_RT + i] = rtab[i];
-  __syncthreads();
-
-  float *stage = lds + LB_STAGE + wave * STAGE_FLOATS;      // transposition image of the sum_p_mem pass
-  float *ptab = lds + LB_PTAB + wave * 128;
-  float *svec = lds + LB_SVEC + wave * 128;
-  const float *vt = lds + LB_VT;
-  const u32 *wbe = (const u32 *)(lds + LB_WE);
-  const u32 *wbp = (const u32 *)(lds + LB_WP);
-  const int cq_w = (0x1320 >> (4 * q)) & 3;                 // c = [0, 2, 3, 1] (see k_pair_bf)
-  const int cq_r = (0x1320 >> (4 * ((p >> 2) & 3))) & 3;
-  const int tw_base = (4 * q) * 16 + (((p >> 2) ^ cq_w) * 4) + (p & 3);
-  const int tr_base = p * 16 + ((q ^ cq_r) * 4);
+  pair_stage_tables<(NP == 3 ? 4096 : 2048) / PAIR_THREADS, MODE>(lds, tid, WBe, WBp, vtab, rtab, update_mode, LB_WE, LB_WP, LB_VT, LB_RT);
+  PAIR_WAVE_LDS(lds, wave, p, q)
 
 #ifdef MIND_PAIR_ABL
   long long pt_[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, pt_t = clock64();
@@ -137,20 +108,15 @@ __global__ __launch_bounds__(PAIR_THREADS, 1) void k_pair_t(const PairJob *__res
 
   PairJob Jc = jobs[job < n_jobs ? job : 0];      // this wave's current job record: read one job ahead (a scalar load and its latency per job otherwise)
   for (; job < n_jobs; job += stride) {
-    const PairJob J = Jc;
-    // the next job of this wave: its first tile is requested during this job's last one
-    const int jn = job + stride;
-    const bool in_range = jn < n_jobs;
-    const PairJob Jn = jobs[in_range ? jn : job];
-    Jc = Jn;
-    if (J.t1 <= J.t0) { primed = false; continue; }       // padding job (pair_jobs.h)
-    const bool has_next = in_range && Jn.t1 > Jn.t0;
+    PairJob J, Jn;
+    bool has_next;
+    // Jn = the next job of this wave: its first tile is requested during this job's last one
+    if (!pair_job_next(jobs, n_jobs, job, stride, Jc, J, Jn, has_next)) { primed = false; continue; }       // padding job (pair_jobs.h)
     const bool do_update = (update_mode == 0) || (update_mode == 1 && (J.flags & 1));
     const int N = J.N;
     const int j = J.j;
-    const int ntile = (N + 15) >> 4;
-    float *ecol = edge + (((size_t)J.edge_base_t + (size_t)j * (ntile * 16)) << ESH);
-    const float *ecolN = edge + (((size_t)Jn.edge_base_t + (size_t)Jn.j * (((Jn.N + 15) >> 4) * 16)) << ESH);
+    float *ecol = pair_tile_col<ESH>(edge, J.edge_base_t, j, N);
+    const float *ecolN = pair_tile_col<ESH>(edge, Jn.edge_base_t, Jn.j, Jn.N);
     PBF_FENCE();
     // S[j] (into the wave's LDS vector) and the folded query A operand (row p < 8 = hi part of head p, row p >= 8 = lo part of head
     // p - 8; zero rows without the split): requested when the previous job of this wave ended, or here
@@ -216,68 +182,7 @@ __global__ __launch_bounds__(PAIR_THREADS, 1) void k_pair_t(const PairJob *__res
         for (int b = 0; b < 8; ++b) ef[b] = (f32x4){0.25f, 0.5f, 0.f, 1.f} * (float)(lp + 1);      // (timing: no edge build)
       } else {
         // ---- layer 0: edge0 = ReLU(LN(W_r rpe + b_r)), zeros on the cls row / column (network.py:326-330)
-        float r5[5];
-        const bool is_cls = (ic == N - 1) || (j == N - 1);
-        if (rpe_ptrs != nullptr) {
-          const float *rp = rpe_ptrs[J.scene];
-          const int n1 = N - 1;
-          const size_t o = is_cls ? 0 : ((size_t)ic * n1 + j);
-#pragma unroll
-          for (int k = 0; k < 5; ++k) r5[k] = rp[(size_t)k * n1 * n1 + o];
-        } else {
-          const f32x4 ti = *(const f32x4 *)(tokpos + (size_t)(J.tok_base + ic) * 4);
-          const float dx = pj[0] - ti[0], dy = pj[1] - ti[1];
-          const float dist = sqrtf(dx * dx + dy * dy);
-          const float nj = sqrtf(pj[2] * pj[2] + pj[3] * pj[3]);
-          const float ni = sqrtf(ti[2] * ti[2] + ti[3] * ti[3]);
-          const float den1 = nj * ni + 1e-10f;
-          const float den2 = nj * dist + 1e-10f;
-          r5[0] = (pj[2] * ti[2] + pj[3] * ti[3]) / den1;
-          r5[1] = (pj[2] * ti[3] - pj[3] * ti[2]) / den1;
-          r5[2] = (pj[2] * dx + pj[3] * dy) / den2;
-          r5[3] = (pj[2] * dy - pj[3] * dx) / den2;
-          r5[4] = dist * 2.0f / 100.0f;
-        }
-        const float *rt = lds + LB_RT + lq * 32;
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-          const float *c = rt + b * 128;
-          f32x4 acc = *(const f32x4 *)(c + 20);  // bias
-#pragma unroll
-          for (int k = 0; k < 5; ++k) {
-            const f32x4 wk = *(const f32x4 *)(c + 4 * k);
-#pragma unroll
-            for (int w = 0; w < 4; ++w) acc[w] = fmaf(wk[w], r5[k], acc[w]);
-          }
-          ef[b] = acc;
-        }
-        {
-          float s = 0.f;
-#pragma unroll
-          for (int b = 0; b < 8; ++b)
-#pragma unroll
-            for (int w = 0; w < 4; ++w) s += ef[b][w];
-          s = red_quad(s);
-          const float mean = s * (1.0f / 128.0f);
-          float v = 0.f;
-#pragma unroll
-          for (int b = 0; b < 8; ++b)
-#pragma unroll
-            for (int w = 0; w < 4; ++w) { const float d = ef[b][w] - mean; v = fmaf(d, d, v); }
-          v = red_quad(v);
-          const float rstd = 1.0f / sqrtf(v * (1.0f / 128.0f) + 1e-5f);
-#pragma unroll
-          for (int b = 0; b < 8; ++b) {
-            const float *c = rt + b * 128;
-            const f32x4 gm = *(const f32x4 *)(c + 24);
-            const f32x4 bt = *(const f32x4 *)(c + 28);
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-              const float y = fmaxf((ef[b][w] - mean) * rstd * gm[w] + bt[w], 0.f);
-              ef[b][w] = is_cls ? 0.f : y;
-            }
-          }
-        }
+        PAIR_EDGE0(ef, lds + LB_RT + lq * 32, tokpos, rpe_ptrs, pj, J.scene, J.tok_base, j, N, ic)
       }
 
       // ---- memory = ReLU(LN(W_e e + S[j] + T[i]))   (network.py:197-199, rank-decomposed, mean folded away)
@@ -390,31 +295,7 @@ __global__ __launch_bounds__(PAIR_THREADS, 1) void k_pair_t(const PairJob *__res
         }
       }
       // ---- online softmax over i: lanes of quarter q (and q ^ 2) own heads 4 (q & 1) .. + 3
-      float pr[4], scl[4];
-      bool grew = false;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float sv = valid ? sa[r] : -INFINITY;
-        const float mx = red_max16(sv);
-        const float m_new = fmaxf(m_run[r], mx);
-        grew = grew || (m_new != m_run[r]);
-        scl[r] = __expf(m_run[r] - m_new);
-        pr[r] = valid ? __expf(sv - m_new) : 0.f;
-        l_part[r] = l_part[r] * scl[r] + pr[r];
-        m_run[r] = m_new;
-      }
-      PBF_FENCE();
-      if (lq < 2) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) ptab[(4 * lq + r) * 16 + lp] = pr[r];
-      }
-      if (__any(grew)) {
-#pragma unroll
-        for (int b = 0; b < 8; ++b)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) mbar[b][r] *= scl[r];
-      }
-      PBF_FENCE();
+      pair_softmax_step(sa, valid, lq, lp, m_run, l_part, mbar, ptab);
       // A operand: p[head = lane & 15][pairs 4q .. 4q+3], each duplicated over the (hi, lo) parts of the memory rows
       u32x4 pah, pal;
       {
@@ -432,8 +313,6 @@ __global__ __launch_bounds__(PAIR_THREADS, 1) void k_pair_t(const PairJob *__res
       }
       // ---- mbar[head][f] += sum_pairs p[head][pair] * mem[pair][f] on the MFMA, the memory tile transposed through the
       //      wave's LDS image one 32-feature quarter (= k-group g) at a time as (hi | lo << 16) dwords
-      const u32 *stu = (const u32 *)stage;
-      u32 *stw = (u32 *)stage;
       PT_TIME(7);              // (timers) scores + softmax
       if (PT_ABL(512)) {
 #pragma unroll
@@ -443,19 +322,8 @@ __global__ __launch_bounds__(PAIR_THREADS, 1) void k_pair_t(const PairJob *__res
       }
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
-#pragma unroll
-        for (int b2 = 0; b2 < 2; ++b2)
-#pragma unroll
-          for (int rr = 0; rr < 2; ++rr) {
-            const u32 X = mhi[g][2 * b2 + rr];
-            const u32 Y = NP == 3 ? mlo[g][2 * b2 + rr] : 0u;
-            stw[tw_base + (16 * b2 + 2 * rr) * 16] = (X & 0xffffu) | (Y << 16);
-            stw[tw_base + (16 * b2 + 2 * rr + 1) * 16] = (X >> 16) | (Y & 0xffff0000u);
-          }
-        PBF_FENCE();
-        const u32x4 f0 = *(const u32x4 *)(stu + tr_base);
-        const u32x4 f1 = *(const u32x4 *)(stu + tr_base + 256);
-        PBF_FENCE();
+        u32x4 f0, f1;
+        pair_stage_quarter<NP == 3>(stq_w, stq_r, mhi[g], mlo[g], f0, f1);
         mbar[2 * g] = MFMA_BF(pah, f0, mbar[2 * g]);
         mbar[2 * g + 1] = MFMA_BF(pah, f1, mbar[2 * g + 1]);
         if (NP == 3) {
@@ -472,43 +340,8 @@ __global__ __launch_bounds__(PAIR_THREADS, 1) void k_pair_t(const PairJob *__res
     // ---- column partial: m[8], l[8], mbar[8][128], through the wave's idle LDS images so that it leaves as nine coalesced 16-byte stores per
     //      lane instead of forty 4-byte ones from half the lanes (in order behind this job's last LDS reads; a wave's LDS accesses keep their order)
     float *po = part + (size_t)J.slot * PART_STRIDE;
-    if (PT_ABL(32768)) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float l = red_sum16(l_part[r]);
-        if (p == 0 && q < 2) { po[4 * q + r] = m_run[r]; po[8 + 4 * q + r] = l; }
-      }
-      if (q < 2) {
-#pragma unroll
-        for (int b = 0; b < 8; ++b)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) po[16 + (4 * q + r) * 128 + 16 * b + p] = mbar[b][r];
-      }
-    } else {
-      float lsum[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) lsum[r] = red_sum16(l_part[r]);
-      if (p == 0 && q < 2) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { ptab[4 * q + r] = m_run[r]; ptab[8 + 4 * q + r] = lsum[r]; }
-      }
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {      // heads 4 h .. 4 h + 3 fill the 512-float transposition image
-        if (q == h) {
-#pragma unroll
-          for (int b = 0; b < 8; ++b)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) stage[r * 128 + 16 * b + p] = mbar[b][r];
-        }
-        PBF_FENCE();
-        const f32x4 v0 = *(const f32x4 *)(stage + lane * 4), v1 = *(const f32x4 *)(stage + 256 + lane * 4);
-        *(f32x4 *)(po + 16 + h * 512 + lane * 4) = v0;
-        *(f32x4 *)(po + 16 + h * 512 + 256 + lane * 4) = v1;
-        PBF_FENCE();
-      }
-      if (lane < 4) *(f32x4 *)(po + lane * 4) = *(const f32x4 *)(ptab + lane * 4);
-      PBF_FENCE();
-    }
+    if (PT_ABL(32768)) PAIR_STORE_PARTIAL_DIRECT(po, m_run, l_part, mbar, p, q)
+    else pair_store_partial(po, stage, ptab, m_run, l_part, mbar, lane, p, q);
   }
 #undef PT_LOAD_E
 #undef PT_LOAD_T

@@ -12,8 +12,7 @@
 #include <string>
 #include <vector>
 #include "../../mind_amd/csrc/pair_jobs.h"
-#include "../../mind_amd/csrc/fusion_kernels.hip"
-#include "../../mind_amd/csrc/pair_bf16_kernels.hip"
+#include "../../mind_amd/csrc/pair_bf16_kernels.hip"   // mind_pair_bf_lds_bytes
 #include "../../mind_amd/csrc/pair_tile_kernels.hip"
 #include "../../mind_amd/csrc/pair_tile6_kernels.hip"
 

@@ -13,7 +13,6 @@
 #include <string>
 #include <vector>
 #include "../../mind_amd/csrc/pair_jobs.h"
-#include "../../mind_amd/csrc/fusion_kernels.hip"
 #include "../../mind_amd/csrc/pair_bf16_kernels.hip"
 #include "../../mind_amd/csrc/pair_tile_kernels.hip"
 #ifdef PAIR_BENCH_EXTRA
