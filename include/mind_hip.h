@@ -150,7 +150,9 @@ int mind_set_pair_precision(mind_ctx *ctx, int mode);
  * most this many nodes write xs / us / statistics to the host staging themselves; default 4 096), "dec_mirror" (mind_aime_plan, unsharded: the
  * round's last glue kernel writes the decisions where the host reads them), "tab_host_max" / "tab_small" (its small index tables are read from
  * the host staging / travel in the kernel arguments), "early_eval" (mind_loop prices a candidate tree as soon as the pending launch marks it
- * complete), "glue_fused" (mind_aime_plan's pruning decisions and branch-time bits from one launch, k_aime_select_branch); MIND_GLUE_FUSED, MIND_UPLOAD_KERNEL_MAX, MIND_ILQR_HOST_OUT_MAX, MIND_DEC_MIRROR, MIND_TAB_HOST_MAX, MIND_TAB_SMALL, MIND_EARLY_EVAL,
+ * complete), "glue_fused" (mind_aime_plan's pruning decisions and branch-time bits from one launch, k_aime_select_branch), "dec_poll" (with
+ * "dec_mirror", rounds of one launch: that kernel marks the mirrored decisions complete with a generation word and the host polls the word,
+ * bounded, instead of draining the stream, sizing the next round's buffers while it waits; MIND_DEC_POLL); MIND_GLUE_FUSED, MIND_UPLOAD_KERNEL_MAX, MIND_ILQR_HOST_OUT_MAX, MIND_DEC_MIRROR, MIND_TAB_HOST_MAX, MIND_TAB_SMALL, MIND_EARLY_EVAL,
  * "actor_f32" (0: the fp32 VALU ActorNet instead of the fp32-MFMA one under the exact-fp32 setting), "actor_f32_min" / "actor_f32_pair_min" (actors per
  * call from which the fp32-MFMA ActorNet runs with two actors per workgroup, under every setting / under exact fp32; default never),
  * "actor_lw_min" (actors per call from which the layer-wise batched ActorNet -- actor_lw_kernels.hip: one conv-as-GEMM launch and one GroupNorm
@@ -166,7 +168,9 @@ int mind_set_pair_precision(mind_ctx *ctx, int mode);
  * per chunk, 0 = the default of 32 768; the scratch arena is one chunk, 2 560 bytes per token; same bits for every value),
  * "enc_mfma" (0: the fp32 VALU ActorNet / decoder kernels under every precision), "actor_split" (6: three-way operand split,
  * fp32-class; 3: two-way), "xcd_order" (XCD-aware job order of the pair kernel), "tok_mfma" (1: the per-token epilogue / prologue of the fusion layers on the fp32 MFMA kernel k_token_mfma instead of the fp32 VALU one; off by default: measured slower), "tok_small_max" (batches of at most this many tokens run k_token with four tokens per workgroup instead of eight; same bits), "tgt_side" (0: the context stream waits for the target embedding before the fusion layers), "dec_overlap" (0: the decoder's actor part as one kernel behind
- * k_dec_scene instead of its actor_proj half beside it on the side stream; bit-identical).  Environment: MIND_DEC_MFMA_MIN, MIND_ENC_MFMA,
+ * k_dec_scene instead of its actor_proj half beside it on the side stream; bit-identical), "dec_head_ra" (agents per workgroup of that form's head:
+ * 0, default = 1 while the call's agents fit one workgroup per CU, else 2, else 4; 1, 2 or 4 = that form whatever the call, 4 being the head as it
+ * was; bit-identical; MIND_DEC_HEAD_RA).  Environment: MIND_DEC_MFMA_MIN, MIND_ENC_MFMA,
  * MIND_ACTOR_SPLIT, MIND_XCD_ORDER, MIND_ILQR_WGS, MIND_DEC_OVERLAP at context creation. */
 int mind_set_tuning(mind_ctx *ctx, const char *name, int value);
 int mind_get_pair_precision(mind_ctx *ctx);   /* -> mode, or MIND_EINVAL */
@@ -198,7 +202,8 @@ int mind_debug_pair_schedule(const int *scene_tokens, const int *scene_actors, i
  *   [19] the last fusion layer walks its own list of consumed columns  [20] XCD grouping factor of the full job list, [21] of that list
  *   [22] decoder actor part (0 k_dec_actor<0>, 1 k_dec_actor<1> + <2> over two streams, 2 k_dec_actor_mfma)  [23] np of the MFMA form, else 0
  *   [24] fp32 decoder  [25] split over two streams  [26] k_dec_scene_mw wanted  [27] its workgroups  [28] k_dec_scene_c + k_dec_cls
- *   [29] the context stream waits for the target embedding before the fusion layers  [30], [31] 0
+ *   [29] the context stream waits for the target embedding before the fusion layers  [30] agents per workgroup of the split form's head
+ *   (k_dec_actor<2, .>: 1, 2 or 4; 0 outside that form)  [31] 0
  * and one row {first token, tokens, kind (0 VALU, 1 fp32 MFMA, 2 bf16 split MFMA), layer-wise, small (four tokens per workgroup), merged
  * (k_token_m)} per token run.  Returns the length of the full record, or MIND_EINVAL for an unknown knob, pair_prec outside 0..3, a scene
  * with no actor or a negative lane count, or a null pointer.  Needs no GPU and no context. */
@@ -244,6 +249,12 @@ int mind_debug_ilqr_plan(const char *const *knob_names, const int *knob_values, 
 int mind_debug_aime_book(int pred_len, int max_depth, int max_rounds, int n_agents, int world, int rank, int force, int n_rounds, const int *dec_len,
                          const float *dec, int n_tokens, int bytes_per_pair, int plan_chunk_mb, int per_scene, long long *out, int cap, char *msg,
                          int msg_cap);
+
+/* host-only helper (tests): the bounded wait of mind_aime_plan's polled decisions (pl_wait_word, mind_amd/csrc/aime_book.h) over the caller's
+ * word and clock: acquire loads of *word until it holds `want`; clock(user) (seconds, any origin; null: the steady clock) is read every
+ * spins_per_look misses and the wait gives up once more than timeout_s have passed.  Returns 1 when the word arrived, 0 after the time-out,
+ * MIND_EINVAL for a null word, a negative time-out or spins_per_look <= 0.  Needs no GPU and no context. */
+int mind_debug_wait_word(const unsigned *word, unsigned want, double timeout_s, double (*clock)(void *user), void *user, int spins_per_look);
 
 /* host-only helper (tests): the launch list of the layer-wise batched ActorNet for a call of n_actors actors in the arithmetic np (6, 3, 1 =
  * bf16x6, bf16x3, bf16; anything else: MIND_EINVAL) with `chunk` actors per chunk (0 = the default) -- exactly what mind_predict_batch issues.

@@ -8,6 +8,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MIND_HIP_LIB", os.path.join(_HERE, "libmind_hip.so"))   # override: diagnostic builds only
 
+WAIT_CLOCK = C.CFUNCTYPE(C.c_double, C.c_void_p)      # mind_debug_wait_word's clock
 MIND_OK = 0
 MIND_EINVAL, MIND_ENOMEM, MIND_EHIP, MIND_ESTATE, MIND_ENOTFOUND = -1, -2, -3, -4, -5     # include/mind_hip.h:21-25
 
@@ -166,7 +167,7 @@ EXPORTS = ["mind_ctx_create", "mind_ctx_destroy", "mind_last_error_string", "min
            "mind_weights_load", "mind_predict_batch", "mind_last_fusion_stats", "mind_last_actor_stats", "mind_debug_actor_lw_plan", "mind_last_token_stats", "mind_last_token_stage_ms", "mind_debug_token_lw_plan", "mind_set_profiling",
            "mind_ilqr_solve_trees", "mind_ilqr_contingency", "mind_ilqr_solve_fields", "mind_cost_eval", "mind_ilqr_score_trees", "mind_ilqr_gains", "mind_ilqr_policy_rollouts", "mind_lane_dist_field", "mind_aime_world", "mind_aime_rebase", "mind_debug_aime_decide", "mind_debug_set_layers",
            "mind_debug_read", "mind_set_pair_precision", "mind_get_pair_precision", "mind_debug_pack_bfrag", "mind_debug_pack_conv_frag", "mind_debug_pack", "mind_debug_weight_image", "mind_debug_weight_bind", "mind_debug_pair_schedule", "mind_debug_predict_choice", "mind_debug_ilqr_plan", "mind_debug_aime_book", "mind_set_tuning", "mind_last_ilqr_stats", "mind_aime_plan", "mind_last_ilqr_profile", "mind_eval_traj_trees", "mind_last_ilqr_trace", "mind_ilqr_contingency_begin", "mind_ilqr_finish", "mind_fill_tracks", "mind_ilqr_contingency_begin_plan", "mind_debug_trig", "mind_aime_plan_begin", "mind_aime_plan_poll", "mind_aime_plan_finish", "mind_ctx_busy", "mind_ilqr_finish_plan",
-           "mind_set_exchange", "mind_last_exchange_stats",
+           "mind_set_exchange", "mind_last_exchange_stats", "mind_debug_wait_word",
            "mind_loop_create", "mind_loop_destroy", "mind_loop_reset", "mind_loop_advance", "mind_loop_state", "mind_loop_last_plan", "mind_loop_export",
            "mind_planner_create", "mind_planner_destroy", "mind_planner_reset", "mind_planner_observe", "mind_planner_set_lanes", "mind_planner_set_target_lane",
            "mind_planner_set_solve_lane", "mind_planner_set_eval_lane", "mind_planner_plan", "mind_planner_last_plan", "mind_planner_export"]
@@ -258,6 +259,7 @@ def load():
                                               C.c_int, C.POINTER(C.c_longlong), C.c_int]
     lib.mind_debug_ilqr_plan.argtypes = [C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int32),
                                          C.POINTER(C.c_longlong), C.c_int, C.POINTER(C.c_int)]
+    lib.mind_debug_wait_word.argtypes = [C.POINTER(C.c_uint), C.c_uint, C.c_double, WAIT_CLOCK, C.c_void_p, C.c_int]
     lib.mind_debug_aime_book.argtypes = [C.c_int] * 8 + [C.POINTER(C.c_int), C.POINTER(C.c_float)] + [C.c_int] * 4 + [C.POINTER(C.c_longlong), C.c_int, C.c_char_p, C.c_int]
     lib.mind_debug_trig.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double)]
     lib.mind_debug_pack_conv_frag.argtypes = [C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_size_t]
@@ -299,7 +301,8 @@ def load():
 # header of mind_debug_predict_choice's record (include/mind_hip.h)
 PRED_CHOICE_FIELDS = ("header", "n_runs", "np", "actor_form", "actor_arg", "actor_grid", "actor_chunk", "actor_chunks", "actor_launches", "qsplit", "qk_stride",
                       "tiled", "edge_bf16", "edge_pair_bytes", "tok_chunk", "tok_lw", "tok_chunks", "pair_family", "pair_np", "l5_jobs5", "xcd_lanes",
-                      "xcd_lanes5", "dec_actor", "dec_np", "fp32_dec", "split_dec", "want_mw", "mw_blocks", "cls_on_side", "tgt_wait_first")
+                      "xcd_lanes5", "dec_actor", "dec_np", "fp32_dec", "split_dec", "want_mw", "mw_blocks", "cls_on_side", "tgt_wait_first",
+                      "dec_head_ra")
 PAIR_PREC = ("f32", "bf16x3", "bf16", "bf16x6")
 
 
@@ -318,7 +321,7 @@ def predict_choice(knobs, prec, scenes, n_cu=256, have_side=True):
     if n == MIND_EINVAL:
         return None
     assert 0 < n <= cap and out[0] == 32 and n == 32 + 6 * out[1], n
-    d = dict(zip(PRED_CHOICE_FIELDS, out[:30]))
+    d = dict(zip(PRED_CHOICE_FIELDS, out[:31]))
     d["runs"] = [tuple(out[32 + 6 * i:38 + 6 * i]) for i in range(out[1])]
     return d
 

@@ -52,6 +52,21 @@ inline int pl_chunk(int n_tokens, int bytes_per_pair, int plan_chunk_mb, int Bk)
   return std::max(1, (int)std::min<double>((double)(Bk > 0 ? Bk : 1), (double)plan_chunk_mb / edge_mb));
 }
 
+// The bounded wait for a word the device stores when a round's mirrored decisions are complete (k_aime_select_branch / k_aime_branch): acquire
+// loads until the word holds `want`; the clock (seconds, any origin) is read every `spins_per_look` misses, and past `timeout_s` the wait gives
+// up -- the caller then drains the stream and reads the same bytes (never hang on a word).  true: the word arrived.
+typedef double (*pl_clock_fn)(void *user);
+inline bool pl_wait_word(const volatile unsigned *word, unsigned want, double timeout_s, pl_clock_fn now, void *user, unsigned spins_per_look) {
+  if (__atomic_load_n((const unsigned *)word, __ATOMIC_ACQUIRE) == want) return true;
+  const double t0 = now(user);
+  for (unsigned spins = 0;;) {
+    if (__atomic_load_n((const unsigned *)word, __ATOMIC_ACQUIRE) == want) return true;
+    if (++spins < spins_per_look) continue;
+    spins = 0;
+    if (now(user) - t0 > timeout_s) return false;
+  }
+}
+
 // a "left to the host path" exit of the bookkeeping: which one and the numbers its message names (pl_err_format: the caller's fail() prints it)
 enum { PL_OK = 0, PL_E_ROUNDS, PL_E_ROOT, PL_E_TRIMMED, PL_E_AGAIN, PL_E_ORDER, PL_E_NO_END };
 struct PlErr { int code = PL_OK, a0 = 0, a1 = 0; explicit operator bool() const { return code != PL_OK; } };

@@ -279,10 +279,25 @@ __global__ __launch_bounds__(64) void k_aime_windows(const float *__restrict__ p
 // One wave per (scene, kept slot), lane = step; sel as written by k_aime_select.
 // h_sel != null (unsharded plans): this last kernel of a round also writes the round's decisions -- kept mode, its probability, the hit bits --
 // where the HOST reads them (page-locked, mapped staging), so that no copy stands between the kernel's end and the host's replay.
+// The round's last kernel tells the host that the mirrored decisions are complete (mind_aime_plan polls instead of draining the stream: the
+// pattern of k_ilqr's per-tree completion words).  Every block calls this behind its own mirror stores, from thread 0: the stores are made
+// visible at system scope, the block is counted on a device word, and the block that arrives last re-arms the counter for the next launch and
+// stores the launch's generation behind the decisions with a system-scope release.  No block waits for another.
+struct AimeDone { unsigned *cnt; unsigned *h_gen; unsigned gen; };
+__device__ __forceinline__ void aime_decisions_done(const AimeDone D) {
+  if (!D.h_gen) return;
+  __threadfence_system();
+  const unsigned prev = __hip_atomic_fetch_add(D.cnt, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+  if (prev + 1u != gridDim.x) return;
+  __hip_atomic_store(D.cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __threadfence_system();
+  __hip_atomic_store(D.h_gen, D.gen, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 __global__ __launch_bounds__(64) void k_aime_branch(const AimeScene *__restrict__ scenes, const float *__restrict__ sel,
                                                     const float *__restrict__ world, unsigned *__restrict__ hit,
                                                     const float *__restrict__ sel_prob, float *__restrict__ h_sel, float *__restrict__ h_selp,
-                                                    unsigned *__restrict__ h_hit, const AimeSmall sm) {
+                                                    unsigned *__restrict__ h_hit, const AimeSmall sm, const AimeDone done) {
   const int b = blockIdx.x / AIME_K, j = blockIdx.x % AIME_K, t = threadIdx.x;
   const AimeScene S = sm.n ? sm.s[b] : scenes[b];
   const int k = (int)sel[(size_t)b * AIME_K + j];
@@ -298,6 +313,7 @@ __global__ __launch_bounds__(64) void k_aime_branch(const AimeScene *__restrict_
   if (h_sel && t == 0) {
     h_hit[2 * (size_t)blockIdx.x] = (unsigned)m; h_hit[2 * (size_t)blockIdx.x + 1] = (unsigned)(m >> 32);
     h_sel[blockIdx.x] = sel[blockIdx.x]; h_selp[blockIdx.x] = sel_prob[blockIdx.x];
+    aime_decisions_done(done);
   }
 }
 
@@ -310,7 +326,7 @@ __global__ __launch_bounds__(64) void k_aime_select_branch(const AimeScene *__re
                                                            const float *__restrict__ ego_end, int lane_check, float dist_thres, float prob_floor,
                                                            const float *__restrict__ world, float *__restrict__ sel, float *__restrict__ sel_prob,
                                                            unsigned *__restrict__ hit, float *__restrict__ h_sel, float *__restrict__ h_selp,
-                                                           unsigned *__restrict__ h_hit, const AimeSmall sm) {
+                                                           unsigned *__restrict__ h_hit, const AimeSmall sm, const AimeDone done) {
   const int b = blockIdx.x / AIME_K, j = blockIdx.x % AIME_K, t = threadIdx.x;
   const AimeScene S = sm.n ? sm.s[b] : scenes[b];
   const float sp = sm.n ? sm.prob[b] : scen_prob[b];
@@ -341,6 +357,7 @@ __global__ __launch_bounds__(64) void k_aime_select_branch(const AimeScene *__re
     if (h_sel) {
       h_hit[2 * (size_t)blockIdx.x] = (unsigned)m; h_hit[2 * (size_t)blockIdx.x + 1] = (unsigned)(m >> 32);
       h_sel[blockIdx.x] = kf; h_selp[blockIdx.x] = pj;
+      aime_decisions_done(done);
     }
   }
 }

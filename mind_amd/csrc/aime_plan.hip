@@ -95,6 +95,8 @@ struct PlTrace {
   }
 };
 
+double pl_steady_now(void *) { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
 // one mind_aime_plan call: what its stages share
 struct PlanRun {
   mind_ctx *c;
@@ -121,6 +123,9 @@ struct PlanRun {
   DevBuf *tabb = nullptr;
   float *d_topo = nullptr, *d_ego = nullptr, *d_sel = nullptr, *d_selp = nullptr, *h_mirror = nullptr, *d_world = nullptr;
   unsigned *d_hit = nullptr;
+  // polled decisions ("dec_poll"): the word behind the mirror that the round's last kernel sets to want_gen (null: the stream is drained)
+  unsigned *h_gen = nullptr, want_gen = 0;
+  int round_no = 0;
   // the next round's inputs and windows (pl_rebase_next)
   int nxt = 0;
   InLayout q{0, 0, 0};
@@ -138,7 +143,7 @@ struct PlanRun {
   bool solves_asked() const { return in->solve_cfg_full && in->solve_x0 && in->solve_lane && in->solve_n_lane_pts >= 2 && !dist; }
   int fail_book(const PlErr &e) const { return fail(c, MIND_ESTATE, pl_err_format(e.code), e.a0, e.a1); }
   // the stages, in the order mind_aime_plan runs them (pl_check needs no PlanRun), and the pieces they share
-  int pl_root(), pl_root_raw(), pl_root_host();
+  int pl_root(), pl_root_raw(), pl_root_host(), pl_presize_next();
   int pl_round_buffers(int round), pl_round_launch(), pl_round_tables(), pl_round_decisions(const float *&h_dec);
   int pl_predict_chunk(int g0, int cb, float *d_cls, float *d_reg, float *d_vel, const float *&d_ctrs, const float *&d_vecs);
   int pl_rebase_next(), pl_exchange_next(int round), pl_next_inputs(), pl_pack_results(), pl_hand_out();
@@ -228,16 +233,31 @@ int PlanRun::pl_root_raw() {
   R.pos = d + o.rpos; R.ang = d + o.rang; R.vel = d + o.rvel; R.pad = d + o.rpad;
   R.lane_ctrs0 = nullptr; R.lane_vecs0 = nullptr; R.travel0 = in->travel0;
   hipLaunchKernelGGL(k_aime_rebase, dim3(1, 1 + RB_FEAT_BLOCKS(a)), dim3(RB_THREADS), 5 * a * sizeof(float), st, R);
-  // The lane graph, the root's world-frame histories and the frame read-back go to the side stream (pl_side_hop): ActorNet, which only needs
-  // k_aime_rebase's features, starts right behind the re-basing (they stood 25 us in front of it)
+  // The lane graph, the root's world-frame histories and the frame read-back go to the side stream: ActorNet only needs k_aime_rebase's
+  // features.  "root_head": the predictor call launches them itself, behind ActorNet -- the lane graph in front of LaneNet, the histories
+  // (read by k_aime_world and the next round's k_aime_windows, behind the decoder's wait for the side stream) and the read-back behind the
+  // target embedding; their launches stood 25 us of host time between the re-basing and ActorNet.  Off: queued here, in front of the call
+  const auto lanes = [this, d](hipStream_t rs) {
+    const RootLayout &o = ro;
+    hipLaunchKernelGGL(k_aime_root_lanes, dim3(l), dim3(64), 0, rs, (const double *)(d + o.lpts), (const int *)(d + o.lfl), (const float *)(d + o.fr),
+                       d + o.lc, d + o.lv, d + o.lanes);
+    HIPCHK(c, hipGetLastError());
+    return (int)MIND_OK;
+  };
+  const auto hist = [this, d](hipStream_t rs) {
+    const RootLayout &o = ro;
+    hipLaunchKernelGGL(k_aime_root_hist, dim3(a), dim3(64), 0, rs, (const float *)(d + o.rpos), (const float *)(d + o.rang), (const float *)(d + o.rvel),
+                       (const float *)(d + o.fr), (const float *)(d + o.ctrs), (const float *)(d + o.vecs), d + o.wpos, d + o.wang, d + o.wvel, d + o.cov);
+    HIPCHK(c, hipGetLastError());
+    return pl_frames_back(d + o.fr, 1, rs);      // the root's frame comes back while the first predictor call runs
+  };
+  if (c->root_head && c->side && !dist) {
+    c->enc_pre = lanes; c->enc_post = hist;
+    return MIND_OK;
+  }
   hipStream_t rs;
-  if ((rc = pl_side_hop(rs))) return rc;
-  hipLaunchKernelGGL(k_aime_root_lanes, dim3(l), dim3(64), 0, rs, (const double *)(d + o.lpts), (const int *)(d + o.lfl), (const float *)(d + o.fr),
-                     d + o.lc, d + o.lv, d + o.lanes);
-  hipLaunchKernelGGL(k_aime_root_hist, dim3(a), dim3(64), 0, rs, (const float *)(d + o.rpos), (const float *)(d + o.rang), (const float *)(d + o.rvel),
-                     (const float *)(d + o.fr), (const float *)(d + o.ctrs), (const float *)(d + o.vecs), d + o.wpos, d + o.wang, d + o.wvel, d + o.cov);
-  HIPCHK(c, hipGetLastError());
-  return pl_frames_back(d + o.fr, 1, rs);      // the root's frame comes back while the first predictor call runs
+  if ((rc = pl_side_hop(rs)) || (rc = lanes(rs))) return rc;
+  return hist(rs);
 }
 
 // ... host-featurised: everything goes up, the root's frame is the caller's
@@ -279,7 +299,13 @@ int PlanRun::pl_root() {
   if ((rc = raw ? pl_root_raw() : pl_root_host())) return rc;
   if ((rc = ensure(c, c->pl_lf, (size_t)l * 128 * sizeof(float)))) return rc;
   // the lane-distance field of the contingency solves this plan will begin: everything it depends on is known now (il_solve adopts it)
-  if (solves_asked() && (rc = il_field_prepare(c, in->solve_cfg_full, in->solve_x0, in->solve_lane, in->solve_n_lane_pts, c->pl_copy))) return rc;
+  if (solves_asked()) {
+    const auto field = [this]() { return il_field_prepare(c, in->solve_cfg_full, in->solve_x0, in->solve_lane, in->solve_n_lane_pts, c->pl_copy); };
+    if (c->enc_post) {      // ("root_head": behind ActorNet's launch with the rest)
+      const std::function<int(hipStream_t)> hist = std::move(c->enc_post);
+      c->enc_post = [hist, field](hipStream_t rs) { const int rc_ = hist(rs); return rc_ ? rc_ : field(); };
+    } else if ((rc = field())) return rc;
+  }
   prev_pos = droot + ro.wpos; prev_ang = droot + ro.wang; prev_vel = droot + ro.wvel;
   cov_last_dev = droot + ro.cov;
   return MIND_OK;
@@ -297,9 +323,10 @@ int PlanRun::pl_round_buffers(int round) {
   d_topo = (float *)c->pl_small.p; d_ego = d_topo + n_topo; d_sel = d_ego + n_ego; d_selp = d_sel + (size_t)Bmax * 6;
   d_hit = (unsigned *)(d_selp + (size_t)Bmax * 6);
   // unsharded: the round's last kernel writes the decisions where the host reads them (same layout as the device buffer)
-  h_mirror = nullptr;
+  h_mirror = nullptr; h_gen = nullptr;
+  round_no = round;
   if (!dist && c->dec_mirror) {
-    if ((rc = pl_pin(c, 2, n_back * sizeof(float)))) return rc;
+    if ((rc = pl_pin(c, 2, n_back * sizeof(float) + 64))) return rc;      // (+ the generation word of the polled decisions)
     h_mirror = (float *)c->pl_pin[2];
   }
   tabb = &c->pl_tab[round & 1];
@@ -322,6 +349,18 @@ int PlanRun::pl_round_buffers(int round) {
   }
   tables_done = false;
   all_small = c->tab_small && std::min(chunk, std::max(Bk, 1)) <= AIME_SMALL;
+  // a round of one launch whose decisions are mirrored: its last kernel marks them complete and the host polls (pl_round_decisions).  The word
+  // is cleared here, before the launch: slot 2's last writer (the previous round's kernel, the previous plan's read-back) has been waited for
+  if (h_mirror && c->dec_poll && Bk > 0 && chunk >= Bk) {
+    if (!c->pl_cnt.p) {
+      if ((rc = ensure(c, c->pl_cnt, 64))) return rc;
+      HIPCHK(c, hipMemsetAsync(c->pl_cnt.p, 0, 64, st));      // (once: the block that arrives last re-arms the counter)
+    }
+    h_gen = (unsigned *)(h_mirror + n_back);
+    if (++c->dec_gen == 0u) c->dec_gen = 1u;
+    want_gen = c->dec_gen;
+    __atomic_store_n(h_gen, 0u, __ATOMIC_RELEASE);
+  }
   return MIND_OK;
 }
 
@@ -441,13 +480,14 @@ int PlanRun::pl_round_launch() {
     float *hs_ = h_mirror ? h_mirror + (size_t)c0 * 6 : nullptr, *hp_ = h_mirror ? h_mirror + (size_t)Bmax * 6 + (size_t)c0 * 6 : nullptr;
     unsigned *hh_ = h_mirror ? (unsigned *)(h_mirror + (size_t)Bmax * 12) + (size_t)c0 * 12 : nullptr;
     const float pf_ = in->prob_floor > 0.f ? in->prob_floor : 0.001f;
+    const AimeDone dn{h_gen ? (unsigned *)c->pl_cnt.p : nullptr, h_gen, want_gen};
     if (c->glue_fused) {
       // pruning decisions + branch-time bits in one launch (every block derives its scene's decisions itself)
       hipLaunchKernelGGL(k_aime_select_branch, dim3(cb * AIME_K), dim3(64), 0, st, t_sc, d_cls, t_prob, topo_c, ego_c, 1, in->dist_thres, pf_, w_c, sel_c, selp_c,
-                         hit_c, hs_, hp_, hh_, sm);
+                         hit_c, hs_, hp_, hh_, sm, dn);
     } else {
       hipLaunchKernelGGL(k_aime_select, dim3(cb), dim3(64), 0, st, t_sc, d_cls, t_prob, topo_c, ego_c, 1, in->dist_thres, sel_c, selp_c, pf_, sm);
-      hipLaunchKernelGGL(k_aime_branch, dim3(cb * AIME_K), dim3(64), 0, st, t_sc, sel_c, w_c, hit_c, (const float *)selp_c, hs_, hp_, hh_, sm);
+      hipLaunchKernelGGL(k_aime_branch, dim3(cb * AIME_K), dim3(64), 0, st, t_sc, sel_c, w_c, hit_c, (const float *)selp_c, hs_, hp_, hh_, sm, dn);
     }
     HIPCHK(c, hipGetLastError());
   }
@@ -468,10 +508,37 @@ int PlanRun::pl_round_decisions(const float *&h_dec) {
     HIPCHK(c, hipMemcpyAsync(c->pl_pin[2], d_sel, n_back * sizeof(float), hipMemcpyDeviceToHost, st));
   }
   TR("round: glue launched, waiting for the decisions");
-  HIPCHK(c, hipStreamSynchronize(st));
+  if (h_gen) {
+    // what the next round needs whatever is decided, while the device works; then the word -- bounded: past the time-out (a round of many
+    // scenes, a launch that failed) the stream is drained as before and the same bytes are read
+    if ((rc = pl_presize_next())) return rc;
+    if (!pl_wait_word(h_gen, want_gen, 0.25, pl_steady_now, nullptr, 1024)) {
+      HIPCHK(c, hipStreamSynchronize(st));
+      HIPCHK(c, hipMemsetAsync(c->pl_cnt.p, 0, 64, st));      // (whatever a failed launch left in the counter)
+    }
+  } else {
+    HIPCHK(c, hipStreamSynchronize(st));
+  }
   TR("round: decisions on the host");
   h_dec = (const float *)c->pl_pin[2];
   return MIND_OK;
+}
+
+// ---- the next round's inputs, windows, repeated lane features and frame staging at the largest branch set this round can produce (every kept
+//      mode of every scene branches), in front of the wait for the decisions instead of behind it.  Only while that bound stays in the
+//      doubling regime of ensure (64 MB): a big round's buffers are sized from its real branch set (pl_rebase_next), not from six times it.
+//      (pl_lrep may be what this round's token kernels are reading: before a buffer grows the stream is drained, as it was before the old
+//      place of these calls -- in the first plans of a process only)
+int PlanRun::pl_presize_next() {
+  if (round_no + 1 >= in->max_rounds) return MIND_OK;
+  const size_t OBS = RB_T, S = (size_t)g.B * AIME_K;
+  const int n = cur_in < 0 ? 0 : cur_in ^ 1;
+  const size_t b_in = InLayout(S, a, l).total * sizeof(float), b_win = S * a * OBS * 5 * sizeof(float), b_rep = S * l * 128 * sizeof(float);
+  if (std::max(b_in, std::max(b_win, b_rep)) >= ((size_t)64 << 20)) return MIND_OK;
+  int rc;
+  if (b_in > c->pl_in[n].cap || b_win > c->pl_win[n].cap || b_rep > c->pl_lrep.cap) HIPCHK(c, hipStreamSynchronize(st));
+  if ((rc = ensure(c, c->pl_in[n], b_in)) || (rc = ensure(c, c->pl_win[n], b_win)) || (rc = ensure(c, c->pl_lrep, b_rep))) return rc;
+  return pl_pin(c, 3, S * 28 * sizeof(float));
 }
 
 // ---- update_obser (:467-567) of the branching nodes: windows + predictor inputs of the next round, on the device; a rank re-bases the
@@ -583,16 +650,26 @@ int PlanRun::pl_next_inputs() {
   int nlo, nhi, rc;
   pl_block(S, XR, XW, nlo, nhi);
   // (unsharded: the repeated lane features -- read by the token kernels, behind the predictor's side-stream work -- and the frames' read-back
-  // go to the side stream; ActorNet follows the re-basing directly)
-  hipStream_t rs;
-  if ((rc = pl_side_hop(rs))) return rc;
-  if (nhi - nlo > 1) {
-    if ((rc = ensure(c, c->pl_lrep, (size_t)(nhi - nlo) * l * 128 * sizeof(float)))) return rc;
-    const size_t n = (size_t)l * 128;
-    hipLaunchKernelGGL(k_repeat_rows, dim3((unsigned)((n * (nhi - nlo) + 255) / 256)), dim3(256), 0, rs, (const float *)c->pl_lf.p, n, nhi - nlo, (float *)c->pl_lrep.p);
-    HIPCHK(c, hipGetLastError());
+  // go to the side stream; ActorNet follows the re-basing directly.  "round_head": the predictor call launches them itself, behind ActorNet --
+  // the lane features in front of the token positions, the read-back behind the target embedding.  Off: queued here, in front of the call)
+  const int n_rep = nhi - nlo;
+  if (n_rep > 1 && (rc = ensure(c, c->pl_lrep, (size_t)n_rep * l * 128 * sizeof(float)))) return rc;
+  const auto rep = [this, n_rep](hipStream_t rs) {
+    if (n_rep > 1) {
+      const size_t n = (size_t)l * 128;
+      hipLaunchKernelGGL(k_repeat_rows, dim3((unsigned)((n * n_rep + 255) / 256)), dim3(256), 0, rs, (const float *)c->pl_lf.p, n, n_rep, (float *)c->pl_lrep.p);
+      HIPCHK(c, hipGetLastError());
+    }
+    return (int)MIND_OK;
+  };
+  const float *d_fr = d_in + q.fr;
+  const auto back = [this, d_fr, S](hipStream_t rs) { return pl_frames_back(d_fr, (size_t)S, rs); };
+  if (c->round_head && c->side && !dist) {
+    c->enc_pre = rep; c->enc_post = back;
+  } else {
+    hipStream_t rs;
+    if ((rc = pl_side_hop(rs)) || (rc = rep(rs)) || (rc = back(rs))) return rc;
   }
-  if ((rc = pl_frames_back(d_in + q.fr, (size_t)S, rs))) return rc;
   prev_pos = w_pos; prev_ang = w_ang; prev_vel = w_vel;
   cov_last_dev = d_in + q.cov;
   cur_in = nxt;
@@ -717,6 +794,7 @@ extern "C" int mind_aime_plan(mind_ctx *c, const mind_aime_plan_in *in, mind_aim
   if (!c->ev_pl) HIPCHK(c, hipEventCreateWithFlags(&c->ev_pl, hipEventDisableTiming));
   if (!c->ev_tab) HIPCHK(c, hipEventCreateWithFlags(&c->ev_tab, hipEventDisableTiming));
   if (!c->pl_copy) HIPCHK(c, hipStreamCreateWithFlags(&c->pl_copy, hipStreamNonBlocking));
+  struct HookGuard { mind_ctx *c; ~HookGuard() { c->enc_pre = nullptr; c->enc_post = nullptr; } } hook_guard{c};      // (they capture this call's PlanRun)
   if ((rc = p.pl_root())) return rc;
   memset(out, 0, sizeof(*out));
   p.TR.t0 = std::chrono::steady_clock::now();      // (the stamps count from here, behind the root upload)
@@ -805,6 +883,12 @@ extern "C" int mind_ctx_busy(mind_ctx *c) {
   if (e == hipErrorNotReady) return 1;
   if (e != hipSuccess) return fail(c, MIND_EHIP, "mind_ctx_busy: %s", hipGetErrorString(e));
   return 0;
+}
+
+// pl_wait_word, the bounded wait of the polled decisions, over the caller's word and clock (clock null: the steady clock)
+extern "C" int mind_debug_wait_word(const unsigned *word, unsigned want, double timeout_s, double (*clock)(void *), void *user, int spins_per_look) {
+  if (!word || !(timeout_s >= 0.0) || spins_per_look <= 0) return MIND_EINVAL;
+  return pl_wait_word(word, want, timeout_s, clock ? clock : pl_steady_now, user, (unsigned)spins_per_look) ? 1 : 0;
 }
 
 // AimeBook's records, pl_route's tables and pl_chunk for a stream of decision words (layout: include/mind_hip.h)

@@ -344,6 +344,71 @@ __device__ __forceinline__ void dense(const float *in, int ldi, int K, const flo
   }
 }
 
+// The K split dense<> takes on its scalar path (R > 8: KP thread groups of NOUT threads, as many as the partial-sum area holds), as a constant
+constexpr int dense_scalar_kp(int R, int NOUT, int K, int nthr, int part_floats) {
+  int KP = NOUT < nthr ? nthr / NOUT : 1;
+  while (KP > 1 && (KP * R * NOUT > part_floats || (K / 4) < KP)) KP >>= 1;
+  int p2 = 1;
+  while (p2 * 2 <= KP) p2 *= 2;
+  return p2;
+}
+
+// dense<>'s scalar K-split path with the split GIVEN (KP > 1 parts of Kc = ceil(K / 4 / KP) * 4 inputs): per output element the same chain of
+// fused multiply-adds over its part and the same bias + partial sums in part order, so R rows here carry the bits of the same rows in a
+// dense<R'> that took KP on that path, whatever R' -- while the threads are dealt over (rows in groups of RPT, part, output) instead of
+// (part, output) alone: with few rows more of the workgroup works.  K a multiple of 4, KP * R * NOUT floats of `part`.
+template <int R, int RPT>
+__device__ __forceinline__ void dense_ksplit(const float *in, int ldi, int K, const float *__restrict__ WT, const float *__restrict__ b, int NOUT,
+                                             float *out, int ldo, float *part, int KP) {
+  const int nthr = blockDim.x;
+  constexpr int NG = (R + RPT - 1) / RPT;
+  const int Kc = ((K / 4 + KP - 1) / KP) * 4;
+  for (int item = threadIdx.x; item < NG * KP * NOUT; item += nthr) {
+    const int o = item % NOUT, kp = (item / NOUT) % KP, r0 = (item / (NOUT * KP)) * RPT;
+    float acc[RPT];
+#pragma unroll
+    for (int j = 0; j < RPT; ++j) acc[j] = 0.f;
+    const int k0 = kp * Kc, k1 = min(K, k0 + Kc);
+    int k = k0;
+    for (; k + DB <= k1; k += DB) {
+      float w[DB];
+#pragma unroll
+      for (int q = 0; q < DB; ++q) w[q] = WT[(size_t)(k + q) * NOUT + o];
+#pragma unroll
+      for (int j = 0; j < RPT; ++j) {
+        if (r0 + j >= R) continue;
+#pragma unroll
+        for (int q4 = 0; q4 < DB / 4; ++q4) {
+          const f32x4 x = *(const f32x4 *)(in + (r0 + j) * ldi + k + 4 * q4);
+          acc[j] = fmaf(w[4 * q4 + 0], x[0], acc[j]);
+          acc[j] = fmaf(w[4 * q4 + 1], x[1], acc[j]);
+          acc[j] = fmaf(w[4 * q4 + 2], x[2], acc[j]);
+          acc[j] = fmaf(w[4 * q4 + 3], x[3], acc[j]);
+        }
+      }
+    }
+    for (; k < k1; k += 4) {
+#pragma unroll
+      for (int j = 0; j < RPT; ++j) {
+        if (r0 + j >= R) continue;
+        const f32x4 x = *(const f32x4 *)(in + (r0 + j) * ldi + k);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[j] = fmaf(WT[(size_t)(k + q) * NOUT + o], x[q], acc[j]);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < RPT; ++j)
+      if (r0 + j < R) part[(kp * R + r0 + j) * NOUT + o] = acc[j];
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < R * NOUT; i += nthr) {
+    const int r = i / NOUT, oo = i % NOUT;
+    float v = b ? b[oo] : 0.f;
+    for (int q = 0; q < KP; ++q) v += part[(q * R + r) * NOUT + oo];
+    out[r * ldo + oo] = v;
+  }
+}
+
 // LayerNorm (+ReLU) over `n` features of each of R rows, in place; one wave per row (4 waves).
 #define LN_REGS 12      // elements per lane held in registers: rows of up to 768 features
 __device__ __forceinline__ void ln_rows(float *buf, int ld, int R, int n, const float *__restrict__ g,
@@ -943,7 +1008,11 @@ __global__ __launch_bounds__(DT) void k_dec_scene_mw(const float *__restrict__ x
 // PART 0: the whole actor part.  PART 1 / 2: its two halves as separate launches -- actor_proj (128 -> 384 -> 768, needs only the
 // fused actor tokens: runs on the side stream beside k_dec_scene) writes h2g [A,768]; the head (mode embedding, reg head, Bezier)
 // reads it once k_dec_scene's Cmode / tgt are there.  Same code, same arithmetic per element in all three.
-template <int PART>
+// RAT (PART 2 only): agents per workgroup of the head.  A demo-size call has a few dozen agents: at RA = 4 the head ran on 9 of 256 CUs, a
+// quarter of each workgroup's threads in its two 128 -> 128 stages (dense<24> is capped at a K split of 2 by the partial-sum area) and the
+// LayerNorms, the 128 -> 40 stage and the Bezier loop four agents deep.  With 1 or 2 agents per workgroup the two stages take that same
+// split explicitly (dense_ksplit: the bits of dense<RA * 6>) with the rows dealt over the idle threads; everything else is per row.
+template <int PART, int RAT = RA>
 __global__ __launch_bounds__(DT) void k_dec_actor(const float *__restrict__ x /*[tokens,128]*/,
                                                   const int *__restrict__ actor_row /*[A]*/,
                                                   const int *__restrict__ actor_scene /*[A]*/, int n_actors,
@@ -959,38 +1028,40 @@ __global__ __launch_bounds__(DT) void k_dec_actor(const float *__restrict__ x /*
   float (*prm)[40] = (float (*)[40])(dsm + 11264);
   float *part = dsm + 12224;
   const int PF = 6144;
+  static_assert(RAT == RA || (PART == 2 && (RAT == 1 || RAT == 2)), "only the head runs with fewer agents per workgroup");
+  constexpr int HEAD_KP = dense_scalar_kp(RA * 6, 128, 128, DT, 6144);      // the split of dense<RA * 6> below
   const int tid = threadIdx.x;
-  const int a0 = blockIdx.x * RA;
+  const int a0 = blockIdx.x * RAT;
   if (PART != 2) {
-    for (int i = tid; i < RA * 128; i += blockDim.x) {
+    for (int i = tid; i < RAT * 128; i += blockDim.x) {
       const int r = i / 128, a = a0 + r;
       xin[r][i % 128] = a < n_actors ? x[(size_t)actor_row[a] * 128 + i % 128] : 0.f;
     }
     __syncthreads();
-    dense<RA>(&xin[0][0], 128, 128, W.a0W, W.a0b, 384, &h1[0][0], 384, part, PF);
+    dense<RAT>(&xin[0][0], 128, 128, W.a0W, W.a0b, 384, &h1[0][0], 384, part, PF);
     __syncthreads();
-    ln_rows(&h1[0][0], 384, RA, 384, W.a0g, W.a0be, true);
+    ln_rows(&h1[0][0], 384, RAT, 384, W.a0g, W.a0be, true);
     __syncthreads();
-    dense<RA>(&h1[0][0], 384, 384, W.a3W, W.a3b, 768, &h2[0][0], 768, part, PF);
+    dense<RAT>(&h1[0][0], 384, 384, W.a3W, W.a3b, 768, &h2[0][0], 768, part, PF);
     __syncthreads();
-    ln_rows(&h2[0][0], 768, RA, 768, W.a3g, W.a3be, true);
+    ln_rows(&h2[0][0], 768, RAT, 768, W.a3g, W.a3be, true);
     __syncthreads();
     if (PART == 1) {
-      for (int i = tid; i < RA * 768; i += blockDim.x) {
+      for (int i = tid; i < RAT * 768; i += blockDim.x) {
         const int r = i / 768, a = a0 + r;
         if (a < n_actors) h2g[(size_t)a * 768 + i % 768] = h2[r][i % 768];
       }
       return;
     }
   } else {
-    for (int i = tid; i < RA * 768; i += blockDim.x) {
+    for (int i = tid; i < RAT * 768; i += blockDim.x) {
       const int r = i / 768, a = a0 + r;
       h2[r][i % 768] = a < n_actors ? h2g[(size_t)a * 768 + i % 768] : 0.f;
     }
     __syncthreads();
   }
   // embed = cls_embed + actor_embed (+ tgt on mode 0 only)  (network.py:506-510)
-  for (int i = tid; i < RA * 768; i += blockDim.x) {
+  for (int i = tid; i < RAT * 768; i += blockDim.x) {
     const int r = i / 768, k = (i % 768) / 128, c = i % 128;
     const int a = a0 + r;
     float v = 0.f;
@@ -1002,16 +1073,18 @@ __global__ __launch_bounds__(DT) void k_dec_actor(const float *__restrict__ x /*
     E[r * 6 + k][c] = v;
   }
   __syncthreads();
-  dense<RA * 6>(&E[0][0], 128, 128, W.r0W, W.r0b, 128, &t1[0][0], 128, part, PF);
+  if (RAT == RA) dense<RA * 6>(&E[0][0], 128, 128, W.r0W, W.r0b, 128, &t1[0][0], 128, part, PF);
+  else dense_ksplit<RAT * 6, RAT + 1>(&E[0][0], 128, 128, W.r0W, W.r0b, 128, &t1[0][0], 128, part, HEAD_KP);
   __syncthreads();
-  ln_rows(&t1[0][0], 128, RA * 6, 128, W.r0g, W.r0be, true);
+  ln_rows(&t1[0][0], 128, RAT * 6, 128, W.r0g, W.r0be, true);
   __syncthreads();
-  dense<RA * 6>(&t1[0][0], 128, 128, W.r3W, W.r3b, 128, &E[0][0], 128, part, PF);
+  if (RAT == RA) dense<RA * 6>(&t1[0][0], 128, 128, W.r3W, W.r3b, 128, &E[0][0], 128, part, PF);
+  else dense_ksplit<RAT * 6, RAT + 1>(&t1[0][0], 128, 128, W.r3W, W.r3b, 128, &E[0][0], 128, part, HEAD_KP);
   __syncthreads();
-  ln_rows(&E[0][0], 128, RA * 6, 128, W.r3g, W.r3be, true);
+  ln_rows(&E[0][0], 128, RAT * 6, 128, W.r3g, W.r3be, true);
   __syncthreads();
   // 128 -> 40 = 8 control points x (x, y, sx, sy, rho)
-  for (int i = tid; i < RA * 6 * 40; i += blockDim.x) {
+  for (int i = tid; i < RAT * 6 * 40; i += blockDim.x) {
     const int r = i / 40, o = i % 40;
     float acc = W.r6b[o];
     for (int k = 0; k < 128; ++k) acc = fmaf(W.r6W[k * 40 + o], E[r][k], acc);
@@ -1019,7 +1092,7 @@ __global__ __launch_bounds__(DT) void k_dec_actor(const float *__restrict__ x /*
   }
   __syncthreads();
   // Bezier evaluation (network.py:515-523,545): pos = T P, cov = exp(T S), vel = Tp dP / 6
-  for (int i = tid; i < RA * 6 * 60; i += blockDim.x) {
+  for (int i = tid; i < RAT * 6 * 60; i += blockDim.x) {
     const int r = i / 60, t = i % 60;
     const int a = a0 + r / 6, k = r % 6;
     if (a >= n_actors) continue;

@@ -96,6 +96,17 @@ struct mind_ctx {
   bool dec_mirror = true;
   // ... and its pruning decisions + branch-time bits come from one launch (k_aime_select_branch) instead of two.  "glue_fused" / MIND_GLUE_FUSED
   bool glue_fused = true;
+  // ... and that kernel marks the mirrored decisions complete (a generation word behind them, counted in by its blocks on pl_cnt): the host
+  // polls the word instead of draining the stream and sizes the next round's buffers while it waits (unchunked rounds).  "dec_poll" / MIND_DEC_POLL
+  bool dec_poll = true;
+  unsigned dec_gen = 0;
+  DevBuf pl_cnt;
+  // ... and what a round queues beside ActorNet -- the root's lane graph, world-frame histories and lane-distance field ("root_head" /
+  // MIND_ROOT_HEAD), a later round's repeated lane features ("round_head" / MIND_ROUND_HEAD), the frames' read-back -- is handed to the round's
+  // first predictor call, which launches ActorNet first: enc_pre goes on the side stream in front of the lane encoders, enc_post behind the
+  // target embedding (pred_encoders; both are the plan's, cleared when it returns)
+  bool root_head = true, round_head = true;
+  std::function<int(hipStream_t)> enc_pre, enc_post;
   // mind_loop: price a candidate tree as soon as the pending tree-iLQR launch marks it complete, beside the trees still being solved.  "early_eval" / MIND_EARLY_EVAL
   bool early_eval = true;
   // ... and its small index tables (the branch set of a round, the job tables of the two packing kernels) are read by the kernels from the
@@ -344,6 +355,9 @@ extern "C" int mind_ctx_create(int device, void *stream, mind_ctx **out) {
   if (const char *we = getenv("MIND_EARLY_EVAL")) c->early_eval = atoi(we) != 0;
   if (const char *we = getenv("MIND_GLUE_FUSED")) c->glue_fused = atoi(we) != 0;
   if (const char *we = getenv("MIND_DEC_MIRROR")) c->dec_mirror = atoi(we) != 0;
+  if (const char *we = getenv("MIND_DEC_POLL")) c->dec_poll = atoi(we) != 0;
+  if (const char *we = getenv("MIND_ROOT_HEAD")) c->root_head = atoi(we) != 0;
+  if (const char *we = getenv("MIND_ROUND_HEAD")) c->round_head = atoi(we) != 0;
   if (const char *we = getenv("MIND_UPLOAD_KERNEL_MAX")) c->upload_kernel_max = std::max(0, atoi(we));
   // (the same clamps as mind_set_tuning: one function sets a knob)
   const char *const il_env[][2] = {{"MIND_ILQR_CHUNK", "ilqr_chunk"}, {"MIND_ILQR_WGS", "ilqr_wgs"}, {"MIND_ILQR_SPEC_DERIV", "ilqr_spec_deriv"},
@@ -358,6 +372,9 @@ extern "C" int mind_ctx_create(int device, void *stream, mind_ctx **out) {
   (void)hipFuncSetAttribute((const void *)k_dec_actor<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_dec_actor_lds_bytes());
   (void)hipFuncSetAttribute((const void *)k_dec_actor<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_dec_actor_lds_bytes());
   (void)hipFuncSetAttribute((const void *)k_dec_actor<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_dec_actor_lds_bytes());
+  (void)hipFuncSetAttribute((const void *)k_dec_actor<2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_dec_actor_lds_bytes());
+  (void)hipFuncSetAttribute((const void *)k_dec_actor<2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_dec_actor_lds_bytes());
+  if (const char *te = getenv("MIND_DEC_HEAD_RA")) (void)pred_tuning_set(c->pt, "dec_head_ra", atoi(te));
   *out = c;
   return MIND_OK;
 }
@@ -379,7 +396,7 @@ extern "C" int mind_ctx_destroy(mind_ctx *c) {
     if (b->p) (void)hipFree(b->p);
   if (c->dec_abort) (void)hipHostFree(c->dec_abort);
   for (DevBuf *b : {&c->pl_root, &c->pl_in[0], &c->pl_in[1], &c->pl_lf, &c->pl_lrep, &c->pl_pred, &c->pl_small, &c->pl_tab[0], &c->pl_tab[1], &c->pl_win[0],
-                    &c->pl_win[1], &c->pl_flat, &c->x_send, &c->x_recv, &c->x_seg})
+                    &c->pl_win[1], &c->pl_flat, &c->x_send, &c->x_recv, &c->x_seg, &c->pl_cnt})
     if (b->p) (void)hipFree(b->p);
   for (DevBuf &b : c->pl_world)
     if (b.p) (void)hipFree(b.p);
@@ -433,6 +450,9 @@ extern "C" int mind_set_tuning(mind_ctx *c, const char *name, int value) {
   else if (n == "early_eval") c->early_eval = value != 0;
   else if (n == "glue_fused") c->glue_fused = value != 0;
   else if (n == "dec_mirror") c->dec_mirror = value != 0;
+  else if (n == "dec_poll") c->dec_poll = value != 0;
+  else if (n == "root_head") c->root_head = value != 0;
+  else if (n == "round_head") c->round_head = value != 0;
   else if (n == "upload_kernel_max") c->upload_kernel_max = value < 0 ? 0 : value;
   else return fail(c, MIND_EINVAL, "mind_set_tuning: unknown knob '%s'", name);
   return MIND_OK;
@@ -905,11 +925,11 @@ extern "C" int mind_debug_aime_decide(mind_ctx *c, int n_scenes, const int32_t *
     const int lc = lane_check ? 1 : 0;
     if (fused) {
       hipLaunchKernelGGL(k_aime_select_branch, dim3(B * AIME_K), dim3(64), 0, st, t_sc, cls, t_prob, topo, ego_end, lc, dist_thres, pf_, world, sel, sel_prob,
-                         hit, (float *)nullptr, (float *)nullptr, (unsigned *)nullptr, sm);
+                         hit, (float *)nullptr, (float *)nullptr, (unsigned *)nullptr, sm, AimeDone{nullptr, nullptr, 0u});
     } else {
       hipLaunchKernelGGL(k_aime_select, dim3(B), dim3(64), 0, st, t_sc, cls, t_prob, topo, ego_end, lc, dist_thres, sel, sel_prob, pf_, sm);
       hipLaunchKernelGGL(k_aime_branch, dim3(B * AIME_K), dim3(64), 0, st, t_sc, (const float *)sel, world, hit, (const float *)sel_prob, (float *)nullptr,
-                         (float *)nullptr, (unsigned *)nullptr, sm);
+                         (float *)nullptr, (unsigned *)nullptr, sm, AimeDone{nullptr, nullptr, 0u});
     }
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(st);

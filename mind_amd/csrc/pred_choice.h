@@ -2,7 +2,7 @@
 // setting and the call's scene sizes into a record of decisions (PredChoice).  No HIP call, no context: predict.hip's stages switch on the
 // record and read no knob themselves; tests read it through mind_debug_predict_choice.  A new kernel form is a knob here (if it has one), a
 // case in pred_choose and a case in the stage that launches its family.
-// Included by mind_hip.hip behind the kernel files (LW_CHUNK, TL_CHUNK, DEC_MW_G, P6_QK_STRIDE, LW_NSTAGE) and pair_jobs.h.
+// Included by mind_hip.hip behind the kernel files (LW_CHUNK, TL_CHUNK, DEC_MW_G, RA, P6_QK_STRIDE, LW_NSTAGE) and pair_jobs.h.
 #pragma once
 #include <cstring>
 #include <vector>
@@ -44,6 +44,10 @@ struct PredTuning {
   int tok_small_max = 2048;     // batches of at most this many tokens run k_token with 4 tokens per workgroup ("tok_small_max")
   int dec_mfma_min = 1 << 30;   // agents per call from which the decoder's actor part runs on the MFMA kernel (MIND_DEC_MFMA_MIN; default: never)
   bool dec_overlap = true;      // actor_proj of the decoder on the side stream beside k_dec_scene (mind_set_tuning("dec_overlap"))
+  // agents per workgroup of the split decoder's head, k_dec_actor<2, .> ("dec_head_ra"): 0 (default) = by the call's agents -- 1 while they fit
+  // one workgroup per CU, else 2, else RA = 4; 1, 2 or 4 = that form whatever the call (4: the head as it was).  The forms give the same bits,
+  // so the rule may look at the batch
+  int dec_head_ra = 0;
   // k_dec_scene_mw: eight workgroups per scene on the decoder's five big stages (bit-identical to the one-workgroup kernel), possible whenever
   // every workgroup of the launch is resident, i.e. for calls of at most n_cu / 8 scenes.  Opt-in ("dec_mw" / MIND_DEC_MW=1): measured 88.6
   // against 94.9 us per demo-size launch (profiles/r06aa_*) -- only ctx_proj's second layer is really bound by one CU's L2 port (30 k -> 20 k
@@ -71,6 +75,7 @@ static bool pred_tuning_set(PredTuning &t, const char *name, int value) {
   else if (is("xcd_order")) t.xcd_order = value != 0;
   else if (is("pair_tile")) t.pair_tile = value != 0;
   else if (is("dec_overlap")) t.dec_overlap = value != 0;
+  else if (is("dec_head_ra")) t.dec_head_ra = (value == 1 || value == 2 || value == RA) ? value : 0;
   else if (is("tok_mfma")) t.tok_mfma = value != 0;
   else if (is("tok_small_max")) t.tok_small_max = value;
   else if (is("tok_merge")) t.tok_merge = value != 0;
@@ -128,6 +133,7 @@ struct PredChoice {
   int xcd_lanes = 1, xcd_lanes5 = 1;
   // decoder: actor part, the wish for k_dec_scene_mw and its workgroups, the cls head on the side stream when the scene part is not mw
   int dec_actor = PRED_DEC_ONE;
+  int dec_head_ra = RA;         // agents per workgroup of the split form's head
   bool fp32_dec = true, split_dec = false, want_mw = false, cls_side = false;
   int mw_blocks = 0;
   bool tgt_wait_first = false;  // the context stream waits for the target embedding before the fusion layers
@@ -212,6 +218,8 @@ static PredChoice pred_choose(const PredTuning &t, int pair_prec, int n_cu, bool
   ch.fp32_dec = pair_prec == 0 || !t.enc_mfma || A < t.dec_mfma_min;
   ch.split_dec = ch.fp32_dec && have_side && t.dec_overlap;
   ch.dec_actor = ch.split_dec ? PRED_DEC_SPLIT : ch.fp32_dec ? PRED_DEC_ONE : PRED_DEC_MFMA;
+  // the split form's head on as many workgroups as the agents give while each has a CU to itself (same bits in every form)
+  if (ch.split_dec) ch.dec_head_ra = t.dec_head_ra ? t.dec_head_ra : A <= n_cu ? 1 : (A + 1) / 2 <= n_cu ? 2 : RA;
   ch.mw_blocks = ((n_scenes + 7) / 8) * 8 * DEC_MW_G;
   ch.want_mw = t.dec_mw && ch.mw_blocks <= n_cu;
   ch.cls_side = ch.split_dec && t.dec_cls_side;

@@ -124,7 +124,7 @@ extern "C" int mind_debug_predict_choice(const char *const *knob_names, const in
       PRED_CHOICE_HEADER, (long long)ch.tok_runs.size(), ch.np, ch.actor_form, ch.actor_arg, ch.actor_grid, ch.actor_chunk, ch.actor_chunks,
       ch.actor_launches, ch.qsplit, ch.qk_stride, ch.tiled, ch.edge_bf16, pred_edge_pair_bytes(t, pair_prec), ch.tok_chunk, ch.tok_lw,
       ch.last_tok_chunks, ch.pair_family, ch.pair_np, ch.l5_jobs5, ch.xcd_lanes, ch.xcd_lanes5, ch.dec_actor, mfma_dec ? ch.np : 0,
-      ch.fp32_dec, ch.split_dec, ch.want_mw, ch.mw_blocks, ch.cls_side && !ch.want_mw, ch.tgt_wait_first, 0, 0};
+      ch.fp32_dec, ch.split_dec, ch.want_mw, ch.mw_blocks, ch.cls_side && !ch.want_mw, ch.tgt_wait_first, ch.split_dec ? ch.dec_head_ra : 0, 0};
   std::vector<long long> rec(head, head + PRED_CHOICE_HEADER);
   for (const PredTokRun &r : ch.tok_runs) rec.insert(rec.end(), {r.t0, r.n, r.kind, r.layerwise, r.small, r.merged});
   for (size_t i = 0; i < rec.size() && (int)i < cap; ++i) out[i] = rec[i];
@@ -287,6 +287,12 @@ static int pred_encoders(PredCall &p) {
   int rc;
   if ((rc = pred_actor_net(p))) return rc;
   if (act_timed) HIPCHK(c, hipEventRecord(c->ev_act1, st));
+  // (a plan's own work for the side stream, launched behind ActorNet: in front of the lane encoders here, behind the target embedding below)
+  if (c->enc_pre) {
+    const std::function<int(hipStream_t)> pre = std::move(c->enc_pre);
+    c->enc_pre = nullptr;
+    if ((rc = pre(ss))) return rc;
+  }
   p.lane_feat = in->lane_feat;
   if (!p.lane_feat) {
     float *lf = p.out->lane_feat ? p.out->lane_feat : (float *)c->lane_feat.p;
@@ -306,6 +312,11 @@ static int pred_encoders(PredCall &p) {
   hipLaunchKernelGGL(k_lane_net, dim3((Bn + PL - 1) / PL), dim3(DT), 0, ss, in->tgt_nodes, Bn, (float *)c->tgt_feat.p, c->W.lane);
   hipLaunchKernelGGL(k_dec_tgt, dim3(Bn), dim3(DT), mind_dec_scene_lds_bytes(), ss, (const float *)c->tgt_feat.p, in->tgt_rpe, (float *)c->tgt_emb.p,
                      c->W.dec);
+  if (c->enc_post) {
+    const std::function<int(hipStream_t)> post = std::move(c->enc_post);
+    c->enc_post = nullptr;
+    if ((rc = post(ss))) return rc;
+  }
   if (c->side) HIPCHK(c, hipEventRecord(c->ev_tgt, c->side));
   if (p.ch.tgt_wait_first) HIPCHK(c, hipStreamWaitEvent(st, c->ev_tgt, 0));
   return MIND_OK;
@@ -499,8 +510,13 @@ static int pred_decoder(PredCall &p) {
   switch (ch.dec_actor) {
   case PRED_DEC_SPLIT:
     HIPCHK(c, hipStreamWaitEvent(st, c->ev_side, 0));
-    hipLaunchKernelGGL(k_dec_actor<2>, agrid, dim3(DT), mind_dec_actor_lds_bytes(), st, x, d_actor_row, d_actor_scene, A, cmode, tgt_emb, out->reg,
-                       out->vel, c->W.dec, (float *)c->dec_h2.p);
+#define DEC_HEAD(RAV)                                                                                                                       \
+  hipLaunchKernelGGL((k_dec_actor<2, RAV>), dim3((A + RAV - 1) / RAV), dim3(DT), mind_dec_actor_lds_bytes(), st, x, d_actor_row, d_actor_scene, A, \
+                     cmode, tgt_emb, out->reg, out->vel, c->W.dec, (float *)c->dec_h2.p)
+    if (ch.dec_head_ra == 1) DEC_HEAD(1);
+    else if (ch.dec_head_ra == 2) DEC_HEAD(2);
+    else DEC_HEAD(RA);
+#undef DEC_HEAD
     break;
   case PRED_DEC_ONE:
     hipLaunchKernelGGL(k_dec_actor<0>, agrid, dim3(DT), mind_dec_actor_lds_bytes(), st, x, d_actor_row, d_actor_scene, A, cmode, tgt_emb, out->reg,
