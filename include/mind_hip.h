@@ -67,7 +67,7 @@ typedef struct {
   const float *tgt_rpe;       /* [B,20]    TGT_RPE                                                 */
 } mind_scene_batch;
 
-/* Outputs of ScenePredNet.forward (network.py:545-556): res_cls, res_reg, res_aux[0]. */
+/* Outputs of ScenePredNet.forward (network.py:545-556): res_cls, res_reg, res_aux[0] (res_aux[1], [2]: mind_pred_aux below). */
 typedef struct {
   float *cls;        /* [B,6]          softmax mode probabilities                                  */
   float *reg;        /* [A,6,60,5]     (x, y, exp sx, exp sy, exp rho)  agent-local frame          */
@@ -79,6 +79,46 @@ typedef struct {
 
 /* replaces ScenePredNet.forward over the whole AIME batch (scenario_tree.py:69-71). */
 int mind_predict_batch(mind_ctx *ctx, const mind_scene_batch *in, mind_pred_out *out);
+
+/* The rest of res_aux[b] = (vel, cov_vel, param) (network.py:554).  mind_pred_out keeps its layout (callers bind it by layout); these
+ * travel beside it.  Device pointers, each may be NULL. */
+typedef struct {
+  float *cov_vel;   /* optional [A,6,60,3]  d/dt of (log sx, log sy, log rho): Tp diff(param[..., 2:]) / 6 in BOTH bases -- the
+                       reference applies diff under the monomial Tp as well (network.py:523 / :534)                                 */
+  float *param;     /* optional [A,6,8,5]   control points (x, y, sx, sy, rho), agent-major like reg (the reference's param is
+                       [6,a,8,5] per scene: network.py:515 / :526)                                                                  */
+} mind_pred_aux;
+/* mind_predict_batch with the aux outputs: the decoder's head kernels write them themselves (no further launch).  aux == NULL is
+ * mind_predict_batch: the same launches, the same bits of cls / reg / vel -- as is any aux. */
+int mind_predict_batch_aux(mind_ctx *ctx, const mind_scene_batch *in, mind_pred_out *out, const mind_pred_aux *aux);
+
+/* The curve basis of the eight control points: SceneDecoder's param_out (network.py:408-435, :449-481).
+ *   MIND_BASIS_BEZIER   (default)  T = C(7,i) (1-t)^(7-i) t^i, Tp = 7 C(6,i) (1-t)^(6-i) t^i, vel = Tp diff(P) / 6     (:514-523)
+ *   MIND_BASIS_MONOMIAL            T = t^i,                    Tp = (i+1) t^i,                 vel = Tp P[1:] / 6      (:525-534)
+ * A checkpoint of either basis has the same tensor shapes: the caller says which one it was trained with.  The setting rewrites the
+ * two tables of the loaded weights in place (it drains the context's stream first), holds across later mind_weights_load calls, and
+ * covers everything that runs the predictor on the context (mind_predict_batch, mind_aime_plan, the native loop and planner).
+ * mind_set_decoder_basis: MIND_EINVAL for an unknown basis; MIND_ESTATE while a plan begun with mind_aime_plan_begin runs or a
+ * tree-iLQR call begun with mind_ilqr_contingency_begin(_plan) is pending on the context.  mind_get_decoder_basis returns the basis. */
+#define MIND_BASIS_BEZIER 0
+#define MIND_BASIS_MONOMIAL 1
+int mind_set_decoder_basis(mind_ctx *ctx, int basis);
+int mind_get_decoder_basis(mind_ctx *ctx);
+
+/* The decoder's curves at arbitrary times (k_dec_curve): the control points are the continuous-time form of a forecast, the 60
+ * samples of reg / vel only its 10 Hz grid.
+ * param: DEVICE [n_rows,8,5] (mind_pred_aux.param: n_rows = 6 A); tau: HOST [n_tau], each in [0,1] (fraction of the 6 s horizon);
+ * basis: MIND_BASIS_* or -1 = the context's.  reg [n_rows,n_tau,5] = (x, y, exp sx, exp sy, exp rho), vel [n_rows,n_tau,2],
+ * cov_vel [n_rows,n_tau,3]: DEVICE, each may be NULL.  The host evaluates the basis rows in double as the weight packer does and
+ * rounds them to fp32; the kernel runs the head kernels' contraction, so that at tau = linspace(0, 1, 60) the results are
+ * bit-identical to the decoder's own reg / vel / cov_vel for the same param.  Queued on the context's stream.
+ * MIND_EINVAL: a non-finite tau or one outside [0,1], n_tau < 1, n_rows < 0, an unknown basis, all three outputs NULL, or
+ * n_rows * n_tau > MIND_CURVE_MAX_POINTS.  n_rows == 0 is a successful no-op. */
+#define MIND_CURVE_MAX_POINTS (1LL << 26)   /* 40 bytes of output per point: 2.7 GB */
+int mind_curve_eval(mind_ctx *ctx, int basis, const float *param, long long n_rows, const double *tau, int n_tau,
+                    float *reg, float *vel, float *cov_vel);
+/* The basis rows mind_curve_eval uploads (host only, no context): T [n_tau,8], Tp [n_tau,7].  MIND_EINVAL as above. */
+int mind_debug_curve_basis(int basis, const double *tau, int n_tau, float *T, float *Tp);
 
 /* Per-kernel timing of the last mind_predict_batch measured with HIP events on the context stream:
  * returns the number of fusion pair-kernel launches and their summed milliseconds. */

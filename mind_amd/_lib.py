@@ -30,6 +30,13 @@ class PredOut(C.Structure):
                 ("actor_emb", C.c_void_p), ("cls_emb", C.c_void_p)]
 
 
+class PredAux(C.Structure):         # mind_pred_aux
+    _fields_ = [("cov_vel", C.c_void_p), ("param", C.c_void_p)]
+
+
+BASIS = ("bezier", "monomial")      # MIND_BASIS_*: SceneDecoder's param_out
+
+
 class CostTree(C.Structure):
     _fields_ = [("n_nodes", C.c_int), ("parent", C.POINTER(C.c_int32)), ("prob", C.POINTER(C.c_float)),
                 ("n_agents", C.c_int), ("agent_mean", C.POINTER(C.c_float)), ("agent_cov", C.POINTER(C.c_float)),
@@ -168,6 +175,7 @@ EXPORTS = ["mind_ctx_create", "mind_ctx_destroy", "mind_last_error_string", "min
            "mind_ilqr_solve_trees", "mind_ilqr_contingency", "mind_ilqr_solve_fields", "mind_cost_eval", "mind_ilqr_score_trees", "mind_ilqr_gains", "mind_ilqr_policy_rollouts", "mind_lane_dist_field", "mind_aime_world", "mind_aime_rebase", "mind_debug_aime_decide", "mind_debug_set_layers",
            "mind_debug_read", "mind_set_pair_precision", "mind_get_pair_precision", "mind_debug_pack_bfrag", "mind_debug_pack_conv_frag", "mind_debug_pack", "mind_debug_weight_image", "mind_debug_weight_bind", "mind_debug_pair_schedule", "mind_debug_predict_choice", "mind_debug_ilqr_plan", "mind_debug_aime_book", "mind_set_tuning", "mind_last_ilqr_stats", "mind_aime_plan", "mind_last_ilqr_profile", "mind_eval_traj_trees", "mind_last_ilqr_trace", "mind_ilqr_contingency_begin", "mind_ilqr_finish", "mind_fill_tracks", "mind_ilqr_contingency_begin_plan", "mind_debug_trig", "mind_aime_plan_begin", "mind_aime_plan_poll", "mind_aime_plan_finish", "mind_ctx_busy", "mind_ilqr_finish_plan",
            "mind_set_exchange", "mind_last_exchange_stats", "mind_debug_wait_word",
+           "mind_predict_batch_aux", "mind_set_decoder_basis", "mind_get_decoder_basis", "mind_curve_eval", "mind_debug_curve_basis",
            "mind_loop_create", "mind_loop_destroy", "mind_loop_reset", "mind_loop_advance", "mind_loop_state", "mind_loop_last_plan", "mind_loop_export",
            "mind_planner_create", "mind_planner_destroy", "mind_planner_reset", "mind_planner_observe", "mind_planner_set_lanes", "mind_planner_set_target_lane",
            "mind_planner_set_solve_lane", "mind_planner_set_eval_lane", "mind_planner_plan", "mind_planner_last_plan", "mind_planner_export"]
@@ -195,6 +203,11 @@ def load():
     lib.mind_ctx_synchronize.argtypes = [C.c_void_p]
     lib.mind_weights_load.argtypes = [C.c_void_p, C.POINTER(TensorDesc), C.c_int]
     lib.mind_predict_batch.argtypes = [C.c_void_p, C.POINTER(SceneBatch), C.POINTER(PredOut)]
+    lib.mind_predict_batch_aux.argtypes = [C.c_void_p, C.POINTER(SceneBatch), C.POINTER(PredOut), C.POINTER(PredAux)]
+    lib.mind_set_decoder_basis.argtypes = [C.c_void_p, C.c_int]
+    lib.mind_get_decoder_basis.argtypes = [C.c_void_p]
+    lib.mind_curve_eval.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.POINTER(C.c_double), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.mind_debug_curve_basis.argtypes = [C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     lib.mind_last_fusion_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_double)]
     lib.mind_last_actor_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float)]
     lib.mind_debug_actor_lw_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong), C.c_int, C.POINTER(C.c_longlong)]
@@ -435,6 +448,22 @@ def weight_image(sd):
     keys = names.value.decode().split("\n")[:-1]
     assert len(keys) == ne
     return blob, [(k, ents[2 * i], ents[2 * i + 1]) for i, k in enumerate(keys)]
+
+
+def curve_basis(basis, tau):
+    """the basis rows mind_curve_eval evaluates for the times `tau` (mind_debug_curve_basis; no GPU): (T [n,8], Tp [n,7]) float32; `basis` a
+    name of BASIS or its number.  Raises ValueError for what the library rejects (a tau outside [0, 1] or not finite, no tau, an unknown basis)"""
+    import numpy as np
+    lib = load()
+    tau = np.ascontiguousarray(tau, np.float64).ravel()
+    b = BASIS.index(basis) if isinstance(basis, str) else int(basis)
+    T, Tp = np.zeros((max(1, tau.size), 8), np.float32), np.zeros((max(1, tau.size), 7), np.float32)
+    rc = lib.mind_debug_curve_basis(b, tau.ctypes.data_as(C.POINTER(C.c_double)), tau.size, T.ctypes.data_as(C.POINTER(C.c_float)),
+                                    Tp.ctypes.data_as(C.POINTER(C.c_float)))
+    if rc == MIND_EINVAL:
+        raise ValueError(f"mind_debug_curve_basis rejects basis {basis!r}, tau {tau!r}")
+    assert rc == MIND_OK, rc
+    return T[:tau.size], Tp[:tau.size]
 
 
 def weight_bind(sd, drop=None):

@@ -21,6 +21,7 @@
 #define DM_LDS_DWORDS (DM_R2 + DM_ROWS * 132)
 
 #include "weight_tables.h"   // DmW
+#include "dec_curve.h"       // dec_curve_point
 
 // out[row][f] = bias[f] + sum_k W[f][k] in[row][k] for `rows` rows, f < n_out (m-tiles past n_out are zero rows of the packing)
 template <int NP, int CP>
@@ -107,7 +108,8 @@ __global__ __launch_bounds__(DM_T) void k_dec_actor_mfma(const float *__restrict
                                                          const int *__restrict__ actor_scene, int n_actors,
                                                          const float *__restrict__ Cmode /*[B,6,128]*/,
                                                          const float *__restrict__ tgt /*[B,128]*/, float *__restrict__ reg,
-                                                         float *__restrict__ vel, DmW W) {
+                                                         float *__restrict__ vel, DmW W, float *__restrict__ cov_vel /*[A,6,60,3] or null*/,
+                                                         float *__restrict__ param /*[A,6,8,5] or null*/) {
   extern __shared__ __attribute__((aligned(16))) u32 dmu[];
   u32 *R1 = dmu + DM_R1;
   float *R2 = (float *)(dmu + DM_R2);
@@ -161,26 +163,15 @@ __global__ __launch_bounds__(DM_T) void k_dec_actor_mfma(const float *__restrict
   float (*prm)[40] = (float (*)[40])R2;
   dm_gemm<NP, 128>(R1, rows, W.r6, 3, W.r6b, 40, R2, 40);
   __syncthreads();
-  // Bezier evaluation (network.py:515-523,545): pos = T P, cov = exp(T S), vel = Tp dP / 6
+  // the control points themselves (network.py:554, res_aux's param), agent-major like reg: the workgroup's rows are consecutive
+  if (param)
+    for (int i = tid; i < rows * 40; i += DM_T) param[(size_t)a0 * 240 + i] = R2[i];
+  // curve evaluation (dec_curve.h; network.py:515-534,545): pos = T P, cov = exp(T S), vel = Tp dP / 6 (monomial: Tp P[1:] / 6), cov_vel = Tp dS / 6
   for (int i = tid; i < rows * 60; i += DM_T) {
     const int r = i / 60, t = i - r * 60;
     const int a = a0 + r / 6, k = r % 6;
-    float o5[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int c = 0; c < 8; ++c) {
-      const float tv = W.T[t * 8 + c];
-#pragma unroll
-      for (int d = 0; d < 5; ++d) o5[d] = fmaf(tv, prm[r][c * 5 + d], o5[d]);
-    }
-    float v2[2] = {0.f, 0.f};
-    for (int c = 0; c < 7; ++c) {
-      const float tv = W.Tp[t * 7 + c];
-      v2[0] = fmaf(tv, prm[r][(c + 1) * 5 + 0] - prm[r][c * 5 + 0], v2[0]);
-      v2[1] = fmaf(tv, prm[r][(c + 1) * 5 + 1] - prm[r][c * 5 + 1], v2[1]);
-    }
-    float *ro = reg + (((size_t)a * 6 + k) * 60 + t) * 5;
-    ro[0] = o5[0]; ro[1] = o5[1]; ro[2] = expf(o5[2]); ro[3] = expf(o5[3]); ro[4] = expf(o5[4]);
-    float *vo = vel + (((size_t)a * 6 + k) * 60 + t) * 2;
-    vo[0] = v2[0] / 6.0f; vo[1] = v2[1] / 6.0f;
+    const size_t o = ((size_t)a * 6 + k) * 60 + t;
+    dec_curve_point(&prm[r][0], W.T + t * 8, W.Tp + t * 7, W.monomial, reg + o * 5, vel + o * 2, cov_vel ? cov_vel + o * 3 : nullptr);
   }
 }
 extern "C" size_t mind_dec_actor_mfma_lds_bytes() { return (size_t)DM_LDS_DWORDS * sizeof(u32); }

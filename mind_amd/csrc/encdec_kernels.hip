@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "weight_tables.h"   // LaneW, ActorW, DecW
+#include "dec_curve.h"       // dec_curve_point
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -1018,7 +1019,8 @@ __global__ __launch_bounds__(DT) void k_dec_actor(const float *__restrict__ x /*
                                                   const int *__restrict__ actor_scene /*[A]*/, int n_actors,
                                                   const float *__restrict__ Cmode /*[B,6,128]*/,
                                                   const float *__restrict__ tgt /*[B,128]*/,
-                                                  float *__restrict__ reg, float *__restrict__ vel, DecW W, float *__restrict__ h2g) {
+                                                  float *__restrict__ reg, float *__restrict__ vel, DecW W, float *__restrict__ h2g,
+                                                  float *__restrict__ cov_vel /*[A,6,60,3] or null*/, float *__restrict__ param /*[A,6,8,5] or null*/) {
   extern __shared__ __attribute__((aligned(16))) float dsm[];
   float (*xin)[128] = (float (*)[128])(dsm);
   float (*h1)[384] = (float (*)[384])(dsm + 512);
@@ -1091,27 +1093,19 @@ __global__ __launch_bounds__(DT) void k_dec_actor(const float *__restrict__ x /*
     prm[r][o] = acc;
   }
   __syncthreads();
-  // Bezier evaluation (network.py:515-523,545): pos = T P, cov = exp(T S), vel = Tp dP / 6
+  // the control points themselves (network.py:554, res_aux's param), agent-major like reg
+  if (param)
+    for (int i = tid; i < RAT * 6 * 40; i += blockDim.x) {
+      const int r = i / 40, a = a0 + r / 6;
+      if (a < n_actors) param[((size_t)a * 6 + r % 6) * 40 + i % 40] = prm[r][i % 40];
+    }
+  // curve evaluation (dec_curve.h; network.py:515-534,545): pos = T P, cov = exp(T S), vel = Tp dP / 6 (monomial: Tp P[1:] / 6), cov_vel = Tp dS / 6
   for (int i = tid; i < RAT * 6 * 60; i += blockDim.x) {
     const int r = i / 60, t = i % 60;
     const int a = a0 + r / 6, k = r % 6;
     if (a >= n_actors) continue;
-    float o5[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int c = 0; c < 8; ++c) {
-      const float tv = W.T[t * 8 + c];
-#pragma unroll
-      for (int d = 0; d < 5; ++d) o5[d] = fmaf(tv, prm[r][c * 5 + d], o5[d]);
-    }
-    float v2[2] = {0.f, 0.f};
-    for (int c = 0; c < 7; ++c) {
-      const float tv = W.Tp[t * 7 + c];
-      v2[0] = fmaf(tv, prm[r][(c + 1) * 5 + 0] - prm[r][c * 5 + 0], v2[0]);
-      v2[1] = fmaf(tv, prm[r][(c + 1) * 5 + 1] - prm[r][c * 5 + 1], v2[1]);
-    }
-    float *ro = reg + (((size_t)a * 6 + k) * 60 + t) * 5;
-    ro[0] = o5[0]; ro[1] = o5[1]; ro[2] = expf(o5[2]); ro[3] = expf(o5[3]); ro[4] = expf(o5[4]);
-    float *vo = vel + (((size_t)a * 6 + k) * 60 + t) * 2;
-    vo[0] = v2[0] / 6.0f; vo[1] = v2[1] / 6.0f;
+    const size_t o = ((size_t)a * 6 + k) * 60 + t;
+    dec_curve_point(&prm[r][0], W.T + t * 8, W.Tp + t * 7, W.monomial, reg + o * 5, vel + o * 2, cov_vel ? cov_vel + o * 3 : nullptr);
   }
 }
 

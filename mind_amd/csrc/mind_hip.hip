@@ -27,6 +27,7 @@
 #include "token_lw_kernels.hip"
 #include "actor_f32_kernels.hip"
 #include "dec_mfma_kernels.hip"
+#include "dec_curve_kernels.hip"
 #include "ilqr_kernels.hip"
 #include "ilqr_score_kernels.hip"
 #include "ilqr_policy_kernels.hip"
@@ -73,6 +74,12 @@ struct mind_ctx {
   bool have_weights = false;
   WeightTables W = {};
   PredTuning pt;      // the predictor's kernel-selection knobs (pred_choice.h)
+  // the decoder's curve basis (mind_set_decoder_basis): which tables the blob entries dec.T / dec.Tp hold and which vel formula the heads run;
+  // survives mind_weights_load.  mind_curve_eval's basis rows on the device, and the (basis, tau) they were evaluated for
+  int dec_basis = MIND_BASIS_BEZIER;
+  DevBuf curve_tab;
+  std::vector<double> curve_tau;
+  int curve_tab_basis = -1;
   // layer-wise token stage (token_lw_kernels.hip): its scratch arena holds one chunk and is allocated at first use
   DevBuf tok_lw_arena;
   std::vector<TlLaunch> tok_lw_plan;
@@ -385,7 +392,8 @@ extern "C" int mind_ctx_destroy(mind_ctx *c) {
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
   DevBuf *bufs[] = {&c->edge, &c->x, &c->ST, &c->QK, &c->part, &c->tokpos, &c->meta, &c->jobs, &c->actor_feat,
-                    &c->lane_feat, &c->tgt_feat, &c->cmode, &c->tgt_emb, &c->rows, &c->rpe_ptrs, &c->ilqr_dev, &c->aime_dev, &c->rebase_dev2[0], &c->rebase_dev2[1], &c->dec_h2};
+                    &c->lane_feat, &c->tgt_feat, &c->cmode, &c->tgt_emb, &c->rows, &c->rpe_ptrs, &c->ilqr_dev, &c->aime_dev, &c->rebase_dev2[0], &c->rebase_dev2[1], &c->dec_h2,
+                    &c->curve_tab};
   for (DevBuf *b : bufs)
     if (b->p) (void)hipFree(b->p);
   for (TableSet &t : c->tabs)
@@ -703,6 +711,8 @@ extern "C" int mind_weights_load(mind_ctx *c, const mind_tensor_desc *tensors, i
   WeightBlob B;       // local: a load that fails here leaves the weights loaded before it in place
   wp_pack(sd, B);
   if (!sd.missing.empty()) return fail(c, MIND_ENOTFOUND, "state_dict tensor missing or wrong size: %s", sd.missing.c_str());
+  // the context's curve basis: the contents of dec.T / dec.Tp, in place (same shapes: no key is added, no offset moves)
+  if (c->dec_basis != MIND_BASIS_BEZIER) wp_basis_tables(c->dec_basis, B.host.data() + B.off.at("dec.T"), B.host.data() + B.off.at("dec.Tp"));
   c->have_weights = false;     // from here on the tables point into freed memory until the bind below
   if (c->wdev) (void)hipFree(c->wdev);
   c->wdev = nullptr;
@@ -710,7 +720,82 @@ extern "C" int mind_weights_load(mind_ctx *c, const mind_tensor_desc *tensors, i
   HIPCHK(c, hipMemcpy(c->wdev, B.host.data(), B.host.size() * sizeof(float), hipMemcpyHostToDevice));
   std::string missing;
   if (!wp_bind(B, c->wdev, c->W, &missing)) return fail(c, MIND_ENOTFOUND, "packed weights hold no entry '%s'", missing.c_str());
+  c->W.dec.monomial = c->W.decB.monomial = c->dec_basis == MIND_BASIS_MONOMIAL;
   c->have_weights = true;
+  return MIND_OK;
+}
+
+// -------------------------------------------------------------------------------------------------
+// the decoder's curve basis, and its curves at arbitrary times
+// -------------------------------------------------------------------------------------------------
+static_assert(MIND_BASIS_BEZIER == WP_BASIS_BEZIER && MIND_BASIS_MONOMIAL == WP_BASIS_MONOMIAL, "the packer's basis numbers are the ABI's");
+
+extern "C" int mind_set_decoder_basis(mind_ctx *c, int basis) {
+  if (!c) return MIND_EINVAL;
+  if (basis != MIND_BASIS_BEZIER && basis != MIND_BASIS_MONOMIAL) return fail(c, MIND_EINVAL, "mind_set_decoder_basis: unknown basis %d", basis);
+  if (c->pa_state.load(std::memory_order_acquire) == 1) return fail(c, MIND_ESTATE, "mind_set_decoder_basis: a plan is running on this context");
+  if (c->il_finish) return fail(c, MIND_ESTATE, "mind_set_decoder_basis: a tree-iLQR call begun on this context has not been finished");
+  if (basis == c->dec_basis) return MIND_OK;
+  if (c->have_weights) {
+    // rewrite the two tables where the kernels read them, behind everything queued that reads the old ones
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->side) HIPCHK(c, hipStreamSynchronize(c->side));
+    std::vector<float> T(60 * 8), Tp(60 * 7);
+    wp_basis_tables(basis, T.data(), Tp.data());
+    HIPCHK(c, hipMemcpy(const_cast<float *>(c->W.dec.T), T.data(), T.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(const_cast<float *>(c->W.dec.Tp), Tp.data(), Tp.size() * sizeof(float), hipMemcpyHostToDevice));
+    c->W.dec.monomial = c->W.decB.monomial = basis == MIND_BASIS_MONOMIAL;
+  }
+  c->dec_basis = basis;
+  return MIND_OK;
+}
+
+extern "C" int mind_get_decoder_basis(mind_ctx *c) { return c ? c->dec_basis : MIND_EINVAL; }
+
+// the arguments mind_curve_eval and mind_debug_curve_basis share
+static bool curve_args_ok(int basis, const double *tau, int n_tau) {
+  if ((basis != MIND_BASIS_BEZIER && basis != MIND_BASIS_MONOMIAL) || !tau || n_tau < 1) return false;
+  for (int t = 0; t < n_tau; ++t)
+    if (!(tau[t] >= 0.0 && tau[t] <= 1.0)) return false;      // (a NaN fails both comparisons)
+  return true;
+}
+
+extern "C" int mind_debug_curve_basis(int basis, const double *tau, int n_tau, float *T, float *Tp) {
+  if (!curve_args_ok(basis, tau, n_tau) || !T || !Tp) return MIND_EINVAL;
+  wp_basis_rows(basis, tau, n_tau, T, Tp);
+  return MIND_OK;
+}
+
+extern "C" int mind_curve_eval(mind_ctx *c, int basis, const float *param, long long n_rows, const double *tau, int n_tau, float *reg, float *vel,
+                               float *cov_vel) {
+  if (!c) return MIND_EINVAL;
+  if (basis == -1) basis = c->dec_basis;
+  if (!curve_args_ok(basis, tau, n_tau)) return fail(c, MIND_EINVAL, "mind_curve_eval: unknown basis, n_tau < 1, or a tau that is not in [0, 1]");
+  if (n_rows < 0 || (!reg && !vel && !cov_vel)) return fail(c, MIND_EINVAL, "mind_curve_eval: n_rows < 0 or no output");
+  if (n_rows > MIND_CURVE_MAX_POINTS || n_rows * n_tau > MIND_CURVE_MAX_POINTS)
+    return fail(c, MIND_EINVAL, "mind_curve_eval: %lld rows x %d times > %lld points supported", n_rows, n_tau, (long long)MIND_CURVE_MAX_POINTS);
+  if (n_rows == 0) return MIND_OK;
+  if (!param) return fail(c, MIND_EINVAL, "mind_curve_eval: null param");
+  HIPCHK(c, hipSetDevice(c->device));
+  // the basis rows of (basis, tau): kept on the device between calls (a tracker samples the same times every cycle)
+  const size_t tab_floats = (size_t)n_tau * 15;
+  if (c->curve_tab_basis != basis || c->curve_tau.size() != (size_t)n_tau || memcmp(c->curve_tau.data(), tau, (size_t)n_tau * sizeof(double)) != 0) {
+    std::vector<float> tab(tab_floats);
+    wp_basis_rows(basis, tau, n_tau, tab.data(), tab.data() + (size_t)n_tau * 8);
+    c->curve_tab_basis = -1;
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // (an earlier call's kernel may still read the old rows; `tab` must outlive the copy)
+    int rc;
+    if ((rc = ensure(c, c->curve_tab, tab_floats * sizeof(float)))) return rc;
+    HIPCHK(c, hipMemcpy(c->curve_tab.p, tab.data(), tab_floats * sizeof(float), hipMemcpyHostToDevice));
+    c->curve_tau.assign(tau, tau + n_tau);
+    c->curve_tab_basis = basis;
+  }
+  const float *T = (const float *)c->curve_tab.p, *Tp = T + (size_t)n_tau * 8;
+  const int n_pts = (int)(n_rows * n_tau);
+  hipLaunchKernelGGL(k_dec_curve, dim3((n_pts + DC_T - 1) / DC_T), dim3(DC_T), dc_lds_bytes(n_tau), c->stream, param, n_pts, n_tau, T, Tp,
+                     basis == MIND_BASIS_MONOMIAL ? 1 : 0, reg, vel, cov_vel, dc_rows_per_block(n_tau));
+  HIPCHK(c, hipGetLastError());
   return MIND_OK;
 }
 

@@ -136,6 +136,7 @@ struct PredCall {
   mind_ctx *c;
   const mind_scene_batch *in;
   mind_pred_out *out;
+  const mind_pred_aux *aux;             // null: mind_predict_batch
   const PredChoice &ch;
   int Bn, A, Ltot;
   hipStream_t st, ss;                   // the context stream; the side stream (the context stream when there is none)
@@ -462,13 +463,16 @@ static int pred_decoder(PredCall &p) {
   const int *d_actor_row = p.rows(), *d_actor_scene = d_actor_row + A, *d_cls_row = d_actor_row + 2 * A;
   const float *cmode = (const float *)c->cmode.p, *tgt_emb = (const float *)c->tgt_emb.p;
   const dim3 agrid((A + RA - 1) / RA), mgrid((A + DM_RA - 1) / DM_RA);
+  // the aux outputs (mind_predict_batch_aux): the head of every form writes them itself when asked
+  float *cov_vel = p.aux ? p.aux->cov_vel : nullptr, *param = p.aux ? p.aux->param : nullptr;
   int rc;
   if (ch.split_dec) {
     if ((rc = ensure(c, c->dec_h2, (size_t)A * 768 * sizeof(float)))) return rc;
     HIPCHK(c, hipEventRecord(c->ev_main, st));
     HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_main, 0));
     hipLaunchKernelGGL(k_dec_actor<1>, agrid, dim3(DT), mind_dec_actor_lds_bytes(), c->side, x, d_actor_row, d_actor_scene, A,
-                       (const float *)nullptr, (const float *)nullptr, (float *)nullptr, (float *)nullptr, c->W.dec, (float *)c->dec_h2.p);
+                       (const float *)nullptr, (const float *)nullptr, (float *)nullptr, (float *)nullptr, c->W.dec, (float *)c->dec_h2.p,
+                       (float *)nullptr, (float *)nullptr);
     HIPCHK(c, hipEventRecord(c->ev_side, c->side));
   }
   // the scene part
@@ -512,7 +516,7 @@ static int pred_decoder(PredCall &p) {
     HIPCHK(c, hipStreamWaitEvent(st, c->ev_side, 0));
 #define DEC_HEAD(RAV)                                                                                                                       \
   hipLaunchKernelGGL((k_dec_actor<2, RAV>), dim3((A + RAV - 1) / RAV), dim3(DT), mind_dec_actor_lds_bytes(), st, x, d_actor_row, d_actor_scene, A, \
-                     cmode, tgt_emb, out->reg, out->vel, c->W.dec, (float *)c->dec_h2.p)
+                     cmode, tgt_emb, out->reg, out->vel, c->W.dec, (float *)c->dec_h2.p, cov_vel, param)
     if (ch.dec_head_ra == 1) DEC_HEAD(1);
     else if (ch.dec_head_ra == 2) DEC_HEAD(2);
     else DEC_HEAD(RA);
@@ -520,12 +524,12 @@ static int pred_decoder(PredCall &p) {
     break;
   case PRED_DEC_ONE:
     hipLaunchKernelGGL(k_dec_actor<0>, agrid, dim3(DT), mind_dec_actor_lds_bytes(), st, x, d_actor_row, d_actor_scene, A, cmode, tgt_emb, out->reg,
-                       out->vel, c->W.dec, (float *)nullptr);
+                       out->vel, c->W.dec, (float *)nullptr, cov_vel, param);
     break;
   default: {
 #define DEC_MFMA(NPV)                                                                                                                     \
   hipLaunchKernelGGL(k_dec_actor_mfma<NPV>, mgrid, dim3(DM_T), mind_dec_actor_mfma_lds_bytes(), st, x, d_actor_row, d_actor_scene, A, cmode, \
-                     tgt_emb, out->reg, out->vel, c->W.decB)
+                     tgt_emb, out->reg, out->vel, c->W.decB, cov_vel, param)
     if (ch.np == 6) DEC_MFMA(6);
     else if (ch.np == 3) DEC_MFMA(3);
     else DEC_MFMA(1);
@@ -568,7 +572,7 @@ static int pred_finish(PredCall &p) {
   return MIND_OK;
 }
 
-extern "C" int mind_predict_batch(mind_ctx *c, const mind_scene_batch *in, mind_pred_out *out) {
+extern "C" int mind_predict_batch_aux(mind_ctx *c, const mind_scene_batch *in, mind_pred_out *out, const mind_pred_aux *aux) {
   if (!c || !in || !out) return MIND_EINVAL;
   if (!c->have_weights) return fail(c, MIND_ESTATE, "weights not loaded");
   const int Bn = in->n_scenes;
@@ -587,7 +591,7 @@ extern "C" int mind_predict_batch(mind_ctx *c, const mind_scene_batch *in, mind_
     if (sa[b] <= 0 || sl[b] < 0) return fail(c, MIND_EINVAL, "scene %d has %d agents, %d lanes", b, sa[b], sl[b]);
   }
   const PredChoice ch = pred_choose(c->pt, c->pair_prec, c->n_cu, c->side != nullptr, Bn, sa.data(), sl.data());
-  PredCall p{c, in, out, ch, Bn, A, Ltot, c->stream, c->side ? c->side : c->stream};
+  PredCall p{c, in, out, aux, ch, Bn, A, Ltot, c->stream, c->side ? c->side : c->stream};
   int rc;
   if ((rc = pred_tables(p, sa.data(), sl.data()))) return rc;
   if ((rc = pred_workspaces(p))) return rc;
@@ -596,3 +600,5 @@ extern "C" int mind_predict_batch(mind_ctx *c, const mind_scene_batch *in, mind_
   if ((rc = pred_decoder(p))) return rc;
   return pred_finish(p);
 }
+
+extern "C" int mind_predict_batch(mind_ctx *c, const mind_scene_batch *in, mind_pred_out *out) { return mind_predict_batch_aux(c, in, out, nullptr); }

@@ -469,16 +469,41 @@ inline void wp_pack_decoder(SD &sd, WeightBlob &B) {
   }
 }
 
-// Bezier basis (network.py:449-464): float64 numpy -> fp32 (Q21)
+// The decoder's curve bases at the times ts (fractions of the horizon): float64 as numpy evaluates them -> fp32 (Q21).  T [n][8], Tp [n][7].
+// basis 0: Bezier (network.py:449-464), T = C(7,i) (1-ts)^(7-i) ts^i, Tp = 7 C(6,i) (1-ts)^(6-i) ts^i
+// basis 1: monomial (network.py:466-481), T = ts^i, Tp = (i+1) ts^i
+#define WP_BASIS_BEZIER 0
+#define WP_BASIS_MONOMIAL 1
+inline void wp_basis_rows(int basis, const double *ts, int n, float *T, float *Tp) {
+  auto comb = [](int n, int k) { double r = 1; for (int i = 1; i <= k; ++i) r = r * (n - k + i) / i; return r; };
+  for (int t = 0; t < n; ++t) {
+    const double s = ts[t];
+    if (basis == WP_BASIS_MONOMIAL) {
+      for (int i = 0; i < 8; ++i) T[t * 8 + i] = (float)std::pow(s, i);
+      for (int i = 0; i < 7; ++i) Tp[t * 7 + i] = (float)((double)(i + 1) * std::pow(s, i));
+    } else {
+      for (int i = 0; i < 8; ++i) T[t * 8 + i] = (float)(comb(7, i) * std::pow(1.0 - s, 7 - i) * std::pow(s, i));
+      for (int i = 0; i < 7; ++i) Tp[t * 7 + i] = (float)(7.0 * comb(6, i) * std::pow(1.0 - s, 6 - i) * std::pow(s, i));
+    }
+  }
+}
+
+// the decoder's own time grid: numpy linspace(0, 1, 60) = start + arange * step, step = 1/59; last point exactly 1
+inline void wp_basis_grid(double ts[60]) {
+  for (int t = 0; t < 60; ++t) ts[t] = (t == 59) ? 1.0 : 0.0 + (double)t * (1.0 / 59.0);
+}
+
+// the tables of `basis` on the decoder's grid, written over the blob entries dec.T / dec.Tp (same shapes in both bases: no key, no offset moves)
+inline void wp_basis_tables(int basis, float *T /*[60][8]*/, float *Tp /*[60][7]*/) {
+  double ts[60];
+  wp_basis_grid(ts);
+  wp_basis_rows(basis, ts, 60, T, Tp);
+}
+
+// the default load packs the Bezier basis
 inline void wp_pack_basis(WeightBlob &B) {
   std::vector<float> T(60 * 8), Tp(60 * 7);
-  auto comb = [](int n, int k) { double r = 1; for (int i = 1; i <= k; ++i) r = r * (n - k + i) / i; return r; };
-  for (int t = 0; t < 60; ++t) {
-    // numpy linspace: start + arange * step, step = 1/59; last point exactly 1
-    const double ts = (t == 59) ? 1.0 : 0.0 + (double)t * (1.0 / 59.0);
-    for (int i = 0; i < 8; ++i) T[t * 8 + i] = (float)(comb(7, i) * std::pow(1.0 - ts, 7 - i) * std::pow(ts, i));
-    for (int i = 0; i < 7; ++i) Tp[t * 7 + i] = (float)(7.0 * comb(6, i) * std::pow(1.0 - ts, 6 - i) * std::pow(ts, i));
-  }
+  wp_basis_tables(WP_BASIS_BEZIER, T.data(), Tp.data());
   B.add("dec.T", T);
   B.add("dec.Tp", Tp);
 }

@@ -87,13 +87,15 @@ struct DecW {                     // encdec_kernels.hip
   const float *n1g[2], *n1b[2], *n2g[2], *n2b[2];
   const float *k0W, *k0b, *k0g, *k0be, *k3W, *k3b, *k3g, *k3be, *k6W, *k6b;  // cls head
   const float *r0W, *r0b, *r0g, *r0be, *r3W, *r3b, *r3g, *r3be, *r6W, *r6b;  // reg head
-  const float *T, *Tp;                                                           // [60][8], [60][7]
+  const float *T, *Tp;                                                           // [60][8], [60][7]: the basis the context is set to (mind_set_decoder_basis)
+  int monomial;                                                                  // the vel formula: 0 = Tp diff(P) / 6 (Bezier), 1 = Tp P[1:] / 6 (network.py:519 / :530)
 };
 
 struct DmW {                      // actor part of the decoder as bf16 fragments (dec_mfma_kernels.hip)
   const u32 *a0, *a3, *r0, *r3, *r6;              // packed fragments
   const float *a0b, *a0g, *a0be, *a3b, *a3g, *a3be, *r0b, *r0g, *r0be, *r3b, *r3g, *r3be, *r6b;
-  const float *T, *Tp;                            // Bezier bases [60][8], [60][7]
+  const float *T, *Tp;                            // the bases [60][8], [60][7] and the vel formula, as in DecW
+  int monomial;
 };
 
 // everything mind_ctx holds of the loaded weights

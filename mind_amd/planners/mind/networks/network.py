@@ -1,6 +1,13 @@
 """``ScenePredNet``: the reference's predictor call surface (planners/mind/networks/network.py:559-606)
 over the hand-written HIP kernels.  ``pre_process(data)`` / ``__call__(data_in)`` / ``load_state_dict`` /
-``to`` / ``eval`` behave like the torch module they replace; there is no torch compute inside."""
+``to`` / ``eval`` behave like the torch module they replace; there is no torch compute inside.
+
+``cfg["param_out"]`` ('bezier', the default, or 'monomial': SceneDecoder's curve basis, network.py:408-435) is set on the net's HIP context
+when the weights are loaded.  Nets built without ``own_context=True`` share their thread's context (``runtime.get_runtime``), and a
+context has ONE basis: build a net with a non-default basis with ``own_context=True``.  ``load_state_dict`` refuses to change the basis of
+a context another loaded net uses."""
+import weakref
+
 import numpy as np
 import torch
 
@@ -9,9 +16,26 @@ from ....runtime import get_runtime
 
 class ScenePredNet:
     computes_rpe_in_kernel = True   # RPE (mind/utils.py:193-212) is evaluated inside the fusion kernel
+    # want_aux: res_aux[b] = (vel, cov_vel, param) as the reference returns it (network.py:554; param in its layout [6, a, 8, 5]) instead of
+    # (vel, None, None) -- nothing in the planner reads the other two, so they are not written unless asked for
+    want_aux = False
+    param_out = "bezier"
+
+    @staticmethod
+    def check_param_out(param_out):
+        """cfg["param_out"] as this net takes it: 'bezier' | 'monomial'"""
+        if param_out == "none":
+            raise NotImplementedError(
+                "ScenePredNet: param_out='none' is not supported: the reference's own 'none' branch reads self.N_ORDER, which that branch "
+                "never sets (network.py:537), and its reg head is [300,128] (60 x 5 samples instead of 8 x 5 control points), which no "
+                "kernel here takes")
+        if param_out not in ("bezier", "monomial"):
+            raise ValueError(f"ScenePredNet: cfg['param_out'] = {param_out!r}: 'bezier' or 'monomial'")
+        return param_out
 
     def __init__(self, cfg=None, device=None, own_context=False):
         self.cfg = cfg or {}
+        self.param_out = self.check_param_out(self.cfg.get("param_out", "bezier"))
         self.device = device
         idx = device.index if isinstance(device, torch.device) and device.index is not None else 0
         # own_context: a context / stream of its own instead of the thread's (several planners driven from one thread, runtime.new_runtime)
@@ -26,7 +50,13 @@ class ScenePredNet:
 
     # torch.nn.Module look-alikes -----------------------------------------------------------------
     def load_state_dict(self, sd, strict=True):
-        self.rt.load_state_dict(sd)
+        rt = self.rt
+        nets = rt.__dict__.setdefault("_loaded_nets", weakref.WeakSet())      # the loaded nets of this context
+        if rt.get_decoder_basis() != self.param_out and any(n is not self for n in nets):
+            raise RuntimeError(f"ScenePredNet: param_out={self.param_out!r}, but this net shares its HIP context with a loaded net of the "
+                               f"{rt.get_decoder_basis()!r} basis, and a context has one basis: build this net with own_context=True")
+        rt.load_state_dict(sd, param_out=self.param_out)
+        nets.add(self)
         self._loaded = True
         return self
 
@@ -101,7 +131,7 @@ class ScenePredNet:
         want = d["lane_feat"] is None
         o = self.rt.predict(d["actors"], d["a_off"], d["lanes"], d["l_off"], d["actor_ctrs"], d["actor_vecs"],
                             d["lane_ctrs"], d["lane_vecs"], d["tgt_nodes"], d["tgt_rpe"], rpe=d["rpe"],
-                            lane_feat=d["lane_feat"], want_lane_feat=want)
+                            lane_feat=d["lane_feat"], want_lane_feat=want, aux=self.want_aux)
         B = len(d["a_off"]) - 1
         if want and d["lane_shared"] and "lane_feat" in o:
             l0 = d["l_off"][1]
@@ -114,7 +144,12 @@ class ScenePredNet:
                             "actor_ctrs": d["actor_ctrs"], "actor_vecs": d["actor_vecs"], "rt": self.rt}
         res_cls = [o["cls"][b:b + 1] for b in range(B)]
         res_reg = [o["reg"][d["a_off"][b]:d["a_off"][b + 1]] for b in range(B)]
-        res_aux = [(o["vel"][d["a_off"][b]:d["a_off"][b + 1]], None, None) for b in range(B)]
+        if self.want_aux:
+            # (the reference's param is mode-major per scene, [6, a, 8, 5]: a permuted view of the agent-major tensor)
+            res_aux = [(o["vel"][d["a_off"][b]:d["a_off"][b + 1]], o["cov_vel"][d["a_off"][b]:d["a_off"][b + 1]],
+                        o["param"][d["a_off"][b]:d["a_off"][b + 1]].permute(1, 0, 2, 3)) for b in range(B)]
+        else:
+            res_aux = [(o["vel"][d["a_off"][b]:d["a_off"][b + 1]], None, None) for b in range(B)]
         return res_cls, res_reg, res_aux
 
     forward = __call__

@@ -195,7 +195,12 @@ class HipPredictor:
         except Exception:
             pass
 
-    def load_state_dict(self, sd):
+    def load_state_dict(self, sd, param_out=None):
+        """``param_out``: the curve basis the checkpoint was trained with ('bezier' | 'monomial', SceneDecoder's param_out), set before the
+        load; None keeps the context's (Bezier unless set_decoder_basis said otherwise).  The two bases have the same tensor shapes, so the
+        state dict cannot tell."""
+        if param_out is not None:
+            self.set_decoder_basis(param_out)
         descs, keep = _lib.tensor_descs(sd)
         rc = self.lib.mind_weights_load(self.ctx, descs, len(sd))
         _lib.check(self.lib, self.ctx, rc, "mind_weights_load")
@@ -214,6 +219,37 @@ class HipPredictor:
 
     def set_pair_precision(self, name):
         _lib.check(self.lib, self.ctx, self.lib.mind_set_pair_precision(self.ctx, self.PAIR_PREC.index(name)), "mind_set_pair_precision")
+
+    def set_decoder_basis(self, name):
+        """the decoder's curve basis, 'bezier' (default) | 'monomial' (mind_set_decoder_basis): holds for every predictor call on this context
+        and across load_state_dict.  The context must be idle."""
+        if name not in _lib.BASIS:
+            raise ValueError(f"unknown decoder basis {name!r}: one of {_lib.BASIS}")
+        _lib.check(self.lib, self.ctx, self.lib.mind_set_decoder_basis(self.ctx, _lib.BASIS.index(name)), "mind_set_decoder_basis")
+
+    def get_decoder_basis(self):
+        return _lib.BASIS[self.lib.mind_get_decoder_basis(self.ctx)]
+
+    def curve_eval(self, param, tau, basis=None, want=("reg", "vel", "cov_vel")):
+        """The decoder's curves at the times ``tau`` (fractions of the 6 s horizon, each in [0, 1]) from control points ``param`` [..., 8, 5]
+        (float32, this device; predict(aux=True)["param"]): dict of reg [..., n_tau, 5] = (x, y, exp sx, exp sy, exp rho), vel [..., n_tau, 2],
+        cov_vel [..., n_tau, 3] as named in ``want``.  ``basis``: 'bezier' | 'monomial' | None = the context's.  At tau = linspace(0, 1, 60) the
+        results are the decoder's own, bit for bit (mind_curve_eval)."""
+        assert param.device == self.device and param.dtype == torch.float32 and tuple(param.shape[-2:]) == (8, 5), (param.device, param.dtype, param.shape)
+        if basis is not None and basis not in _lib.BASIS:
+            raise ValueError(f"unknown decoder basis {basis!r}: one of {_lib.BASIS}")
+        widths = {"reg": 5, "vel": 2, "cov_vel": 3}
+        if any(k not in widths for k in want):
+            raise ValueError(f"curve_eval: want names {tuple(want)!r}, of {tuple(widths)}")
+        param = param.contiguous()
+        tau = np.ascontiguousarray(tau, np.float64).ravel()
+        lead, n = tuple(param.shape[:-2]), param.numel() // 40
+        out = {k: torch.empty(lead + (tau.size, w), device=self.device) for k, w in widths.items() if k in want}
+        ptr = lambda k: C.c_void_p(out[k].data_ptr()) if k in out and out[k].numel() > 0 else None
+        rc = self.lib.mind_curve_eval(self.ctx, -1 if basis is None else _lib.BASIS.index(basis), C.c_void_p(param.data_ptr()) if n else None, n,
+                                      tau.ctypes.data_as(C.POINTER(C.c_double)), tau.size, ptr("reg"), ptr("vel"), ptr("cov_vel"))
+        _lib.check(self.lib, self.ctx, rc, "mind_curve_eval")
+        return out
 
     def set_profiling(self, on):
         self.lib.mind_set_profiling(self.ctx, 1 if on else 0)
@@ -280,9 +316,10 @@ class HipPredictor:
         _lib.check(self.lib, self.ctx, self.lib.mind_ctx_synchronize(self.ctx), "mind_ctx_synchronize")
 
     def predict(self, actors, actor_off, lanes, lane_off, actor_ctrs, actor_vecs, lane_ctrs, lane_vecs,
-                tgt_nodes, tgt_rpe, rpe=None, lane_feat=None, want_lane_feat=False, taps=False):
+                tgt_nodes, tgt_rpe, rpe=None, lane_feat=None, want_lane_feat=False, taps=False, aux=False):
         """All tensors fp32 contiguous on ``self.device``; actor_off/lane_off are int prefix-sum lists [B+1].
-        Returns dict(cls [B,6], reg [A,6,60,5], vel [A,6,60,2], ...)."""
+        Returns dict(cls [B,6], reg [A,6,60,5], vel [A,6,60,2], ...); with ``aux`` also cov_vel [A,6,60,3] and param [A,6,8,5] (the control
+        points, agent-major: the rest of the reference's res_aux, network.py:554)."""
         dev = self.device
         B = len(actor_off) - 1
         A, L = int(actor_off[-1]), int(lane_off[-1])
@@ -325,7 +362,13 @@ class HipPredictor:
             out["actor_emb"] = torch.empty(A, 128, device=dev)
             out["cls_emb"] = torch.empty(B, 128, device=dev)
             po.actor_emb, po.cls_emb = ptr(out["actor_emb"]), ptr(out["cls_emb"])
-        rc = self.lib.mind_predict_batch(self.ctx, C.byref(sb), C.byref(po))
+        if aux:
+            out["cov_vel"] = torch.empty(A, 6, 60, 3, device=dev)
+            out["param"] = torch.empty(A, 6, 8, 5, device=dev)
+            pa = _lib.PredAux(ptr(out["cov_vel"]), ptr(out["param"]))
+            rc = self.lib.mind_predict_batch_aux(self.ctx, C.byref(sb), C.byref(po), C.byref(pa))
+        else:
+            rc = self.lib.mind_predict_batch(self.ctx, C.byref(sb), C.byref(po))
         _lib.check(self.lib, self.ctx, rc, "mind_predict_batch")
         return out
 

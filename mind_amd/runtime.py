@@ -53,6 +53,21 @@ def ilqr_policy_rollouts(cfg, flats, x0, lane, target_vel, use_exo, us, k, K, al
                                               want_us=want_us, want_L=want_L)
 
 
+def set_decoder_basis(name):
+    """``HipPredictor.set_decoder_basis`` on this thread's runtime: 'bezier' | 'monomial' for every net and planner that shares it."""
+    return get_runtime().set_decoder_basis(name)
+
+
+def get_decoder_basis():
+    """``HipPredictor.get_decoder_basis`` on this thread's runtime."""
+    return get_runtime().get_decoder_basis()
+
+
+def curve_eval(param, tau, basis=None, want=("reg", "vel", "cov_vel")):
+    """``HipPredictor.curve_eval`` on this thread's runtime: the decoder's curves at the times ``tau`` from control points ``param``."""
+    return get_runtime().curve_eval(param, tau, basis=basis, want=want)
+
+
 def reset_runtime():
     rt = getattr(_local, "rt", None)
     if rt is not None:
