@@ -914,6 +914,62 @@ int mind_ilqr_policy_rollouts(mind_ctx *ctx, const mind_ilqr_cfg *cfg, const min
                               const double *K, int n_cand, const double *alpha, const double *dx0, double *xs,
                               double *us_out, double *L, double *J);
 
+/* ------------------------------------------------------------------------------------------------
+ * Clearance audit of plans and closed-loop episodes (mind_amd/csrc/box_geom.h, audit_kernels.hip).  The reference gives
+ * every agent a BBox by object type (agent.py:92-105, common/bbox.py), draws it centred on state[:2]
+ * (visualization.py:69-72) and never tests it against anything; evaluate_traj_tree (planner.py:180-198) ignores every exo
+ * agent.  These calls say what a plan or an episode did to the other road users.  They sit outside every planning cycle:
+ * synchronous on the context's stream, with scratch of their own.  Hit convention: clearance < 0 (touching, 0.0, is no hit).
+ * A box is {length, width, center_offset}: its centre is (x, y) + center_offset (cos yaw, sin yaw); 0 is the reference's
+ * footprint convention.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct { double length, width, center_offset; } mind_audit_box;
+
+/* n_cand candidate state sets xs HOST [n_cand, sum M, 6] (rows in key order, tree after tree, as mind_ilqr_score_trees
+ * returns them) on the cost trees of a plan; only n_nodes, prob, n_agents, agent_mean and agent_cov of the trees are read.
+ * For trajectory node i of tree t, paired with agent_mean[i] as the solver pairs them (trajectory_tree.py:78-118),
+ *   node_clear[i] = min over exo agents j = 1..a_t-1 of
+ *                   dist(mean[i,j] -> ego box at xs[i], yaw xs[i][3]) - ((double)cov[i,j] + exo_margin),
+ * the signed distance of the disc the exo term prices (trajectory_tree.py:95-102) to the ego box; node_agent[i] = that j,
+ * the lowest winning ties; a_t == 1: +inf / -1.  Per (candidate, tree): tree_min with tree_node and tree_agent (the lowest
+ * key wins ties), tree_hits = nodes with clearance < 0, tree_first = the lowest such key (-1: none), tree_mass = the
+ * sequential key-order sum from 0.0 of (double)prob[i] over the hit nodes.  A node whose state is not finite reports
+ * NaN / -1, and its tree min = NaN, node = that key, agent = -1, hits = -1, first = -1, mass = NaN.
+ * Outputs HOST, each may be NULL (not all): node_* [n_cand, sum M], tree_* [n_cand, n_trees].
+ * MIND_EINVAL: a NULL required pointer, a negative count, a non-finite or negative box dimension, margin or cov, a
+ * non-finite mean, all outputs NULL, n_cand x sum M > 2^20.  n_cand == 0 is a successful no-op.  MIND_ESTATE while a plan
+ * begun with mind_aime_plan_begin runs or a tree-iLQR call begun on the context is pending. */
+typedef struct {
+  double *node_clear; int32_t *node_agent;
+  double *tree_min; int32_t *tree_node, *tree_agent, *tree_hits, *tree_first; double *tree_mass;
+} mind_audit_plan_out;
+int mind_audit_plan(mind_ctx *ctx, const mind_audit_box *ego, double exo_margin, const mind_cost_tree *trees,
+                    int n_trees, int n_cand, const double *xs, const mind_audit_plan_out *out);
+
+/* n_ego ego traces ego_states HOST [n_ego, n_steps, 4] = (x, y, v, yaw) against one replayed scene: exo HOST
+ * [n_steps, n_tracks, 5] = (x, y, heading, vx, vy) and valid HOST [n_steps, n_tracks] uint8, the layouts of
+ * mind_loop_desc.exo_obs / exo_valid (row 0 is the ego's and is not read); boxes HOST [n_tracks, 2] = (length, width)
+ * centred on the track's (x, y).  Per (ego, step): step_clear = the minimum signed rectangle-rectangle clearance over
+ * the valid tracks 1..n_tracks-1 and step_track = that track, the lowest winning ties; no valid track: +inf / -1.  Per ego:
+ * ego_min with ego_step and ego_track (the lowest step wins ties), ego_hits = steps with clearance < 0, ego_first = the
+ * first of them (-1: none).  Outputs HOST, each may be NULL (not all): step_* [n_ego, n_steps], ego_* [n_ego].
+ * MIND_EINVAL: a NULL required pointer, a negative count, n_tracks < 1, a non-finite or negative box dimension, a
+ * non-finite ego state or valid track row, all outputs NULL, n_ego x n_steps > 2^22, n_steps x n_tracks > 2^24.
+ * n_ego == 0 or n_steps == 0 is a successful no-op.  MIND_ESTATE as mind_audit_plan. */
+typedef struct {
+  double *step_clear; int32_t *step_track;
+  double *ego_min; int32_t *ego_step, *ego_track, *ego_hits, *ego_first;
+} mind_audit_episode_out;
+int mind_audit_episode(mind_ctx *ctx, const mind_audit_box *ego, int n_ego, int n_steps, int n_tracks,
+                       const double *ego_states, const double *exo, const uint8_t *valid, const double *boxes,
+                       const mind_audit_episode_out *out);
+
+/* box_geom.h on the CPU (host only, no context): n pairs, a HOST [n, 5] = (x, y, yaw, L, W), the offset taken as b - a.
+ * kind 0: rectangle a against the disc b = (x, y, r, -, -): bg_point_rect - r.  kind 1: rectangle a against the rectangle
+ * b [n, 5]: bg_rect_rect.  trig HOST [n, 4] = (cos a, sin a, cos b, sin b), or NULL = the kernels' own sin / cos
+ * (mind_trig.h).  out HOST [n].  MIND_EINVAL for another kind, n < 0 or a NULL pointer. */
+int mind_debug_box_clearance(int kind, int n, const double *a, const double *b, const double *trig, double *out);
+
 #ifdef __cplusplus
 }
 #endif

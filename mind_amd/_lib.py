@@ -52,6 +52,22 @@ class IlqrGainsOut(C.Structure):     # mind_ilqr_gains_out
     _fields_ = [(n, C.POINTER(C.c_double)) for n in ("k", "K", "dV", "V_x", "V_xx", "xs", "L", "J")] + [("bad_node", C.POINTER(C.c_int32))]
 
 
+class AuditBox(C.Structure):        # mind_audit_box
+    _fields_ = [("length", C.c_double), ("width", C.c_double), ("center_offset", C.c_double)]
+
+
+class AuditPlanOut(C.Structure):    # mind_audit_plan_out
+    _fields_ = [("node_clear", C.POINTER(C.c_double)), ("node_agent", C.POINTER(C.c_int32)), ("tree_min", C.POINTER(C.c_double)),
+                ("tree_node", C.POINTER(C.c_int32)), ("tree_agent", C.POINTER(C.c_int32)), ("tree_hits", C.POINTER(C.c_int32)),
+                ("tree_first", C.POINTER(C.c_int32)), ("tree_mass", C.POINTER(C.c_double))]
+
+
+class AuditEpisodeOut(C.Structure):     # mind_audit_episode_out
+    _fields_ = [("step_clear", C.POINTER(C.c_double)), ("step_track", C.POINTER(C.c_int32)), ("ego_min", C.POINTER(C.c_double)),
+                ("ego_step", C.POINTER(C.c_int32)), ("ego_track", C.POINTER(C.c_int32)), ("ego_hits", C.POINTER(C.c_int32)),
+                ("ego_first", C.POINTER(C.c_int32))]
+
+
 class WorldIn(C.Structure):
     _fields_ = [("n_scenes", C.c_int), ("actor_off", C.POINTER(C.c_int32)), ("reg", C.c_void_p), ("vel", C.c_void_p),
                 ("actor_ctrs", C.c_void_p), ("actor_vecs", C.c_void_p), ("rot", C.POINTER(C.c_float)),
@@ -176,6 +192,7 @@ EXPORTS = ["mind_ctx_create", "mind_ctx_destroy", "mind_last_error_string", "min
            "mind_debug_read", "mind_set_pair_precision", "mind_get_pair_precision", "mind_debug_pack_bfrag", "mind_debug_pack_conv_frag", "mind_debug_pack", "mind_debug_weight_image", "mind_debug_weight_bind", "mind_debug_pair_schedule", "mind_debug_predict_choice", "mind_debug_ilqr_plan", "mind_debug_aime_book", "mind_set_tuning", "mind_last_ilqr_stats", "mind_aime_plan", "mind_last_ilqr_profile", "mind_eval_traj_trees", "mind_last_ilqr_trace", "mind_ilqr_contingency_begin", "mind_ilqr_finish", "mind_fill_tracks", "mind_ilqr_contingency_begin_plan", "mind_debug_trig", "mind_aime_plan_begin", "mind_aime_plan_poll", "mind_aime_plan_finish", "mind_ctx_busy", "mind_ilqr_finish_plan",
            "mind_set_exchange", "mind_last_exchange_stats", "mind_debug_wait_word",
            "mind_predict_batch_aux", "mind_set_decoder_basis", "mind_get_decoder_basis", "mind_curve_eval", "mind_debug_curve_basis",
+           "mind_audit_plan", "mind_audit_episode", "mind_debug_box_clearance",
            "mind_loop_create", "mind_loop_destroy", "mind_loop_reset", "mind_loop_advance", "mind_loop_state", "mind_loop_last_plan", "mind_loop_export",
            "mind_planner_create", "mind_planner_destroy", "mind_planner_reset", "mind_planner_observe", "mind_planner_set_lanes", "mind_planner_set_target_lane",
            "mind_planner_set_solve_lane", "mind_planner_set_eval_lane", "mind_planner_plan", "mind_planner_last_plan", "mind_planner_export"]
@@ -302,6 +319,11 @@ def load():
     lib.mind_planner_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PlannerOut)]
     lib.mind_planner_last_plan.argtypes = [C.c_void_p, C.POINTER(AimePlanOut)] + [C.POINTER(C.c_void_p)] * 6 + [C.c_void_p]
     lib.mind_planner_export.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.mind_audit_plan.argtypes = [C.c_void_p, C.POINTER(AuditBox), C.c_double, C.POINTER(CostTree), C.c_int, C.c_int, C.POINTER(C.c_double),
+                                    C.POINTER(AuditPlanOut)]
+    lib.mind_audit_episode.argtypes = [C.c_void_p, C.POINTER(AuditBox), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                       C.POINTER(C.c_uint8), C.POINTER(C.c_double), C.POINTER(AuditEpisodeOut)]
+    lib.mind_debug_box_clearance.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     for n in EXPORTS:
         getattr(lib, n)
         if n not in ("mind_last_error_string", "mind_debug_read"):
@@ -486,6 +508,26 @@ def pack(what, w, a=0, b=0, c=0, cap=1 << 20):
     n = lib.mind_debug_pack(what.encode(), w.ctypes.data_as(C.POINTER(C.c_float)), a, b, c, out.ctypes.data_as(C.POINTER(C.c_float)), cap)
     assert n > 0, (what, n)
     return out[:n].copy()
+
+
+def box_clearance(kind, a, b, trig=None):
+    """box_geom.h on the CPU (mind_debug_box_clearance; no GPU), pair by pair: a [n, 5] = (x, y, yaw, L, W) against b [n, 5] -- kind 0 (or
+    "disc"): discs (x, y, r, -, -), kind 1 (or "rect"): rectangles; trig [n, 4] = (cos a, sin a, cos b, sin b), None = the kernels' own
+    sin / cos.  -> float64 [n]"""
+    import numpy as np
+    lib = load()
+    kind = {"disc": 0, "rect": 1}.get(kind, kind)
+    a = np.ascontiguousarray(a, np.float64).reshape(-1, 5)
+    b = np.ascontiguousarray(b, np.float64).reshape(-1, 5)
+    tg = None if trig is None else np.ascontiguousarray(trig, np.float64).reshape(-1, 4)
+    if len(b) != len(a) or (tg is not None and len(tg) != len(a)):
+        raise ValueError(f"box_clearance: {len(a)} boxes a, {len(b)} b" + ("" if tg is None else f", {len(tg)} trig rows"))
+    out = np.zeros(len(a))
+    dp = lambda v: None if v is None else v.ctypes.data_as(C.POINTER(C.c_double))
+    rc = lib.mind_debug_box_clearance(int(kind), len(a), dp(a), dp(b), dp(tg), dp(out))
+    if rc != MIND_OK:
+        raise ValueError(f"mind_debug_box_clearance rejects kind {kind!r}")
+    return out
 
 
 class MindError(RuntimeError):

@@ -1,0 +1,161 @@
+"""Clearance audit of plans and closed-loop episodes: what the planner did to the other road users.
+
+The reference gives every agent a ``BBox`` by object type (agent.py:92-105, common/bbox.py), carries it in each observation and draws it
+centred on ``state[:2]`` (visualization.py:69-72), but never tests it against anything; ``evaluate_traj_tree`` (planner.py:180-198) prices
+comfort, speed and lane distance and ignores every exo agent.  This module measures outcomes -- it is called from no planning cycle and
+changes no choice:
+
+* ``audit_plan(scen_tree, traj_tree)``: signed distance of the ego box at every trajectory node to the discs the solver's exo term prices
+  (the predicted mean of the node's step, radius max-sigma + ``w_exo_cov_offset``; trajectory_tree.py:78-118), per node and per tree;
+* ``audit_rollouts(flat, xs)``: the same for candidate state sets ``[C, M, 6]`` as ``HipPredictor.ilqr_score`` / ``ilqr_policy_rollouts``
+  return them;
+* ``EpisodeAuditor(sim)``: box-to-box clearance of the ego actually driven in a ``ClosedLoopSim`` against the replayed tracks, per step.
+
+All numbers come from the device (mind_audit_plan / mind_audit_episode; geometry: mind_amd/csrc/box_geom.h).  Hit convention:
+clearance < 0; touching (0.0) is no hit.  The nominal boxes are nominal: every box is an argument."""
+import numpy as np
+
+from .planners.mind.utils import _name
+
+# (length, width) by object type: the table of agent.py:92-105 over common/bbox.py
+BOXES = {"VEHICLE": (4.5, 2.0), "PEDESTRIAN": (0.5, 0.75), "CYCLIST": (1.5, 0.75), "MOTORCYCLIST": (1.5, 0.75), "BUS": (7.0, 2.1)}
+UNKNOWN_BOX = (1.0, 1.0)        # ObjectType.UNKNOWN and every static object
+DEFAULT_EXO_MARGIN = 2.5        # opt_cfg["w_exo_cov_offset"] of every planning config (configs/planning/_base.py)
+
+
+def box_for(object_type):
+    """(length, width) of an av2 ObjectType (or a look-alike, or its name)"""
+    return BOXES.get(_name(object_type), UNKNOWN_BOX)
+
+
+def _runtime(runtime):
+    if runtime is not None:
+        return runtime
+    from .runtime import get_runtime
+    return get_runtime()
+
+
+def _margin(exo_margin, planner):
+    if exo_margin is not None:
+        return float(exo_margin)
+    if planner is not None:
+        return float(planner.traj_tree_opt.config.opt_cfg["w_exo_cov_offset"])
+    return DEFAULT_EXO_MARGIN
+
+
+def _flat_of(scen_tree):
+    from .planners.mind.trajectory_tree import flatten_scenario_tree
+    return getattr(scen_tree, "_flat", None) or flatten_scenario_tree(scen_tree)
+
+
+def _states_of(traj_tree, M):
+    """states [M, 6] of the trajectory-tree keys 0..M-1 (the root, key -1, holds x0 and is no trajectory node)"""
+    arr = getattr(traj_tree, "_arrays", None)
+    xs = np.asarray(arr[0], np.float64)[1:] if arr is not None else np.array([traj_tree.get_node(k).data[0] for k in range(M)], np.float64)
+    if xs.shape != (M, 6):
+        raise ValueError(f"the trajectory tree holds {list(xs.shape)} states, the scenario tree flattens to {M} trajectory nodes")
+    return xs
+
+
+def audit_plan(scen_tree, traj_tree, ego_box=BOXES["VEHICLE"], exo_margin=None, runtime=None, planner=None):
+    """Audit what ``plan()`` returned (``[[scen_tree], [traj_tree]]`` of MINDPlanner.plan, native_plan or the native loop's
+    ``last_result``): ``scen_tree`` / ``traj_tree`` are the two lists (or one tree each).  Tree t's states are read from its trajectory-tree
+    keys 0..M-1 and paired with the flattened scenario tree's agents; ONE device call for all trees.  ``exo_margin``: None = the
+    ``w_exo_cov_offset`` of ``planner``'s config, 2.5 without a planner.  Returns a dict: per-tree lists node_clear [M_t] / node_agent [M_t]
+    and arrays tree_min, tree_node, tree_agent, tree_hits, tree_first, tree_mass [n_trees]."""
+    scen = list(scen_tree) if isinstance(scen_tree, (list, tuple)) else [scen_tree]
+    traj = list(traj_tree) if isinstance(traj_tree, (list, tuple)) else [traj_tree]
+    if len(scen) != len(traj) or not scen:
+        raise ValueError(f"audit_plan: {len(scen)} scenario trees, {len(traj)} trajectory trees")
+    flats = [_flat_of(t) for t in scen]
+    xs = [_states_of(t, len(f["parent"]))[None] for t, f in zip(traj, flats)]
+    res = _runtime(runtime).audit_plan(flats, xs, ego_box, _margin(exo_margin, planner))
+    out = {k: [a[0] for a in res[k]] for k in ("node_clear", "node_agent")}
+    out.update({k: v[0] for k, v in res.items() if k.startswith("tree_")})
+    return out
+
+
+def audit_rollouts(solver_or_flat, xs, ego_box=BOXES["VEHICLE"], exo_margin=None, runtime=None):
+    """The audit of C candidate state sets ``xs`` [C, M, 6] (or [M, 6]) on ONE cost tree: a flat dict (parent, prob, mean, cov) or a
+    ``TrajectoryTreeOptimizer`` (its last prepared cost tree; ``exo_margin`` then defaults to its config's).  Returns node_clear [C, M],
+    node_agent [C, M] and tree_min, tree_node, tree_agent, tree_hits, tree_first, tree_mass [C]."""
+    flat = solver_or_flat if isinstance(solver_or_flat, dict) else getattr(solver_or_flat, "cost_tree", None)
+    if not isinstance(flat, dict) or not all(k in flat for k in ("parent", "prob", "mean", "cov")):
+        raise TypeError("audit_rollouts: a flat cost tree (parent, prob, mean, cov) or a TrajectoryTreeOptimizer with a prepared cost tree is needed")
+    if exo_margin is None and not isinstance(solver_or_flat, dict) and getattr(solver_or_flat, "config", None) is not None:
+        exo_margin = solver_or_flat.config.opt_cfg["w_exo_cov_offset"]
+    x = np.asarray(xs, np.float64)
+    one = x.ndim == 2
+    x = x[None] if one else x
+    M = len(flat["parent"])
+    if x.ndim != 3 or x.shape[1:] != (M, 6):
+        raise ValueError(f"audit_rollouts: xs must be [C, {M}, 6] or [{M}, 6], got {list(np.shape(xs))}")
+    res = _runtime(runtime).audit_plan([flat], x, ego_box, _margin(exo_margin, None))
+    out = {k: res[k][0] for k in ("node_clear", "node_agent")}
+    out.update({k: v[:, 0] for k, v in res.items() if k.startswith("tree_")})
+    return {k: v[0] for k, v in out.items()} if one else out
+
+
+def tabulate_exo(world, times):
+    """The world's exo rows at ``times``: exo [S, n, 5] = (x, y, heading, vx, vy), valid uint8 [S, n] (the layouts of the native loop's
+    tables; row 0, the ego's, stays empty) and boxes [n, 2] from the tracks' object types"""
+    n, S = int(world.n_agents), len(times)
+    is_valid = getattr(world, "is_valid", None)
+    exo, valid = np.zeros((S, n, 5)), np.zeros((S, n), np.uint8)
+    for s, t in enumerate(times):
+        for i in range(1, n):
+            if is_valid is None or is_valid(i, t):
+                x, y, v, yaw = (float(q) for q in world.agent_state(i, t))
+                exo[s, i] = (x, y, yaw, v * np.cos(yaw), v * np.sin(yaw))
+                valid[s, i] = 1
+    boxes = np.array([box_for(world.object_type(i)) for i in range(n)], np.float64).reshape(n, 2)
+    return exo, valid, boxes
+
+
+class EpisodeAuditor:
+    """Wraps a ClosedLoopSim the way FrameRecorder does: ``step()`` records the ego state in force, the ``enabled`` flag and the time, then
+    advances the simulation; ``report()`` tabulates the world's tracks at the recorded times and audits the whole trace in one device call."""
+
+    def __init__(self, sim, ego_box=BOXES["VEHICLE"], runtime=None):
+        self.sim, self.ego_box, self.runtime = sim, ego_box, runtime
+        self.states, self.enabled, self.times = [], [], []
+
+    def step(self):
+        sim = self.sim
+        t = sim.sim_time
+        self.states.append(np.array(sim.state if sim.enabled else sim.world.agent_state(0, t), dtype=np.float64))
+        self.enabled.append(bool(sim.enabled))
+        self.times.append(t)
+        return sim.step()
+
+    def run(self, n_steps):
+        for _ in range(n_steps):
+            self.step()
+        return self
+
+    def report(self):
+        """-> dict: ego_min, ego_step, ego_track, ego_hits, ego_first of the whole trace; times [S], enabled [S], step_clear [S],
+        step_track [S]; ``before`` / ``after``: the same summary and per-step arrays of the steps before and from the take-over (None
+        when there is no such step); steps are indices into the recorded trace"""
+        S = len(self.times)
+        if S == 0:
+            raise RuntimeError("EpisodeAuditor.report: no step was recorded")
+        ego = np.stack(self.states)
+        exo, valid, boxes = tabulate_exo(self.sim.world, self.times)
+        res = _runtime(self.runtime).audit_episode(ego[None], exo, valid, boxes, self.ego_box)
+        clear, track = res["step_clear"][0], res["step_track"][0]
+        en = np.array(self.enabled, bool)
+        out = dict(times=np.array(self.times), enabled=en, step_clear=clear, step_track=track,
+                   **{k: (float if k == "ego_min" else int)(res[k][0]) for k in ("ego_min", "ego_step", "ego_track", "ego_hits", "ego_first")})
+        out["before"], out["after"] = _part(clear, track, np.flatnonzero(~en)), _part(clear, track, np.flatnonzero(en))
+        return out
+
+
+def _part(clear, track, idx):
+    """summary of the steps ``idx`` of a trace, by the rules of the whole-trace summary (the lowest step wins ties)"""
+    if len(idx) == 0:
+        return None
+    c, hit = clear[idx], np.flatnonzero(clear[idx] < 0.0)
+    k = int(np.argmin(c))               # (first minimum)
+    return dict(steps=idx, step_clear=c, step_track=track[idx], ego_min=float(c[k]), ego_step=int(idx[k]), ego_track=int(track[idx[k]]),
+                ego_hits=int(len(hit)), ego_first=int(idx[hit[0]]) if len(hit) else -1)

@@ -599,6 +599,83 @@ class HipPredictor:
         split = lambda a: None if a is None else [a[:, offs[i]:offs[i + 1]].copy() for i in range(n)]
         return split(xs), split(uo), split(L), J
 
+    # ---- clearance audit (mind_audit_plan / mind_audit_episode): outside every planning cycle -------------
+    @staticmethod
+    def _audit_box(box, name):
+        """(length, width[, center_offset]) -> mind_audit_box"""
+        b = np.asarray(box, np.float64).ravel()
+        if b.size not in (2, 3) or not np.all(np.isfinite(b)) or np.any(b[:2] < 0.0):
+            raise ValueError(f"{name} must be (length, width[, center_offset]) with finite length, width >= 0, got {box!r}")
+        return _lib.AuditBox(float(b[0]), float(b[1]), float(b[2]) if b.size == 3 else 0.0)
+
+    def audit_plan(self, flats, xs, ego_box, exo_margin):
+        """Clearance of C candidate state sets on every cost tree of ``flats`` (planner-mode flat dicts as ``ilqr_solve`` takes them) in one
+        call (mind_audit_plan, k_audit_plan).  ``xs``: [C, sum M, 6], or one [C, M_t, 6] per tree, as ``ilqr_score`` returns them; ``ego_box``:
+        (length, width[, center_offset]); ``exo_margin``: what is added to every agent's max-sigma.  Returns a dict: per-tree lists node_clear
+        [C, M_t] / node_agent int32 [C, M_t], and tree_min, tree_node, tree_agent, tree_hits, tree_first, tree_mass [C, n_trees]."""
+        n = len(flats)
+        keep = []
+        trees, Ms = self._cost_trees(flats, None, keep)
+        Mt = int(sum(Ms))
+        if isinstance(xs, (list, tuple)):
+            xs = np.concatenate([np.asarray(x, np.float64) for x in xs], axis=1)
+        x = np.ascontiguousarray(xs, np.float64)
+        if x.ndim != 3 or x.shape[1:] != (Mt, 6):
+            raise ValueError(f"xs must be [C, {Mt}, 6] for these cost trees, got {list(x.shape)}")
+        for i, f in enumerate(flats):
+            a = trees[i].n_agents
+            if np.shape(f["mean"]) != (Ms[i], a, 2) or np.shape(f["cov"]) != (Ms[i], a) or np.shape(f["prob"]) != (Ms[i],):
+                raise ValueError(f"cost tree {i}: prob [M] / mean [M, a, 2] / cov [M, a] do not match parent [M = {Ms[i]}]")
+        margin = float(exo_margin)
+        if not np.isfinite(margin) or margin < 0.0:
+            raise ValueError(f"exo_margin must be finite and >= 0, got {exo_margin!r}")
+        box = self._audit_box(ego_box, "ego_box")
+        nc = x.shape[0]
+        res = dict(node_clear=np.zeros((nc, Mt)), node_agent=np.zeros((nc, Mt), np.int32), tree_min=np.zeros((nc, n)),
+                   tree_node=np.zeros((nc, n), np.int32), tree_agent=np.zeros((nc, n), np.int32), tree_hits=np.zeros((nc, n), np.int32),
+                   tree_first=np.zeros((nc, n), np.int32), tree_mass=np.zeros((nc, n)))
+        out = _lib.AuditPlanOut()
+        for name, a in res.items():
+            setattr(out, name, a.ctypes.data_as(C.POINTER(C.c_double if a.dtype == np.float64 else C.c_int32)))
+        rc = self.lib.mind_audit_plan(self.ctx, C.byref(box), C.c_double(margin), trees, n, nc, x.ctypes.data_as(C.POINTER(C.c_double)), C.byref(out))
+        _lib.check(self.lib, self.ctx, rc, "mind_audit_plan")
+        offs = np.cumsum([0] + Ms)
+        for name in ("node_clear", "node_agent"):
+            res[name] = [res[name][:, offs[i]:offs[i + 1]].copy() for i in range(n)]
+        return res
+
+    def audit_episode(self, ego_states, exo, valid, boxes, ego_box):
+        """Clearance of E ego traces against one replayed scene in one call (mind_audit_episode, k_audit_episode).  ``ego_states``: [E, S, 4]
+        (or [S, 4]) = (x, y, v, yaw); ``exo`` [S, n, 5] = (x, y, heading, vx, vy) and ``valid`` [S, n], the layouts of the native loop's
+        tables (row 0 is the ego's: not read); ``boxes`` [n, 2] = (length, width) per track; ``ego_box``: (length, width[, center_offset]).
+        Returns a dict: step_clear [E, S], step_track int32 [E, S], ego_min [E], ego_step, ego_track, ego_hits, ego_first int32 [E]."""
+        eg = np.ascontiguousarray(ego_states, np.float64)
+        if eg.ndim == 2:
+            eg = eg[None]
+        if eg.ndim != 3 or eg.shape[2] != 4:
+            raise ValueError(f"ego_states must be [E, S, 4], got {list(eg.shape)}")
+        E, S = eg.shape[:2]
+        ex = np.ascontiguousarray(exo, np.float64)
+        va = np.ascontiguousarray(valid, np.uint8)
+        bx = np.ascontiguousarray(boxes, np.float64)
+        if ex.ndim != 3 or ex.shape[0] != S or ex.shape[2] != 5 or ex.shape[1] < 1:
+            raise ValueError(f"exo must be [S = {S}, n >= 1, 5], got {list(ex.shape)}")
+        nt = ex.shape[1]
+        if va.shape != (S, nt) or bx.shape != (nt, 2):
+            raise ValueError(f"valid must be [{S}, {nt}] and boxes [{nt}, 2], got {list(va.shape)} and {list(bx.shape)}")
+        if not np.all(np.isfinite(bx[1:])) or np.any(bx[1:] < 0.0):
+            raise ValueError("boxes must be finite and >= 0")
+        box = self._audit_box(ego_box, "ego_box")
+        res = dict(step_clear=np.zeros((E, S)), step_track=np.zeros((E, S), np.int32), ego_min=np.zeros(E), ego_step=np.zeros(E, np.int32),
+                   ego_track=np.zeros(E, np.int32), ego_hits=np.zeros(E, np.int32), ego_first=np.zeros(E, np.int32))
+        out = _lib.AuditEpisodeOut()
+        for name, a in res.items():
+            setattr(out, name, a.ctypes.data_as(C.POINTER(C.c_double if a.dtype == np.float64 else C.c_int32)))
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        rc = self.lib.mind_audit_episode(self.ctx, C.byref(box), E, S, nt, dp(eg), dp(ex), va.ctypes.data_as(C.POINTER(C.c_uint8)), dp(bx), C.byref(out))
+        _lib.check(self.lib, self.ctx, rc, "mind_audit_episode")
+        return res
+
     def aime_world(self, reg, vel, actor_ctrs, actor_vecs, a_off, rots, origs, cov_last, last, target_lane=None, cls=None,
                    scen_prob=None, dist_thres=None):
         """k7 on the device (mind_aime_world): reg [A,6,60,5] / vel [A,6,60,2] / actor_ctrs, actor_vecs [A,2] device

@@ -53,6 +53,16 @@ def ilqr_policy_rollouts(cfg, flats, x0, lane, target_vel, use_exo, us, k, K, al
                                               want_us=want_us, want_L=want_L)
 
 
+def audit_plan(flats, xs, ego_box, exo_margin):
+    """``HipPredictor.audit_plan`` on this thread's runtime: clearance of candidate state sets on the cost trees of a plan."""
+    return get_runtime().audit_plan(flats, xs, ego_box, exo_margin)
+
+
+def audit_episode(ego_states, exo, valid, boxes, ego_box):
+    """``HipPredictor.audit_episode`` on this thread's runtime: clearance of ego traces against one replayed scene."""
+    return get_runtime().audit_episode(ego_states, exo, valid, boxes, ego_box)
+
+
 def set_decoder_basis(name):
     """``HipPredictor.set_decoder_basis`` on this thread's runtime: 'bezier' | 'monomial' for every net and planner that shares it."""
     return get_runtime().set_decoder_basis(name)
