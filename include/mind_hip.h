@@ -970,6 +970,50 @@ int mind_audit_episode(mind_ctx *ctx, const mind_audit_box *ego, int n_ego, int 
  * (mind_trig.h).  out HOST [n].  MIND_EINVAL for another kind, n < 0 or a NULL pointer. */
 int mind_debug_box_clearance(int kind, int n, const double *a, const double *b, const double *trig, double *out);
 
+/* ------------------------------------------------------------------------------------------------
+ * Forecast scoring (mind_amd/csrc/forecast_score.h, forecast_kernels.hip): what the predictor said about the other road
+ * users against what they went on to do.  The reference carries reg [a,6,60,5] = (x, y, sx, sy, exp rho) per agent in the
+ * agent-local frame (network.py:545), prices every other agent as a disc of radius max(sx, sy) + w_exo_cov_offset around
+ * the predicted mean (trajectory_tree.py:95-102, scenario_tree.py:325) and never compares either with a recorded future.
+ * Like the audit this call sits outside every planning cycle: synchronous on the context's stream (a mind_predict_batch
+ * queued before it is ordered in front), with scratch of its own.
+ *
+ * Inputs: reg DEVICE [A, K, T, 5] and cls DEVICE [B, K] exactly as mind_pred_out holds them (K = 6, T = 60 there); gt HOST
+ * [A, T, 2] float64, the truth in the same agent-local frame; valid HOST [A, T] uint8; scored HOST [A] uint8 or NULL = all;
+ * actor_off HOST [B + 1], actor_off[0] = 0.  cfg: K in 1..8, T in 1..256, n_h in 1..4 horizons, strictly ascending within
+ * 1..T (horizon h covers the samples t < horizon[h]); miss_radius, disc_scale, disc_offset finite and >= 0.
+ *
+ * Per valid sample, after conversion to double: d = sqrt(dx dx + dy dy), inside when d <= disc_scale max(sx, sy) + disc_offset.
+ * Per (agent, horizon, mode) over the valid samples below the horizon in ascending t: ade = (sequential sum of d) / n_valid,
+ * fde = d at the last valid sample, cover = inside samples, first_out = the first sample not inside (-1: none); no valid
+ * sample: NaN, NaN, 0, -1.  Per (agent, horizon): n_valid, last (-1: none), k_ade / k_fde = the arg-minima over the modes
+ * (the lowest k wins ties, a NaN never wins, -1 when every mode is NaN or +inf), brier_fde = fde[k_fde] + (1 - cls[b, k_fde])^2
+ * (NaN for -1).  Per (scene, horizon) over the agents with scored[a] and n_valid > 0, in index order: s_n_scored, s_ade[k] /
+ * s_fde[k] = the means over those agents (sequential sums; NaN without one), s_k_ade, s_k_fde, s_brier_fde as above -- the
+ * joint metrics: one mode index serves every agent of the scene --, s_miss_rate = the share of those agents with
+ * fde[a, h, s_k_fde] > miss_radius, s_k_top = argmax cls[b] (the lowest k on ties), s_miss_top = the same share at s_k_top.
+ * A non-finite forecast value has no special case: the arithmetic and comparisons decide (forecast_score.h).
+ * Outputs HOST, each may be NULL (not all).
+ * MIND_EINVAL: a NULL required pointer, K, T, n_h or a horizon out of range or not ascending, a negative or non-finite
+ * radius, scale or offset, actor_off not starting at 0 or not monotone, a non-finite gt at a valid sample, all outputs NULL,
+ * A > 2^20.  A == 0 or n_scenes == 0 is a successful no-op; an empty scene inside a batch is legal.  MIND_ESTATE as
+ * mind_audit_plan. */
+typedef struct { int K, T, n_h; const int32_t *horizon; double miss_radius, disc_scale, disc_offset; } mind_forecast_cfg;
+typedef struct {
+  double *ade, *fde; int32_t *cover, *first_out;                                           /* [A, n_h, K] */
+  int32_t *n_valid, *last, *k_ade, *k_fde; double *brier_fde;                              /* [A, n_h] */
+  int32_t *s_n_scored; double *s_ade, *s_fde;                                              /* [B, n_h], [B, n_h, K] x 2 */
+  int32_t *s_k_ade, *s_k_fde, *s_k_top; double *s_brier_fde, *s_miss_rate, *s_miss_top;    /* [B, n_h] */
+} mind_forecast_out;
+int mind_forecast_score(mind_ctx *ctx, const mind_forecast_cfg *cfg, int n_scenes, const int32_t *actor_off,
+                        const float *reg, const float *cls, const double *gt, const uint8_t *valid,
+                        const uint8_t *scored, const mind_forecast_out *out);
+
+/* forecast_score.h on the CPU (host only, no context): the same call with reg / cls HOST. */
+int mind_debug_forecast_score(const mind_forecast_cfg *cfg, int n_scenes, const int32_t *actor_off, const float *reg,
+                              const float *cls, const double *gt, const uint8_t *valid, const uint8_t *scored,
+                              const mind_forecast_out *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -68,6 +68,23 @@ class AuditEpisodeOut(C.Structure):     # mind_audit_episode_out
                 ("ego_first", C.POINTER(C.c_int32))]
 
 
+class ForecastCfg(C.Structure):     # mind_forecast_cfg
+    _fields_ = [("K", C.c_int), ("T", C.c_int), ("n_h", C.c_int), ("horizon", C.POINTER(C.c_int32)), ("miss_radius", C.c_double),
+                ("disc_scale", C.c_double), ("disc_offset", C.c_double)]
+
+
+# mind_forecast_out, in its field order: name -> (dtype, "a" = per agent / "s" = per scene, trailing K axis)
+FORECAST_OUT = (("ade", "f8", "a", True), ("fde", "f8", "a", True), ("cover", "i4", "a", True), ("first_out", "i4", "a", True),
+                ("n_valid", "i4", "a", False), ("last", "i4", "a", False), ("k_ade", "i4", "a", False), ("k_fde", "i4", "a", False),
+                ("brier_fde", "f8", "a", False), ("s_n_scored", "i4", "s", False), ("s_ade", "f8", "s", True), ("s_fde", "f8", "s", True),
+                ("s_k_ade", "i4", "s", False), ("s_k_fde", "i4", "s", False), ("s_k_top", "i4", "s", False), ("s_brier_fde", "f8", "s", False),
+                ("s_miss_rate", "f8", "s", False), ("s_miss_top", "f8", "s", False))
+
+
+class ForecastOut(C.Structure):     # mind_forecast_out
+    _fields_ = [(n, C.POINTER(C.c_double if dt == "f8" else C.c_int32)) for n, dt, _, _ in FORECAST_OUT]
+
+
 class WorldIn(C.Structure):
     _fields_ = [("n_scenes", C.c_int), ("actor_off", C.POINTER(C.c_int32)), ("reg", C.c_void_p), ("vel", C.c_void_p),
                 ("actor_ctrs", C.c_void_p), ("actor_vecs", C.c_void_p), ("rot", C.POINTER(C.c_float)),
@@ -193,6 +210,7 @@ EXPORTS = ["mind_ctx_create", "mind_ctx_destroy", "mind_last_error_string", "min
            "mind_set_exchange", "mind_last_exchange_stats", "mind_debug_wait_word",
            "mind_predict_batch_aux", "mind_set_decoder_basis", "mind_get_decoder_basis", "mind_curve_eval", "mind_debug_curve_basis",
            "mind_audit_plan", "mind_audit_episode", "mind_debug_box_clearance",
+           "mind_forecast_score", "mind_debug_forecast_score",
            "mind_loop_create", "mind_loop_destroy", "mind_loop_reset", "mind_loop_advance", "mind_loop_state", "mind_loop_last_plan", "mind_loop_export",
            "mind_planner_create", "mind_planner_destroy", "mind_planner_reset", "mind_planner_observe", "mind_planner_set_lanes", "mind_planner_set_target_lane",
            "mind_planner_set_solve_lane", "mind_planner_set_eval_lane", "mind_planner_plan", "mind_planner_last_plan", "mind_planner_export"]
@@ -324,6 +342,10 @@ def load():
     lib.mind_audit_episode.argtypes = [C.c_void_p, C.POINTER(AuditBox), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                        C.POINTER(C.c_uint8), C.POINTER(C.c_double), C.POINTER(AuditEpisodeOut)]
     lib.mind_debug_box_clearance.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    fc_tail = [C.POINTER(ForecastCfg), C.c_int, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint8),
+               C.POINTER(C.c_uint8), C.POINTER(ForecastOut)]
+    lib.mind_forecast_score.argtypes = [C.c_void_p] + fc_tail
+    lib.mind_debug_forecast_score.argtypes = fc_tail
     for n in EXPORTS:
         getattr(lib, n)
         if n not in ("mind_last_error_string", "mind_debug_read"):
@@ -528,6 +550,67 @@ def box_clearance(kind, a, b, trig=None):
     if rc != MIND_OK:
         raise ValueError(f"mind_debug_box_clearance rejects kind {kind!r}")
     return out
+
+
+def forecast_args(K, T, actor_off, gt, valid, scored, horizons, miss_radius, disc_scale, disc_offset, want=None):
+    """The host-side arguments of mind_forecast_score / mind_debug_forecast_score: checked numpy arrays, the configuration and the output
+    record over freshly allocated result arrays (``want``: names of mind_forecast_out, None = all).  -> (cfg, B, actor_off, gt, valid,
+    scored, out, results, keep)"""
+    import numpy as np
+    off = np.ascontiguousarray(actor_off, np.int32).ravel()
+    if off.size < 1:
+        raise ValueError("actor_off must hold B + 1 offsets")
+    B, A = off.size - 1, int(off[-1])
+    g = np.ascontiguousarray(gt, np.float64)
+    v = np.ascontiguousarray(valid, np.uint8)
+    if g.shape != (A, T, 2) or v.shape != (A, T):
+        raise ValueError(f"gt must be [{A}, {T}, 2] and valid [{A}, {T}], got {list(g.shape)} and {list(v.shape)}")
+    sc = None if scored is None else np.ascontiguousarray(scored, np.uint8)
+    if sc is not None and sc.shape != (A,):
+        raise ValueError(f"scored must be [{A}], got {list(sc.shape)}")
+    hz = np.ascontiguousarray(horizons, np.int32).ravel()
+    cfg = ForecastCfg(int(K), int(T), int(hz.size), hz.ctypes.data_as(C.POINTER(C.c_int32)), float(miss_radius), float(disc_scale), float(disc_offset))
+    names = [n for n, _, _, _ in FORECAST_OUT]
+    if want is not None and any(n not in names for n in want):
+        raise ValueError(f"forecast outputs are {names}, got {list(want)}")
+    out, res = ForecastOut(), {}
+    for n, dt, per, has_k in FORECAST_OUT:
+        if want is None or n in want:
+            res[n] = np.zeros((A if per == "a" else B, hz.size) + ((int(K),) if has_k else ()), np.float64 if dt == "f8" else np.int32)
+            setattr(out, n, res[n].ctypes.data_as(C.POINTER(C.c_double if dt == "f8" else C.c_int32)))
+    u8 = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_uint8))
+    return (cfg, B, off.ctypes.data_as(C.POINTER(C.c_int32)), g.ctypes.data_as(C.POINTER(C.c_double)), u8(v), u8(sc), out, res, (off, g, v, sc, hz))
+
+
+def forecast_gather(res):
+    """the conveniences min_ade, min_fde [A, n_h] and s_min_ade, s_min_fde [B, n_h]: the values at the arg-minima (NaN for -1)"""
+    import numpy as np
+    for pre in ("", "s_"):
+        for m in ("ade", "fde"):
+            v, k = res.get(pre + m), res.get(pre + "k_" + m)
+            if v is not None and k is not None:
+                g = np.take_along_axis(v, np.maximum(k, 0)[..., None], axis=-1)[..., 0] if v.size else np.zeros(k.shape)
+                res[pre + "min_" + m] = np.where(k >= 0, g, np.nan)
+    return res
+
+
+def forecast_score_host(reg, cls, actor_off, gt, valid, scored=None, horizons=(60,), miss_radius=2.0, disc_scale=1.0, disc_offset=0.0, want=None):
+    """forecast_score.h on the CPU (mind_debug_forecast_score; no GPU): reg [A, K, T, 5] / cls [B, K] float32 host arrays, the rest as
+    HipPredictor.forecast_score takes it.  -> the same dict of numpy arrays"""
+    import numpy as np
+    lib = load()
+    r = np.ascontiguousarray(reg, np.float32)
+    c = np.ascontiguousarray(cls, np.float32)
+    if r.ndim != 4 or r.shape[3] != 5 or c.ndim != 2 or c.shape[1] != r.shape[1]:
+        raise ValueError(f"reg must be [A, K, T, 5] and cls [B, K], got {list(r.shape)} and {list(c.shape)}")
+    K, T = r.shape[1], r.shape[2]
+    cfg, B, off, g, v, sc, out, res, keep = forecast_args(K, T, actor_off, gt, valid, scored, horizons, miss_radius, disc_scale, disc_offset, want)
+    if r.shape[0] != keep[0][-1] or c.shape[0] != B:
+        raise ValueError(f"reg holds {r.shape[0]} agents and cls {c.shape[0]} scenes, actor_off says {int(keep[0][-1])} and {B}")
+    rc = lib.mind_debug_forecast_score(C.byref(cfg), B, off, C.c_void_p(r.ctypes.data), C.c_void_p(c.ctypes.data), g, v, sc, C.byref(out))
+    if rc != MIND_OK:
+        raise ValueError(f"mind_debug_forecast_score rejects its arguments ({rc})")
+    return forecast_gather(res)
 
 
 class MindError(RuntimeError):

@@ -676,6 +676,31 @@ class HipPredictor:
         _lib.check(self.lib, self.ctx, rc, "mind_audit_episode")
         return res
 
+    # ---- forecast scoring (mind_forecast_score): outside every planning cycle ------------------------------
+    def forecast_score(self, reg, cls, actor_off, gt, valid, scored=None, horizons=(60,), miss_radius=2.0, disc_scale=1.0, disc_offset=0.0,
+                       want=None):
+        """Score a forecast against recorded futures in one call (mind_forecast_score, k_forecast_modes / k_forecast_scenes); the forecast
+        never leaves the device.  ``reg`` [A, K, T, 5] / ``cls`` [B, K]: the device tensors ``predict()`` returns; ``actor_off`` [B + 1];
+        ``gt`` [A, T, 2] float64 in the agents' local frames and ``valid`` [A, T] (mind_amd.forecast.ground_truth); ``scored`` [A] or None =
+        all; ``horizons``: up to four ascending sample counts; ``disc_scale`` / ``disc_offset``: the disc max(sx, sy) * scale + offset.
+        Returns a dict of numpy arrays: ade, fde, cover, first_out [A, n_h, K]; n_valid, last, k_ade, k_fde, brier_fde [A, n_h];
+        s_n_scored, s_k_ade, s_k_fde, s_k_top, s_brier_fde, s_miss_rate, s_miss_top [B, n_h]; s_ade, s_fde [B, n_h, K]; and the values at the
+        arg-minima min_ade, min_fde [A, n_h], s_min_ade, s_min_fde [B, n_h] (NaN for -1).  ``want``: names of the outputs to read back."""
+        for t, name in ((reg, "reg"), (cls, "cls")):
+            assert t.device == self.device and t.dtype == torch.float32, (name, t.device, t.dtype)
+        if reg.dim() != 4 or reg.shape[3] != 5 or cls.dim() != 2 or cls.shape[1] != reg.shape[1]:
+            raise ValueError(f"reg must be [A, K, T, 5] and cls [B, K], got {list(reg.shape)} and {list(cls.shape)}")
+        reg, cls = reg.contiguous(), cls.contiguous()
+        K, T = int(reg.shape[1]), int(reg.shape[2])
+        cfg, B, off, g, v, sc, out, res, keep = _lib.forecast_args(K, T, actor_off, gt, valid, scored, horizons, miss_radius, disc_scale, disc_offset,
+                                                                   want)
+        if reg.shape[0] != int(keep[0][-1]) or cls.shape[0] != B:
+            raise ValueError(f"reg holds {reg.shape[0]} agents and cls {cls.shape[0]} scenes, actor_off says {int(keep[0][-1])} and {B}")
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t.numel() > 0 else None
+        rc = self.lib.mind_forecast_score(self.ctx, C.byref(cfg), B, off, ptr(reg), ptr(cls), g, v, sc, C.byref(out))
+        _lib.check(self.lib, self.ctx, rc, "mind_forecast_score")
+        return _lib.forecast_gather(res)
+
     def aime_world(self, reg, vel, actor_ctrs, actor_vecs, a_off, rots, origs, cov_last, last, target_lane=None, cls=None,
                    scen_prob=None, dist_thres=None):
         """k7 on the device (mind_aime_world): reg [A,6,60,5] / vel [A,6,60,2] / actor_ctrs, actor_vecs [A,2] device

@@ -63,6 +63,11 @@ def audit_episode(ego_states, exo, valid, boxes, ego_box):
     return get_runtime().audit_episode(ego_states, exo, valid, boxes, ego_box)
 
 
+def forecast_score(reg, cls, actor_off, gt, valid, scored=None, **cfg):
+    """``HipPredictor.forecast_score`` on this thread's runtime: a forecast on the device against recorded futures."""
+    return get_runtime().forecast_score(reg, cls, actor_off, gt, valid, scored, **cfg)
+
+
 def set_decoder_basis(name):
     """``HipPredictor.set_decoder_basis`` on this thread's runtime: 'bezier' | 'monomial' for every net and planner that shares it."""
     return get_runtime().set_decoder_basis(name)

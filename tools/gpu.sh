@@ -7,6 +7,7 @@
 #   quick <tag>                         predictor / AIME / plan parity tests + the headline bench line
 #   tests <tag> <pytest args...>        pytest -m gpu on the given files / -k expression
 #   kstats <tag> <workload> [ENV=..]    rocprofv3 --kernel-trace --stats over a short bench run of the workload (demo_1, cfg4tree, stress128tree ...)
+#   forecast <tag>                      tools/forecast_rate.py (mind_forecast_score against read-back + numpy) and a kernel trace of its two kernels
 #   pmc <tag> <kernel> <workload>       two --pmc passes (SQ activity | LDS + instruction mix), kernel trace only beside them, summarised per kernel
 #   ab-env <tag> "<ENV=..>" ...         same-box A/B of environment variants on the headline loop (three interleaved repetitions)
 #   ab-tree <tag> "<ENV=..>" ...        the same on the full cfg4 tree
@@ -82,6 +83,19 @@ kstats)
 import csv
 for r in list(csv.DictReader(open("$O/kernel_stats_$wl.csv")))[:16]:
     print(r["Name"][:72].ljust(72), r["Calls"].rjust(6), ("%.1f us avg" % (float(r["AverageNs"]) / 1e3)).rjust(14), (r["Percentage"] + " %").rjust(10), ("max %.1f us" % (float(r["MaxNs"]) / 1e3)).rjust(16))
+PY
+  ;;
+forecast)
+  # forecast scoring: call times against the read-back + numpy path (-> $O/forecast_rate.json), then, in a run of its own, the two kernels' times
+  timeout -k 10 600 python tools/forecast_rate.py --out $O/forecast_rate.json > $O/forecast_rate.txt 2> $O/forecast_rate.err || { tail -5 $O/forecast_rate.err; exit 1; }
+  cat $O/forecast_rate.txt
+  (cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$O/trace -- python $ROOT/tools/forecast_rate.py --once > /dev/null 2> $ROOT/$O/trace.err) || { tail -5 $O/trace.err; exit 1; }
+  f=$(find $O/trace -name "*kernel_trace.csv" | head -1); cp $f $O/forecast_kernel_trace.csv; rm -rf $O/trace
+  python - <<PY
+import csv
+for r in csv.DictReader(open("$O/forecast_kernel_trace.csv")):
+    if "k_forecast" in r["Kernel_Name"]:
+        print(r["Kernel_Name"][:40].ljust(40), "grid", r.get("Grid_Size_X", "?").rjust(8), ("%.1f us" % ((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)).rjust(12))
 PY
   ;;
 pmc)
