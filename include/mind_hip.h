@@ -1014,6 +1014,62 @@ int mind_debug_forecast_score(const mind_forecast_cfg *cfg, int n_scenes, const 
                               const float *cls, const double *gt, const uint8_t *valid, const uint8_t *scored,
                               const mind_forecast_out *out);
 
+/* ------------------------------------------------------------------------------------------------
+ * Road audit of plans and closed-loop episodes (mind_amd/csrc/road_geom.h, road_kernels.hip): what the ego did to the ROAD.
+ * Every AV2 map carries `drivable_areas` polygons beside `lane_segments`; the reference reads the file and never looks at
+ * them, and no cost term of the tree-iLQR knows where the pavement ends.  Like the clearance audit these calls sit outside
+ * every planning cycle: synchronous on the context's stream, with scratch of their own.
+ *
+ * A road is n_rings >= 1 rings: verts HOST [V, 2] float64 world coordinates and poly_off HOST [n_rings + 1], poly_off[0] = 0,
+ * ring r = the vertices poly_off[r] .. poly_off[r + 1] - 1, implicitly closed (last -> first), at least three, no holes.
+ * The ego box is a mind_audit_box at (x, y, yaw).  Per corner, in the order (+,+), (+,-), (-,-), (-,+) of (long, lat): in at
+ * least one ring, its margin = the maximum over the containing rings of the distance to that ring's boundary; otherwise
+ * -(the minimum over all rings of that distance).  Outside this is the exact distance to the road; inside it is a LOWER
+ * BOUND of the distance to the boundary of the rings' union, exact wherever rings neither overlap nor abut near the point.
+ * Per box: margin = the minimum over the corners (the first wins ties) with that corner, its ring and its edge (index within
+ * the ring; edge e joins vertex e to vertex e + 1, the last to the first); corners only -- a verge passing under the middle
+ * of a box whose corners are all inside is not seen.  Hit: margin < 0; touching (0.0) is no hit.  A state row holding a
+ * non-finite value reports NaN / -1 / -1 / -1.  A duplicated vertex (a zero-length edge) is skipped.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* n_cand candidate state sets xs HOST [n_cand, sum M, 6] (as mind_audit_plan takes them) on the cost trees of a plan; only
+ * n_nodes and prob of the trees are read.  Per node: node_margin, node_corner, node_ring, node_edge.  Per (candidate, tree):
+ * tree_min with tree_node and tree_corner (the lowest key wins ties), tree_hits = nodes with margin < 0, tree_first = the
+ * lowest such key (-1: none), tree_mass = the sequential key-order sum from 0.0 of (double)prob[i] over the hit nodes; a tree
+ * holding a NaN node: min = NaN, node = that key, corner = -1, hits = -1, first = -1, mass = NaN.
+ * Outputs HOST, each may be NULL (not all): node_* [n_cand, sum M], tree_* [n_cand, n_trees].
+ * MIND_EINVAL: a NULL required pointer, a negative count, n_rings < 1 or > 2^16, a ring of fewer than three vertices,
+ * poly_off not starting at 0 or not ascending, more than 2^20 vertices, a non-finite vertex, a non-finite or negative box
+ * dimension, all outputs NULL, n_cand x sum M > 2^20.  n_cand == 0 is a successful no-op.  MIND_ESTATE as mind_audit_plan. */
+typedef struct {
+  double *node_margin; int32_t *node_corner, *node_ring, *node_edge;
+  double *tree_min; int32_t *tree_node, *tree_corner, *tree_hits, *tree_first; double *tree_mass;
+} mind_audit_road_plan_out;
+int mind_audit_road_plan(mind_ctx *ctx, const mind_audit_box *ego, const double *verts, const int32_t *poly_off, int n_rings,
+                         const mind_cost_tree *trees, int n_trees, int n_cand, const double *xs,
+                         const mind_audit_road_plan_out *out);
+
+/* n_ego ego traces ego_states HOST [n_ego, n_steps, 4] = (x, y, v, yaw).  Per (ego, step): step_margin, step_corner,
+ * step_ring, step_edge.  Per ego: ego_min with ego_step and ego_corner (the lowest step wins ties), ego_hits = steps with
+ * margin < 0, ego_first = the first of them (-1: none); a trace holding a NaN step: min = NaN, step = the first such step,
+ * corner = -1, hits = -1, first = -1.  Outputs HOST, each may be NULL (not all): step_* [n_ego, n_steps], ego_* [n_ego].
+ * MIND_EINVAL as above, with n_ego x n_steps > 2^22 in place of the plan's cap.  n_ego == 0 or n_steps == 0 is a successful
+ * no-op.  MIND_ESTATE as mind_audit_plan. */
+typedef struct {
+  double *step_margin; int32_t *step_corner, *step_ring, *step_edge;
+  double *ego_min; int32_t *ego_step, *ego_corner, *ego_hits, *ego_first;
+} mind_audit_road_episode_out;
+int mind_audit_road_episode(mind_ctx *ctx, const mind_audit_box *ego, const double *verts, const int32_t *poly_off,
+                            int n_rings, int n_ego, int n_steps, const double *ego_states,
+                            const mind_audit_road_episode_out *out);
+
+/* road_geom.h on the CPU (host only, no context): n boxes HOST [n, 3] = (x, y, yaw) of the box `ego` against the road.
+ * trig HOST [n, 2] = (cos yaw, sin yaw), or NULL = the kernels' own sin / cos (mind_trig.h).  Outputs HOST [n], each may be
+ * NULL (not all).  MIND_EINVAL for n < 0, a NULL required pointer, a bad box or a bad road (the rules above). */
+int mind_debug_road_margin(int n, const double *boxes, const mind_audit_box *ego, const double *verts,
+                           const int32_t *poly_off, int n_rings, const double *trig, double *margin, int32_t *corner,
+                           int32_t *ring, int32_t *edge);
+
 #ifdef __cplusplus
 }
 #endif

@@ -68,6 +68,19 @@ class AuditEpisodeOut(C.Structure):     # mind_audit_episode_out
                 ("ego_first", C.POINTER(C.c_int32))]
 
 
+class AuditRoadPlanOut(C.Structure):    # mind_audit_road_plan_out
+    _fields_ = [("node_margin", C.POINTER(C.c_double)), ("node_corner", C.POINTER(C.c_int32)), ("node_ring", C.POINTER(C.c_int32)),
+                ("node_edge", C.POINTER(C.c_int32)), ("tree_min", C.POINTER(C.c_double)), ("tree_node", C.POINTER(C.c_int32)),
+                ("tree_corner", C.POINTER(C.c_int32)), ("tree_hits", C.POINTER(C.c_int32)), ("tree_first", C.POINTER(C.c_int32)),
+                ("tree_mass", C.POINTER(C.c_double))]
+
+
+class AuditRoadEpisodeOut(C.Structure):     # mind_audit_road_episode_out
+    _fields_ = [("step_margin", C.POINTER(C.c_double)), ("step_corner", C.POINTER(C.c_int32)), ("step_ring", C.POINTER(C.c_int32)),
+                ("step_edge", C.POINTER(C.c_int32)), ("ego_min", C.POINTER(C.c_double)), ("ego_step", C.POINTER(C.c_int32)),
+                ("ego_corner", C.POINTER(C.c_int32)), ("ego_hits", C.POINTER(C.c_int32)), ("ego_first", C.POINTER(C.c_int32))]
+
+
 class ForecastCfg(C.Structure):     # mind_forecast_cfg
     _fields_ = [("K", C.c_int), ("T", C.c_int), ("n_h", C.c_int), ("horizon", C.POINTER(C.c_int32)), ("miss_radius", C.c_double),
                 ("disc_scale", C.c_double), ("disc_offset", C.c_double)]
@@ -211,6 +224,7 @@ EXPORTS = ["mind_ctx_create", "mind_ctx_destroy", "mind_last_error_string", "min
            "mind_predict_batch_aux", "mind_set_decoder_basis", "mind_get_decoder_basis", "mind_curve_eval", "mind_debug_curve_basis",
            "mind_audit_plan", "mind_audit_episode", "mind_debug_box_clearance",
            "mind_forecast_score", "mind_debug_forecast_score",
+           "mind_audit_road_plan", "mind_audit_road_episode", "mind_debug_road_margin",
            "mind_loop_create", "mind_loop_destroy", "mind_loop_reset", "mind_loop_advance", "mind_loop_state", "mind_loop_last_plan", "mind_loop_export",
            "mind_planner_create", "mind_planner_destroy", "mind_planner_reset", "mind_planner_observe", "mind_planner_set_lanes", "mind_planner_set_target_lane",
            "mind_planner_set_solve_lane", "mind_planner_set_eval_lane", "mind_planner_plan", "mind_planner_last_plan", "mind_planner_export"]
@@ -346,6 +360,13 @@ def load():
                C.POINTER(C.c_uint8), C.POINTER(ForecastOut)]
     lib.mind_forecast_score.argtypes = [C.c_void_p] + fc_tail
     lib.mind_debug_forecast_score.argtypes = fc_tail
+    road = [C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int]
+    lib.mind_audit_road_plan.argtypes = [C.c_void_p, C.POINTER(AuditBox)] + road + [C.POINTER(CostTree), C.c_int, C.c_int, C.POINTER(C.c_double),
+                                                                                   C.POINTER(AuditRoadPlanOut)]
+    lib.mind_audit_road_episode.argtypes = [C.c_void_p, C.POINTER(AuditBox)] + road + [C.c_int, C.c_int, C.POINTER(C.c_double),
+                                                                                      C.POINTER(AuditRoadEpisodeOut)]
+    lib.mind_debug_road_margin.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(AuditBox)] + road + [C.POINTER(C.c_double), C.POINTER(C.c_double)] + \
+        [C.POINTER(C.c_int32)] * 3
     for n in EXPORTS:
         getattr(lib, n)
         if n not in ("mind_last_error_string", "mind_debug_read"):
@@ -550,6 +571,48 @@ def box_clearance(kind, a, b, trig=None):
     if rc != MIND_OK:
         raise ValueError(f"mind_debug_box_clearance rejects kind {kind!r}")
     return out
+
+
+def audit_box(box, name="ego_box"):
+    """(length, width[, center_offset]) -> mind_audit_box"""
+    import numpy as np
+    b = np.asarray(box, np.float64).ravel()
+    if b.size not in (2, 3) or not np.all(np.isfinite(b)) or np.any(b[:2] < 0.0):
+        raise ValueError(f"{name} must be (length, width[, center_offset]) with finite length, width >= 0, got {box!r}")
+    return AuditBox(float(b[0]), float(b[1]), float(b[2]) if b.size == 3 else 0.0)
+
+
+def road_args(verts, poly_off):
+    """a road as the C entries take it: (verts float64 [V, 2], poly_off int32 [P + 1], their pointers, P); the shapes are checked here, the
+    road's own rules (three vertices per ring, finite, ascending) by the library"""
+    import numpy as np
+    v = np.ascontiguousarray(verts, np.float64)
+    off = np.ascontiguousarray(poly_off, np.int32).ravel()
+    if v.ndim != 2 or v.shape[1] != 2 or off.size < 2 or int(off[-1]) != len(v):
+        raise ValueError(f"a road is verts [V, 2] and poly_off [P + 1] ending in V, got {list(v.shape)} and poly_off {off.tolist()[:8]}")
+    return v, off, v.ctypes.data_as(C.POINTER(C.c_double)), off.ctypes.data_as(C.POINTER(C.c_int32)), off.size - 1
+
+
+def road_margin(boxes, ego_box, verts, poly_off, trig=None):
+    """road_geom.h on the CPU (mind_debug_road_margin; no GPU): boxes [n, 3] = (x, y, yaw) of the box ``ego_box`` = (length, width[,
+    center_offset]) against the road verts [V, 2] / poly_off [P + 1]; trig [n, 2] = (cos, sin), None = the kernels' own sin / cos.
+    -> dict margin float64 [n], corner, ring, edge int32 [n]"""
+    import numpy as np
+    lib = load()
+    b = np.ascontiguousarray(boxes, np.float64).reshape(-1, 3)
+    tg = None if trig is None else np.ascontiguousarray(trig, np.float64).reshape(-1, 2)
+    if tg is not None and len(tg) != len(b):
+        raise ValueError(f"road_margin: {len(b)} boxes, {len(tg)} trig rows")
+    v, off, vp, op, P = road_args(verts, poly_off)
+    res = dict(margin=np.zeros(len(b)), corner=np.zeros(len(b), np.int32), ring=np.zeros(len(b), np.int32), edge=np.zeros(len(b), np.int32))
+    dp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    box = audit_box(ego_box)
+    rc = lib.mind_debug_road_margin(len(b), dp(b), C.byref(box), vp, op, P, dp(tg), dp(res["margin"]), ip(res["corner"]), ip(res["ring"]), ip(res["edge"]))
+    if rc != MIND_OK:
+        raise ValueError(f"mind_debug_road_margin rejects its arguments ({rc}): a ring needs three vertices, poly_off must start at 0 and ascend, "
+                         "vertices must be finite")
+    return res
 
 
 def forecast_args(K, T, actor_off, gt, valid, scored, horizons, miss_radius, disc_scale, disc_offset, want=None):

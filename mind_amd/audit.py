@@ -12,7 +12,11 @@ changes no choice:
 * ``EpisodeAuditor(sim)``: box-to-box clearance of the ego actually driven in a ``ClosedLoopSim`` against the replayed tracks, per step.
 
 All numbers come from the device (mind_audit_plan / mind_audit_episode; geometry: mind_amd/csrc/box_geom.h).  Hit convention:
-clearance < 0; touching (0.0) is no hit.  The nominal boxes are nominal: every box is an argument."""
+clearance < 0; touching (0.0) is no hit.  The nominal boxes are nominal: every box is an argument.
+
+The ROAD audit says what the ego did to the road, by the same conventions (mind_audit_road_plan / mind_audit_road_episode; geometry:
+mind_amd/csrc/road_geom.h): ``Road`` holds the drivable area of a map as rings, ``audit_road_plan`` / ``audit_road_rollouts`` /
+``EpisodeRoadAuditor`` mirror the three above with the signed margin of the ego box's corners to the road (negative: off the road)."""
 import numpy as np
 
 from .planners.mind.utils import _name
@@ -159,3 +163,145 @@ def _part(clear, track, idx):
     k = int(np.argmin(c))               # (first minimum)
     return dict(steps=idx, step_clear=c, step_track=track[idx], ego_min=float(c[k]), ego_step=int(idx[k]), ego_track=int(track[idx[k]]),
                 ego_hits=int(len(hit)), ego_first=int(idx[hit[0]]) if len(hit) else -1)
+
+
+# ---- the road audit -----------------------------------------------------------------------------------------------------------------
+
+class Road:
+    """The drivable area of a map as the road audit takes it: ``verts`` float64 [V, 2] (world coordinates) and ``poly_off`` int32 [P + 1];
+    ring r = verts[poly_off[r]:poly_off[r + 1]], implicitly closed, at least three vertices, no holes."""
+
+    def __init__(self, verts, poly_off):
+        self.verts = np.ascontiguousarray(verts, np.float64).reshape(-1, 2)
+        self.poly_off = np.ascontiguousarray(poly_off, np.int32).ravel()
+        n = np.diff(self.poly_off)
+        if len(n) < 1 or self.poly_off[0] != 0 or self.poly_off[-1] != len(self.verts) or np.any(n < 3):
+            raise ValueError(f"Road: poly_off {self.poly_off.tolist()[:8]} must start at 0, end at V = {len(self.verts)} and give every ring three vertices")
+        if not np.all(np.isfinite(self.verts)):
+            raise ValueError("Road: a vertex is not finite")
+
+    @property
+    def n_rings(self):
+        return len(self.poly_off) - 1
+
+    def ring(self, r):
+        return self.verts[self.poly_off[r]:self.poly_off[r + 1]]
+
+    @classmethod
+    def from_polygons(cls, polygons):
+        """rings as [n, 2] (or [n, 3]: z is dropped) arrays; a closing vertex equal to the first is dropped"""
+        rings = []
+        for p in polygons:
+            a = np.asarray(p, np.float64)
+            if a.ndim != 2 or a.shape[1] not in (2, 3):
+                raise ValueError(f"Road.from_polygons: a ring must be [n, 2], got {list(a.shape)}")
+            a = a[:, :2]
+            if len(a) > 1 and np.array_equal(a[0], a[-1]):
+                a = a[:-1]
+            rings.append(a)
+        if not rings:
+            raise ValueError("Road.from_polygons: no ring")
+        return cls(np.concatenate(rings), np.concatenate([[0], np.cumsum([len(r) for r in rings])]))
+
+    @classmethod
+    def from_static_map(cls, static_map):
+        """the ``drivable_areas`` of an ``av2_lite.StaticMap`` read from a map JSON"""
+        areas = getattr(static_map, "drivable_areas", None)
+        if areas is None:
+            raise ValueError("this map holds no drivable areas: it was loaded from a compact scene file (or built from arrays), which keeps the lane "
+                             "segments only.  Load the map JSON (log_map_archive_<seq_id>.json) with av2_lite.StaticMap.from_json or "
+                             "Road.from_map_json")
+        if not areas:
+            raise ValueError("the map JSON holds no drivable_areas polygon")
+        return cls.from_polygons(areas)
+
+    @classmethod
+    def from_map_json(cls, path):
+        from . import av2_lite
+        return cls.from_static_map(av2_lite.StaticMap.from_json(path))
+
+
+def _road(road):
+    if not isinstance(road, Road):
+        road = Road.from_static_map(road) if hasattr(road, "vector_lane_segments") else Road.from_polygons(road)
+    return road
+
+
+def audit_road_plan(scen_tree, traj_tree, road, ego_box=BOXES["VEHICLE"], runtime=None):
+    """The road audit of what ``plan()`` returned, the lists ``audit_plan`` takes; ``road``: a ``Road`` (or a StaticMap read from a map
+    JSON, or a list of rings).  ONE device call for all trees.  Returns a dict: per-tree lists node_margin / node_corner / node_ring /
+    node_edge [M_t] and arrays tree_min, tree_node, tree_corner, tree_hits, tree_first, tree_mass [n_trees]."""
+    road = _road(road)
+    scen = list(scen_tree) if isinstance(scen_tree, (list, tuple)) else [scen_tree]
+    traj = list(traj_tree) if isinstance(traj_tree, (list, tuple)) else [traj_tree]
+    if len(scen) != len(traj) or not scen:
+        raise ValueError(f"audit_road_plan: {len(scen)} scenario trees, {len(traj)} trajectory trees")
+    flats = [_flat_of(t) for t in scen]
+    xs = [_states_of(t, len(f["parent"]))[None] for t, f in zip(traj, flats)]
+    res = _runtime(runtime).audit_road_plan(flats, xs, road.verts, road.poly_off, ego_box)
+    out = {k: [a[0] for a in v] for k, v in res.items() if k.startswith("node_")}
+    out.update({k: v[0] for k, v in res.items() if k.startswith("tree_")})
+    return out
+
+
+def audit_road_rollouts(solver_or_flat, xs, road, ego_box=BOXES["VEHICLE"], runtime=None):
+    """The road audit of C candidate state sets ``xs`` [C, M, 6] (or [M, 6]) on ONE cost tree: a flat dict (parent, prob, mean, cov) or a
+    ``TrajectoryTreeOptimizer`` (its last prepared cost tree).  Returns node_margin, node_corner, node_ring, node_edge [C, M] and tree_min,
+    tree_node, tree_corner, tree_hits, tree_first, tree_mass [C]."""
+    road = _road(road)
+    flat = solver_or_flat if isinstance(solver_or_flat, dict) else getattr(solver_or_flat, "cost_tree", None)
+    if not isinstance(flat, dict) or not all(k in flat for k in ("parent", "prob", "mean", "cov")):
+        raise TypeError("audit_road_rollouts: a flat cost tree (parent, prob, mean, cov) or a TrajectoryTreeOptimizer with a prepared cost tree is needed")
+    x = np.asarray(xs, np.float64)
+    one = x.ndim == 2
+    x = x[None] if one else x
+    M = len(flat["parent"])
+    if x.ndim != 3 or x.shape[1:] != (M, 6):
+        raise ValueError(f"audit_road_rollouts: xs must be [C, {M}, 6] or [{M}, 6], got {list(np.shape(xs))}")
+    res = _runtime(runtime).audit_road_plan([flat], x, road.verts, road.poly_off, ego_box)
+    out = {k: v[0] for k, v in res.items() if k.startswith("node_")}
+    out.update({k: v[:, 0] for k, v in res.items() if k.startswith("tree_")})
+    return {k: v[0] for k, v in out.items()} if one else out
+
+
+class EpisodeRoadAuditor:
+    """Wraps a ClosedLoopSim exactly as EpisodeAuditor does; ``report()`` audits the recorded ego trace against ``road`` in one device call."""
+
+    def __init__(self, sim, road, ego_box=BOXES["VEHICLE"], runtime=None):
+        self.sim, self.road, self.ego_box, self.runtime = sim, _road(road), ego_box, runtime
+        self.states, self.enabled, self.times = [], [], []
+
+    step = EpisodeAuditor.step
+    run = EpisodeAuditor.run
+
+    def report(self):
+        """-> dict: ego_min, ego_step, ego_corner, ego_hits, ego_first of the whole trace; times [S], enabled [S], step_margin, step_corner,
+        step_ring, step_edge [S]; ``before`` / ``after``: the same summary and per-step arrays of the steps before and from the take-over
+        (None when there is no such step); steps are indices into the recorded trace"""
+        if len(self.times) == 0:
+            raise RuntimeError("EpisodeRoadAuditor.report: no step was recorded")
+        ego = np.stack(self.states)
+        res = _runtime(self.runtime).audit_road_episode(ego[None], self.road.verts, self.road.poly_off, self.ego_box)
+        per = {k: res[k][0] for k in ("step_margin", "step_corner", "step_ring", "step_edge")}
+        en = np.array(self.enabled, bool)
+        out = dict(times=np.array(self.times), enabled=en, **per,
+                   **{k: (float if k == "ego_min" else int)(res[k][0]) for k in ("ego_min", "ego_step", "ego_corner", "ego_hits", "ego_first")})
+        out["before"], out["after"] = _road_part(per, np.flatnonzero(~en)), _road_part(per, np.flatnonzero(en))
+        return out
+
+
+def _road_part(per, idx):
+    """summary of the steps ``idx`` of a trace, by the rules of the whole-trace summary (the lowest step wins ties; a NaN step: NaN, that
+    step, -1, -1, -1)"""
+    if len(idx) == 0:
+        return None
+    m = per["step_margin"][idx]
+    out = dict(steps=idx, **{k: v[idx] for k, v in per.items()})
+    bad = np.flatnonzero(np.isnan(m))
+    if len(bad):
+        out.update(ego_min=float("nan"), ego_step=int(idx[bad[0]]), ego_corner=-1, ego_hits=-1, ego_first=-1)
+        return out
+    hit, k = np.flatnonzero(m < 0.0), int(np.argmin(m))               # (first minimum)
+    out.update(ego_min=float(m[k]), ego_step=int(idx[k]), ego_corner=int(per["step_corner"][idx[k]]), ego_hits=int(len(hit)),
+               ego_first=int(idx[hit[0]]) if len(hit) else -1)
+    return out

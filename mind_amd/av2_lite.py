@@ -129,8 +129,11 @@ class LaneSegment:
 class StaticMap:
     """The slice of av2's ArgoverseStaticMap that the reference touches."""
 
-    def __init__(self, lane_segments):
+    def __init__(self, lane_segments, drivable_areas=None):
         self.vector_lane_segments = {ls.id: ls for ls in lane_segments}
+        # the map file's `drivable_areas` rings: [n, 2] float64 arrays in the file's order, a closing vertex equal to the first dropped.
+        # None for a map that did not come from a map JSON: the compact scene files (to_arrays / from_arrays) do not carry them.
+        self.drivable_areas = drivable_areas
 
     @classmethod
     def from_json(cls, path, lane_type_cls=LaneType, lane_mark_cls=LaneMarkType):
@@ -147,7 +150,13 @@ class StaticMap:
                 predecessors=list(d["predecessors"]), successors=list(d["successors"]),
                 right_neighbor_id=d["right_neighbor_id"], left_neighbor_id=d["left_neighbor_id"],
                 recorded_centerline=(Polyline.from_json_data(d["centerline"]) if "centerline" in d else None)))
-        return cls(segs)
+        areas = []
+        for d in data.get("drivable_areas", {}).values():
+            ring = np.array([[p["x"], p["y"]] for p in d["area_boundary"]], np.float64).reshape(-1, 2)
+            if len(ring) > 1 and np.array_equal(ring[0], ring[-1]):
+                ring = ring[:-1]
+            areas.append(ring)
+        return cls(segs, areas)
 
     def get_lane_segment_centerline(self, lane_segment_id):
         ls = self.vector_lane_segments[lane_segment_id]

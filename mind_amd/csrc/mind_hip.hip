@@ -33,6 +33,7 @@
 #include "ilqr_policy_kernels.hip"
 #include "audit_kernels.hip"
 #include "forecast_kernels.hip"
+#include "road_kernels.hip"
 #include "pair_jobs.h"
 #include "pred_choice.h"
 #include "ilqr_choice.h"
@@ -153,6 +154,7 @@ struct mind_ctx {
   DevBuf ilqr_dev, aime_dev, rebase_dev2[2], dec_h2;
   DevBuf audit_dev;     // scratch of mind_audit_plan / mind_audit_episode (audit_host.hip)
   DevBuf forecast_dev;  // scratch of mind_forecast_score (forecast_host.hip)
+  DevBuf road_dev;      // scratch of mind_audit_road_plan / mind_audit_road_episode (road_host.hip)
   // mind_aime_plan (aime_plan.hip): device arenas, page-locked staging (uploads / read-backs are true async copies: a pageable
   // source makes hipMemcpyAsync wait for the stream to drain first), host result tables
   DevBuf pl_root, pl_in[2], pl_lf, pl_lrep, pl_pred, pl_small, pl_tab[2], pl_win[2];
@@ -397,7 +399,7 @@ extern "C" int mind_ctx_destroy(mind_ctx *c) {
   (void)hipStreamSynchronize(c->stream);
   DevBuf *bufs[] = {&c->edge, &c->x, &c->ST, &c->QK, &c->part, &c->tokpos, &c->meta, &c->jobs, &c->actor_feat,
                     &c->lane_feat, &c->tgt_feat, &c->cmode, &c->tgt_emb, &c->rows, &c->rpe_ptrs, &c->ilqr_dev, &c->aime_dev, &c->rebase_dev2[0], &c->rebase_dev2[1], &c->dec_h2,
-                    &c->curve_tab, &c->audit_dev, &c->forecast_dev};
+                    &c->curve_tab, &c->audit_dev, &c->forecast_dev, &c->road_dev};
   for (DevBuf *b : bufs)
     if (b->p) (void)hipFree(b->p);
   for (TableSet &t : c->tabs)
@@ -1293,3 +1295,6 @@ extern "C" int64_t mind_debug_read(mind_ctx *c, const char *name, float *host, i
 
 // ---- forecast scoring against recorded futures (outside every planning cycle)
 #include "forecast_host.hip"
+
+// ---- the road audit of plans and episodes (outside every planning cycle)
+#include "road_host.hip"

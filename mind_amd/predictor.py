@@ -603,10 +603,7 @@ class HipPredictor:
     @staticmethod
     def _audit_box(box, name):
         """(length, width[, center_offset]) -> mind_audit_box"""
-        b = np.asarray(box, np.float64).ravel()
-        if b.size not in (2, 3) or not np.all(np.isfinite(b)) or np.any(b[:2] < 0.0):
-            raise ValueError(f"{name} must be (length, width[, center_offset]) with finite length, width >= 0, got {box!r}")
-        return _lib.AuditBox(float(b[0]), float(b[1]), float(b[2]) if b.size == 3 else 0.0)
+        return _lib.audit_box(box, name)
 
     def audit_plan(self, flats, xs, ego_box, exo_margin):
         """Clearance of C candidate state sets on every cost tree of ``flats`` (planner-mode flat dicts as ``ilqr_solve`` takes them) in one
@@ -674,6 +671,64 @@ class HipPredictor:
         dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
         rc = self.lib.mind_audit_episode(self.ctx, C.byref(box), E, S, nt, dp(eg), dp(ex), va.ctypes.data_as(C.POINTER(C.c_uint8)), dp(bx), C.byref(out))
         _lib.check(self.lib, self.ctx, rc, "mind_audit_episode")
+        return res
+
+    # ---- road audit (mind_audit_road_plan / mind_audit_road_episode): outside every planning cycle ---------
+    def audit_road_plan(self, flats, xs, verts, poly_off, ego_box):
+        """Road margin of C candidate state sets on every cost tree of ``flats`` in one call (mind_audit_road_plan, k_road_boxes): the ego
+        box at every trajectory node against the drivable area ``verts`` [V, 2] / ``poly_off`` [P + 1] (mind_amd.audit.Road).  ``xs``:
+        [C, sum M, 6], or one [C, M_t, 6] per tree; only ``parent`` (for M) and ``prob`` of the trees are read.  Returns a dict: per-tree
+        lists node_margin [C, M_t] / node_corner, node_ring, node_edge int32 [C, M_t], and tree_min, tree_node, tree_corner, tree_hits,
+        tree_first, tree_mass [C, n_trees]."""
+        n = len(flats)
+        keep = []
+        trees, Ms = self._cost_trees(flats, None, keep)
+        Mt = int(sum(Ms))
+        if isinstance(xs, (list, tuple)):
+            xs = np.concatenate([np.asarray(x, np.float64) for x in xs], axis=1)
+        x = np.ascontiguousarray(xs, np.float64)
+        if x.ndim != 3 or x.shape[1:] != (Mt, 6):
+            raise ValueError(f"xs must be [C, {Mt}, 6] for these cost trees, got {list(x.shape)}")
+        for i, f in enumerate(flats):
+            if np.shape(f["prob"]) != (Ms[i],):
+                raise ValueError(f"cost tree {i}: prob [M] does not match parent [M = {Ms[i]}]")
+        v, off, vp, op, P = _lib.road_args(verts, poly_off)
+        box = self._audit_box(ego_box, "ego_box")
+        nc = x.shape[0]
+        res = dict(node_margin=np.zeros((nc, Mt)), node_corner=np.zeros((nc, Mt), np.int32), node_ring=np.zeros((nc, Mt), np.int32),
+                   node_edge=np.zeros((nc, Mt), np.int32), tree_min=np.zeros((nc, n)), tree_node=np.zeros((nc, n), np.int32),
+                   tree_corner=np.zeros((nc, n), np.int32), tree_hits=np.zeros((nc, n), np.int32), tree_first=np.zeros((nc, n), np.int32),
+                   tree_mass=np.zeros((nc, n)))
+        out = _lib.AuditRoadPlanOut()
+        for name, a in res.items():
+            setattr(out, name, a.ctypes.data_as(C.POINTER(C.c_double if a.dtype == np.float64 else C.c_int32)))
+        rc = self.lib.mind_audit_road_plan(self.ctx, C.byref(box), vp, op, P, trees, n, nc, x.ctypes.data_as(C.POINTER(C.c_double)), C.byref(out))
+        _lib.check(self.lib, self.ctx, rc, "mind_audit_road_plan")
+        offs = np.cumsum([0] + Ms)
+        for name in ("node_margin", "node_corner", "node_ring", "node_edge"):
+            res[name] = [res[name][:, offs[i]:offs[i + 1]].copy() for i in range(n)]
+        return res
+
+    def audit_road_episode(self, ego_states, verts, poly_off, ego_box):
+        """Road margin of E ego traces in one call (mind_audit_road_episode, k_road_boxes).  ``ego_states``: [E, S, 4] (or [S, 4]) =
+        (x, y, v, yaw); the road as ``audit_road_plan`` takes it.  Returns a dict: step_margin [E, S], step_corner, step_ring, step_edge
+        int32 [E, S], ego_min [E], ego_step, ego_corner, ego_hits, ego_first int32 [E]."""
+        eg = np.ascontiguousarray(ego_states, np.float64)
+        if eg.ndim == 2:
+            eg = eg[None]
+        if eg.ndim != 3 or eg.shape[2] != 4:
+            raise ValueError(f"ego_states must be [E, S, 4], got {list(eg.shape)}")
+        E, S = eg.shape[:2]
+        v, off, vp, op, P = _lib.road_args(verts, poly_off)
+        box = self._audit_box(ego_box, "ego_box")
+        res = dict(step_margin=np.zeros((E, S)), step_corner=np.zeros((E, S), np.int32), step_ring=np.zeros((E, S), np.int32),
+                   step_edge=np.zeros((E, S), np.int32), ego_min=np.zeros(E), ego_step=np.zeros(E, np.int32), ego_corner=np.zeros(E, np.int32),
+                   ego_hits=np.zeros(E, np.int32), ego_first=np.zeros(E, np.int32))
+        out = _lib.AuditRoadEpisodeOut()
+        for name, a in res.items():
+            setattr(out, name, a.ctypes.data_as(C.POINTER(C.c_double if a.dtype == np.float64 else C.c_int32)))
+        rc = self.lib.mind_audit_road_episode(self.ctx, C.byref(box), vp, op, P, E, S, eg.ctypes.data_as(C.POINTER(C.c_double)), C.byref(out))
+        _lib.check(self.lib, self.ctx, rc, "mind_audit_road_episode")
         return res
 
     # ---- forecast scoring (mind_forecast_score): outside every planning cycle ------------------------------

@@ -63,6 +63,16 @@ def audit_episode(ego_states, exo, valid, boxes, ego_box):
     return get_runtime().audit_episode(ego_states, exo, valid, boxes, ego_box)
 
 
+def audit_road_plan(flats, xs, verts, poly_off, ego_box):
+    """``HipPredictor.audit_road_plan`` on this thread's runtime: road margin of candidate state sets on the cost trees of a plan."""
+    return get_runtime().audit_road_plan(flats, xs, verts, poly_off, ego_box)
+
+
+def audit_road_episode(ego_states, verts, poly_off, ego_box):
+    """``HipPredictor.audit_road_episode`` on this thread's runtime: road margin of ego traces against a drivable area."""
+    return get_runtime().audit_road_episode(ego_states, verts, poly_off, ego_box)
+
+
 def forecast_score(reg, cls, actor_off, gt, valid, scored=None, **cfg):
     """``HipPredictor.forecast_score`` on this thread's runtime: a forecast on the device against recorded futures."""
     return get_runtime().forecast_score(reg, cls, actor_off, gt, valid, scored, **cfg)
