@@ -120,7 +120,7 @@ int mind_curve_eval(mind_ctx *ctx, int basis, const float *param, long long n_ro
 /* The basis rows mind_curve_eval uploads (host only, no context): T [n_tau,8], Tp [n_tau,7].  MIND_EINVAL as above. */
 int mind_debug_curve_basis(int basis, const double *tau, int n_tau, float *T, float *Tp);
 
-/* Per-kernel timing of the last mind_predict_batch measured with HIP events on the context stream:
+/* Per-kernel timing of the last mind_predict_batch (profiling on: the launch clock, or HIP events on the context stream under "prof_clock" 0):
  * returns the number of fusion pair-kernel launches and their summed milliseconds. */
 int mind_last_fusion_stats(mind_ctx *ctx, int *n_launches, float *total_ms, double *pairs_processed);
 /* The ActorNet of the last mind_predict_batch: layerwise = 1 when the layer-wise batched kernels ran (mind_set_tuning "actor_lw_min"), 0 for
@@ -151,8 +151,28 @@ int mind_last_ilqr_profile(mind_ctx *ctx, double *out9);
  * iterations to *n_rows.  MIND_ESTATE when the last call holds no such fit.  Parity diagnostics: the tests compare this trace with the
  * reference's own, iteration by iteration. */
 int mind_last_ilqr_trace(mind_ctx *ctx, int tree, int phase, double *out, int cap_rows, int *n_rows);
-/* enable/disable event timing (off by default: events add a little latency) */
+/* enable/disable kernel timing (off by default).  With mind_set_tuning("prof_clock", 1) (the default; MIND_PROF_CLOCK) the pair kernels and the
+ * one-launch ActorNet forms are timed by the launch clock (mind_amd/csrc/launch_clock.h): their workgroups stamp the device's constant-rate
+ * wall clock at entry and behind their last store, and a launch counts from its first workgroup in to its last workgroup out -- no HIP event is
+ * recorded around them, so the timed path keeps the launch chain of the untimed one.  "prof_clock" 0: HIP events on the context stream around
+ * every timed launch, as before (a marker packet on either side of a kernel: DESIGN.md 6).  "prof_clock" 2: both on the same launches
+ * (mind_debug_launch_times).  The figures go out under the same names either way (mind_last_fusion_stats, mind_last_actor_stats,
+ * mind_aime_plan_out.pair_ms, mind_loop_totals.pair_ms).  The tree-iLQR launch, the token launches and the layer-wise ActorNet keep their events. */
 int mind_set_profiling(mind_ctx *ctx, int enable);
+/* The timed launches of the last read of kind (0 pair kernels, 1 ActorNet) -- the last mind_predict_batch with profiling on, or the last
+ * mind_aime_plan's predictor calls -- one duration in ms per launch in launch order: by the launch clock ("prof_clock" 1, 2) and by HIP events
+ * ("prof_clock" 0, 2).  Up to cap values each; *n_clock / *n_event = how many there are.  Any output may be NULL. */
+int mind_debug_launch_times(mind_ctx *ctx, int kind, float *clock_ms, float *event_ms, int cap, int *n_clock, int *n_event);
+/* host-only helper (tests): the launch clock's ring bookkeeping and reduction (mind_amd/csrc/launch_clock.h) on a ring of n_blocks blocks of
+ * block_slots slots, driven by n_ops operations of four long long {op, a, b, 0}:
+ *   0 take(grid a, kind b) -> block or -1     1 runs of the pending records a .. a + b - 1 -> count, first0, count0, first1, count1
+ *   2 drain the oldest a records               3 fits(records a, grid b) -> 0 / 1          4 grow for (records a, grid b): the ring is reset to the
+ *   geometry returned -> blocks, slots         5 reduce block a over a grid of b workgroups of `stamps` (n_slots pairs {t0, t1}: the host
+ *   mirror of the ring) -> ticks, ms at rate_khz   6 mark the copy of records a .. a + b - 1 queued   7 the oldest a records have one -> 0 / 1
+ * out receives eight doubles per operation: the results above in [0..4], then pending records, head block, launches dropped so far.  Returns
+ * the doubles written or MIND_EINVAL (unknown op, a reduce outside `stamps`, cap too small).  Needs no GPU and no context. */
+int mind_debug_launch_clock(int n_blocks, int block_slots, int rate_khz, const long long *ops, int n_ops, const unsigned long long *stamps,
+                            long long n_slots, double *out, int cap);
 
 /* Arithmetic of the RelaFusionLayer pair contractions (planners/mind/networks/network.py:165-232; the reference runs them
  * in torch fp32) -- and of every other MFMA contraction of the predictor (ActorNet, the MFMA decoder / token kernels where enabled):

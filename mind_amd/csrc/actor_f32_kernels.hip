@@ -37,6 +37,7 @@
 #define AF_LDS_FLOATS(NACT) ((NACT) * AF_ACT + 128)
 
 #include "weight_tables.h"   // AfW
+#include "launch_clock.h"    // LcSlot, the stamps
 
 // sums of NACT values over the workgroup (one per actor); `flip` alternates the scratch so that two reductions need no barrier in between
 template <int NACT>
@@ -223,7 +224,9 @@ __device__ __forceinline__ void af_lateral(const float *src, int T, const AfLat 
 }
 
 template <int NACT>
-__global__ __launch_bounds__(AF_T) void k_actor_f32(const float *__restrict__ actors /*[A,14,48]*/, int n_actors, float *__restrict__ out /*[A,128]*/, AfW W) {
+__global__ __launch_bounds__(AF_T) void k_actor_f32(const float *__restrict__ actors /*[A,14,48]*/, int n_actors, float *__restrict__ out /*[A,128]*/, AfW W,
+                                                   LcSlot *clk) {
+  lc_stamp_in(clk);
   extern __shared__ __attribute__((aligned(16))) float smf[];
   float *xin = smf + AF_XIN;
   float *o0 = smf + AF_O0, *o1 = o0 + AF_BUF, *o2 = o1 + AF_BUF, *o3 = o2 + AF_BUF;
@@ -232,7 +235,7 @@ __global__ __launch_bounds__(AF_T) void k_actor_f32(const float *__restrict__ ac
   float *red = smf + NACT * AF_ACT;
   const int tid = threadIdx.x;
   const int a0 = blockIdx.x * NACT;
-  if (a0 >= n_actors) return;
+  if (a0 >= n_actors) { lc_stamp_both(clk); return; }
   // input [14][48] -> image [48] x AF_RS(16), channels 14, 15 zero; an actor past the end (odd count, two per workgroup) is all zeros
   for (int i = tid; i < NACT * 48 * 16; i += AF_T) {
     const int e = i / (48 * 16), t = (i / 16) % 48, c = i & 15;
@@ -263,5 +266,6 @@ __global__ __launch_bounds__(AF_T) void k_actor_f32(const float *__restrict__ ac
     af_conv<NACT, 7, 3, 1>(o0, 48, R.c2, 128, 48, acc);
     af_gn<NACT, true>(acc, 128, 48, R.g2, R.b2, fa, nullptr, true, nullptr, out, a0, n_actors, red);
   }
+  lc_stamp_out(clk);
 }
 extern "C" size_t mind_actor_f32_lds_bytes(int nact) { return (size_t)AF_LDS_FLOATS(nact) * sizeof(float); }

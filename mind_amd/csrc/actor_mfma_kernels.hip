@@ -40,6 +40,7 @@ __device__ int am_trn_;
 #define AM_LDS_DWORDS (AM_RED + 64)
 
 #include "weight_tables.h"   // AmW
+#include "launch_clock.h"    // LcSlot, the stamps
 typedef u32 u32x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ float am_block_sum(float v, float *red, int flip) {
@@ -248,7 +249,8 @@ __device__ __forceinline__ void am_lateral(const u32 *src, int T, const AmLat &W
 
 template <int NP>
 __global__ __launch_bounds__(AM_T) void k_actor_mfma(const float *__restrict__ actors /*[A,14,48]*/, int n_actors,
-                                                     float *__restrict__ out /*[A,128]*/, AmW W) {
+                                                     float *__restrict__ out /*[A,128]*/, AmW W, LcSlot *clk) {
+  lc_stamp_in(clk);
   extern __shared__ __attribute__((aligned(16))) u32 smu[];
   u32 *xin = smu + AM_XIN;
   u32 *o0 = smu + AM_O0, *o1 = o0 + AM_BUF, *o2 = o1 + AM_BUF, *o3 = o2 + AM_BUF;
@@ -257,7 +259,7 @@ __global__ __launch_bounds__(AM_T) void k_actor_mfma(const float *__restrict__ a
   float *red = (float *)(smu + AM_RED);
   const int tid = threadIdx.x;
   const int a = blockIdx.x;
-  if (a >= n_actors) return;
+  if (a >= n_actors) { lc_stamp_both(clk); return; }
   // input [14][48] -> split image [48] x AM_RSD(16), channels 14, 15 zero: a thread takes two channels of one time step
   if (tid < 48 * 8) {
     const int t = tid >> 3, c = (tid & 7) * 2;
@@ -307,5 +309,6 @@ __global__ __launch_bounds__(AM_T) void k_actor_mfma(const float *__restrict__ a
     printf("\n");
   }
 #endif
+  lc_stamp_out(clk);
 }
 extern "C" size_t mind_actor_mfma_lds_bytes() { return (size_t)AM_LDS_DWORDS * sizeof(u32); }

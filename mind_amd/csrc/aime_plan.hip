@@ -115,6 +115,7 @@ struct PlanRun {
   const float *prev_pos = nullptr, *prev_ang = nullptr, *prev_vel = nullptr, *cov_last_dev = nullptr;
   bool frames_pending = false;    // the frames (ROT, ORIG, TGT_PTS) of the current round's scenes are still on their way to page-locked slot 3
   int n_expanded = 0, pair_launches = 0;
+  int lc_n = 0;      // the plan's pair launches pending in the launch clock's ring (their copy to the host rides behind the read-back)
   // the round in flight: its geometry, chunk size and small buffers (pl_round_buffers)
   PlGeom g = {0, 0, 0, 0, 0};
   int chunk = 1;
@@ -692,6 +693,7 @@ void PlanRun::pl_begin_solves() {
 int PlanRun::pl_pack_results() {
   const size_t Mtot = (size_t)book.tree_off.back(), n_rows = (size_t)book.n_rows, n_flat = Mtot * a * 3, n_res = n_rows + n_flat;
   want_solves = solves_asked() && !book.tree_top.empty();
+  lc_n = lc_on(c) ? (int)c->lc.pending.size() : 0;      // (before the plan's own solves take a block)
   int rc;
   c->plan.agents = a;
   c->plan.rows_p = c->plan.fmean_p = c->plan.fcov_p = nullptr;
@@ -742,17 +744,20 @@ int PlanRun::pl_pack_results() {
       gather(c->pl_copy);
       HIPCHK(c, hipGetLastError());
       HIPCHK(c, hipMemcpyAsync(hp, d_rows, n_res * sizeof(float), hipMemcpyDeviceToHost, c->pl_copy));
+      if (lc_n > 0 && (rc = lc_copy_async(c, c->pl_copy, 0, lc_n))) return rc;
       HIPCHK(c, hipEventRecord(c->ev_rows, c->pl_copy));
       HIPCHK(c, hipEventSynchronize(c->ev_rows));
       TR("end: read-back on the host");
     } else {
       HIPCHK(c, hipMemcpyAsync(hp, d_rows, n_res * sizeof(float), hipMemcpyDeviceToHost, st));
+      if (lc_n > 0 && (rc = lc_copy_async(c, st, 0, lc_n))) return rc;
       HIPCHK(c, hipStreamSynchronize(st));
     }
     // the plan's rows and flattened cost trees are handed out where the read-back put them (page-locked slot 2: nothing touches it before
     // the context's next plan, the lifetime mind_aime_plan_out promises); the deep stress trees return 0.9 GB here
     c->plan.rows_p = hp; c->plan.fmean_p = hp + n_rows; c->plan.fcov_p = hp + n_rows + Mtot * a * 2;
   } else {
+    if (lc_n > 0 && (rc = lc_copy_async(c, st, 0, lc_n))) return rc;
     HIPCHK(c, hipStreamSynchronize(st));
   }
   return MIND_OK;
@@ -766,6 +771,13 @@ int PlanRun::pl_hand_out() {
   out->n_expanded = n_expanded; out->n_rounds = book.n_rounds;
   out->root_flags = book.root_flags();
   if (c->profiling && (rc = mind_pair_events_resolve(c, &pair_ms))) return rc;      // (the plan's kernels have completed: every exit above waited for the read-back behind them)
+  if (lc_on(c)) {
+    // the launch clock's figure is the one handed out (with "prof_clock" 2 the events above were read too: mind_debug_launch_times)
+    double ms[LC_KINDS];
+    int n[LC_KINDS];
+    if ((rc = lc_resolve(c, lc_n, 1u << LC_PAIR, ms, n))) return rc;
+    pair_ms = (float)ms[LC_PAIR];
+  }
   out->pair_ms = pair_ms; out->pair_launches = pair_launches;
   out->n_trees = (int)book.tree_top.size(); out->tree_top = book.tree_top.data(); out->tree_off = book.tree_off.data();
   out->flat_parent = book.flat_parent.data(); out->flat_prob = book.flat_prob.data();
@@ -803,6 +815,9 @@ extern "C" int mind_aime_plan(mind_ctx *c, const mind_aime_plan_in *in, mind_aim
   struct DeferGuard { mind_ctx *c; ~DeferGuard() { c->ev_defer = false; c->ev_pending.clear(); c->ev_pool_used = 0; } } defer_guard{c};
   c->ev_defer = c->profiling;
   c->ev_pending.clear(); c->ev_pool_used = 0;
+  // (launch-clock records a failed call left behind are dropped, behind a drained stream)
+  if (!c->lc.pending.empty() && (rc = lc_flush(c, false))) return rc;
+  for (int k = 0; k < LC_KINDS; ++k) { c->lc_carry_ms[k] = 0.0; c->lc_carry_n[k] = 0; }
   for (int round = 0;; ++round) {
     PlErr e = p.book.begin_round(in->max_rounds, p.g);
     if (e) return p.fail_book(e);

@@ -14,6 +14,7 @@
 
 #include "weight_tables.h"   // LaneW, ActorW, DecW
 #include "dec_curve.h"       // dec_curve_point
+#include "launch_clock.h"    // LcSlot, the stamps
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -697,7 +698,8 @@ __device__ __forceinline__ void res1d(const float *in, int Cin, int Tin, const R
 #define ACT_PART 12288
 #define ACT_LDS_FLOATS (672 + 7 * 1536 + 2 * 6144 + 32 + ACT_PART)
 __global__ __launch_bounds__(AT) void k_actor_net(const float *__restrict__ actors, int n_actors,
-                                                  float *__restrict__ out, ActorW W) {
+                                                  float *__restrict__ out, ActorW W, LcSlot *clk) {
+  lc_stamp_in(clk);
   extern __shared__ float sm[];
   float *xin = sm;
   float *o0 = sm + 672, *o1 = o0 + 1536, *o2 = o1 + 1536, *o3 = o2 + 1536;
@@ -709,7 +711,7 @@ __global__ __launch_bounds__(AT) void k_actor_net(const float *__restrict__ acto
   float *fo = o0;  // 10752 floats available, needs 6144
   const int tid = threadIdx.x;
   const int a = blockIdx.x;
-  if (a >= n_actors) return;
+  if (a >= n_actors) { lc_stamp_both(clk); return; }
 #ifdef MIND_ENC_TRACE
   long long at_[12], aq_ = clock64();
   int an_ = 0;
@@ -776,6 +778,7 @@ __global__ __launch_bounds__(AT) void k_actor_net(const float *__restrict__ acto
     printf("[k_actor_net n=%d] cycles: load %lld group0 %lld group1 %lld group2 %lld group3 %lld fpn %lld out-res %lld\n", n_actors, at_[0], at_[1], at_[2],
            at_[3], at_[4], at_[5], at_[6]);
 #endif
+  lc_stamp_out(clk);
 }
 extern "C" size_t mind_actor_lds_bytes() { return (size_t)ACT_LDS_FLOATS * sizeof(float); }
 

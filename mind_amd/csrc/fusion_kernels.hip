@@ -77,7 +77,8 @@ __global__ __launch_bounds__(PAIR_THREADS, 1) void k_pair(const PairJob *__restr
                                                  const float *__restrict__ WAe, const float *__restrict__ WAp,
                                                  const float *__restrict__ vtab, const float *__restrict__ rtab,
                                                  const float *__restrict__ tokpos,
-                                                 const float *const *__restrict__ rpe_ptrs, int update_mode) {
+                                                 const float *const *__restrict__ rpe_ptrs, int update_mode, LcSlot *clk) {
+  lc_stamp_in(clk);
   extern __shared__ float lds[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -312,14 +313,15 @@ __global__ __launch_bounds__(PAIR_THREADS, 1) void k_pair(const PairJob *__restr
     printf("[k_pair<%d> um=%d] cycles: load %lld gemm1 %lld T+LN1 %lld scores %lld softmax %lld mbar %lld gemm2 %lld LN23+store %lld\n", MODE,
            update_mode, pt_[0], pt_[1], pt_[2], pt_[3], pt_[4], pt_[5], pt_[6], pt_[7]);
 #endif
+  lc_stamp_out(clk);
 }
 
 template __global__ void k_pair<0>(const PairJob *, int, float *, const float *, const float *, float *,
                                    const float *, const float *, const float *, const float *,
-                                   const float *, const float *const *, int);
+                                   const float *, const float *const *, int, LcSlot *);
 template __global__ void k_pair<1>(const PairJob *, int, float *, const float *, const float *, float *,
                                    const float *, const float *, const float *, const float *,
-                                   const float *, const float *const *, int);
+                                   const float *, const float *const *, int, LcSlot *);
 
 extern "C" size_t mind_pair_lds_bytes() { return (size_t)LDS_TOTAL * sizeof(float); }
 

@@ -231,6 +231,17 @@ struct mind_ctx {
   std::vector<hipEvent_t> ev_pool;
   size_t ev_pool_used = 0;
   std::vector<size_t> ev_pending;      // first pool index of every predictor call not read yet
+  // the launch clock (launch_clock.h, predict.hip): "prof_clock" / MIND_PROF_CLOCK 1 (default) = with profiling on, the kernels that take a slot
+  // pointer (the pair kernels, k_actor_mfma) are timed by stamps of their own workgroups and no HIP event is recorded around them; 0 = HIP
+  // events as before; 2 = both on the same launches (the cross-check: mind_debug_launch_times).  The ring on the device, its page-locked
+  // mirror, the wall clock's rate (0: no such clock -- events), sums of records read early, the per-launch times of the last read
+  int prof_clock = 1, wall_khz = 0;
+  LcRing lc;
+  DevBuf lc_dev;
+  LcSlot *lc_host = nullptr;
+  double lc_carry_ms[LC_KINDS] = {0, 0, 0};
+  int lc_carry_n[LC_KINDS] = {0, 0, 0};
+  std::vector<float> lc_last[LC_KINDS], ev_last[LC_KINDS];
   int n_cu = 256;
   int debug_layers = 6;
   int last_ntok = 0;
@@ -307,6 +318,8 @@ extern "C" int mind_ctx_create(int device, void *stream, mind_ctx **out) {
   if (hipEventCreateWithFlags(&c->ev_stage, hipEventDisableTiming) != hipSuccess) { *out = nullptr; delete c; return MIND_EHIP; }
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->n_cu = prop.multiProcessorCount;
+  if (hipDeviceGetAttribute(&c->wall_khz, hipDeviceAttributeWallClockRate, device) != hipSuccess || c->wall_khz < 0) c->wall_khz = 0;
+  if (const char *pe = getenv("MIND_PROF_CLOCK")) c->prof_clock = std::min(2, std::max(0, atoi(pe)));
   (void)hipFuncSetAttribute((const void *)k_pair<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_pair_lds_bytes());
   (void)hipFuncSetAttribute((const void *)k_pair<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_pair_lds_bytes());
   (void)hipFuncSetAttribute((const void *)k_pair_bf<0, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_pair_bf_lds_bytes());
@@ -409,6 +422,8 @@ extern "C" int mind_ctx_destroy(mind_ctx *c) {
   for (DevBuf *b : {&c->dec_xbuf, &c->dec_bars})
     if (b->p) (void)hipFree(b->p);
   if (c->dec_abort) (void)hipHostFree(c->dec_abort);
+  if (c->lc_dev.p) (void)hipFree(c->lc_dev.p);
+  if (c->lc_host) (void)hipHostFree(c->lc_host);
   for (DevBuf *b : {&c->pl_root, &c->pl_in[0], &c->pl_in[1], &c->pl_lf, &c->pl_lrep, &c->pl_pred, &c->pl_small, &c->pl_tab[0], &c->pl_tab[1], &c->pl_win[0],
                     &c->pl_win[1], &c->pl_flat, &c->x_send, &c->x_recv, &c->x_seg, &c->pl_cnt})
     if (b->p) (void)hipFree(b->p);
@@ -468,6 +483,7 @@ extern "C" int mind_set_tuning(mind_ctx *c, const char *name, int value) {
   else if (n == "root_head") c->root_head = value != 0;
   else if (n == "round_head") c->round_head = value != 0;
   else if (n == "upload_kernel_max") c->upload_kernel_max = value < 0 ? 0 : value;
+  else if (n == "prof_clock") c->prof_clock = value < 0 ? 0 : (value > 2 ? 2 : value);
   else return fail(c, MIND_EINVAL, "mind_set_tuning: unknown knob '%s'", name);
   return MIND_OK;
 }
@@ -504,9 +520,16 @@ extern "C" int mind_debug_pack_bfrag(const float *w, int row_stride, uint32_t *o
   return MIND_OK;
 }
 
+static int lc_reserve(mind_ctx *c, int records, int grid);      // (predict.hip)
 extern "C" int mind_set_profiling(mind_ctx *c, int enable) {
   if (!c) return MIND_EINVAL;
   c->profiling = enable != 0;
+  // the launch clock's ring and its page-locked mirror are allocated here, outside anything timed: two predictor calls of pair launches on
+  // every CU (a call with larger grids or more records grows it in front of its launches)
+  if (c->profiling && c->prof_clock != 0 && c->wall_khz > 0 && c->lc.n_blocks == 0) {
+    HIPCHK(c, hipSetDevice(c->device));
+    return lc_reserve(c, 12, c->n_cu);
+  }
   return MIND_OK;
 }
 
@@ -543,11 +566,13 @@ extern "C" int mind_last_ilqr_profile(mind_ctx *c, double *out9) {
 // deferred pair-kernel events of a plan (ev_defer): summed once the stream has been drained
 static int mind_pair_events_resolve(mind_ctx *c, float *total_ms) {
   float sum = 0.f;
+  c->ev_last[LC_PAIR].clear(); c->lc_last[LC_PAIR].clear();
   for (size_t base : c->ev_pending)
     for (int L = 0; L < c->debug_layers; ++L) {
       float ms = 0.f;
       HIPCHK(c, hipEventElapsedTime(&ms, c->ev_pool[base + 2 * L], c->ev_pool[base + 2 * L + 1]));
       sum += ms;
+      c->ev_last[LC_PAIR].push_back(ms);
     }
   c->ev_pending.clear();
   c->ev_pool_used = 0;
@@ -561,6 +586,59 @@ extern "C" int mind_last_fusion_stats(mind_ctx *c, int *n_launches, float *total
   if (total_ms) *total_ms = c->pair_ms;
   if (pairs) *pairs = c->pairs_done;
   return MIND_OK;
+}
+
+extern "C" int mind_debug_launch_times(mind_ctx *c, int kind, float *clock_ms, float *event_ms, int cap, int *n_clock, int *n_event) {
+  if (!c || kind < 0 || kind >= LC_KINDS || cap < 0) return MIND_EINVAL;
+  const std::vector<float> &lc = c->lc_last[kind], &ev = c->ev_last[kind];
+  for (int i = 0; clock_ms && i < cap && i < (int)lc.size(); ++i) clock_ms[i] = lc[i];
+  for (int i = 0; event_ms && i < cap && i < (int)ev.size(); ++i) event_ms[i] = ev[i];
+  if (n_clock) *n_clock = (int)lc.size();
+  if (n_event) *n_event = (int)ev.size();
+  return MIND_OK;
+}
+
+extern "C" int mind_debug_launch_clock(int n_blocks, int block_slots, int rate_khz, const long long *ops, int n_ops, const unsigned long long *stamps,
+                                       long long n_slots, double *out, int cap) {
+  if (n_blocks < 0 || block_slots < 0 || n_ops < 0 || (n_ops > 0 && (!ops || !out)) || cap < 8 * n_ops || n_slots < 0 || (n_slots > 0 && !stamps))
+    return MIND_EINVAL;
+  LcRing R;
+  R.reset(n_blocks, block_slots);
+  for (int k = 0; k < n_ops; ++k) {
+    const long long op = ops[4 * k], a = ops[4 * k + 1], b = ops[4 * k + 2];
+    double *o = out + 8 * k;
+    for (int i = 0; i < 8; ++i) o[i] = 0.0;
+    if (a < -(1LL << 30) || a > (1LL << 30) || b < -(1LL << 30) || b > (1LL << 30)) return MIND_EINVAL;
+    switch (op) {
+    case 0: o[0] = R.take((int)a, (int)b); break;
+    case 1: {
+      int first[2] = {0, 0}, count[2] = {0, 0};
+      o[0] = R.pending_runs((int)a, (int)b, first, count);
+      o[1] = first[0]; o[2] = count[0]; o[3] = first[1]; o[4] = count[1];
+      break;
+    }
+    case 2: R.drained((int)a); break;
+    case 3: o[0] = R.fits((int)a, (int)b) ? 1 : 0; break;
+    case 4: {
+      int blocks, slots;
+      R.grown((int)a, (int)b, blocks, slots);
+      R.reset(blocks, slots);
+      o[0] = blocks; o[1] = slots;
+      break;
+    }
+    case 5: {
+      if (a < 0 || b < 0 || a >= R.n_blocks || (long long)R.slot_of((int)a) + b > n_slots) return MIND_EINVAL;
+      const unsigned long long t = lc_reduce((const LcSlot *)stamps + R.slot_of((int)a), (int)b);
+      o[0] = (double)t; o[1] = lc_ticks_ms(t, rate_khz);
+      break;
+    }
+    case 6: R.mark_copied((int)a, (int)b); break;
+    case 7: o[0] = R.copied((int)a) ? 1 : 0; break;
+    default: return MIND_EINVAL;
+    }
+    o[5] = (double)R.pending.size(); o[6] = R.head; o[7] = (double)R.dropped;
+  }
+  return 8 * n_ops;
 }
 
 extern "C" int mind_last_actor_stats(mind_ctx *c, int *layerwise, int *n_launches, int *n_chunks, float *total_ms) {

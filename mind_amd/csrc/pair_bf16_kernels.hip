@@ -48,7 +48,8 @@ __global__ __launch_bounds__(PAIR_THREADS, 1) void k_pair_bf(const PairJob *__re
                                                              float *__restrict__ part, const u32 *__restrict__ WBe,
                                                              const u32 *__restrict__ WBp, const float *__restrict__ vtab,
                                                              const float *__restrict__ rtab, const float *__restrict__ tokpos,
-                                                             const float *const *__restrict__ rpe_ptrs, int update_mode) {
+                                                             const float *const *__restrict__ rpe_ptrs, int update_mode, LcSlot *clk) {
+  lc_stamp_in(clk);
   extern __shared__ float lds[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -267,12 +268,13 @@ __global__ __launch_bounds__(PAIR_THREADS, 1) void k_pair_bf(const PairJob *__re
            "LN2/3+store %lld | prefetch issue %lld | WAIT query frags (+stores) %lld | scores+softmax %lld | sum_p_mem %lld\n",
            MODE, NP, update_mode, pt_[7], pt_[8], pt_[0], pt_[1], pt_[2], pt_[3], pt_[4], pt_[9], pt_[10], pt_[5], pt_[6]);
 #endif
+  lc_stamp_out(clk);
 }
 
 #define PAIR_BF_INST(M, NPV)                                                                                           \
   template __global__ void k_pair_bf<M, NPV>(const PairJob *, int, float *, const float *, const float *, float *,     \
                                              const u32 *, const u32 *, const float *, const float *, const float *,    \
-                                             const float *const *, int);
+                                             const float *const *, int, LcSlot *);
 PAIR_BF_INST(0, 3)
 PAIR_BF_INST(1, 3)
 PAIR_BF_INST(0, 1)

@@ -19,6 +19,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 #include "weight_tables.h"   // u32, VT_*, TokWeights
+#include "launch_clock.h"    // LcSlot, lc_stamp_in / lc_stamp_out: the kernels' last argument (null: not timed)
 
 typedef u32 u32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));

@@ -169,7 +169,8 @@ __global__ __launch_bounds__(PAIR_THREADS, 1) void k_pair_t6(const PairJob *__re
                                                              const u32 *__restrict__ WBp, const u32 *__restrict__ WLe,
                                                              const u32 *__restrict__ WLp, const float *__restrict__ vtab,
                                                              const float *__restrict__ rtab, const float *__restrict__ tokpos,
-                                                             const float *const *__restrict__ rpe_ptrs, int update_mode) {
+                                                             const float *const *__restrict__ rpe_ptrs, int update_mode, LcSlot *clk) {
+  lc_stamp_in(clk);
   extern __shared__ float lds[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -439,9 +440,10 @@ __global__ __launch_bounds__(PAIR_THREADS, 1) void k_pair_t6(const PairJob *__re
 #undef P6_LOAD_E
 #undef P6_LOAD_S
 #undef P6_PREFETCH
+  lc_stamp_out(clk);
 }
 
 template __global__ void k_pair_t6<0, 0>(const PairJob *, int, float *, const float *, const float *, float *, const u32 *, const u32 *, const u32 *,
-                                      const u32 *, const float *, const float *, const float *, const float *const *, int);
+                                      const u32 *, const float *, const float *, const float *, const float *const *, int, LcSlot *);
 template __global__ void k_pair_t6<1, 0>(const PairJob *, int, float *, const float *, const float *, float *, const u32 *, const u32 *, const u32 *,
-                                      const u32 *, const float *, const float *, const float *, const float *const *, int);
+                                      const u32 *, const float *, const float *, const float *, const float *const *, int, LcSlot *);

@@ -131,6 +131,95 @@ extern "C" int mind_debug_predict_choice(const char *const *knob_names, const in
   return (int)rec.size();
 }
 
+// ---- the launch clock's host side (launch_clock.h: the ring's bookkeeping and the reduction): the device ring and its page-locked mirror, the
+//      copies, the sums.  With profiling on and "prof_clock" 1 a timed launch takes the next block of the ring and records no HIP event; whoever
+//      read event pairs reads slots instead, behind a completed stream or copy -- the device never waits on the host.
+static bool lc_on(const mind_ctx *c) { return c->profiling && c->prof_clock != 0 && c->wall_khz > 0; }
+static bool lc_events(const mind_ctx *c) { return c->profiling && !(c->prof_clock == 1 && c->wall_khz > 0); }      // 0: events as before; 2 (debug): both
+
+// a record's slots on the host -> its sum and per-launch list
+static void lc_account(mind_ctx *c, const LcRecord &r, double (&ms)[LC_KINDS], int (&n)[LC_KINDS]) {
+  const double t = lc_ticks_ms(lc_reduce(c->lc_host + c->lc.slot_of(r.block), r.grid), c->wall_khz);
+  ms[r.kind] += t; n[r.kind] += 1;
+  c->lc_last[r.kind].push_back((float)t);
+}
+
+// everything pending, read behind a drained context stream; kept in the carry sums (keep) or dropped
+static int lc_flush(mind_ctx *c, bool keep) {
+  const int n = (int)c->lc.pending.size();
+  if (n > 0) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->pl_copy) HIPCHK(c, hipStreamSynchronize(c->pl_copy));      // (a queued copy into the mirror)
+    int first[2], count[2];
+    const int runs = c->lc.pending_runs(0, n, first, count);
+    for (int k = 0; k < runs; ++k) {
+      const size_t o = c->lc.slot_of(first[k]), b = (size_t)count[k] * c->lc.block_slots * sizeof(LcSlot);
+      HIPCHK(c, hipMemcpy(c->lc_host + o, (const LcSlot *)c->lc_dev.p + o, b, hipMemcpyDeviceToHost));
+    }
+    if (keep)
+      for (const LcRecord &r : c->lc.pending) lc_account(c, r, c->lc_carry_ms, c->lc_carry_n);
+    c->lc.drained(n);
+  }
+  return MIND_OK;
+}
+
+// room for `records` launches of at most `grid` workgroups: called outside the timed launches (growing drains the stream; what was pending
+// is kept in the carry sums)
+static int lc_reserve(mind_ctx *c, int records, int grid) {
+  if (c->lc.fits(records, grid)) return MIND_OK;
+  int rc, blocks, slots;
+  if ((rc = lc_flush(c, true))) return rc;
+  c->lc.grown(records, grid, blocks, slots);
+  if (blocks != c->lc.n_blocks || slots != c->lc.block_slots) {
+    const size_t bytes = (size_t)blocks * slots * sizeof(LcSlot);
+    if ((rc = ensure_exact(c, c->lc_dev, bytes, "the launch clock's ring"))) return rc;
+    if (c->lc_host) (void)hipHostFree(c->lc_host);
+    c->lc_host = nullptr;
+    if (hipHostMalloc((void **)&c->lc_host, bytes, hipHostMallocDefault) != hipSuccess) { c->lc_host = nullptr; c->lc.reset(0, 0); return fail(c, MIND_ENOMEM, "hipHostMalloc(%zu) for the launch clock failed", bytes); }
+    c->lc.reset(blocks, slots);
+  }
+  return MIND_OK;
+}
+
+// the next block's slots for a launch of `grid` workgroups, or null (clock off, or no block: the launch then is not timed)
+static LcSlot *lc_take(mind_ctx *c, int grid, int kind) {
+  if (!lc_on(c)) return nullptr;
+  const int b = c->lc.take(grid, kind);
+  return b < 0 ? nullptr : (LcSlot *)c->lc_dev.p + c->lc.slot_of(b);
+}
+
+// the pending records i0 .. i0 + n - 1 to the mirror, queued on s behind their launches
+static int lc_copy_async(mind_ctx *c, hipStream_t s, int i0, int n) {
+  int first[2], count[2];
+  const int runs = c->lc.pending_runs(i0, n, first, count);
+  for (int k = 0; k < runs; ++k) {
+    const size_t o = c->lc.slot_of(first[k]), b = (size_t)count[k] * c->lc.block_slots * sizeof(LcSlot);
+    HIPCHK(c, hipMemcpyAsync(c->lc_host + o, (const LcSlot *)c->lc_dev.p + o, b, hipMemcpyDeviceToHost, s));
+  }
+  if (runs > 0) c->lc.mark_copied(i0, n);
+  return MIND_OK;
+}
+
+// the oldest n pending records, whose copy has completed (n < 0: all of them), go to the carry sums, and the carry of the kinds in `kinds`
+// (bits 1 << LC_*) is handed out and cleared.  Records that no completed copy covers are read behind a drained stream instead
+static int lc_resolve(mind_ctx *c, int n, unsigned kinds, double (&ms)[LC_KINDS], int (&cnt)[LC_KINDS]) {
+  for (int k = 0; k < LC_KINDS; ++k) {
+    ms[k] = 0.0; cnt[k] = 0;
+    if (kinds >> k & 1u) c->lc_last[k].clear();
+  }
+  if (n < 0 || n > (int)c->lc.pending.size()) n = (int)c->lc.pending.size();
+  if (!c->lc.copied(n)) {
+    int rc;
+    if ((rc = lc_flush(c, true))) return rc;
+  } else {
+    for (int i = 0; i < n; ++i) lc_account(c, c->lc.pending[i], c->lc_carry_ms, c->lc_carry_n);
+    c->lc.drained(n);
+  }
+  for (int k = 0; k < LC_KINDS; ++k)
+    if (kinds >> k & 1u) { ms[k] = c->lc_carry_ms[k]; cnt[k] = c->lc_carry_n[k]; c->lc_carry_ms[k] = 0.0; c->lc_carry_n[k] = 0; }
+  return MIND_OK;
+}
+
 // ---- one mind_predict_batch call: what its stages share
 struct PredCall {
   mind_ctx *c;
@@ -145,6 +234,8 @@ struct PredCall {
   const float *const *rpe_dev = nullptr;
   hipEvent_t *evs = nullptr;            // profiling: two events per pair layer
   bool tok_timed = false;               // ... and HIP events around every token launch, outside a plan
+  bool act_ev = false, pair_ev = false; // this call records the ActorNet's / the pair layers' HIP events (profiling on, and not timed by the launch clock alone)
+  bool pair_clk = false;                // the pair layers take blocks of the launch clock's ring
   size_t ev_tok_used = 0;
   float *x() const { return (float *)c->x.p; }
   const int *rows() const { return (const int *)ts->rows.p; }      // actor_row[A], actor_scene[A], cls_row[Bn]
@@ -228,8 +319,8 @@ static int pred_workspaces(PredCall &p) {
   return MIND_OK;
 }
 
-// the ActorNet in the form pred_choose took, on the context stream
-static int pred_actor_net(PredCall &p) {
+// the ActorNet in the form pred_choose took, on the context stream (clk: the launch clock's slots of a one-launch form, or null)
+static int pred_actor_net(PredCall &p, LcSlot *clk) {
   mind_ctx *c = p.c;
   const PredChoice &ch = p.ch;
   const float *actors = p.in->actors;
@@ -238,11 +329,11 @@ static int pred_actor_net(PredCall &p) {
   const dim3 grid(ch.actor_grid);
   switch (ch.actor_form) {
   case PRED_ACTOR_F32:
-    if (ch.actor_arg == 2) hipLaunchKernelGGL(k_actor_f32<2>, grid, dim3(AF_T), mind_actor_f32_lds_bytes(2), p.st, actors, A, actor_feat, c->W.actorF);
-    else hipLaunchKernelGGL(k_actor_f32<1>, grid, dim3(AF_T), mind_actor_f32_lds_bytes(1), p.st, actors, A, actor_feat, c->W.actorF);
+    if (ch.actor_arg == 2) hipLaunchKernelGGL(k_actor_f32<2>, grid, dim3(AF_T), mind_actor_f32_lds_bytes(2), p.st, actors, A, actor_feat, c->W.actorF, clk);
+    else hipLaunchKernelGGL(k_actor_f32<1>, grid, dim3(AF_T), mind_actor_f32_lds_bytes(1), p.st, actors, A, actor_feat, c->W.actorF, clk);
     break;
   case PRED_ACTOR_VALU:
-    hipLaunchKernelGGL(k_actor_net, grid, dim3(AT), mind_actor_lds_bytes(), p.st, actors, A, actor_feat, c->W.actor);
+    hipLaunchKernelGGL(k_actor_net, grid, dim3(AT), mind_actor_lds_bytes(), p.st, actors, A, actor_feat, c->W.actor, clk);
     break;
   case PRED_ACTOR_LW: {
     // the weight fragments stationary, one arena of one chunk (allocated at first use)
@@ -258,9 +349,9 @@ static int pred_actor_net(PredCall &p) {
     break;
   }
   default:
-    if (ch.np == 6) hipLaunchKernelGGL(k_actor_mfma<6>, grid, dim3(AM_T), mind_actor_mfma_lds_bytes(), p.st, actors, A, actor_feat, c->W.actorB);
-    else if (ch.np == 3) hipLaunchKernelGGL(k_actor_mfma<3>, grid, dim3(AM_T), mind_actor_mfma_lds_bytes(), p.st, actors, A, actor_feat, c->W.actorB);
-    else hipLaunchKernelGGL(k_actor_mfma<1>, grid, dim3(AM_T), mind_actor_mfma_lds_bytes(), p.st, actors, A, actor_feat, c->W.actorB);
+    if (ch.np == 6) hipLaunchKernelGGL(k_actor_mfma<6>, grid, dim3(AM_T), mind_actor_mfma_lds_bytes(), p.st, actors, A, actor_feat, c->W.actorB, clk);
+    else if (ch.np == 3) hipLaunchKernelGGL(k_actor_mfma<3>, grid, dim3(AM_T), mind_actor_mfma_lds_bytes(), p.st, actors, A, actor_feat, c->W.actorB, clk);
+    else hipLaunchKernelGGL(k_actor_mfma<1>, grid, dim3(AM_T), mind_actor_mfma_lds_bytes(), p.st, actors, A, actor_feat, c->W.actorB, clk);
   }
   return MIND_OK;
 }
@@ -279,15 +370,22 @@ static int pred_encoders(PredCall &p) {
     HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_main, 0));
   }
   const bool act_timed = c->profiling && !c->ev_defer;      // (inside a plan nothing drains the stream per call: no ActorNet time there)
-  if (act_timed && !c->ev_act0) {
+  // the one-launch forms by the launch clock; the layer-wise form (a dozen launches per chunk) stays on its two events
+  int rc;
+  LcSlot *act_clk = nullptr;
+  if (act_timed && lc_on(c) && p.ch.actor_form != PRED_ACTOR_LW) {
+    if ((rc = lc_reserve(c, 1, p.ch.actor_grid))) return rc;
+    act_clk = lc_take(c, p.ch.actor_grid, LC_ACTOR);
+  }
+  p.act_ev = act_timed && (lc_events(c) || !act_clk);
+  if (p.act_ev && !c->ev_act0) {
     HIPCHK(c, hipEventCreate(&c->ev_act0));
     HIPCHK(c, hipEventCreate(&c->ev_act1));
   }
   c->last_actor_lw = 0; c->last_actor_launches = 1; c->last_actor_chunks = 1; c->actor_ms = 0.f;
-  if (act_timed) HIPCHK(c, hipEventRecord(c->ev_act0, st));
-  int rc;
-  if ((rc = pred_actor_net(p))) return rc;
-  if (act_timed) HIPCHK(c, hipEventRecord(c->ev_act1, st));
+  if (p.act_ev) HIPCHK(c, hipEventRecord(c->ev_act0, st));
+  if ((rc = pred_actor_net(p, act_clk))) return rc;
+  if (p.act_ev) HIPCHK(c, hipEventRecord(c->ev_act1, st));
   // (a plan's own work for the side stream, launched behind ActorNet: in front of the lane encoders here, behind the target embedding below)
   if (c->enc_pre) {
     const std::function<int(hipStream_t)> pre = std::move(c->enc_pre);
@@ -389,11 +487,12 @@ static int pred_pair_layer(PredCall &p, int L) {
   float *edge = (float *)c->edge.p, *ST = (float *)c->ST.p, *QK = (float *)c->QK.p, *part = (float *)c->part.p, *tokpos = (float *)c->tokpos.p;
   const size_t ldsb = mind_pair_bf_lds_bytes();
   const u32 *we = c->W.pair.WBe[L], *wp = last ? c->W.pair.WBe[L] : c->W.pair.WBp[L];
-  if (c->profiling) HIPCHK(c, hipEventRecord(p.evs[2 * L], p.st));
+  LcSlot *clk = p.pair_clk ? lc_take(c, (int)grid.x, LC_PAIR) : nullptr;      // (room was made in pred_fusion)
+  if (p.pair_ev) HIPCHK(c, hipEventRecord(p.evs[2 * L], p.st));
 #define PAIR_GO(K0, K1, LDS, ...)                                                                                                             \
   do {                                                                                                                                        \
-    if (L == 0) hipLaunchKernelGGL(K0, grid, block, LDS, p.st, jl, nj, edge, ST, QK, part, __VA_ARGS__, c->W.pair.vtab[L], c->W.pair.rtab, tokpos, p.rpe_dev, um); \
-    else hipLaunchKernelGGL(K1, grid, block, LDS, p.st, jl, nj, edge, ST, QK, part, __VA_ARGS__, c->W.pair.vtab[L], c->W.pair.rtab, tokpos, p.rpe_dev, um);        \
+    if (L == 0) hipLaunchKernelGGL(K0, grid, block, LDS, p.st, jl, nj, edge, ST, QK, part, __VA_ARGS__, c->W.pair.vtab[L], c->W.pair.rtab, tokpos, p.rpe_dev, um, clk); \
+    else hipLaunchKernelGGL(K1, grid, block, LDS, p.st, jl, nj, edge, ST, QK, part, __VA_ARGS__, c->W.pair.vtab[L], c->W.pair.rtab, tokpos, p.rpe_dev, um, clk);   \
   } while (0)
   switch (ch.pair_family) {
   case PRED_PAIR_F32: PAIR_GO((k_pair<0>), (k_pair<1>), mind_pair_lds_bytes(), c->W.pair.WAe[L], last ? c->W.pair.WAe[L] : c->W.pair.WAp[L]); break;
@@ -407,7 +506,7 @@ static int pred_pair_layer(PredCall &p, int L) {
     else PAIR_GO((k_pair_bf<0, 1>), (k_pair_bf<1, 1>), ldsb, we, wp);
   }
 #undef PAIR_GO
-  if (c->profiling) HIPCHK(c, hipEventRecord(p.evs[2 * L + 1], p.st));
+  if (p.pair_ev) HIPCHK(c, hipEventRecord(p.evs[2 * L + 1], p.st));
   c->n_pair_launch++;
   c->pairs_done += last ? ts->pairs_l5 : ts->pairs_full;
   return MIND_OK;
@@ -426,7 +525,11 @@ static int pred_fusion(PredCall &p) {
   if ((rc = pred_token_step(p, 1 | 4 | ch.qsplit, 0))) return rc;
   c->n_pair_launch = 0;
   c->pairs_done = 0;
-  if (c->profiling && c->ev.size() < 12) {
+  // the pair layers' timing: blocks of the launch clock's ring ("prof_clock" 1, 2), HIP events around every launch ("prof_clock" 0, 2)
+  p.pair_clk = lc_on(c);
+  p.pair_ev = lc_events(c);
+  if (p.pair_clk && (rc = lc_reserve(c, c->debug_layers, std::max(pair_grid(ts->njobs, c->n_cu), pair_grid(ts->njobs5, c->n_cu))))) return rc;
+  if (p.pair_ev && c->ev.size() < 12) {
     while (c->ev.size() < 12) {
       hipEvent_t e;
       HIPCHK(c, hipEventCreate(&e));
@@ -434,7 +537,7 @@ static int pred_fusion(PredCall &p) {
     }
   }
   p.evs = c->ev.data();
-  if (c->profiling && c->ev_defer) {
+  if (p.pair_ev && c->ev_defer) {
     while (c->ev_pool.size() < c->ev_pool_used + 12) {
       hipEvent_t e;
       HIPCHK(c, hipEventCreate(&e));
@@ -555,12 +658,25 @@ static int pred_finish(PredCall &p) {
   } else if (c->profiling) {
     HIPCHK(c, hipStreamSynchronize(p.st));
     c->pair_ms = 0.f;
-    for (int L = 0; L < c->debug_layers; ++L) {
+    for (int k : {LC_PAIR, LC_ACTOR}) { c->ev_last[k].clear(); c->lc_last[k].clear(); }
+    for (int L = 0; L < c->debug_layers && p.pair_ev; ++L) {
       float ms = 0.f;
       HIPCHK(c, hipEventElapsedTime(&ms, c->ev[2 * L], c->ev[2 * L + 1]));
       c->pair_ms += ms;
+      c->ev_last[LC_PAIR].push_back(ms);
     }
-    if (c->ev_act0) HIPCHK(c, hipEventElapsedTime(&c->actor_ms, c->ev_act0, c->ev_act1));
+    if (p.act_ev) {
+      HIPCHK(c, hipEventElapsedTime(&c->actor_ms, c->ev_act0, c->ev_act1));
+      c->ev_last[LC_ACTOR].push_back(c->actor_ms);
+    }
+    if (lc_on(c)) {
+      // the launch clock's records of this call, read behind the drained stream: its figures are the ones handed out
+      double ms[LC_KINDS];
+      int n[LC_KINDS], rc;
+      if ((rc = lc_resolve(c, -1, 1u << LC_PAIR | 1u << LC_ACTOR, ms, n))) return rc;
+      if (n[LC_PAIR] > 0) c->pair_ms = (float)ms[LC_PAIR];
+      if (n[LC_ACTOR] > 0) c->actor_ms = (float)ms[LC_ACTOR];
+    }
     for (size_t i = 1; i < p.ev_tok_used; ++i) {
       if (c->ev_tok_tag[i] < 0) continue;
       float ms = 0.f;

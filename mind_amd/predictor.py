@@ -283,6 +283,16 @@ class HipPredictor:
         self.lib.mind_last_fusion_stats(self.ctx, C.byref(n), C.byref(ms), C.byref(pairs))
         return n.value, ms.value, pairs.value
 
+    def launch_times(self, kind="pair"):
+        """(by the launch clock, by HIP events): ms per timed launch of the last read, in launch order (mind_debug_launch_times; kind "pair" or
+        "actor").  Either list is empty when its mechanism was not armed: mind_set_tuning("prof_clock", 0 events | 1 clock | 2 both)"""
+        cap = 4096
+        ck, ev = (C.c_float * cap)(), (C.c_float * cap)()
+        nc, ne = C.c_int(), C.c_int()
+        _lib.check(self.lib, self.ctx, self.lib.mind_debug_launch_times(self.ctx, {"pair": 0, "actor": 1}[kind], ck, ev, cap, C.byref(nc), C.byref(ne)),
+                   "mind_debug_launch_times")
+        return [float(v) for v in ck[:min(nc.value, cap)]], [float(v) for v in ev[:min(ne.value, cap)]]
+
     def last_actor_stats(self):
         """ActorNet of the last predictor call (mind_last_actor_stats): dict(layerwise = 1 when the layer-wise batched kernels ran, launches,
         chunks, ms = first launch to last on the context stream, 0 unless profiling)"""

@@ -21,9 +21,9 @@ static u32 bf16_bits(float v) { u32 u; memcpy(&u, &v, 4); u += 0x7fffu + ((u >> 
 static float bf16_val(u32 b) { u32 u = b << 16; float f; memcpy(&f, &u, 4); return f; }
 
 typedef void (*Kernel3)(const PairJob *, int, float *, const float *, const float *, float *, const u32 *, const u32 *, const float *, const float *,
-                        const float *, const float *const *, int);
+                        const float *, const float *const *, int, LcSlot *);
 typedef void (*Kernel6)(const PairJob *, int, float *, const float *, const float *, float *, const u32 *, const u32 *, const u32 *, const u32 *,
-                        const float *, const float *, const float *, const float *const *, int);
+                        const float *, const float *, const float *, const float *const *, int, LcSlot *);
 struct Variant { std::string name; Kernel3 f3; Kernel6 f6; std::vector<float> ms; };
 
 int main(int argc, char **argv) {
@@ -128,10 +128,10 @@ int main(int argc, char **argv) {
       CK(hipEventRecord(e0, 0));
       if (v.f3)
         hipLaunchKernelGGL(v.f3, dim3(grid), dim3(PAIR_THREADS), lds, 0, d_jobs, njobs, d_edge, d_ST, d_QK, d_part, d_W, d_W + 16384, d_vt, d_rt, d_tp,
-                           (const float *const *)nullptr, um);
+                           (const float *const *)nullptr, um, (LcSlot *)nullptr);
       else
         hipLaunchKernelGGL(v.f6, dim3(grid), dim3(PAIR_THREADS), lds, 0, d_jobs, njobs, d_edge, d_ST, d_QK, d_part, d_W, d_W + 16384, d_WL, d_WL + 8192, d_vt,
-                           d_rt, d_tp, (const float *const *)nullptr, um);
+                           d_rt, d_tp, (const float *const *)nullptr, um, (LcSlot *)nullptr);
       CK(hipEventRecord(e1, 0)); CK(hipEventSynchronize(e1));
       float ms; CK(hipEventElapsedTime(&ms, e0, e1));
       if (r > 0) v.ms.push_back(ms);

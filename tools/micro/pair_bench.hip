@@ -25,7 +25,7 @@ static u32 bf16_bits(float v) { u32 u; memcpy(&u, &v, 4); u += 0x7fffu + ((u >> 
 static float bf16_val(u32 b) { u32 u = b << 16; float f; memcpy(&f, &u, 4); return f; }
 
 typedef void (*KernelT)(const PairJob *, int, float *, const float *, const float *, float *, const u32 *, const u32 *, const float *,
-                        const float *, const float *, const float *const *, int);
+                        const float *, const float *, const float *const *, int, LcSlot *);
 struct Variant { std::string name; KernelT fn; bool tiled; int um; std::vector<float> ms; };
 
 int main(int argc, char **argv) {
@@ -162,7 +162,7 @@ int main(int argc, char **argv) {
       if (v.name.find("timers") != std::string::npos && r != 1) continue;
       CK(hipEventRecord(e0, 0));
       hipLaunchKernelGGL(v.fn, dim3(grid), dim3(PAIR_THREADS), lds, 0, d_jobs, njobs, d_edge, d_ST, d_QK, d_part, d_W, d_W + 16384, d_vt, d_rt, d_tp,
-                         (const float *const *)nullptr, v.um);
+                         (const float *const *)nullptr, v.um, (LcSlot *)nullptr);
       CK(hipEventRecord(e1, 0)); CK(hipEventSynchronize(e1));
       float ms; CK(hipEventElapsedTime(&ms, e0, e1));
       if (r > 0) v.ms.push_back(ms);
@@ -187,7 +187,7 @@ int main(int argc, char **argv) {
         CK(hipMemcpy(d_edge, h_edge.data(), edge_floats * 4, hipMemcpyHostToDevice));
         CK(hipMemset(d_part, 0, part_floats * 4));
         hipLaunchKernelGGL(v ? c.alt : c.base, dim3(grid), dim3(PAIR_THREADS), lds, 0, d_jobs, njobs, d_edge, d_ST, d_QK, d_part, d_W, d_W + 16384, d_vt, d_rt, d_tp,
-                           (const float *const *)nullptr, c.um);
+                           (const float *const *)nullptr, c.um, (LcSlot *)nullptr);
         CK(hipDeviceSynchronize());
         CK(hipMemcpy((v ? e1 : e0).data(), d_edge, edge_floats * 4, hipMemcpyDeviceToHost));
         CK(hipMemcpy((v ? p1 : p0).data(), d_part, part_floats * 4, hipMemcpyDeviceToHost));
