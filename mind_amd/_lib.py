@@ -618,6 +618,20 @@ def road_margin(boxes, ego_box, verts, poly_off, trig=None):
     return res
 
 
+def out_record(rec, shape_of, want=None):
+    """A record of optional output pointers (mind_audit_*_out, mind_forecast_out) over freshly allocated result arrays: every field of
+    the ctypes record ``rec`` that ``want`` names (None = all) gets a zeroed array of shape ``shape_of(name)`` and of the element type its
+    pointer declares; the others stay null.  -> (record, results by name in field order)"""
+    import numpy as np
+    out, res = rec(), {}
+    dtype = {C.c_double: np.float64, C.c_int32: np.int32}
+    for name, ptr in rec._fields_:
+        if want is None or name in want:
+            res[name] = np.zeros(shape_of(name), dtype[ptr._type_])
+            setattr(out, name, res[name].ctypes.data_as(ptr))
+    return out, res
+
+
 def forecast_args(K, T, actor_off, gt, valid, scored, horizons, miss_radius, disc_scale, disc_offset, want=None):
     """The host-side arguments of mind_forecast_score / mind_debug_forecast_score: checked numpy arrays, the configuration and the output
     record over freshly allocated result arrays (``want``: names of mind_forecast_out, None = all).  -> (cfg, B, actor_off, gt, valid,
@@ -639,11 +653,8 @@ def forecast_args(K, T, actor_off, gt, valid, scored, horizons, miss_radius, dis
     names = [n for n, _, _, _ in FORECAST_OUT]
     if want is not None and any(n not in names for n in want):
         raise ValueError(f"forecast outputs are {names}, got {list(want)}")
-    out, res = ForecastOut(), {}
-    for n, dt, per, has_k in FORECAST_OUT:
-        if want is None or n in want:
-            res[n] = np.zeros((A if per == "a" else B, hz.size) + ((int(K),) if has_k else ()), np.float64 if dt == "f8" else np.int32)
-            setattr(out, n, res[n].ctypes.data_as(C.POINTER(C.c_double if dt == "f8" else C.c_int32)))
+    shape = {n: (A if per == "a" else B, hz.size) + ((int(K),) if has_k else ()) for n, _, per, has_k in FORECAST_OUT}
+    out, res = out_record(ForecastOut, shape.__getitem__, want)
     u8 = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_uint8))
     return (cfg, B, off.ctypes.data_as(C.POINTER(C.c_int32)), g.ctypes.data_as(C.POINTER(C.c_double)), u8(v), u8(sc), out, res, (off, g, v, sc, hz))
 

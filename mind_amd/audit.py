@@ -61,43 +61,59 @@ def _states_of(traj_tree, M):
     return xs
 
 
+def _plan_args(who, scen_tree, traj_tree):
+    """the arguments of the two plan audits -> (flat cost trees, one [1, M_t, 6] state set per tree)"""
+    scen = list(scen_tree) if isinstance(scen_tree, (list, tuple)) else [scen_tree]
+    traj = list(traj_tree) if isinstance(traj_tree, (list, tuple)) else [traj_tree]
+    if len(scen) != len(traj) or not scen:
+        raise ValueError(f"{who}: {len(scen)} scenario trees, {len(traj)} trajectory trees")
+    flats = [_flat_of(t) for t in scen]
+    return flats, [_states_of(t, len(f["parent"]))[None] for t, f in zip(traj, flats)]
+
+
+def _plan_result(res):
+    """one candidate on n trees: per-tree lists of the node_* arrays [M_t], the tree_* arrays [n_trees]"""
+    return {k: [a[0] for a in v] if k.startswith("node_") else v[0] for k, v in res.items()}
+
+
+def _rollout_args(who, solver_or_flat, xs):
+    """the arguments of the two rollout audits -> (flat cost tree, xs [C, M, 6], whether xs was one [M, 6] set)"""
+    flat = solver_or_flat if isinstance(solver_or_flat, dict) else getattr(solver_or_flat, "cost_tree", None)
+    if not isinstance(flat, dict) or not all(k in flat for k in ("parent", "prob", "mean", "cov")):
+        raise TypeError(f"{who}: a flat cost tree (parent, prob, mean, cov) or a TrajectoryTreeOptimizer with a prepared cost tree is needed")
+    x = np.asarray(xs, np.float64)
+    one = x.ndim == 2
+    x = x[None] if one else x
+    M = len(flat["parent"])
+    if x.ndim != 3 or x.shape[1:] != (M, 6):
+        raise ValueError(f"{who}: xs must be [C, {M}, 6] or [{M}, 6], got {list(np.shape(xs))}")
+    return flat, x, one
+
+
+def _rollout_result(res, one):
+    """C candidates on one tree: the node_* arrays [C, M], the tree_* arrays [C]; without the C axis for one [M, 6] set"""
+    out = {k: v[0] if k.startswith("node_") else v[:, 0] for k, v in res.items()}
+    return {k: v[0] for k, v in out.items()} if one else out
+
+
 def audit_plan(scen_tree, traj_tree, ego_box=BOXES["VEHICLE"], exo_margin=None, runtime=None, planner=None):
     """Audit what ``plan()`` returned (``[[scen_tree], [traj_tree]]`` of MINDPlanner.plan, native_plan or the native loop's
     ``last_result``): ``scen_tree`` / ``traj_tree`` are the two lists (or one tree each).  Tree t's states are read from its trajectory-tree
     keys 0..M-1 and paired with the flattened scenario tree's agents; ONE device call for all trees.  ``exo_margin``: None = the
     ``w_exo_cov_offset`` of ``planner``'s config, 2.5 without a planner.  Returns a dict: per-tree lists node_clear [M_t] / node_agent [M_t]
     and arrays tree_min, tree_node, tree_agent, tree_hits, tree_first, tree_mass [n_trees]."""
-    scen = list(scen_tree) if isinstance(scen_tree, (list, tuple)) else [scen_tree]
-    traj = list(traj_tree) if isinstance(traj_tree, (list, tuple)) else [traj_tree]
-    if len(scen) != len(traj) or not scen:
-        raise ValueError(f"audit_plan: {len(scen)} scenario trees, {len(traj)} trajectory trees")
-    flats = [_flat_of(t) for t in scen]
-    xs = [_states_of(t, len(f["parent"]))[None] for t, f in zip(traj, flats)]
-    res = _runtime(runtime).audit_plan(flats, xs, ego_box, _margin(exo_margin, planner))
-    out = {k: [a[0] for a in res[k]] for k in ("node_clear", "node_agent")}
-    out.update({k: v[0] for k, v in res.items() if k.startswith("tree_")})
-    return out
+    flats, xs = _plan_args("audit_plan", scen_tree, traj_tree)
+    return _plan_result(_runtime(runtime).audit_plan(flats, xs, ego_box, _margin(exo_margin, planner)))
 
 
 def audit_rollouts(solver_or_flat, xs, ego_box=BOXES["VEHICLE"], exo_margin=None, runtime=None):
     """The audit of C candidate state sets ``xs`` [C, M, 6] (or [M, 6]) on ONE cost tree: a flat dict (parent, prob, mean, cov) or a
     ``TrajectoryTreeOptimizer`` (its last prepared cost tree; ``exo_margin`` then defaults to its config's).  Returns node_clear [C, M],
     node_agent [C, M] and tree_min, tree_node, tree_agent, tree_hits, tree_first, tree_mass [C]."""
-    flat = solver_or_flat if isinstance(solver_or_flat, dict) else getattr(solver_or_flat, "cost_tree", None)
-    if not isinstance(flat, dict) or not all(k in flat for k in ("parent", "prob", "mean", "cov")):
-        raise TypeError("audit_rollouts: a flat cost tree (parent, prob, mean, cov) or a TrajectoryTreeOptimizer with a prepared cost tree is needed")
+    flat, x, one = _rollout_args("audit_rollouts", solver_or_flat, xs)
     if exo_margin is None and not isinstance(solver_or_flat, dict) and getattr(solver_or_flat, "config", None) is not None:
         exo_margin = solver_or_flat.config.opt_cfg["w_exo_cov_offset"]
-    x = np.asarray(xs, np.float64)
-    one = x.ndim == 2
-    x = x[None] if one else x
-    M = len(flat["parent"])
-    if x.ndim != 3 or x.shape[1:] != (M, 6):
-        raise ValueError(f"audit_rollouts: xs must be [C, {M}, 6] or [{M}, 6], got {list(np.shape(xs))}")
-    res = _runtime(runtime).audit_plan([flat], x, ego_box, _margin(exo_margin, None))
-    out = {k: res[k][0] for k in ("node_clear", "node_agent")}
-    out.update({k: v[:, 0] for k, v in res.items() if k.startswith("tree_")})
-    return {k: v[0] for k, v in out.items()} if one else out
+    return _rollout_result(_runtime(runtime).audit_plan([flat], x, ego_box, _margin(exo_margin, None)), one)
 
 
 def tabulate_exo(world, times):
@@ -147,22 +163,30 @@ class EpisodeAuditor:
         ego = np.stack(self.states)
         exo, valid, boxes = tabulate_exo(self.sim.world, self.times)
         res = _runtime(self.runtime).audit_episode(ego[None], exo, valid, boxes, self.ego_box)
-        clear, track = res["step_clear"][0], res["step_track"][0]
+        per = {k: res[k][0] for k in ("step_clear", "step_track")}
         en = np.array(self.enabled, bool)
-        out = dict(times=np.array(self.times), enabled=en, step_clear=clear, step_track=track,
+        out = dict(times=np.array(self.times), enabled=en, **per,
                    **{k: (float if k == "ego_min" else int)(res[k][0]) for k in ("ego_min", "ego_step", "ego_track", "ego_hits", "ego_first")})
-        out["before"], out["after"] = _part(clear, track, np.flatnonzero(~en)), _part(clear, track, np.flatnonzero(en))
+        out["before"], out["after"] = (_part(per, i, "step_clear", "track", nan_step=False) for i in (np.flatnonzero(~en), np.flatnonzero(en)))
         return out
 
 
-def _part(clear, track, idx):
-    """summary of the steps ``idx`` of a trace, by the rules of the whole-trace summary (the lowest step wins ties)"""
+def _part(per, idx, value, tag, nan_step):
+    """summary of the steps ``idx`` of a trace whose per-step arrays are ``per``, by the rules of the whole-trace summary over
+    per[value] with the tag per["step_" + tag] (the lowest step wins ties).  ``nan_step`` (the road audit): a NaN step reports NaN, that
+    step, -1, -1, -1; without it (the clearance audit) the first minimum is numpy's argmin"""
     if len(idx) == 0:
         return None
-    c, hit = clear[idx], np.flatnonzero(clear[idx] < 0.0)
-    k = int(np.argmin(c))               # (first minimum)
-    return dict(steps=idx, step_clear=c, step_track=track[idx], ego_min=float(c[k]), ego_step=int(idx[k]), ego_track=int(track[idx[k]]),
-                ego_hits=int(len(hit)), ego_first=int(idx[hit[0]]) if len(hit) else -1)
+    m = per[value][idx]
+    out = dict(steps=idx, **{k: v[idx] for k, v in per.items()})
+    bad = np.flatnonzero(np.isnan(m)) if nan_step else ()
+    if len(bad):
+        out.update({"ego_min": float("nan"), "ego_step": int(idx[bad[0]]), "ego_" + tag: -1, "ego_hits": -1, "ego_first": -1})
+        return out
+    hit, k = np.flatnonzero(m < 0.0), int(np.argmin(m))               # (first minimum)
+    out.update({"ego_min": float(m[k]), "ego_step": int(idx[k]), "ego_" + tag: int(per["step_" + tag][idx[k]]), "ego_hits": int(len(hit)),
+                "ego_first": int(idx[hit[0]]) if len(hit) else -1})
+    return out
 
 
 # ---- the road audit -----------------------------------------------------------------------------------------------------------------
@@ -232,16 +256,8 @@ def audit_road_plan(scen_tree, traj_tree, road, ego_box=BOXES["VEHICLE"], runtim
     JSON, or a list of rings).  ONE device call for all trees.  Returns a dict: per-tree lists node_margin / node_corner / node_ring /
     node_edge [M_t] and arrays tree_min, tree_node, tree_corner, tree_hits, tree_first, tree_mass [n_trees]."""
     road = _road(road)
-    scen = list(scen_tree) if isinstance(scen_tree, (list, tuple)) else [scen_tree]
-    traj = list(traj_tree) if isinstance(traj_tree, (list, tuple)) else [traj_tree]
-    if len(scen) != len(traj) or not scen:
-        raise ValueError(f"audit_road_plan: {len(scen)} scenario trees, {len(traj)} trajectory trees")
-    flats = [_flat_of(t) for t in scen]
-    xs = [_states_of(t, len(f["parent"]))[None] for t, f in zip(traj, flats)]
-    res = _runtime(runtime).audit_road_plan(flats, xs, road.verts, road.poly_off, ego_box)
-    out = {k: [a[0] for a in v] for k, v in res.items() if k.startswith("node_")}
-    out.update({k: v[0] for k, v in res.items() if k.startswith("tree_")})
-    return out
+    flats, xs = _plan_args("audit_road_plan", scen_tree, traj_tree)
+    return _plan_result(_runtime(runtime).audit_road_plan(flats, xs, road.verts, road.poly_off, ego_box))
 
 
 def audit_road_rollouts(solver_or_flat, xs, road, ego_box=BOXES["VEHICLE"], runtime=None):
@@ -249,19 +265,8 @@ def audit_road_rollouts(solver_or_flat, xs, road, ego_box=BOXES["VEHICLE"], runt
     ``TrajectoryTreeOptimizer`` (its last prepared cost tree).  Returns node_margin, node_corner, node_ring, node_edge [C, M] and tree_min,
     tree_node, tree_corner, tree_hits, tree_first, tree_mass [C]."""
     road = _road(road)
-    flat = solver_or_flat if isinstance(solver_or_flat, dict) else getattr(solver_or_flat, "cost_tree", None)
-    if not isinstance(flat, dict) or not all(k in flat for k in ("parent", "prob", "mean", "cov")):
-        raise TypeError("audit_road_rollouts: a flat cost tree (parent, prob, mean, cov) or a TrajectoryTreeOptimizer with a prepared cost tree is needed")
-    x = np.asarray(xs, np.float64)
-    one = x.ndim == 2
-    x = x[None] if one else x
-    M = len(flat["parent"])
-    if x.ndim != 3 or x.shape[1:] != (M, 6):
-        raise ValueError(f"audit_road_rollouts: xs must be [C, {M}, 6] or [{M}, 6], got {list(np.shape(xs))}")
-    res = _runtime(runtime).audit_road_plan([flat], x, road.verts, road.poly_off, ego_box)
-    out = {k: v[0] for k, v in res.items() if k.startswith("node_")}
-    out.update({k: v[:, 0] for k, v in res.items() if k.startswith("tree_")})
-    return {k: v[0] for k, v in out.items()} if one else out
+    flat, x, one = _rollout_args("audit_road_rollouts", solver_or_flat, xs)
+    return _rollout_result(_runtime(runtime).audit_road_plan([flat], x, road.verts, road.poly_off, ego_box), one)
 
 
 class EpisodeRoadAuditor:
@@ -286,22 +291,5 @@ class EpisodeRoadAuditor:
         en = np.array(self.enabled, bool)
         out = dict(times=np.array(self.times), enabled=en, **per,
                    **{k: (float if k == "ego_min" else int)(res[k][0]) for k in ("ego_min", "ego_step", "ego_corner", "ego_hits", "ego_first")})
-        out["before"], out["after"] = _road_part(per, np.flatnonzero(~en)), _road_part(per, np.flatnonzero(en))
+        out["before"], out["after"] = (_part(per, i, "step_margin", "corner", nan_step=True) for i in (np.flatnonzero(~en), np.flatnonzero(en)))
         return out
-
-
-def _road_part(per, idx):
-    """summary of the steps ``idx`` of a trace, by the rules of the whole-trace summary (the lowest step wins ties; a NaN step: NaN, that
-    step, -1, -1, -1)"""
-    if len(idx) == 0:
-        return None
-    m = per["step_margin"][idx]
-    out = dict(steps=idx, **{k: v[idx] for k, v in per.items()})
-    bad = np.flatnonzero(np.isnan(m))
-    if len(bad):
-        out.update(ego_min=float("nan"), ego_step=int(idx[bad[0]]), ego_corner=-1, ego_hits=-1, ego_first=-1)
-        return out
-    hit, k = np.flatnonzero(m < 0.0), int(np.argmin(m))               # (first minimum)
-    out.update(ego_min=float(m[k]), ego_step=int(idx[k]), ego_corner=int(per["step_corner"][idx[k]]), ego_hits=int(len(hit)),
-               ego_first=int(idx[hit[0]]) if len(hit) else -1)
-    return out

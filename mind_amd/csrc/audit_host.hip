@@ -1,5 +1,6 @@
 // Host side of the clearance audit (kernels: audit_kernels.hip; geometry: box_geom.h): mind_audit_plan, mind_audit_episode and the host-only
-// mind_debug_box_clearance.  Both device calls are synchronous on the context's stream and keep their scratch in c->audit_dev.
+// mind_debug_box_clearance -- and the scaffold the five synchronous "upload, launch, read back" entries share (these two, mind_forecast_score,
+// mind_audit_road_plan, mind_audit_road_episode): the arena's head, upload and tail over audit_arena.h, and the cost trees of a plan audit.
 // Included by mind_hip.hip behind loop.hip.
 #pragma clang fp contract(off)
 
@@ -19,8 +20,8 @@ namespace au_host {
 #pragma pop_macro("__HIPCC__")
 }  // namespace au_host
 
-#define AU_PLAN_MAX_ROWS (1L << 20)       // n_cand x sum M a plan audit admits (48 MB of states)
-#define AU_EPISODE_MAX_ROWS (1L << 22)    // n_ego x n_steps an episode audit admits (128 MB of ego states)
+#define AU_PLAN_MAX_ROWS (1L << 20)       // n_cand x sum M a plan audit admits, clearance or road (48 MB of states)
+#define AU_EPISODE_MAX_ROWS (1L << 22)    // n_ego x n_steps an episode audit admits, clearance or road (128 MB of ego states)
 #define AU_SCENE_MAX_ROWS (1L << 24)      // n_steps x n_tracks of the replayed scene
 
 static bool au_fin(double v) { return std::isfinite(v); }
@@ -32,11 +33,51 @@ static int au_busy(mind_ctx *c, const char *who) {
   if (c->il_finish) return fail(c, MIND_ESTATE, "%s: a tree-iLQR call begun on this context has not been finished (mind_ilqr_finish)", who);
   return MIND_OK;
 }
-// a carving of the scratch arena: `n` elements of `sz` bytes, 16-byte aligned
-static size_t au_take(size_t &top, size_t n, size_t sz) {
-  const size_t o = (top + 15) & ~(size_t)15;
-  top = o + n * sz;
-  return o;
+
+// ---- the arena on the device.  A call carves its fields, uploads every input a kernel will read and reads back only what it wrote: nothing
+// in c->audit_dev outlives the call that put it there
+// head: the context's device, room for the whole arena -> its base
+static int ar_begin(mind_ctx *c, const Arena &ar, char **d) {
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc;
+  if ((rc = ensure(c, c->audit_dev, ar.top))) return rc;
+  *d = (char *)c->audit_dev.p;
+  return MIND_OK;
+}
+template <class T>
+static int ar_put(mind_ctx *c, char *d, const ArField<T> &f, const T *src) {
+  HIPCHK(c, hipMemcpyAsync(f.at(d), src, f.bytes(), hipMemcpyHostToDevice, c->stream));
+  return MIND_OK;
+}
+// tail: copy back every field whose host pointer is non-null, then synchronise
+static int ar_finish(mind_ctx *c, const char *d, std::initializer_list<ArBack> back) {
+  for (const ArBack &b : back)
+    if (b.h) HIPCHK(c, hipMemcpyAsync(b.h, d + b.off, b.bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return MIND_OK;
+}
+
+// the cost trees of a plan audit, clearance or road: the rules both read (n_nodes, prob, the two row caps), then the AuTree table and the
+// probabilities, carved from `ar` and filled into the image `img` (which then spans the arena so far)
+struct AuPlanTrees { ArField<AuTree> trees; ArField<float> prob; long Mtot = 0; };
+static int au_plan_trees(mind_ctx *c, const char *who, const mind_cost_tree *trees, int n_trees, int n_cand, Arena &ar, std::vector<char> &img, AuPlanTrees &pt) {
+  for (int t = 0; t < n_trees; ++t) {
+    if (trees[t].n_nodes <= 0 || !trees[t].prob) return fail(c, MIND_EINVAL, "%s: tree %d: bad n_nodes or null prob", who, t);
+    pt.Mtot += trees[t].n_nodes;
+    if (pt.Mtot > AU_PLAN_MAX_ROWS) return fail(c, MIND_EINVAL, "%s: more than %ld nodes", who, AU_PLAN_MAX_ROWS);
+  }
+  if ((long)n_cand * pt.Mtot > AU_PLAN_MAX_ROWS)
+    return fail(c, MIND_EINVAL, "%s: %d candidates x %ld nodes > %ld rows supported", who, n_cand, pt.Mtot, AU_PLAN_MAX_ROWS);
+  pt.trees = ar.take<AuTree>(n_trees);
+  pt.prob = ar.take<float>(pt.Mtot);
+  img.resize(ar.top, 0);
+  long moff = 0;
+  for (int t = 0; t < n_trees; ++t) {
+    pt.trees.at(img.data())[t] = AuTree{(int)moff, trees[t].n_nodes};
+    std::copy_n(trees[t].prob, trees[t].n_nodes, pt.prob.at(img.data()) + moff);
+    moff += trees[t].n_nodes;
+  }
+  return MIND_OK;
 }
 
 extern "C" int mind_audit_plan(mind_ctx *c, const mind_audit_box *ego, double exo_margin, const mind_cost_tree *trees, int n_trees, int n_cand,
@@ -48,13 +89,19 @@ extern "C" int mind_audit_plan(mind_ctx *c, const mind_audit_box *ego, double ex
   if (!au_fin(exo_margin) || exo_margin < 0.0) return fail(c, MIND_EINVAL, "%s: exo_margin = %g, a finite value >= 0 is needed", who, exo_margin);
   if (!out->node_clear && !out->node_agent && !out->tree_min && !out->tree_node && !out->tree_agent && !out->tree_hits && !out->tree_first && !out->tree_mass)
     return fail(c, MIND_EINVAL, "%s: every output is null", who);
-  long Mtot = 0, Atot = 0;
+  int rc;
+  Arena ar;
+  std::vector<char> img;
+  AuPlanTrees pt;
+  if ((rc = au_plan_trees(c, who, trees, n_trees, n_cand, ar, img, pt))) return rc;
+  const long Mtot = pt.Mtot;
+  long Atot = 0;
   for (int t = 0; t < n_trees; ++t) {
     const mind_cost_tree &tr = trees[t];
-    if (tr.n_nodes <= 0 || tr.n_agents <= 0 || !tr.prob || (tr.n_agents > 1 && (!tr.agent_mean || !tr.agent_cov)))
-      return fail(c, MIND_EINVAL, "%s: tree %d: bad n_nodes / n_agents or null prob / agent_mean / agent_cov", who, t);
-    Mtot += tr.n_nodes; Atot += (long)tr.n_nodes * tr.n_agents;
-    if (Mtot > AU_PLAN_MAX_ROWS || Atot > (1L << 30)) return fail(c, MIND_EINVAL, "%s: more than %ld nodes or 2^30 (node, agent) rows", who, AU_PLAN_MAX_ROWS);
+    if (tr.n_agents <= 0 || (tr.n_agents > 1 && (!tr.agent_mean || !tr.agent_cov)))
+      return fail(c, MIND_EINVAL, "%s: tree %d: bad n_agents or null agent_mean / agent_cov", who, t);
+    Atot += (long)tr.n_nodes * tr.n_agents;
+    if (Atot > (1L << 30)) return fail(c, MIND_EINVAL, "%s: more than 2^30 (node, agent) rows", who);
     const size_t na = (size_t)tr.n_nodes * tr.n_agents;
     for (size_t i = 0; i < na; ++i) {
       if (i % tr.n_agents == 0) continue;           // (agent 0 is the ego: not read)
@@ -64,62 +111,47 @@ extern "C" int mind_audit_plan(mind_ctx *c, const mind_audit_box *ego, double ex
                     (long)(i % tr.n_agents));
     }
   }
-  if ((long)n_cand * Mtot > AU_PLAN_MAX_ROWS) return fail(c, MIND_EINVAL, "%s: %d candidates x %ld nodes > %ld rows supported", who, n_cand, Mtot, AU_PLAN_MAX_ROWS);
   if (n_cand > 0 && Mtot > 0 && !xs) return fail(c, MIND_EINVAL, "%s: null xs", who);
-  int rc;
   if ((rc = au_busy(c, who))) return rc;
   if (n_cand == 0 || Mtot == 0) return MIND_OK;
 
-  // the arena: inputs (node / tree tables, prob, mean, cov, xs), then outputs
+  // the arena: the image (tree table, prob, node table, mean, cov), xs, then the outputs.  A tree without exo agents (n_agents == 1) leaves
+  // its mean / cov rows of the image zero: k_audit_plan reads no agent of such a node
   const size_t R = (size_t)n_cand * (size_t)Mtot, RT = (size_t)n_cand * (size_t)n_trees;
-  size_t top = 0;
-  const size_t o_nodes = au_take(top, Mtot, sizeof(AuNode)), o_trees = au_take(top, n_trees, sizeof(AuTree)), o_prob = au_take(top, Mtot, sizeof(float)),
-               o_mean = au_take(top, (size_t)Atot * 2, sizeof(float)), o_cov = au_take(top, Atot, sizeof(float));
-  const size_t n_img = top;
-  const size_t o_xs = au_take(top, R * 6, sizeof(double)), o_clear = au_take(top, R, sizeof(double)), o_agent = au_take(top, R, sizeof(int)),
-               o_tmin = au_take(top, RT, sizeof(double)), o_tmass = au_take(top, RT, sizeof(double)), o_tnode = au_take(top, RT, sizeof(int)),
-               o_tagent = au_take(top, RT, sizeof(int)), o_thits = au_take(top, RT, sizeof(int)), o_tfirst = au_take(top, RT, sizeof(int));
-  std::vector<char> img(n_img, 0);
+  const auto f_nodes = ar.take<AuNode>(Mtot);
+  const auto f_mean = ar.take<float>((size_t)Atot * 2), f_cov = ar.take<float>(Atot);
+  img.resize(ar.top, 0);
+  const auto f_xs = ar.take<double>(R * 6), f_clear = ar.take<double>(R);
+  const auto f_agent = ar.take<int>(R);
+  const auto f_tmin = ar.take<double>(RT), f_tmass = ar.take<double>(RT);
+  const auto f_tnode = ar.take<int>(RT), f_tagent = ar.take<int>(RT), f_thits = ar.take<int>(RT), f_tfirst = ar.take<int>(RT);
   {
-    AuNode *hn = (AuNode *)(img.data() + o_nodes);
-    AuTree *ht = (AuTree *)(img.data() + o_trees);
     long moff = 0, aoff = 0;
     for (int t = 0; t < n_trees; ++t) {
       const mind_cost_tree &tr = trees[t];
       const size_t M = tr.n_nodes, a = tr.n_agents;
-      ht[t] = AuTree{(int)moff, tr.n_nodes};
-      for (size_t i = 0; i < M; ++i) hn[moff + i] = AuNode{(int)(aoff + (long)(i * a)), tr.n_agents};
-      memcpy(img.data() + o_prob + moff * sizeof(float), tr.prob, M * sizeof(float));
+      for (size_t i = 0; i < M; ++i) f_nodes.at(img.data())[moff + i] = AuNode{(int)(aoff + (long)(i * a)), tr.n_agents};
       if (a > 1) {
-        memcpy(img.data() + o_mean + (size_t)aoff * 2 * sizeof(float), tr.agent_mean, M * a * 2 * sizeof(float));
-        memcpy(img.data() + o_cov + (size_t)aoff * sizeof(float), tr.agent_cov, M * a * sizeof(float));
+        std::copy_n(tr.agent_mean, M * a * 2, f_mean.at(img.data()) + aoff * 2);
+        std::copy_n(tr.agent_cov, M * a, f_cov.at(img.data()) + aoff);
       }
       moff += (long)M; aoff += (long)(M * a);
     }
   }
-  HIPCHK(c, hipSetDevice(c->device));
-  if ((rc = ensure(c, c->audit_dev, top))) return rc;
-  char *d = (char *)c->audit_dev.p;
+  char *d;
+  if ((rc = ar_begin(c, ar, &d))) return rc;
   hipStream_t s = c->stream;
-  HIPCHK(c, hipMemcpyAsync(d, img.data(), n_img, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(d + o_xs, xs, R * 6 * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(d, img.data(), img.size(), hipMemcpyHostToDevice, s));
+  if ((rc = ar_put(c, d, f_xs, xs))) return rc;
   const AuBox eb{ego->length, ego->width, ego->center_offset};
   hipLaunchKernelGGL(k_audit_plan, dim3((unsigned)((Mtot + AU_NB - 1) / AU_NB), (unsigned)((n_cand + AU_CB - 1) / AU_CB)), dim3(AU_CB), 0, s, eb, exo_margin,
-                     (int)Mtot, n_cand, (const AuNode *)(d + o_nodes), (const float *)(d + o_mean), (const float *)(d + o_cov), (const double *)(d + o_xs),
-                     (double *)(d + o_clear), (int *)(d + o_agent));
+                     (int)Mtot, n_cand, f_nodes.at(d), f_mean.at(d), f_cov.at(d), f_xs.at(d), f_clear.at(d), f_agent.at(d));
   HIPCHK(c, hipGetLastError());
-  hipLaunchKernelGGL(k_audit_plan_trees, dim3((unsigned)((RT + 255) / 256)), dim3(256), 0, s, (int)Mtot, n_cand, n_trees, (const AuTree *)(d + o_trees),
-                     (const float *)(d + o_prob), (const double *)(d + o_clear), (const int *)(d + o_agent), (double *)(d + o_tmin), (int *)(d + o_tnode),
-                     (int *)(d + o_tagent), (int *)(d + o_thits), (int *)(d + o_tfirst), (double *)(d + o_tmass));
+  hipLaunchKernelGGL(k_audit_plan_trees, dim3((unsigned)((RT + 255) / 256)), dim3(256), 0, s, (int)Mtot, n_cand, n_trees, pt.trees.at(d), pt.prob.at(d),
+                     f_clear.at(d), f_agent.at(d), f_tmin.at(d), f_tnode.at(d), f_tagent.at(d), f_thits.at(d), f_tfirst.at(d), f_tmass.at(d));
   HIPCHK(c, hipGetLastError());
-  const struct { void *h; size_t o, bytes; } back[8] = {
-      {out->node_clear, o_clear, R * sizeof(double)}, {out->node_agent, o_agent, R * sizeof(int)}, {out->tree_min, o_tmin, RT * sizeof(double)},
-      {out->tree_node, o_tnode, RT * sizeof(int)},    {out->tree_agent, o_tagent, RT * sizeof(int)}, {out->tree_hits, o_thits, RT * sizeof(int)},
-      {out->tree_first, o_tfirst, RT * sizeof(int)},  {out->tree_mass, o_tmass, RT * sizeof(double)}};
-  for (const auto &b : back)
-    if (b.h) HIPCHK(c, hipMemcpyAsync(b.h, d + b.o, b.bytes, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  return MIND_OK;
+  return ar_finish(c, d, {{out->node_clear, f_clear}, {out->node_agent, f_agent}, {out->tree_min, f_tmin}, {out->tree_node, f_tnode},
+                          {out->tree_agent, f_tagent}, {out->tree_hits, f_thits}, {out->tree_first, f_tfirst}, {out->tree_mass, f_tmass}});
 }
 
 extern "C" int mind_audit_episode(mind_ctx *c, const mind_audit_box *ego, int n_ego, int n_steps, int n_tracks, const double *ego_states, const double *exo,
@@ -150,37 +182,28 @@ extern "C" int mind_audit_episode(mind_ctx *c, const mind_audit_box *ego, int n_
   if (R == 0) return MIND_OK;
 
   const size_t ne = (size_t)n_ego;
-  size_t top = 0;
-  const size_t o_ego = au_take(top, R * 4, sizeof(double)), o_exo = au_take(top, RS * 5, sizeof(double)), o_box = au_take(top, (size_t)n_tracks * 2, sizeof(double)),
-               o_val = au_take(top, RS, 1), o_clear = au_take(top, R, sizeof(double)), o_track = au_take(top, R, sizeof(int)),
-               o_emin = au_take(top, ne, sizeof(double)), o_estep = au_take(top, ne, sizeof(int)), o_etrack = au_take(top, ne, sizeof(int)),
-               o_ehits = au_take(top, ne, sizeof(int)), o_efirst = au_take(top, ne, sizeof(int));
-  HIPCHK(c, hipSetDevice(c->device));
-  if ((rc = ensure(c, c->audit_dev, top))) return rc;
-  char *d = (char *)c->audit_dev.p;
+  Arena ar;
+  const auto f_ego = ar.take<double>(R * 4), f_exo = ar.take<double>(RS * 5), f_box = ar.take<double>((size_t)n_tracks * 2);
+  const auto f_val = ar.take<uint8_t>(RS);
+  const auto f_clear = ar.take<double>(R);
+  const auto f_track = ar.take<int>(R);
+  const auto f_emin = ar.take<double>(ne);
+  const auto f_estep = ar.take<int>(ne), f_etrack = ar.take<int>(ne), f_ehits = ar.take<int>(ne), f_efirst = ar.take<int>(ne);
+  char *d;
+  if ((rc = ar_begin(c, ar, &d))) return rc;
   hipStream_t s = c->stream;
-  HIPCHK(c, hipMemcpyAsync(d + o_ego, ego_states, R * 4 * sizeof(double), hipMemcpyHostToDevice, s));
-  if (n_tracks > 1) {
-    HIPCHK(c, hipMemcpyAsync(d + o_exo, exo, RS * 5 * sizeof(double), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d + o_box, boxes, (size_t)n_tracks * 2 * sizeof(double), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d + o_val, valid, RS, hipMemcpyHostToDevice, s));
-  }
+  if ((rc = ar_put(c, d, f_ego, ego_states))) return rc;
+  // without a track beside the ego's row the scene is not uploaded: k_audit_episode's loop over the tracks 1..n-1 reads none of it
+  if (n_tracks > 1 && ((rc = ar_put(c, d, f_exo, exo)) || (rc = ar_put(c, d, f_box, boxes)) || (rc = ar_put(c, d, f_val, valid)))) return rc;
   const AuBox eb{ego->length, ego->width, ego->center_offset};
   hipLaunchKernelGGL(k_audit_episode, dim3((unsigned)n_steps, (unsigned)((n_ego + AU_EB - 1) / AU_EB)), dim3(AU_EB), 0, s, eb, n_ego, n_steps, n_tracks,
-                     (const double *)(d + o_ego), (const double *)(d + o_exo), (const unsigned char *)(d + o_val), (const double *)(d + o_box),
-                     (double *)(d + o_clear), (int *)(d + o_track));
+                     f_ego.at(d), f_exo.at(d), f_val.at(d), f_box.at(d), f_clear.at(d), f_track.at(d));
   HIPCHK(c, hipGetLastError());
-  hipLaunchKernelGGL(k_audit_episode_egos, dim3((unsigned)((n_ego + 63) / 64)), dim3(64), 0, s, n_ego, n_steps, (const double *)(d + o_clear),
-                     (const int *)(d + o_track), (double *)(d + o_emin), (int *)(d + o_estep), (int *)(d + o_etrack), (int *)(d + o_ehits), (int *)(d + o_efirst));
+  hipLaunchKernelGGL(k_audit_episode_egos<false>, dim3((unsigned)((n_ego + 63) / 64)), dim3(64), 0, s, n_ego, n_steps, f_clear.at(d), f_track.at(d),
+                     f_emin.at(d), f_estep.at(d), f_etrack.at(d), f_ehits.at(d), f_efirst.at(d));
   HIPCHK(c, hipGetLastError());
-  const struct { void *h; size_t o, bytes; } back[7] = {
-      {out->step_clear, o_clear, R * sizeof(double)}, {out->step_track, o_track, R * sizeof(int)},  {out->ego_min, o_emin, ne * sizeof(double)},
-      {out->ego_step, o_estep, ne * sizeof(int)},     {out->ego_track, o_etrack, ne * sizeof(int)}, {out->ego_hits, o_ehits, ne * sizeof(int)},
-      {out->ego_first, o_efirst, ne * sizeof(int)}};
-  for (const auto &b : back)
-    if (b.h) HIPCHK(c, hipMemcpyAsync(b.h, d + b.o, b.bytes, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  return MIND_OK;
+  return ar_finish(c, d, {{out->step_clear, f_clear}, {out->step_track, f_track}, {out->ego_min, f_emin}, {out->ego_step, f_estep},
+                          {out->ego_track, f_etrack}, {out->ego_hits, f_ehits}, {out->ego_first, f_efirst}});
 }
 
 extern "C" int mind_debug_box_clearance(int kind, int n, const double *a, const double *b, const double *trig, double *out) {

@@ -83,12 +83,14 @@ __global__ __launch_bounds__(AU_CB) void k_audit_plan(AuBox ego, double exo_marg
   }
 }
 
-// per (candidate, tree): the minimum clearance with its node and agent (the lowest key wins ties), n_hit, first_hit, hit_mass.  A tree holding a
-// NaN node reports min = NaN, node = the lowest such key, agent = -1, n_hit = -1, first_hit = -1, hit_mass = NaN.
+// per (candidate, tree), for both audits -- mind_audit_plan folds (node_clear, node_agent), mind_audit_road_plan (node_margin, node_corner):
+// the minimum value with its node and that node's tag (the lowest key wins ties), the nodes below zero (hits), the first of them and
+// their probability mass.  A tree holding a NaN node reports min = NaN, node = the lowest such key, tag = -1, hits = -1, first = -1,
+// mass = NaN.
 __global__ __launch_bounds__(256) void k_audit_plan_trees(int Mtot, int n_cand, int n_trees, const AuTree *__restrict__ trees,
-                                                          const float *__restrict__ prob, const double *__restrict__ node_clear,
-                                                          const int *__restrict__ node_agent, double *__restrict__ tree_min,
-                                                          int *__restrict__ tree_node, int *__restrict__ tree_agent, int *__restrict__ tree_hits,
+                                                          const float *__restrict__ prob, const double *__restrict__ node_val,
+                                                          const int *__restrict__ node_tag, double *__restrict__ tree_min,
+                                                          int *__restrict__ tree_node, int *__restrict__ tree_tag, int *__restrict__ tree_hits,
                                                           int *__restrict__ tree_first, double *__restrict__ tree_mass) {
   const long e = (long)blockIdx.x * 256 + threadIdx.x;
   if (e >= (long)n_cand * n_trees) return;
@@ -96,19 +98,19 @@ __global__ __launch_bounds__(256) void k_audit_plan_trees(int Mtot, int n_cand, 
   const AuTree T = trees[t];
   const size_t row = (size_t)c * (size_t)Mtot + (size_t)T.moff;
   double mn = INFINITY, mass = 0.0;
-  int mi = -1, ma = -1, hits = 0, first = -1, bad = -1;
+  int mi = -1, mt = -1, hits = 0, first = -1, bad = -1;
   for (int i = 0; i < T.M; ++i) {
-    const double d = node_clear[row + i];
+    const double d = node_val[row + i];
     if (d != d) { bad = i; break; }
-    if (i == 0 || d < mn) { mn = d; mi = i; ma = node_agent[row + i]; }
+    if (i == 0 || d < mn) { mn = d; mi = i; mt = node_tag[row + i]; }
     if (d < 0.0) {
       if (first < 0) first = i;
       ++hits;
       mass += (double)prob[T.moff + i];
     }
   }
-  if (bad >= 0) { mn = NAN; mi = bad; ma = -1; hits = -1; first = -1; mass = NAN; }
-  tree_min[e] = mn; tree_node[e] = mi; tree_agent[e] = ma; tree_hits[e] = hits; tree_first[e] = first; tree_mass[e] = mass;
+  if (bad >= 0) { mn = NAN; mi = bad; mt = -1; hits = -1; first = -1; mass = NAN; }
+  tree_min[e] = mn; tree_node[e] = mi; tree_tag[e] = mt; tree_hits[e] = hits; tree_first[e] = first; tree_mass[e] = mass;
 }
 
 __global__ __launch_bounds__(AU_EB) void k_audit_episode(AuBox ego, int n_ego, int S, int n, const double *__restrict__ ego_states,
@@ -151,22 +153,31 @@ __global__ __launch_bounds__(AU_EB) void k_audit_episode(AuBox ego, int n_ego, i
   if (act) { step_clear[row] = best; step_track[row] = bj; }
 }
 
-// per ego: the minimum over the steps with its step and track (the lowest step wins ties), the number of hit steps and the first of them
-__global__ __launch_bounds__(64) void k_audit_episode_egos(int n_ego, int S, const double *__restrict__ step_clear, const int *__restrict__ step_track,
-                                                           double *__restrict__ ego_min, int *__restrict__ ego_step, int *__restrict__ ego_track,
+// per ego, for both audits -- mind_audit_episode folds (step_clear, step_track), mind_audit_road_episode (step_margin, step_corner): the
+// minimum value over the steps with its step and that step's tag (the lowest step wins ties), the steps below zero (hits) and the first of
+// them.  NAN_STEP (the road audit, whose boxes report NaN for a non-finite state row): a trace holding a NaN step reports min = NaN,
+// step = the first such step, tag = -1, hits = -1, first = -1.  Without it (the clearance audit, whose host entry admits finite inputs
+// only) a NaN is compared like any value: at step 0 it stays the minimum, at a later step it is passed over.
+template <bool NAN_STEP>
+__global__ __launch_bounds__(64) void k_audit_episode_egos(int n_ego, int S, const double *__restrict__ step_val, const int *__restrict__ step_tag,
+                                                           double *__restrict__ ego_min, int *__restrict__ ego_step, int *__restrict__ ego_tag,
                                                            int *__restrict__ ego_hits, int *__restrict__ ego_first) {
   const int g = blockIdx.x * 64 + threadIdx.x;
   if (g >= n_ego) return;
   const size_t row = (size_t)g * (size_t)S;
   double mn = INFINITY;
-  int ms = -1, mt = -1, hits = 0, first = -1;
+  int ms = -1, mt = -1, hits = 0, first = -1, bad = -1;
   for (int s = 0; s < S; ++s) {
-    const double d = step_clear[row + s];
-    if (s == 0 || d < mn) { mn = d; ms = s; mt = step_track[row + s]; }
+    const double d = step_val[row + s];
+    if constexpr (NAN_STEP)
+      if (d != d) { bad = s; break; }
+    if (s == 0 || d < mn) { mn = d; ms = s; mt = step_tag[row + s]; }
     if (d < 0.0) {
       if (first < 0) first = s;
       ++hits;
     }
   }
-  ego_min[g] = mn; ego_step[g] = ms; ego_track[g] = mt; ego_hits[g] = hits; ego_first[g] = first;
+  if constexpr (NAN_STEP)
+    if (bad >= 0) { mn = NAN; ms = bad; mt = -1; hits = -1; first = -1; }
+  ego_min[g] = mn; ego_step[g] = ms; ego_tag[g] = mt; ego_hits[g] = hits; ego_first[g] = first;
 }

@@ -1,5 +1,5 @@
 // Host side of the forecast scoring (kernels: forecast_kernels.hip; definitions: forecast_score.h): mind_forecast_score and the host-only
-// mind_debug_forecast_score.  The device call is synchronous on the context's stream and keeps its scratch in c->forecast_dev.
+// mind_debug_forecast_score.  The device call is synchronous on the context's stream and runs on the scaffold of audit_host.hip.
 // Included by mind_hip.hip behind audit_host.hip.
 #pragma clang fp contract(off)
 
@@ -60,48 +60,40 @@ extern "C" int mind_forecast_score(mind_ctx *c, const mind_forecast_cfg *cfg, in
   std::vector<int32_t> scene_of(A);
   for (size_t b = 0; b < B; ++b)
     for (int32_t a = actor_off[b]; a < actor_off[b + 1]; ++a) scene_of[a] = (int32_t)b;
-  // the arena: inputs (gt, valid, scored, scene_of, actor_off), then outputs
-  size_t top = 0;
-  const size_t o_gt = au_take(top, A * T * 2, sizeof(double)), o_val = au_take(top, A * T, 1), o_sc = au_take(top, A, 1), o_so = au_take(top, A, sizeof(int)),
-               o_off = au_take(top, B + 1, sizeof(int));
-  const size_t o_ade = au_take(top, A * H * K, sizeof(double)), o_fde = au_take(top, A * H * K, sizeof(double)), o_cov = au_take(top, A * H * K, sizeof(int)),
-               o_fo = au_take(top, A * H * K, sizeof(int)), o_nv = au_take(top, A * H, sizeof(int)), o_last = au_take(top, A * H, sizeof(int)),
-               o_ka = au_take(top, A * H, sizeof(int)), o_kf = au_take(top, A * H, sizeof(int)), o_br = au_take(top, A * H, sizeof(double));
-  const size_t o_sn = au_take(top, B * H, sizeof(int)), o_sa = au_take(top, B * H * K, sizeof(double)), o_sf = au_take(top, B * H * K, sizeof(double)),
-               o_ska = au_take(top, B * H, sizeof(int)), o_skf = au_take(top, B * H, sizeof(int)), o_skt = au_take(top, B * H, sizeof(int)),
-               o_sbr = au_take(top, B * H, sizeof(double)), o_smr = au_take(top, B * H, sizeof(double)), o_smt = au_take(top, B * H, sizeof(double));
-  HIPCHK(c, hipSetDevice(c->device));
-  if ((rc = ensure(c, c->forecast_dev, top))) return rc;
-  char *d = (char *)c->forecast_dev.p;
+  // the arena: inputs (gt, valid, scored, scene_of, actor_off), then outputs.  Without `scored` its field is not uploaded, and
+  // k_forecast_scenes gets a null pointer for it: nothing reads what an earlier call left there
+  Arena ar;
+  const auto f_gt = ar.take<double>(A * T * 2);
+  const auto f_val = ar.take<uint8_t>(A * T), f_sc = ar.take<uint8_t>(A);
+  const auto f_so = ar.take<int>(A), f_off = ar.take<int>(B + 1);
+  const auto f_ade = ar.take<double>(A * H * K), f_fde = ar.take<double>(A * H * K);
+  const auto f_cov = ar.take<int>(A * H * K), f_fo = ar.take<int>(A * H * K), f_nv = ar.take<int>(A * H), f_last = ar.take<int>(A * H),
+             f_ka = ar.take<int>(A * H), f_kf = ar.take<int>(A * H);
+  const auto f_br = ar.take<double>(A * H);
+  const auto f_sn = ar.take<int>(B * H);
+  const auto f_sa = ar.take<double>(B * H * K), f_sf = ar.take<double>(B * H * K);
+  const auto f_ska = ar.take<int>(B * H), f_skf = ar.take<int>(B * H), f_skt = ar.take<int>(B * H);
+  const auto f_sbr = ar.take<double>(B * H), f_smr = ar.take<double>(B * H), f_smt = ar.take<double>(B * H);
+  char *d;
+  if ((rc = ar_begin(c, ar, &d))) return rc;
   hipStream_t s = c->stream;
-  HIPCHK(c, hipMemcpyAsync(d + o_gt, gt, A * T * 2 * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(d + o_val, valid, A * T, hipMemcpyHostToDevice, s));
-  if (scored) HIPCHK(c, hipMemcpyAsync(d + o_sc, scored, A, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(d + o_so, scene_of.data(), A * sizeof(int), hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(d + o_off, actor_off, (B + 1) * sizeof(int), hipMemcpyHostToDevice, s));
+  if ((rc = ar_put(c, d, f_gt, gt)) || (rc = ar_put(c, d, f_val, valid)) || (scored && (rc = ar_put(c, d, f_sc, scored))) ||
+      (rc = ar_put(c, d, f_so, scene_of.data())) || (rc = ar_put(c, d, f_off, actor_off)))
+    return rc;
   const int nb = fc_block(fc.K, fc.T);
   const FcLay L = fc_layout(fc.K, fc.T, nb);
   const int wide = (K * T) % 4 == 0 && ((uintptr_t)reg % 16) == 0;
-  hipLaunchKernelGGL(k_forecast_modes, dim3((unsigned)((A + nb - 1) / nb)), dim3(FC_THREADS), L.bytes, s, fc, (int)A, nb, wide, reg, cls, (const double *)(d + o_gt),
-                     (const unsigned char *)(d + o_val), (const int *)(d + o_so), (double *)(d + o_ade), (double *)(d + o_fde), (int *)(d + o_cov),
-                     (int *)(d + o_fo), (int *)(d + o_nv), (int *)(d + o_last), (int *)(d + o_ka), (int *)(d + o_kf), (double *)(d + o_br));
+  hipLaunchKernelGGL(k_forecast_modes, dim3((unsigned)((A + nb - 1) / nb)), dim3(FC_THREADS), L.bytes, s, fc, (int)A, nb, wide, reg, cls, f_gt.at(d), f_val.at(d),
+                     f_so.at(d), f_ade.at(d), f_fde.at(d), f_cov.at(d), f_fo.at(d), f_nv.at(d), f_last.at(d), f_ka.at(d), f_kf.at(d), f_br.at(d));
   HIPCHK(c, hipGetLastError());
-  hipLaunchKernelGGL(k_forecast_scenes, dim3((unsigned)((B * H + FC_SB - 1) / FC_SB)), dim3(FC_SB), 0, s, fc, n_scenes, (const int *)(d + o_off), cls,
-                     scored ? (const unsigned char *)(d + o_sc) : (const unsigned char *)nullptr, (const double *)(d + o_ade), (const double *)(d + o_fde),
-                     (const int *)(d + o_nv), (int *)(d + o_sn), (double *)(d + o_sa), (double *)(d + o_sf), (int *)(d + o_ska), (int *)(d + o_skf),
-                     (int *)(d + o_skt), (double *)(d + o_sbr), (double *)(d + o_smr), (double *)(d + o_smt));
+  hipLaunchKernelGGL(k_forecast_scenes, dim3((unsigned)((B * H + FC_SB - 1) / FC_SB)), dim3(FC_SB), 0, s, fc, n_scenes, f_off.at(d), cls,
+                     scored ? f_sc.at(d) : nullptr, f_ade.at(d), f_fde.at(d), f_nv.at(d), f_sn.at(d), f_sa.at(d), f_sf.at(d), f_ska.at(d), f_skf.at(d),
+                     f_skt.at(d), f_sbr.at(d), f_smr.at(d), f_smt.at(d));
   HIPCHK(c, hipGetLastError());
-  const struct { void *h; size_t o, bytes; } back[18] = {
-      {out->ade, o_ade, A * H * K * sizeof(double)},   {out->fde, o_fde, A * H * K * sizeof(double)},   {out->cover, o_cov, A * H * K * sizeof(int)},
-      {out->first_out, o_fo, A * H * K * sizeof(int)}, {out->n_valid, o_nv, A * H * sizeof(int)},       {out->last, o_last, A * H * sizeof(int)},
-      {out->k_ade, o_ka, A * H * sizeof(int)},         {out->k_fde, o_kf, A * H * sizeof(int)},         {out->brier_fde, o_br, A * H * sizeof(double)},
-      {out->s_n_scored, o_sn, B * H * sizeof(int)},    {out->s_ade, o_sa, B * H * K * sizeof(double)},  {out->s_fde, o_sf, B * H * K * sizeof(double)},
-      {out->s_k_ade, o_ska, B * H * sizeof(int)},      {out->s_k_fde, o_skf, B * H * sizeof(int)},      {out->s_k_top, o_skt, B * H * sizeof(int)},
-      {out->s_brier_fde, o_sbr, B * H * sizeof(double)}, {out->s_miss_rate, o_smr, B * H * sizeof(double)}, {out->s_miss_top, o_smt, B * H * sizeof(double)}};
-  for (const auto &b : back)
-    if (b.h) HIPCHK(c, hipMemcpyAsync(b.h, d + b.o, b.bytes, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  return MIND_OK;
+  return ar_finish(c, d, {{out->ade, f_ade}, {out->fde, f_fde}, {out->cover, f_cov}, {out->first_out, f_fo}, {out->n_valid, f_nv}, {out->last, f_last},
+                          {out->k_ade, f_ka}, {out->k_fde, f_kf}, {out->brier_fde, f_br}, {out->s_n_scored, f_sn}, {out->s_ade, f_sa}, {out->s_fde, f_sf},
+                          {out->s_k_ade, f_ska}, {out->s_k_fde, f_skf}, {out->s_k_top, f_skt}, {out->s_brier_fde, f_sbr}, {out->s_miss_rate, f_smr},
+                          {out->s_miss_top, f_smt}});
 }
 
 // forecast_score.h on the CPU: the same passes, agent after agent
@@ -143,17 +135,10 @@ extern "C" int mind_debug_forecast_score(const mind_forecast_cfg *cfg, int n_sce
     fs_scene_pass(&fc, (int)(e % H), actor_off[sb], actor_off[sb + 1], ade.data(), fde.data(), n_valid.data(), scored, cls + sb * K, &s_n[e], s_ade.data() + e * K,
                   s_fde.data() + e * K, &s_ka[e], &s_kf[e], &s_kt[e], &s_br[e], &s_mr[e], &s_mt[e]);
   }
-  const struct { void *h; const void *src; size_t bytes; } back[18] = {
-      {out->ade, ade.data(), A * H * K * sizeof(double)},      {out->fde, fde.data(), A * H * K * sizeof(double)},
-      {out->cover, cover.data(), A * H * K * sizeof(int)},     {out->first_out, first_out.data(), A * H * K * sizeof(int)},
-      {out->n_valid, n_valid.data(), A * H * sizeof(int)},     {out->last, last.data(), A * H * sizeof(int)},
-      {out->k_ade, k_ade.data(), A * H * sizeof(int)},         {out->k_fde, k_fde.data(), A * H * sizeof(int)},
-      {out->brier_fde, brier.data(), A * H * sizeof(double)},  {out->s_n_scored, s_n.data(), B * H * sizeof(int)},
-      {out->s_ade, s_ade.data(), B * H * K * sizeof(double)},  {out->s_fde, s_fde.data(), B * H * K * sizeof(double)},
-      {out->s_k_ade, s_ka.data(), B * H * sizeof(int)},        {out->s_k_fde, s_kf.data(), B * H * sizeof(int)},
-      {out->s_k_top, s_kt.data(), B * H * sizeof(int)},        {out->s_brier_fde, s_br.data(), B * H * sizeof(double)},
-      {out->s_miss_rate, s_mr.data(), B * H * sizeof(double)}, {out->s_miss_top, s_mt.data(), B * H * sizeof(double)}};
-  for (const auto &r : back)
-    if (r.h) memcpy(r.h, r.src, r.bytes);
+  const auto give = [](auto *h, const auto &v) { if (h) std::copy(v.begin(), v.end(), h); };      // (every output is optional)
+  give(out->ade, ade); give(out->fde, fde); give(out->cover, cover); give(out->first_out, first_out); give(out->n_valid, n_valid); give(out->last, last);
+  give(out->k_ade, k_ade); give(out->k_fde, k_fde); give(out->brier_fde, brier); give(out->s_n_scored, s_n); give(out->s_ade, s_ade); give(out->s_fde, s_fde);
+  give(out->s_k_ade, s_ka); give(out->s_k_fde, s_kf); give(out->s_k_top, s_kt); give(out->s_brier_fde, s_br); give(out->s_miss_rate, s_mr);
+  give(out->s_miss_top, s_mt);
   return MIND_OK;
 }

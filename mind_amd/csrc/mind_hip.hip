@@ -38,6 +38,7 @@
 #include "pred_choice.h"
 #include "ilqr_choice.h"
 #include "aime_book.h"
+#include "audit_arena.h"
 #include "weight_pack.h"
 #include "aime_kernels.hip"
 
@@ -152,9 +153,10 @@ struct mind_ctx {
       rows, rpe_ptrs;
   // ilqr workspaces
   DevBuf ilqr_dev, aime_dev, rebase_dev2[2], dec_h2;
-  DevBuf audit_dev;     // scratch of mind_audit_plan / mind_audit_episode (audit_host.hip)
-  DevBuf forecast_dev;  // scratch of mind_forecast_score (forecast_host.hip)
-  DevBuf road_dev;      // scratch of mind_audit_road_plan / mind_audit_road_episode (road_host.hip)
+  // scratch of the two clearance audits, the two road audits and mind_forecast_score (ar_begin, audit_host.hip).  One buffer serves all five:
+  // each is synchronous on the context's stream and refuses a busy context, so a call never sees another call's scratch in flight -- and
+  // each uploads every input its kernels read, so none relies on what an earlier call left
+  DevBuf audit_dev;
   // mind_aime_plan (aime_plan.hip): device arenas, page-locked staging (uploads / read-backs are true async copies: a pageable
   // source makes hipMemcpyAsync wait for the stream to drain first), host result tables
   DevBuf pl_root, pl_in[2], pl_lf, pl_lrep, pl_pred, pl_small, pl_tab[2], pl_win[2];
@@ -412,7 +414,7 @@ extern "C" int mind_ctx_destroy(mind_ctx *c) {
   (void)hipStreamSynchronize(c->stream);
   DevBuf *bufs[] = {&c->edge, &c->x, &c->ST, &c->QK, &c->part, &c->tokpos, &c->meta, &c->jobs, &c->actor_feat,
                     &c->lane_feat, &c->tgt_feat, &c->cmode, &c->tgt_emb, &c->rows, &c->rpe_ptrs, &c->ilqr_dev, &c->aime_dev, &c->rebase_dev2[0], &c->rebase_dev2[1], &c->dec_h2,
-                    &c->curve_tab, &c->audit_dev, &c->forecast_dev, &c->road_dev};
+                    &c->curve_tab, &c->audit_dev};
   for (DevBuf *b : bufs)
     if (b->p) (void)hipFree(b->p);
   for (TableSet &t : c->tabs)

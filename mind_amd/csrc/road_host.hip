@@ -1,12 +1,10 @@
 // Host side of the road audit (kernels: road_kernels.hip; geometry: road_geom.h): mind_audit_road_plan, mind_audit_road_episode and the
-// host-only mind_debug_road_margin.  Both device calls are synchronous on the context's stream and keep their scratch in c->road_dev.
-// Included by mind_hip.hip behind forecast_host.hip (au_host::mind_sincos, au_fin, au_box_ok, au_busy, au_take: audit_host.hip).
+// host-only mind_debug_road_margin.  Both device calls are synchronous on the context's stream and run on the scaffold of audit_host.hip.
+// Included by mind_hip.hip behind forecast_host.hip (au_host::mind_sincos, au_fin, au_box_ok, au_busy, au_plan_trees, ar_*: audit_host.hip).
 #pragma clang fp contract(off)
 
 #define RD_MAX_VERTS (1 << 20)            // vertices of a road (16 MB)
 #define RD_MAX_RINGS (1 << 16)            // rings of a road
-#define RD_PLAN_MAX_ROWS (1L << 20)       // n_cand x sum M a plan audit admits, as mind_audit_plan
-#define RD_EPISODE_MAX_ROWS (1L << 22)    // n_ego x n_steps an episode audit admits, as mind_audit_episode
 
 // the road's own rules; `c` may be null (the host entry): then only the code is returned
 static int rd_road_ok(mind_ctx *c, const char *who, const double *verts, const int32_t *poly_off, int P) {
@@ -27,20 +25,18 @@ static int rd_road_ok(mind_ctx *c, const char *who, const double *verts, const i
 }
 
 // the road in the arena: verts, then poly_off with one entry more (V once again: k_road_boxes reads one bound past the last ring)
-struct RdRoadAt { size_t o_verts, o_off; int V; };
-static RdRoadAt rd_road_take(size_t &top, const int32_t *poly_off, int P) {
-  RdRoadAt a;
-  a.V = poly_off[P];
-  a.o_verts = au_take(top, (size_t)a.V * 2, sizeof(double));
-  a.o_off = au_take(top, (size_t)P + 2, sizeof(int));
-  return a;
+struct RdRoad { ArField<double> verts; ArField<int> off; int V; std::vector<int> off2; };
+static void rd_road_take(Arena &ar, RdRoad &r, const int32_t *poly_off, int P) {
+  r.V = poly_off[P];
+  r.verts = ar.take<double>((size_t)r.V * 2);
+  r.off = ar.take<int>((size_t)P + 2);
+  r.off2.assign(poly_off, poly_off + P + 1);
+  r.off2.push_back(r.V);
 }
-static int rd_road_upload(mind_ctx *c, char *d, const RdRoadAt &a, const double *verts, const int32_t *poly_off, int P, std::vector<int> &off2) {
-  off2.assign(poly_off, poly_off + P + 1);
-  off2.push_back(a.V);
-  HIPCHK(c, hipMemcpyAsync(d + a.o_verts, verts, (size_t)a.V * 2 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d + a.o_off, off2.data(), off2.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  return MIND_OK;
+static int rd_road_upload(mind_ctx *c, char *d, const RdRoad &r, const double *verts) {
+  int rc;
+  if ((rc = ar_put(c, d, r.verts, verts))) return rc;
+  return ar_put(c, d, r.off, r.off2.data());
 }
 
 extern "C" int mind_audit_road_plan(mind_ctx *c, const mind_audit_box *ego, const double *verts, const int32_t *poly_off, int n_rings,
@@ -54,62 +50,37 @@ extern "C" int mind_audit_road_plan(mind_ctx *c, const mind_audit_box *ego, cons
   if (!out->node_margin && !out->node_corner && !out->node_ring && !out->node_edge && !out->tree_min && !out->tree_node && !out->tree_corner &&
       !out->tree_hits && !out->tree_first && !out->tree_mass)
     return fail(c, MIND_EINVAL, "%s: every output is null", who);
-  long Mtot = 0;
-  for (int t = 0; t < n_trees; ++t) {
-    if (trees[t].n_nodes <= 0 || !trees[t].prob) return fail(c, MIND_EINVAL, "%s: tree %d: bad n_nodes or null prob", who, t);
-    Mtot += trees[t].n_nodes;
-    if (Mtot > RD_PLAN_MAX_ROWS) return fail(c, MIND_EINVAL, "%s: more than %ld nodes", who, RD_PLAN_MAX_ROWS);
-  }
-  if ((long)n_cand * Mtot > RD_PLAN_MAX_ROWS) return fail(c, MIND_EINVAL, "%s: %d candidates x %ld nodes > %ld rows supported", who, n_cand, Mtot, RD_PLAN_MAX_ROWS);
+  Arena ar;
+  std::vector<char> img;
+  AuPlanTrees pt;
+  if ((rc = au_plan_trees(c, who, trees, n_trees, n_cand, ar, img, pt))) return rc;
+  const long Mtot = pt.Mtot;
   if (n_cand > 0 && Mtot > 0 && !xs) return fail(c, MIND_EINVAL, "%s: null xs", who);
   if ((rc = au_busy(c, who))) return rc;
   if (n_cand == 0 || Mtot == 0) return MIND_OK;
 
   const size_t R = (size_t)n_cand * (size_t)Mtot, RT = (size_t)n_cand * (size_t)n_trees;
-  size_t top = 0;
-  const size_t o_trees = au_take(top, n_trees, sizeof(AuTree)), o_prob = au_take(top, Mtot, sizeof(float));
-  const size_t n_img = top;
-  const RdRoadAt road = rd_road_take(top, poly_off, n_rings);
-  const size_t o_xs = au_take(top, R * 6, sizeof(double)), o_m = au_take(top, R, sizeof(double)), o_c = au_take(top, R, sizeof(int)),
-               o_r = au_take(top, R, sizeof(int)), o_e = au_take(top, R, sizeof(int)), o_tmin = au_take(top, RT, sizeof(double)),
-               o_tmass = au_take(top, RT, sizeof(double)), o_tnode = au_take(top, RT, sizeof(int)), o_tcorner = au_take(top, RT, sizeof(int)),
-               o_thits = au_take(top, RT, sizeof(int)), o_tfirst = au_take(top, RT, sizeof(int));
-  std::vector<char> img(n_img, 0);
-  {
-    AuTree *ht = (AuTree *)(img.data() + o_trees);
-    long moff = 0;
-    for (int t = 0; t < n_trees; ++t) {
-      ht[t] = AuTree{(int)moff, trees[t].n_nodes};
-      memcpy(img.data() + o_prob + moff * sizeof(float), trees[t].prob, (size_t)trees[t].n_nodes * sizeof(float));
-      moff += trees[t].n_nodes;
-    }
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  if ((rc = ensure(c, c->road_dev, top))) return rc;
-  char *d = (char *)c->road_dev.p;
+  RdRoad road;
+  rd_road_take(ar, road, poly_off, n_rings);
+  const auto f_xs = ar.take<double>(R * 6), f_m = ar.take<double>(R);
+  const auto f_c = ar.take<int>(R), f_r = ar.take<int>(R), f_e = ar.take<int>(R);
+  const auto f_tmin = ar.take<double>(RT), f_tmass = ar.take<double>(RT);
+  const auto f_tnode = ar.take<int>(RT), f_tcorner = ar.take<int>(RT), f_thits = ar.take<int>(RT), f_tfirst = ar.take<int>(RT);
+  char *d;
+  if ((rc = ar_begin(c, ar, &d))) return rc;
   hipStream_t s = c->stream;
-  std::vector<int> off2;
-  HIPCHK(c, hipMemcpyAsync(d, img.data(), n_img, hipMemcpyHostToDevice, s));
-  if ((rc = rd_road_upload(c, d, road, verts, poly_off, n_rings, off2))) return rc;
-  HIPCHK(c, hipMemcpyAsync(d + o_xs, xs, R * 6 * sizeof(double), hipMemcpyHostToDevice, s));
-  const RdBox eb{ego->length, ego->width, ego->center_offset};
-  hipLaunchKernelGGL(k_road_boxes, dim3((unsigned)((R + RD_BB - 1) / RD_BB)), dim3(RD_BB), 0, s, eb, (long)R, (const double *)(d + o_xs), 6, 3,
-                     (const double *)(d + road.o_verts), (const int *)(d + road.o_off), road.V, (double *)(d + o_m), (int *)(d + o_c), (int *)(d + o_r),
-                     (int *)(d + o_e));
+  HIPCHK(c, hipMemcpyAsync(d, img.data(), img.size(), hipMemcpyHostToDevice, s));
+  if ((rc = rd_road_upload(c, d, road, verts)) || (rc = ar_put(c, d, f_xs, xs))) return rc;
+  const AuBox eb{ego->length, ego->width, ego->center_offset};
+  hipLaunchKernelGGL(k_road_boxes, dim3((unsigned)((R + RD_BB - 1) / RD_BB)), dim3(RD_BB), 0, s, eb, (long)R, f_xs.at(d), 6, 3, road.verts.at(d), road.off.at(d),
+                     road.V, f_m.at(d), f_c.at(d), f_r.at(d), f_e.at(d));
   HIPCHK(c, hipGetLastError());
-  hipLaunchKernelGGL(k_road_plan_trees, dim3((unsigned)((RT + 255) / 256)), dim3(256), 0, s, (int)Mtot, n_cand, n_trees, (const AuTree *)(d + o_trees),
-                     (const float *)(d + o_prob), (const double *)(d + o_m), (const int *)(d + o_c), (double *)(d + o_tmin), (int *)(d + o_tnode),
-                     (int *)(d + o_tcorner), (int *)(d + o_thits), (int *)(d + o_tfirst), (double *)(d + o_tmass));
+  hipLaunchKernelGGL(k_audit_plan_trees, dim3((unsigned)((RT + 255) / 256)), dim3(256), 0, s, (int)Mtot, n_cand, n_trees, pt.trees.at(d), pt.prob.at(d),
+                     f_m.at(d), f_c.at(d), f_tmin.at(d), f_tnode.at(d), f_tcorner.at(d), f_thits.at(d), f_tfirst.at(d), f_tmass.at(d));
   HIPCHK(c, hipGetLastError());
-  const struct { void *h; size_t o, bytes; } back[10] = {
-      {out->node_margin, o_m, R * sizeof(double)},   {out->node_corner, o_c, R * sizeof(int)},         {out->node_ring, o_r, R * sizeof(int)},
-      {out->node_edge, o_e, R * sizeof(int)},        {out->tree_min, o_tmin, RT * sizeof(double)},     {out->tree_node, o_tnode, RT * sizeof(int)},
-      {out->tree_corner, o_tcorner, RT * sizeof(int)}, {out->tree_hits, o_thits, RT * sizeof(int)},    {out->tree_first, o_tfirst, RT * sizeof(int)},
-      {out->tree_mass, o_tmass, RT * sizeof(double)}};
-  for (const auto &b : back)
-    if (b.h) HIPCHK(c, hipMemcpyAsync(b.h, d + b.o, b.bytes, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  return MIND_OK;
+  return ar_finish(c, d, {{out->node_margin, f_m}, {out->node_corner, f_c}, {out->node_ring, f_r}, {out->node_edge, f_e}, {out->tree_min, f_tmin},
+                          {out->tree_node, f_tnode}, {out->tree_corner, f_tcorner}, {out->tree_hits, f_thits}, {out->tree_first, f_tfirst},
+                          {out->tree_mass, f_tmass}});
 }
 
 extern "C" int mind_audit_road_episode(mind_ctx *c, const mind_audit_box *ego, const double *verts, const int32_t *poly_off, int n_rings, int n_ego,
@@ -124,40 +95,31 @@ extern "C" int mind_audit_road_episode(mind_ctx *c, const mind_audit_box *ego, c
       !out->ego_hits && !out->ego_first)
     return fail(c, MIND_EINVAL, "%s: every output is null", who);
   const size_t R = (size_t)n_ego * (size_t)n_steps, ne = (size_t)n_ego;
-  if ((long)R > RD_EPISODE_MAX_ROWS) return fail(c, MIND_EINVAL, "%s: %d egos x %d steps > %ld rows supported", who, n_ego, n_steps, RD_EPISODE_MAX_ROWS);
+  if ((long)R > AU_EPISODE_MAX_ROWS) return fail(c, MIND_EINVAL, "%s: %d egos x %d steps > %ld rows supported", who, n_ego, n_steps, AU_EPISODE_MAX_ROWS);
   if (R > 0 && !ego_states) return fail(c, MIND_EINVAL, "%s: null ego_states", who);
   if ((rc = au_busy(c, who))) return rc;
   if (R == 0) return MIND_OK;
 
-  size_t top = 0;
-  const RdRoadAt road = rd_road_take(top, poly_off, n_rings);
-  const size_t o_ego = au_take(top, R * 4, sizeof(double)), o_m = au_take(top, R, sizeof(double)), o_c = au_take(top, R, sizeof(int)),
-               o_r = au_take(top, R, sizeof(int)), o_e = au_take(top, R, sizeof(int)), o_emin = au_take(top, ne, sizeof(double)),
-               o_estep = au_take(top, ne, sizeof(int)), o_ecorner = au_take(top, ne, sizeof(int)), o_ehits = au_take(top, ne, sizeof(int)),
-               o_efirst = au_take(top, ne, sizeof(int));
-  HIPCHK(c, hipSetDevice(c->device));
-  if ((rc = ensure(c, c->road_dev, top))) return rc;
-  char *d = (char *)c->road_dev.p;
+  Arena ar;
+  RdRoad road;
+  rd_road_take(ar, road, poly_off, n_rings);
+  const auto f_ego = ar.take<double>(R * 4), f_m = ar.take<double>(R);
+  const auto f_c = ar.take<int>(R), f_r = ar.take<int>(R), f_e = ar.take<int>(R);
+  const auto f_emin = ar.take<double>(ne);
+  const auto f_estep = ar.take<int>(ne), f_ecorner = ar.take<int>(ne), f_ehits = ar.take<int>(ne), f_efirst = ar.take<int>(ne);
+  char *d;
+  if ((rc = ar_begin(c, ar, &d))) return rc;
   hipStream_t s = c->stream;
-  std::vector<int> off2;
-  if ((rc = rd_road_upload(c, d, road, verts, poly_off, n_rings, off2))) return rc;
-  HIPCHK(c, hipMemcpyAsync(d + o_ego, ego_states, R * 4 * sizeof(double), hipMemcpyHostToDevice, s));
-  const RdBox eb{ego->length, ego->width, ego->center_offset};
-  hipLaunchKernelGGL(k_road_boxes, dim3((unsigned)((R + RD_BB - 1) / RD_BB)), dim3(RD_BB), 0, s, eb, (long)R, (const double *)(d + o_ego), 4, 3,
-                     (const double *)(d + road.o_verts), (const int *)(d + road.o_off), road.V, (double *)(d + o_m), (int *)(d + o_c), (int *)(d + o_r),
-                     (int *)(d + o_e));
+  if ((rc = rd_road_upload(c, d, road, verts)) || (rc = ar_put(c, d, f_ego, ego_states))) return rc;
+  const AuBox eb{ego->length, ego->width, ego->center_offset};
+  hipLaunchKernelGGL(k_road_boxes, dim3((unsigned)((R + RD_BB - 1) / RD_BB)), dim3(RD_BB), 0, s, eb, (long)R, f_ego.at(d), 4, 3, road.verts.at(d), road.off.at(d),
+                     road.V, f_m.at(d), f_c.at(d), f_r.at(d), f_e.at(d));
   HIPCHK(c, hipGetLastError());
-  hipLaunchKernelGGL(k_road_episode_egos, dim3((unsigned)((n_ego + 63) / 64)), dim3(64), 0, s, n_ego, n_steps, (const double *)(d + o_m),
-                     (const int *)(d + o_c), (double *)(d + o_emin), (int *)(d + o_estep), (int *)(d + o_ecorner), (int *)(d + o_ehits), (int *)(d + o_efirst));
+  hipLaunchKernelGGL(k_audit_episode_egos<true>, dim3((unsigned)((n_ego + 63) / 64)), dim3(64), 0, s, n_ego, n_steps, f_m.at(d), f_c.at(d), f_emin.at(d),
+                     f_estep.at(d), f_ecorner.at(d), f_ehits.at(d), f_efirst.at(d));
   HIPCHK(c, hipGetLastError());
-  const struct { void *h; size_t o, bytes; } back[9] = {
-      {out->step_margin, o_m, R * sizeof(double)},  {out->step_corner, o_c, R * sizeof(int)},      {out->step_ring, o_r, R * sizeof(int)},
-      {out->step_edge, o_e, R * sizeof(int)},       {out->ego_min, o_emin, ne * sizeof(double)},   {out->ego_step, o_estep, ne * sizeof(int)},
-      {out->ego_corner, o_ecorner, ne * sizeof(int)}, {out->ego_hits, o_ehits, ne * sizeof(int)},  {out->ego_first, o_efirst, ne * sizeof(int)}};
-  for (const auto &b : back)
-    if (b.h) HIPCHK(c, hipMemcpyAsync(b.h, d + b.o, b.bytes, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  return MIND_OK;
+  return ar_finish(c, d, {{out->step_margin, f_m}, {out->step_corner, f_c}, {out->step_ring, f_r}, {out->step_edge, f_e}, {out->ego_min, f_emin},
+                          {out->ego_step, f_estep}, {out->ego_corner, f_ecorner}, {out->ego_hits, f_ehits}, {out->ego_first, f_efirst}});
 }
 
 extern "C" int mind_debug_road_margin(int n, const double *boxes, const mind_audit_box *ego, const double *verts, const int32_t *poly_off, int n_rings,

@@ -12,7 +12,8 @@
 // vertex j in every lane at once -- one address, a broadcast, no bank conflict.  A ring may straddle turns: its first vertex and the
 // previous vertex stay in registers, and a ring is folded (rg_ring_end) when its last vertex has been walked, edges in index order; the
 // ring bounds come from poly_off by a wave-uniform index.  No result depends on RD_BB, RD_TV or the grid.  No atomics.
-// k_road_plan_trees / k_road_episode_egos: one thread per (candidate, tree) / per ego, sequential in key / step order.
+// The per-tree / per-ego reductions are the clearance audit's (audit_kernels.hip: k_audit_plan_trees, k_audit_episode_egos<true>), and so
+// is the ego box (AuBox).
 // Included by mind_hip.hip behind forecast_kernels.hip.
 #pragma clang fp contract(off)
 #include "road_geom.h"
@@ -20,9 +21,7 @@
 #define RD_BB 256          // boxes per workgroup = threads
 #define RD_TV 256          // vertices staged at a time (4 KB of LDS)
 
-struct RdBox { double L, W, off; };                 // mind_audit_box
-
-__global__ __launch_bounds__(RD_BB) void k_road_boxes(RdBox ego, long n_boxes, const double *__restrict__ states, int stride, int iyaw,
+__global__ __launch_bounds__(RD_BB) void k_road_boxes(AuBox ego, long n_boxes, const double *__restrict__ states, int stride, int iyaw,
                                                       const double *__restrict__ verts, const int *__restrict__ poly_off, int V,
                                                       double *__restrict__ margin, int *__restrict__ corner, int *__restrict__ ring,
                                                       int *__restrict__ edge) {
@@ -70,56 +69,4 @@ __global__ __launch_bounds__(RD_BB) void k_road_boxes(RdBox ego, long n_boxes, c
   double m = rg_box_end(q, &bk, &br, &be);
   if (!ok) { m = NAN; bk = -1; br = -1; be = -1; }
   if (act) { margin[g] = m; corner[g] = bk; ring[g] = br; edge[g] = be; }
-}
-
-// per (candidate, tree): the least margin with its node and corner (the lowest key wins ties), the nodes off the road, the first of them
-// and their probability mass.  A tree holding a NaN node reports min = NaN, node = the lowest such key, corner = -1, hits = -1,
-// first = -1, mass = NaN (the rule of k_audit_plan_trees).
-__global__ __launch_bounds__(256) void k_road_plan_trees(int Mtot, int n_cand, int n_trees, const AuTree *__restrict__ trees,
-                                                         const float *__restrict__ prob, const double *__restrict__ node_margin,
-                                                         const int *__restrict__ node_corner, double *__restrict__ tree_min,
-                                                         int *__restrict__ tree_node, int *__restrict__ tree_corner, int *__restrict__ tree_hits,
-                                                         int *__restrict__ tree_first, double *__restrict__ tree_mass) {
-  const long e = (long)blockIdx.x * 256 + threadIdx.x;
-  if (e >= (long)n_cand * n_trees) return;
-  const int c = (int)(e / n_trees), t = (int)(e % n_trees);
-  const AuTree T = trees[t];
-  const size_t row = (size_t)c * (size_t)Mtot + (size_t)T.moff;
-  double mn = INFINITY, mass = 0.0;
-  int mi = -1, mc = -1, hits = 0, first = -1, bad = -1;
-  for (int i = 0; i < T.M; ++i) {
-    const double d = node_margin[row + i];
-    if (d != d) { bad = i; break; }
-    if (i == 0 || d < mn) { mn = d; mi = i; mc = node_corner[row + i]; }
-    if (d < 0.0) {
-      if (first < 0) first = i;
-      ++hits;
-      mass += (double)prob[T.moff + i];
-    }
-  }
-  if (bad >= 0) { mn = NAN; mi = bad; mc = -1; hits = -1; first = -1; mass = NAN; }
-  tree_min[e] = mn; tree_node[e] = mi; tree_corner[e] = mc; tree_hits[e] = hits; tree_first[e] = first; tree_mass[e] = mass;
-}
-
-// per ego: the least margin over the steps with its step and corner (the lowest step wins ties), the steps off the road and the first of
-// them.  A trace holding a NaN step reports min = NaN, step = the first such step, corner = -1, hits = -1, first = -1.
-__global__ __launch_bounds__(64) void k_road_episode_egos(int n_ego, int S, const double *__restrict__ step_margin, const int *__restrict__ step_corner,
-                                                          double *__restrict__ ego_min, int *__restrict__ ego_step, int *__restrict__ ego_corner,
-                                                          int *__restrict__ ego_hits, int *__restrict__ ego_first) {
-  const int g = blockIdx.x * 64 + threadIdx.x;
-  if (g >= n_ego) return;
-  const size_t row = (size_t)g * (size_t)S;
-  double mn = INFINITY;
-  int ms = -1, mc = -1, hits = 0, first = -1, bad = -1;
-  for (int s = 0; s < S; ++s) {
-    const double d = step_margin[row + s];
-    if (d != d) { bad = s; break; }
-    if (s == 0 || d < mn) { mn = d; ms = s; mc = step_corner[row + s]; }
-    if (d < 0.0) {
-      if (first < 0) first = s;
-      ++hits;
-    }
-  }
-  if (bad >= 0) { mn = NAN; ms = bad; mc = -1; hits = -1; first = -1; }
-  ego_min[g] = mn; ego_step[g] = ms; ego_corner[g] = mc; ego_hits[g] = hits; ego_first[g] = first;
 }

@@ -615,6 +615,35 @@ class HipPredictor:
         """(length, width[, center_offset]) -> mind_audit_box"""
         return _lib.audit_box(box, name)
 
+    @staticmethod
+    def _audit_xs(xs, Mt):
+        """``xs`` of a plan audit -- [C, sum M, 6], or one [C, M_t, 6] per tree -> the checked contiguous [C, Mt, 6] array"""
+        if isinstance(xs, (list, tuple)):
+            xs = np.concatenate([np.asarray(x, np.float64) for x in xs], axis=1)
+        x = np.ascontiguousarray(xs, np.float64)
+        if x.ndim != 3 or x.shape[1:] != (Mt, 6):
+            raise ValueError(f"xs must be [C, {Mt}, 6] for these cost trees, got {list(x.shape)}")
+        return x
+
+    @staticmethod
+    def _split_nodes(res, Ms):
+        """the node_* arrays [C, sum M] of a plan audit's results, in place -> per-tree lists of [C, M_t]"""
+        offs = np.cumsum([0] + list(Ms))
+        for name in res:
+            if name.startswith("node_"):
+                res[name] = [res[name][:, offs[i]:offs[i + 1]].copy() for i in range(len(Ms))]
+        return res
+
+    @staticmethod
+    def _ego_traces(ego_states):
+        """``ego_states`` of an episode audit -- [E, S, 4] or [S, 4] -> the checked contiguous [E, S, 4] array"""
+        eg = np.ascontiguousarray(ego_states, np.float64)
+        if eg.ndim == 2:
+            eg = eg[None]
+        if eg.ndim != 3 or eg.shape[2] != 4:
+            raise ValueError(f"ego_states must be [E, S, 4], got {list(eg.shape)}")
+        return eg
+
     def audit_plan(self, flats, xs, ego_box, exo_margin):
         """Clearance of C candidate state sets on every cost tree of ``flats`` (planner-mode flat dicts as ``ilqr_solve`` takes them) in one
         call (mind_audit_plan, k_audit_plan).  ``xs``: [C, sum M, 6], or one [C, M_t, 6] per tree, as ``ilqr_score`` returns them; ``ego_box``:
@@ -623,12 +652,7 @@ class HipPredictor:
         n = len(flats)
         keep = []
         trees, Ms = self._cost_trees(flats, None, keep)
-        Mt = int(sum(Ms))
-        if isinstance(xs, (list, tuple)):
-            xs = np.concatenate([np.asarray(x, np.float64) for x in xs], axis=1)
-        x = np.ascontiguousarray(xs, np.float64)
-        if x.ndim != 3 or x.shape[1:] != (Mt, 6):
-            raise ValueError(f"xs must be [C, {Mt}, 6] for these cost trees, got {list(x.shape)}")
+        x = self._audit_xs(xs, int(sum(Ms)))
         for i, f in enumerate(flats):
             a = trees[i].n_agents
             if np.shape(f["mean"]) != (Ms[i], a, 2) or np.shape(f["cov"]) != (Ms[i], a) or np.shape(f["prob"]) != (Ms[i],):
@@ -638,29 +662,17 @@ class HipPredictor:
             raise ValueError(f"exo_margin must be finite and >= 0, got {exo_margin!r}")
         box = self._audit_box(ego_box, "ego_box")
         nc = x.shape[0]
-        res = dict(node_clear=np.zeros((nc, Mt)), node_agent=np.zeros((nc, Mt), np.int32), tree_min=np.zeros((nc, n)),
-                   tree_node=np.zeros((nc, n), np.int32), tree_agent=np.zeros((nc, n), np.int32), tree_hits=np.zeros((nc, n), np.int32),
-                   tree_first=np.zeros((nc, n), np.int32), tree_mass=np.zeros((nc, n)))
-        out = _lib.AuditPlanOut()
-        for name, a in res.items():
-            setattr(out, name, a.ctypes.data_as(C.POINTER(C.c_double if a.dtype == np.float64 else C.c_int32)))
+        out, res = _lib.out_record(_lib.AuditPlanOut, lambda k: (nc, x.shape[1]) if k.startswith("node_") else (nc, n))
         rc = self.lib.mind_audit_plan(self.ctx, C.byref(box), C.c_double(margin), trees, n, nc, x.ctypes.data_as(C.POINTER(C.c_double)), C.byref(out))
         _lib.check(self.lib, self.ctx, rc, "mind_audit_plan")
-        offs = np.cumsum([0] + Ms)
-        for name in ("node_clear", "node_agent"):
-            res[name] = [res[name][:, offs[i]:offs[i + 1]].copy() for i in range(n)]
-        return res
+        return self._split_nodes(res, Ms)
 
     def audit_episode(self, ego_states, exo, valid, boxes, ego_box):
         """Clearance of E ego traces against one replayed scene in one call (mind_audit_episode, k_audit_episode).  ``ego_states``: [E, S, 4]
         (or [S, 4]) = (x, y, v, yaw); ``exo`` [S, n, 5] = (x, y, heading, vx, vy) and ``valid`` [S, n], the layouts of the native loop's
         tables (row 0 is the ego's: not read); ``boxes`` [n, 2] = (length, width) per track; ``ego_box``: (length, width[, center_offset]).
         Returns a dict: step_clear [E, S], step_track int32 [E, S], ego_min [E], ego_step, ego_track, ego_hits, ego_first int32 [E]."""
-        eg = np.ascontiguousarray(ego_states, np.float64)
-        if eg.ndim == 2:
-            eg = eg[None]
-        if eg.ndim != 3 or eg.shape[2] != 4:
-            raise ValueError(f"ego_states must be [E, S, 4], got {list(eg.shape)}")
+        eg = self._ego_traces(ego_states)
         E, S = eg.shape[:2]
         ex = np.ascontiguousarray(exo, np.float64)
         va = np.ascontiguousarray(valid, np.uint8)
@@ -673,11 +685,7 @@ class HipPredictor:
         if not np.all(np.isfinite(bx[1:])) or np.any(bx[1:] < 0.0):
             raise ValueError("boxes must be finite and >= 0")
         box = self._audit_box(ego_box, "ego_box")
-        res = dict(step_clear=np.zeros((E, S)), step_track=np.zeros((E, S), np.int32), ego_min=np.zeros(E), ego_step=np.zeros(E, np.int32),
-                   ego_track=np.zeros(E, np.int32), ego_hits=np.zeros(E, np.int32), ego_first=np.zeros(E, np.int32))
-        out = _lib.AuditEpisodeOut()
-        for name, a in res.items():
-            setattr(out, name, a.ctypes.data_as(C.POINTER(C.c_double if a.dtype == np.float64 else C.c_int32)))
+        out, res = _lib.out_record(_lib.AuditEpisodeOut, lambda k: (E, S) if k.startswith("step_") else (E,))
         dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
         rc = self.lib.mind_audit_episode(self.ctx, C.byref(box), E, S, nt, dp(eg), dp(ex), va.ctypes.data_as(C.POINTER(C.c_uint8)), dp(bx), C.byref(out))
         _lib.check(self.lib, self.ctx, rc, "mind_audit_episode")
@@ -693,50 +701,27 @@ class HipPredictor:
         n = len(flats)
         keep = []
         trees, Ms = self._cost_trees(flats, None, keep)
-        Mt = int(sum(Ms))
-        if isinstance(xs, (list, tuple)):
-            xs = np.concatenate([np.asarray(x, np.float64) for x in xs], axis=1)
-        x = np.ascontiguousarray(xs, np.float64)
-        if x.ndim != 3 or x.shape[1:] != (Mt, 6):
-            raise ValueError(f"xs must be [C, {Mt}, 6] for these cost trees, got {list(x.shape)}")
+        x = self._audit_xs(xs, int(sum(Ms)))
         for i, f in enumerate(flats):
             if np.shape(f["prob"]) != (Ms[i],):
                 raise ValueError(f"cost tree {i}: prob [M] does not match parent [M = {Ms[i]}]")
         v, off, vp, op, P = _lib.road_args(verts, poly_off)
         box = self._audit_box(ego_box, "ego_box")
         nc = x.shape[0]
-        res = dict(node_margin=np.zeros((nc, Mt)), node_corner=np.zeros((nc, Mt), np.int32), node_ring=np.zeros((nc, Mt), np.int32),
-                   node_edge=np.zeros((nc, Mt), np.int32), tree_min=np.zeros((nc, n)), tree_node=np.zeros((nc, n), np.int32),
-                   tree_corner=np.zeros((nc, n), np.int32), tree_hits=np.zeros((nc, n), np.int32), tree_first=np.zeros((nc, n), np.int32),
-                   tree_mass=np.zeros((nc, n)))
-        out = _lib.AuditRoadPlanOut()
-        for name, a in res.items():
-            setattr(out, name, a.ctypes.data_as(C.POINTER(C.c_double if a.dtype == np.float64 else C.c_int32)))
+        out, res = _lib.out_record(_lib.AuditRoadPlanOut, lambda k: (nc, x.shape[1]) if k.startswith("node_") else (nc, n))
         rc = self.lib.mind_audit_road_plan(self.ctx, C.byref(box), vp, op, P, trees, n, nc, x.ctypes.data_as(C.POINTER(C.c_double)), C.byref(out))
         _lib.check(self.lib, self.ctx, rc, "mind_audit_road_plan")
-        offs = np.cumsum([0] + Ms)
-        for name in ("node_margin", "node_corner", "node_ring", "node_edge"):
-            res[name] = [res[name][:, offs[i]:offs[i + 1]].copy() for i in range(n)]
-        return res
+        return self._split_nodes(res, Ms)
 
     def audit_road_episode(self, ego_states, verts, poly_off, ego_box):
         """Road margin of E ego traces in one call (mind_audit_road_episode, k_road_boxes).  ``ego_states``: [E, S, 4] (or [S, 4]) =
         (x, y, v, yaw); the road as ``audit_road_plan`` takes it.  Returns a dict: step_margin [E, S], step_corner, step_ring, step_edge
         int32 [E, S], ego_min [E], ego_step, ego_corner, ego_hits, ego_first int32 [E]."""
-        eg = np.ascontiguousarray(ego_states, np.float64)
-        if eg.ndim == 2:
-            eg = eg[None]
-        if eg.ndim != 3 or eg.shape[2] != 4:
-            raise ValueError(f"ego_states must be [E, S, 4], got {list(eg.shape)}")
+        eg = self._ego_traces(ego_states)
         E, S = eg.shape[:2]
         v, off, vp, op, P = _lib.road_args(verts, poly_off)
         box = self._audit_box(ego_box, "ego_box")
-        res = dict(step_margin=np.zeros((E, S)), step_corner=np.zeros((E, S), np.int32), step_ring=np.zeros((E, S), np.int32),
-                   step_edge=np.zeros((E, S), np.int32), ego_min=np.zeros(E), ego_step=np.zeros(E, np.int32), ego_corner=np.zeros(E, np.int32),
-                   ego_hits=np.zeros(E, np.int32), ego_first=np.zeros(E, np.int32))
-        out = _lib.AuditRoadEpisodeOut()
-        for name, a in res.items():
-            setattr(out, name, a.ctypes.data_as(C.POINTER(C.c_double if a.dtype == np.float64 else C.c_int32)))
+        out, res = _lib.out_record(_lib.AuditRoadEpisodeOut, lambda k: (E, S) if k.startswith("step_") else (E,))
         rc = self.lib.mind_audit_road_episode(self.ctx, C.byref(box), vp, op, P, E, S, eg.ctypes.data_as(C.POINTER(C.c_double)), C.byref(out))
         _lib.check(self.lib, self.ctx, rc, "mind_audit_road_episode")
         return res

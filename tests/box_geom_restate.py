@@ -74,28 +74,33 @@ def reduce_agents(pair_clear):
     return best, bj
 
 
-def reduce_tree(node_clear, node_agent, prob):
-    """k_audit_plan_trees: -> (min, node, agent, n_hit, first_hit, hit_mass); prob float32 [M]"""
-    mn, mi, ma, hits, first, mass = F(np.inf), -1, -1, 0, -1, F(0.0)
-    for i, v in enumerate(node_clear):
+def reduce_tree(node_val, node_tag, prob):
+    """k_audit_plan_trees, for both audits (clearance: node_clear / node_agent; road: node_margin / node_corner):
+    -> (min, node, tag, n_hit, first_hit, hit_mass); prob float32 [M]"""
+    mn, mi, mt, hits, first, mass = F(np.inf), -1, -1, 0, -1, F(0.0)
+    for i, v in enumerate(node_val):
         if v != v:
             return F(np.nan), i, -1, -1, -1, F(np.nan)
         if i == 0 or v < mn:
-            mn, mi, ma = v, i, int(node_agent[i])
+            mn, mi, mt = v, i, int(node_tag[i])
         if v < 0.0:
             if first < 0:
                 first = i
             hits += 1
             mass = mass + F(np.float32(prob[i]))
-    return mn, mi, ma, hits, first, mass
+    return mn, mi, mt, hits, first, mass
 
 
-def reduce_ego(step_clear, step_track):
-    """k_audit_episode_egos: -> (min, step, track, n_hit_steps, first_hit_step)"""
+def reduce_ego(step_val, step_tag, nan_step=False):
+    """k_audit_episode_egos<nan_step>, for both audits (clearance: step_clear / step_track, nan_step False; road: step_margin /
+    step_corner, nan_step True): -> (min, step, tag, n_hit_steps, first_hit_step).  nan_step: a NaN step reports NaN, that step, -1, -1,
+    -1; without it a NaN is compared like any value (at step 0 it stays the minimum, later it is passed over)"""
     mn, ms, mt, hits, first = F(np.inf), -1, -1, 0, -1
-    for s, v in enumerate(step_clear):
+    for s, v in enumerate(step_val):
+        if nan_step and v != v:
+            return F(np.nan), s, -1, -1, -1
         if s == 0 or v < mn:
-            mn, ms, mt = v, s, int(step_track[s])
+            mn, ms, mt = v, s, int(step_tag[s])
         if v < 0.0:
             if first < 0:
                 first = s

@@ -1,7 +1,9 @@
-"""numpy float64 restatement of mind_amd/csrc/road_geom.h and of the reductions of the road audit (road_kernels.hip): scalar operations in
+"""numpy float64 restatement of mind_amd/csrc/road_geom.h and of the reductions of the road audit (audit_kernels.hip): scalar operations in
 the header's order on np.float64 values -- IEEE double, no fused multiply-add -- so that the host entry and the kernels can be held to it
 bit for bit.  (cos, sin) are inputs, as in the header.  Not a test module."""
 import numpy as np
+
+from box_geom_restate import reduce_ego as _ego_fold, reduce_tree  # noqa: F401  (reduce_tree: k_audit_plan_trees over node_margin / node_corner)
 
 F = np.float64
 _SL = (1.0, 1.0, -1.0, -1.0)
@@ -128,34 +130,8 @@ def margins(boxes, ego_box, verts, poly_off, trig=numpy_trig):
     return out
 
 
-# ---- the reductions of the two audits, given the per-box results ---------------------------------------------------------------------
-
-def reduce_tree(node_margin, node_corner, prob):
-    """k_road_plan_trees: -> (min, node, corner, n_hit, first_hit, hit_mass); prob float32 [M]"""
-    mn, mi, mc, hits, first, mass = F(np.inf), -1, -1, 0, -1, F(0.0)
-    for i, v in enumerate(node_margin):
-        if v != v:
-            return F(np.nan), i, -1, -1, -1, F(np.nan)
-        if i == 0 or v < mn:
-            mn, mi, mc = v, i, int(node_corner[i])
-        if v < 0.0:
-            if first < 0:
-                first = i
-            hits += 1
-            mass = mass + F(np.float32(prob[i]))
-    return mn, mi, mc, hits, first, mass
-
+# ---- the reductions of the two audits, given the per-box results: the clearance audit's folds, the NaN rule on ----------------------------
 
 def reduce_ego(step_margin, step_corner):
-    """k_road_episode_egos: -> (min, step, corner, n_hit_steps, first_hit_step)"""
-    mn, ms, mc, hits, first = F(np.inf), -1, -1, 0, -1
-    for s, v in enumerate(step_margin):
-        if v != v:
-            return F(np.nan), s, -1, -1, -1
-        if s == 0 or v < mn:
-            mn, ms, mc = v, s, int(step_corner[s])
-        if v < 0.0:
-            if first < 0:
-                first = s
-            hits += 1
-    return mn, ms, mc, hits, first
+    """k_audit_episode_egos<true>: -> (min, step, corner, n_hit_steps, first_hit_step)"""
+    return _ego_fold(step_margin, step_corner, nan_step=True)

@@ -154,6 +154,30 @@ def test_recorded_scenes(scene_audits, name):
         assert hits == 0 and first == -1 and mn > 0.0
 
 
+def test_ego_fold_is_one_restatement_with_the_nan_rule_as_a_parameter(scene_audits):
+    """k_audit_episode_egos<false> (clearance) and <true> (road) are one body: on a finite trace the rule changes nothing; a NaN step in
+    the middle is passed over without the rule and reported with it; a NaN at step 0 stays the minimum without the rule"""
+    import road_geom_restate as rr
+    assert rr.reduce_tree is rs.reduce_tree
+    for name, ((clear, track), _, _) in scene_audits.items():
+        assert rs.reduce_ego(clear, track, nan_step=True) == rs.reduce_ego(clear, track, nan_step=False) == rs.reduce_ego(clear, track), name
+        assert rr.reduce_ego(clear, track) == rs.reduce_ego(clear, track), name
+    val, tag = np.array([3.0, -1.0, np.nan, -2.5, 4.0]), np.array([7, 8, 9, 10, 11], np.int32)
+    assert rs.reduce_ego(val, tag) == (-2.5, 3, 10, 2, 1)
+    on = rs.reduce_ego(val, tag, nan_step=True)
+    assert np.isnan(on[0]) and on[1:] == (2, -1, -1, -1) and rr.reduce_ego(val, tag)[1:] == on[1:]
+    first = rs.reduce_ego(val[::-1][2:], tag[2:])                          # (nan, -1.0, 3.0): nothing compares below a NaN
+    assert np.isnan(first[0]) and first[1:] == (0, 9, 1, 1)
+    # the partial summaries of the two episode auditors follow the same split
+    per = dict(step_clear=val, step_track=tag)
+    idx = np.arange(1, 5)
+    off = audit._part(per, idx, "step_clear", "track", nan_step=False)
+    assert np.isnan(off["ego_min"]) and (off["ego_step"], off["ego_track"], off["ego_hits"], off["ego_first"]) == (2, 9, 2, 1)      # (numpy's argmin)
+    on = audit._part(dict(step_margin=val, step_corner=tag), idx, "step_margin", "corner", nan_step=True)
+    assert np.isnan(on["ego_min"]) and (on["ego_step"], on["ego_corner"], on["ego_hits"], on["ego_first"]) == (2, -1, -1, -1)
+    assert audit._part(per, idx[:0], "step_clear", "track", nan_step=False) is None
+
+
 def test_box_table():
     assert audit.box_for("vehicle") == (4.5, 2.0) and audit.box_for("PEDESTRIAN") == (0.5, 0.75)
     assert audit.box_for("cyclist") == audit.box_for("MOTORCYCLIST") == (1.5, 0.75) and audit.box_for("bus") == (7.0, 2.1)

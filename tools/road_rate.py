@@ -1,7 +1,7 @@
 """What the road audit's device call costs, against the path it replaces: device events on the context's stream around each call, after a
 warm-up call, median of `--reps`, the two paths alternating in one process:
 
-  device   HipPredictor.audit_road_plan (mind_audit_road_plan: upload of road and states, k_road_boxes, k_road_plan_trees, read-back of
+  device   HipPredictor.audit_road_plan (mind_audit_road_plan: upload of road and states, k_road_boxes, k_audit_plan_trees, read-back of
            every output)
   numpy    the candidate states read back from the device (a torch tensor's .cpu()) and a vectorised numpy evaluation of the same margins
            (world coordinates, projection form, crossing parity; 4 096 boxes at a time)
