@@ -190,49 +190,93 @@ int mind_debug_launch_clock(int n_blocks, int block_slots, int rate_khz, const l
 #define MIND_PAIR_BF16X6 3
 int mind_set_pair_precision(mind_ctx *ctx, int mode);
 
-/* Kernel-selection knobs (A/B measurements and tests; the defaults are the measured winners, the results are the same within the
- * arithmetic's accuracy): "dec_mfma_min" (agents per call from which the decoder's actor part uses the MFMA kernel; default: never),
- * "ilqr_wgs" (workgroups per wide cost tree, default 16, halved until the launch is resident; 1 = the one-workgroup kernel), "ilqr_multi_min" (node count from which a
- * tree is "wide", default 192; a wide-tree launch that is not fully resident -- another context holds CUs -- aborts at its first
- * barrier and the call is solved again by the one-workgroup kernel: mind_last_ilqr_stats then reports 1 workgroup per tree),
- * "ilqr_wgs_big" / "ilqr_big_min" (workgroups per tree of at least ilqr_big_min nodes: 32 from 12 288 nodes),
- * "ilqr_slots" (narrow cost trees: workgroups per tree that take the fit's Levenberg-Marquardt slots -- the master evaluates slot 0 of every
- * pass, a follower the value the schedule reaches after its number of rejections; default 10, at most 12, 1 = everything in one workgroup; followers
- * that are not resident are simply not used; same bits for every value; MIND_ILQR_SLOTS),
- * "ilqr_spec_deriv" (1, default: with slots on follower workgroups one more workgroup per tree runs the derivative pass of a pass's first
- * candidate beside the master's pricing of the candidates, and the master swaps derivative sets instead of differentiating when that
- * candidate is the accepted one; same bits; mind_last_ilqr_stats counts it among the workgroups per tree; MIND_ILQR_SPEC_DERIV),
- * "ilqr_score_block" (mind_ilqr_score_trees: candidates per workgroup, rounded down to a power of two 1 .. 64; 0, default: 64 while that keeps
- * two workgroups per CU, halved otherwise down to 4; same bits for every value),
- * copies off the planning cycle's critical path (all of them leave every result bit for bit): "upload_kernel_max" (uploads of at most this many
- * bytes from the context's page-locked staging -- the root scene, the solver's tables -- run as a kernel on the consumer's queue that reads the
- * host buffer, instead of a copy the SDMA engine hands over; default 1 MB, 0 = always copies), "ilqr_host_out_max" (tree-iLQR launches of at
- * most this many nodes write xs / us / statistics to the host staging themselves; default 4 096), "dec_mirror" (mind_aime_plan, unsharded: the
- * round's last glue kernel writes the decisions where the host reads them), "tab_host_max" / "tab_small" (its small index tables are read from
- * the host staging / travel in the kernel arguments), "early_eval" (mind_loop prices a candidate tree as soon as the pending launch marks it
- * complete), "glue_fused" (mind_aime_plan's pruning decisions and branch-time bits from one launch, k_aime_select_branch), "dec_poll" (with
- * "dec_mirror", rounds of one launch: that kernel marks the mirrored decisions complete with a generation word and the host polls the word,
- * bounded, instead of draining the stream, sizing the next round's buffers while it waits; MIND_DEC_POLL); MIND_GLUE_FUSED, MIND_UPLOAD_KERNEL_MAX, MIND_ILQR_HOST_OUT_MAX, MIND_DEC_MIRROR, MIND_TAB_HOST_MAX, MIND_TAB_SMALL, MIND_EARLY_EVAL,
- * "actor_f32" (0: the fp32 VALU ActorNet instead of the fp32-MFMA one under the exact-fp32 setting), "actor_f32_min" / "actor_f32_pair_min" (actors per
- * call from which the fp32-MFMA ActorNet runs with two actors per workgroup, under every setting / under exact fp32; default never),
- * "actor_lw_min" (actors per call from which the layer-wise batched ActorNet -- actor_lw_kernels.hip: one conv-as-GEMM launch and one GroupNorm
- * launch per layer over chunks of actors, the layer's weight fragments stationary in LDS -- replaces k_actor_mfma<NP> under the bf16x6 / bf16x3 /
- * bf16 settings; default 1 << 30 = never; bit-identical to k_actor_mfma<NP>, so calls, rounds and ranks may differ in which of the two they take;
- * MIND_PAIR_F32, "enc_mfma" 0 and "actor_f32_min" keep their precedence; MIND_ACTOR_LW_MIN at context creation), "actor_lw_chunk" (its actors per
- * chunk, 0 = the default of 1024; the scratch arena is one chunk, 137 472 bytes per actor; for tests and A/B runs only: same bits for every value),
- * "tok_lw_min_n" (a SCENE of at least this many tokens takes the fp32-MFMA token class -- the bits of k_token_mfma<0> -- whatever its batch, round or
- * rank; "tok_mfma" 1 still puts every scene there and "tok_bf_min_n" keeps its precedence under bf16x3 / bf16; default 1 << 30 = never;
- * MIND_TOK_LW_MIN_N), "tok_lw_min" (a run of consecutive scenes of that class with at least this many tokens runs the layer-wise token kernels --
- * token_lw_kernels.hip: one launch per stage over chunks of tokens, the stage's weight fragments stationary in registers -- instead of
- * k_token_mfma<0>; bit-identical to it, so calls, rounds and ranks may differ; default 1 << 30 = never; MIND_TOK_LW_MIN), "tok_lw_chunk" (its tokens
- * per chunk, 0 = the default of 32 768; the scratch arena is one chunk, 2 560 bytes per token; same bits for every value),
- * "enc_mfma" (0: the fp32 VALU ActorNet / decoder kernels under every precision), "actor_split" (6: three-way operand split,
- * fp32-class; 3: two-way), "xcd_order" (XCD-aware job order of the pair kernel), "tok_mfma" (1: the per-token epilogue / prologue of the fusion layers on the fp32 MFMA kernel k_token_mfma instead of the fp32 VALU one; off by default: measured slower), "tok_small_max" (batches of at most this many tokens run k_token with four tokens per workgroup instead of eight; same bits), "tgt_side" (0: the context stream waits for the target embedding before the fusion layers), "dec_overlap" (0: the decoder's actor part as one kernel behind
- * k_dec_scene instead of its actor_proj half beside it on the side stream; bit-identical), "dec_head_ra" (agents per workgroup of that form's head:
- * 0, default = 1 while the call's agents fit one workgroup per CU, else 2, else 4; 1, 2 or 4 = that form whatever the call, 4 being the head as it
- * was; bit-identical; MIND_DEC_HEAD_RA).  Environment: MIND_DEC_MFMA_MIN, MIND_ENC_MFMA,
- * MIND_ACTOR_SPLIT, MIND_XCD_ORDER, MIND_ILQR_WGS, MIND_DEC_OVERLAP at context creation. */
+/* Tuning knobs (A/B measurements and tests; the defaults are the measured winners, the results are the same within the arithmetic's
+ * accuracy).  Every knob is one row of the table in mind_amd/csrc/tuning.h; this list is in the table's order.  Per knob: its name for
+ * mind_set_tuning / mind_get_tuning, the environment variable read once at mind_ctx_create (- = none), its default, the values it stores (a
+ * value outside them is clamped as shown, never refused), what it does.  A flag stores value != 0; its variable is read either by its first
+ * character ("char": on unless the text begins with '0') or as a number ("atoi": on when atoi(text) != 0), as the knob was introduced.
+ *   the predictor (mind_predict_batch)
+ *   "dec_mfma_min"       MIND_DEC_MFMA_MIN      1 << 30  any int   agents per call from which the decoder's actor part uses the MFMA kernel; default: never
+ *   "enc_mfma"           MIND_ENC_MFMA          1        flag char 0: the fp32 VALU ActorNet / decoder kernels under every precision
+ *   "actor_f32"          MIND_ACTOR_F32         1        flag char 0: the fp32 VALU ActorNet instead of the fp32-MFMA one under the exact-fp32 setting
+ *   "actor_f32_min"      MIND_ACTOR_F32_MIN     1 << 30  any int   actors per call from which the fp32-MFMA ActorNet runs with two actors per workgroup under every setting; default never
+ *   "actor_f32_pair_min" -                      1 << 30  any int   the same threshold under exact fp32
+ *   "actor_lw_min"       MIND_ACTOR_LW_MIN      1 << 30  any int   actors per call from which the layer-wise batched ActorNet -- actor_lw_kernels.hip: one conv-as-GEMM
+ *       launch and one GroupNorm launch per layer over chunks of actors, the layer's weight fragments stationary in LDS -- replaces k_actor_mfma<NP> under
+ *       the bf16x6 / bf16x3 / bf16 settings; default never; bit-identical to k_actor_mfma<NP>, so calls, rounds and ranks may differ in which of the two
+ *       they take; MIND_PAIR_F32, "enc_mfma" 0 and "actor_f32_min" keep their precedence
+ *   "actor_lw_chunk"     -                      0        >= 0      its actors per chunk, 0 = the default of 1024; the scratch arena is one chunk, 137 472 bytes per actor; for
+ *       tests and A/B runs only: same bits for every value
+ *   "actor_split"        MIND_ACTOR_SPLIT       6        3, else 6 6: three-way operand split, fp32-class; 3: two-way
+ *   "xcd_order"          MIND_XCD_ORDER         1        flag char XCD-aware job order of the pair kernel
+ *   "pair_tile"          MIND_PAIR_TILE         1        flag char 0: the row-major k_pair_bf instead of the tile-native k_pair_t under bf16x3 / bf16 (same-box A/B measurements)
+ *   "dec_overlap"        MIND_DEC_OVERLAP       1        flag char 0: the decoder's actor part as one kernel behind k_dec_scene instead of its actor_proj half beside it on
+ *       the side stream; bit-identical
+ *   "dec_head_ra"        MIND_DEC_HEAD_RA       0        1, 2, 4, else 0   agents per workgroup of that form's head: 0 = 1 while the call's agents fit one workgroup per CU,
+ *       else 2, else 4; 1, 2 or 4 = that form whatever the call, 4 being the head as it was; bit-identical
+ *   "tok_mfma"           MIND_TOK_MFMA          0        flag char 1: the per-token epilogue / prologue of the fusion layers on the fp32 MFMA kernel k_token_mfma instead of
+ *       the fp32 VALU one; off by default: measured slower
+ *   "tok_small_max"      MIND_TOK_SMALL_MAX     2048     any int   batches of at most this many tokens run k_token with four tokens per workgroup instead of eight; same bits
+ *   "tok_merge"          MIND_TOK_MERGE         1        flag char small token launches merge their independent projections (k_token_m); 0: the plain kernel
+ *   "dec_mw"             MIND_DEC_MW            0        flag char 1: k_dec_scene_mw, eight workgroups per scene on the decoder's five big stages while every workgroup of the
+ *       launch is resident (calls of at most n_cu / 8 scenes); bit-identical to the one-workgroup kernel
+ *   "dec_cls_side"       MIND_DEC_CLS_SIDE      0        flag char 1: the decoder's cls head as its own launch on the side stream beside the actor part's head; bit-identical
+ *   "tok_bf_min_n"       MIND_TOK_BF_MIN_N      0        any int   scenes of at least this many tokens run k_token_mfma<1> (bf16 hi + lo split operands) under bf16x3 / bf16; 0 = never
+ *   "tok_lw_min_n"       MIND_TOK_LW_MIN_N      1 << 30  any int   a SCENE of at least this many tokens takes the fp32-MFMA token class -- the bits of k_token_mfma<0> --
+ *       whatever its batch, round or rank; "tok_mfma" 1 still puts every scene there and "tok_bf_min_n" keeps its precedence under bf16x3 / bf16; default never
+ *   "tok_lw_min"         MIND_TOK_LW_MIN        1 << 30  any int   a run of consecutive scenes of that class with at least this many tokens runs the layer-wise token kernels
+ *       -- token_lw_kernels.hip: one launch per stage over chunks of tokens, the stage's weight fragments stationary in registers -- instead of
+ *       k_token_mfma<0>; bit-identical to it, so calls, rounds and ranks may differ; default never
+ *   "tok_lw_chunk"       -                      0        >= 0      its tokens per chunk, 0 = the default of 32 768; the scratch arena is one chunk, 2 560 bytes per token; same bits
+ *       for every value
+ *   "tgt_side"           MIND_TGT_SIDE          1        flag char 0: the context stream waits for the target embedding before the fusion layers
+ *   the tree-iLQR solver
+ *   "ilqr_chunk"         MIND_ILQR_CHUNK        0        >= 0      nodes per forward step of a narrow tree's line search; 0: whole segments
+ *   "ilqr_wgs"           MIND_ILQR_WGS          16       1 .. 32   workgroups per wide cost tree, halved until the launch is resident; 1 = the one-workgroup kernel
+ *   "ilqr_multi_min"     -                      192      any int   node count from which a tree is "wide"; a wide-tree launch that is not fully resident -- another context
+ *       holds CUs -- aborts at its first barrier and the call is solved again by the one-workgroup kernel: mind_last_ilqr_stats then reports 1
+ *       workgroup per tree
+ *   "ilqr_wgs_big"       -                      32       1 .. 32   workgroups per tree of at least "ilqr_big_min" nodes
+ *   "ilqr_big_min"       -                      12288    any int   ... and that node count
+ *   "ilqr_slots"         MIND_ILQR_SLOTS        10       1 .. 12   narrow cost trees: workgroups per tree that take the fit's Levenberg-Marquardt slots -- the master evaluates
+ *       slot 0 of every pass, a follower the value the schedule reaches after its number of rejections; 1 = everything in one workgroup; followers
+ *       that are not resident are simply not used; same bits for every value
+ *   "ilqr_spec_deriv"    MIND_ILQR_SPEC_DERIV   1        flag atoi with slots on follower workgroups one more workgroup per tree runs the derivative pass of a pass's first
+ *       candidate beside the master's pricing of the candidates, and the master swaps derivative sets instead of differentiating when that
+ *       candidate is the accepted one; same bits; mind_last_ilqr_stats counts it among the workgroups per tree
+ *   "ilqr_host_out_max"  MIND_ILQR_HOST_OUT_MAX 4096     >= 0      tree-iLQR launches of at most this many nodes write xs / us / statistics to the host staging themselves; 0 =
+ *       always copies
+ *   "ilqr_score_block"   -                      0        0, 1, 2, 4 .. 64   mind_ilqr_score_trees: candidates per workgroup, rounded down to a power of two 1 .. 64; 0: 64 while
+ *       that keeps two workgroups per CU, halved otherwise down to 4; same bits for every value
+ *   "ilqr_test_starve"   -                      0        flag      tests: launch a wide tree without its last workgroups / let the followers of a narrow tree leave at once
+ *   the context: copies and launches off the planning cycle's critical path (all of them leave every result bit for bit)
+ *   "plan_chunk_mb"      MIND_PLAN_CHUNK_MB     98304    >= 1      mind_aime_plan: a round whose edge tensor would exceed this many MB goes through the predictor in chunks of
+ *       scenes.  The variable is ignored unless it is > 0
+ *   "pl_tab_side"        MIND_PL_TAB_SIDE       0        flag char 1: the round tables travel on their own stream while the round's predictor runs; measured: no difference
+ *   "tab_small"          MIND_TAB_SMALL         1        flag atoi mind_aime_plan's scene tables of a small round travel in the kernel arguments
+ *   "tab_host_max"       MIND_TAB_HOST_MAX      4096     >= 0      its small index tables are read from the host staging while they name at most this many workgroups; 0 = always uploaded
+ *   "early_eval"         MIND_EARLY_EVAL        1        flag atoi mind_loop prices a candidate tree as soon as the pending launch marks it complete
+ *   "glue_fused"         MIND_GLUE_FUSED        1        flag atoi mind_aime_plan's pruning decisions and branch-time bits from one launch, k_aime_select_branch
+ *   "dec_mirror"         MIND_DEC_MIRROR        1        flag atoi mind_aime_plan, unsharded: the round's last glue kernel writes the decisions where the host reads them
+ *   "dec_poll"           MIND_DEC_POLL          1        flag atoi with "dec_mirror", rounds of one launch: that kernel marks the mirrored decisions complete with a generation
+ *       word and the host polls the word, bounded, instead of draining the stream, sizing the next round's buffers while it waits
+ *   "root_head"          MIND_ROOT_HEAD         1        flag atoi the root's lane graph, world-frame histories and lane-distance field are queued beside the first round's ActorNet
+ *   "round_head"         MIND_ROUND_HEAD        1        flag atoi ... and a later round's repeated lane features beside that round's
+ *   "upload_kernel_max"  MIND_UPLOAD_KERNEL_MAX 1 << 20  >= 0      uploads of at most this many bytes from the context's page-locked staging -- the root scene, the solver's
+ *       tables -- run as a kernel on the consumer's queue that reads the host buffer, instead of a copy the SDMA engine hands over; 0 = always copies
+ *   "prof_clock"         MIND_PROF_CLOCK        1        0 .. 2    which clock times the pair kernels and the one-launch ActorNet forms with profiling on (mind_set_profiling)
+ * mind_set_tuning and mind_get_tuning return MIND_EINVAL for an unknown name ("unknown knob '<name>'" in mind_last_error_string).
+ * mind_get_tuning writes the stored value: a flag as 0 or 1, "actor_split" as 3 or 6. */
 int mind_set_tuning(mind_ctx *ctx, const char *name, int value);
+int mind_get_tuning(mind_ctx *ctx, const char *name, int *value);
+/* host-only helper (tests): the knob table without a context.  name == NULL: row `index` of the table -- *out_name, *out_env (NULL: the knob
+ * has no variable) and *out_value = its default; returns the number of rows, MIND_EINVAL for an index outside them.  name != NULL: what a fresh
+ * record stores for that knob after mind_set_tuning(name, value) (text == NULL) or after its variable was read with the text `text` (MIND_EINVAL
+ * for a knob without a variable) -> *out_value; returns MIND_OK, MIND_EINVAL for an unknown name.  out_name / out_env may be NULL. */
+int mind_debug_tuning(int index, const char *name, const char *text, int value, const char **out_name, const char **out_env, int *out_value);
+/* handles the library's contexts hold in this process -- device and page-locked allocations, events, streams: acquisitions less releases.
+ * Back at its earlier value once a context is destroyed.  Needs no GPU. */
+int mind_debug_live_handles(void);
 int mind_get_pair_precision(mind_ctx *ctx);   /* -> mode, or MIND_EINVAL */
 /* host-only helper (tests): the bf16 hi / lo MFMA fragment packing of one [128][row_stride] weight matrix,
  * out[16384] dwords = [part 2][out block 8][k group 4][lane 64][4] (see pair_bf16_kernels.hip).  Needs no GPU. */

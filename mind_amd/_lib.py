@@ -219,7 +219,7 @@ class PlannerOut(C.Structure):     # mind_planner_out
 EXPORTS = ["mind_ctx_create", "mind_ctx_destroy", "mind_last_error_string", "mind_ctx_synchronize",
            "mind_weights_load", "mind_predict_batch", "mind_last_fusion_stats", "mind_last_actor_stats", "mind_debug_actor_lw_plan", "mind_last_token_stats", "mind_last_token_stage_ms", "mind_debug_token_lw_plan", "mind_set_profiling", "mind_debug_launch_times", "mind_debug_launch_clock",
            "mind_ilqr_solve_trees", "mind_ilqr_contingency", "mind_ilqr_solve_fields", "mind_cost_eval", "mind_ilqr_score_trees", "mind_ilqr_gains", "mind_ilqr_policy_rollouts", "mind_lane_dist_field", "mind_aime_world", "mind_aime_rebase", "mind_debug_aime_decide", "mind_debug_set_layers",
-           "mind_debug_read", "mind_set_pair_precision", "mind_get_pair_precision", "mind_debug_pack_bfrag", "mind_debug_pack_conv_frag", "mind_debug_pack", "mind_debug_weight_image", "mind_debug_weight_bind", "mind_debug_pair_schedule", "mind_debug_predict_choice", "mind_debug_ilqr_plan", "mind_debug_aime_book", "mind_set_tuning", "mind_last_ilqr_stats", "mind_aime_plan", "mind_last_ilqr_profile", "mind_eval_traj_trees", "mind_last_ilqr_trace", "mind_ilqr_contingency_begin", "mind_ilqr_finish", "mind_fill_tracks", "mind_ilqr_contingency_begin_plan", "mind_debug_trig", "mind_aime_plan_begin", "mind_aime_plan_poll", "mind_aime_plan_finish", "mind_ctx_busy", "mind_ilqr_finish_plan",
+           "mind_debug_read", "mind_set_pair_precision", "mind_get_pair_precision", "mind_debug_pack_bfrag", "mind_debug_pack_conv_frag", "mind_debug_pack", "mind_debug_weight_image", "mind_debug_weight_bind", "mind_debug_pair_schedule", "mind_debug_predict_choice", "mind_debug_ilqr_plan", "mind_debug_aime_book", "mind_set_tuning", "mind_get_tuning", "mind_debug_tuning", "mind_debug_live_handles", "mind_last_ilqr_stats", "mind_aime_plan", "mind_last_ilqr_profile", "mind_eval_traj_trees", "mind_last_ilqr_trace", "mind_ilqr_contingency_begin", "mind_ilqr_finish", "mind_fill_tracks", "mind_ilqr_contingency_begin_plan", "mind_debug_trig", "mind_aime_plan_begin", "mind_aime_plan_poll", "mind_aime_plan_finish", "mind_ctx_busy", "mind_ilqr_finish_plan",
            "mind_set_exchange", "mind_last_exchange_stats", "mind_debug_wait_word",
            "mind_predict_batch_aux", "mind_set_decoder_basis", "mind_get_decoder_basis", "mind_curve_eval", "mind_debug_curve_basis",
            "mind_audit_plan", "mind_audit_episode", "mind_debug_box_clearance",
@@ -312,6 +312,9 @@ def load():
     lib.mind_ilqr_finish_plan.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.mind_set_pair_precision.argtypes = [C.c_void_p, C.c_int]
     lib.mind_set_tuning.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
+    lib.mind_get_tuning.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_int)]
+    lib.mind_debug_tuning.argtypes = [C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_int)]
+    lib.mind_debug_live_handles.argtypes = []
     lib.mind_last_ilqr_stats.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.mind_last_ilqr_profile.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     lib.mind_last_ilqr_trace.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int)]
@@ -405,6 +408,26 @@ def predict_choice(knobs, prec, scenes, n_cu=256, have_side=True):
     d = dict(zip(PRED_CHOICE_FIELDS, out[:31]))
     d["runs"] = [tuple(out[32 + 6 * i:38 + 6 * i]) for i in range(out[1])]
     return d
+
+
+def knobs():
+    """the knob table (mind_debug_tuning; no GPU), in its order: [(mind_set_tuning name, environment variable or None, default), ...]"""
+    lib = load()
+    name, env, val = C.c_char_p(), C.c_char_p(), C.c_int()
+    rows = []
+    while not rows or len(rows) < n:
+        n = lib.mind_debug_tuning(len(rows), None, None, 0, C.byref(name), C.byref(env), C.byref(val))
+        assert n > 0, n
+        rows.append((name.value.decode(), env.value.decode() if env.value else None, val.value))
+    return rows
+
+
+def knob_stored(name, value=None, text=None):
+    """what a fresh record stores for knob `name` after mind_set_tuning(name, value), or after its variable was read with `text` (no GPU);
+    None when the library rejects the name, or the text of a knob without a variable"""
+    val = C.c_int()
+    rc = load().mind_debug_tuning(-1, name.encode(), None if text is None else text.encode(), 0 if value is None else int(value), None, None, C.byref(val))
+    return val.value if rc == MIND_OK else None
 
 
 # header and per-tree tables of mind_debug_ilqr_plan's record (include/mind_hip.h)

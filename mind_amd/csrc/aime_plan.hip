@@ -23,14 +23,10 @@
 namespace {
 
 int pl_pin(mind_ctx *c, int which, size_t bytes) {      // (declared ahead of il_solve in ilqr_host.hip)
-  if (bytes <= c->pl_pin_cap[which]) return MIND_OK;
-  if (c->pl_pin[which]) (void)hipHostFree(c->pl_pin[which]);
-  c->pl_pin[which] = nullptr; c->pl_pin_cap[which] = 0;
+  if (bytes <= c->pl_pin[which].cap) return MIND_OK;
   // (page-locked staging follows the device buffers' policy: small ones double from 1 MB -- hipHostFree + hipHostMalloc cost a millisecond)
   const size_t want = bytes < ((size_t)64 << 20) ? std::max<size_t>(2 * bytes, (size_t)1 << 20) : bytes + bytes / 2 + 4096;
-  if (hipHostMalloc(&c->pl_pin[which], want, hipHostMallocDefault) != hipSuccess)
-    return fail(c, MIND_ENOMEM, "hipHostMalloc(%zu) failed", want);
-  c->pl_pin_cap[which] = want;
+  if (c->pl_pin[which].alloc(want) != hipSuccess) return fail(c, MIND_ENOMEM, "hipHostMalloc(%zu) failed", want);
   return MIND_OK;
 }
 
@@ -158,7 +154,7 @@ struct PlanRun {
 int PlanRun::pl_side_hop(hipStream_t &rs) {
   rs = st;
   if (c->side && !dist) {
-    if (!c->ev_root) HIPCHK(c, hipEventCreateWithFlags(&c->ev_root, hipEventDisableTiming));
+    if (!c->ev_root) HIPCHK(c, c->ev_root.create(hipEventDisableTiming));
     HIPCHK(c, hipEventRecord(c->ev_root, st));
     HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_root, 0));
     rs = c->side;
@@ -216,7 +212,7 @@ int PlanRun::pl_root_raw() {
   const RootLayout &o = ro;
   const size_t OBS = RB_T;
   int rc;
-  float *h = (float *)c->pl_pin[0];
+  float *h = c->pl_pin[0].as<float>();
   memcpy(h + o.types, in->types, a * OBS * 7 * sizeof(float));
   memcpy(h + o.tl, in->target_lane, P * 2 * sizeof(float));
   memcpy(h + o.ti, in->target_lane_info, P * 12 * sizeof(float));
@@ -252,7 +248,7 @@ int PlanRun::pl_root_raw() {
     HIPCHK(c, hipGetLastError());
     return pl_frames_back(d + o.fr, 1, rs);      // the root's frame comes back while the first predictor call runs
   };
-  if (c->root_head && c->side && !dist) {
+  if (c->ct.root_head && c->side && !dist) {
     c->enc_pre = lanes; c->enc_post = hist;
     return MIND_OK;
   }
@@ -265,7 +261,7 @@ int PlanRun::pl_root_raw() {
 int PlanRun::pl_root_host() {
   const RootLayout &o = ro;
   const size_t OBS = RB_T;
-  float *h = (float *)c->pl_pin[0];
+  float *h = c->pl_pin[0].as<float>();
   memcpy(h + o.actors, in->actors, a * 14 * 48 * sizeof(float));
   memcpy(h + o.ctrs, in->actor_ctrs, a * 2 * sizeof(float));
   memcpy(h + o.vecs, in->actor_vecs, a * 2 * sizeof(float));
@@ -326,9 +322,9 @@ int PlanRun::pl_round_buffers(int round) {
   // unsharded: the round's last kernel writes the decisions where the host reads them (same layout as the device buffer)
   h_mirror = nullptr; h_gen = nullptr;
   round_no = round;
-  if (!dist && c->dec_mirror) {
+  if (!dist && c->ct.dec_mirror) {
     if ((rc = pl_pin(c, 2, n_back * sizeof(float) + 64))) return rc;      // (+ the generation word of the polled decisions)
-    h_mirror = (float *)c->pl_pin[2];
+    h_mirror = c->pl_pin[2].as<float>();
   }
   tabb = &c->pl_tab[round & 1];
   bS = ((size_t)Bk * sizeof(AimeScene) + 15) & ~(size_t)15; bI = ((size_t)A * sizeof(int) + 15) & ~(size_t)15;
@@ -340,7 +336,7 @@ int PlanRun::pl_round_buffers(int round) {
   if ((rc = pl_pin(c, 1, tab_bytes + 3 * (size_t)6 * Bmax * sizeof(int) + 64))) return rc;
   if ((int)c->pl_world.size() <= round) c->pl_world.resize(round + 1);
   d_world = nullptr;
-  chunk = pl_chunk(a + l + 1, pred_edge_pair_bytes(c->pt, c->pair_prec), c->plan_chunk_mb, Bk);
+  chunk = pl_chunk(a + l + 1, pred_edge_pair_bytes(c->pt, c->pair_prec), c->ct.plan_chunk_mb, Bk);
   if (Bk > 0) {
     if ((rc = ensure(c, c->pl_world[round], (size_t)A * 6 * AIME_T * 6 * sizeof(float)))) return rc;
     d_world = (float *)c->pl_world[round].p;
@@ -349,10 +345,10 @@ int PlanRun::pl_round_buffers(int round) {
     if ((rc = ensure(c, c->pl_pred, (n_cls + (size_t)cbm * a * 6 * AIME_T * 7) * sizeof(float)))) return rc;
   }
   tables_done = false;
-  all_small = c->tab_small && std::min(chunk, std::max(Bk, 1)) <= AIME_SMALL;
+  all_small = c->ct.tab_small && std::min(chunk, std::max(Bk, 1)) <= AIME_SMALL;
   // a round of one launch whose decisions are mirrored: its last kernel marks them complete and the host polls (pl_round_decisions).  The word
   // is cleared here, before the launch: slot 2's last writer (the previous round's kernel, the previous plan's read-back) has been waited for
-  if (h_mirror && c->dec_poll && Bk > 0 && chunk >= Bk) {
+  if (h_mirror && c->ct.dec_poll && Bk > 0 && chunk >= Bk) {
     if (!c->pl_cnt.p) {
       if ((rc = ensure(c, c->pl_cnt, 64))) return rc;
       HIPCHK(c, hipMemsetAsync(c->pl_cnt.p, 0, 64, st));      // (once: the block that arrives last re-arms the counter)
@@ -374,7 +370,7 @@ int PlanRun::pl_round_tables() {
   // ---- the frames of the re-based scenes (ROT, ORIG, TGT_PTS; queued behind k_aime_rebase / the unpacking): needed by the scene tables
   if (frames_pending) {
     HIPCHK(c, hipEventSynchronize(c->ev_pl));
-    const float *fr = (const float *)c->pl_pin[3];
+    const float *fr = c->pl_pin[3].as<float>();
     for (int b = 0; b < g.B; ++b) {
       memcpy(batch[b].rot, fr + (size_t)b * 28, 4 * sizeof(float));
       memcpy(batch[b].orig, fr + (size_t)b * 28 + 4, 2 * sizeof(float));
@@ -384,7 +380,7 @@ int PlanRun::pl_round_tables() {
   }
   if (Bk <= 0) return MIND_OK;
   // the scene tables of the whole block, one upload; agent rows are counted from the start of a scene's chunk
-  char *h = (char *)c->pl_pin[1];
+  char *h = c->pl_pin[1].as<char>();
   AimeScene *hs = (AimeScene *)h;
   int *as = (int *)(h + bS);
   float *sp = (float *)(h + bS + bI);
@@ -401,7 +397,7 @@ int PlanRun::pl_round_tables() {
   }
   if (all_small) {
     // (the glue kernels take these tables by value: AimeSmall)
-  } else if (c->pl_tab_side) {
+  } else if (c->ct.pl_tab_side) {
     HIPCHK(c, hipMemcpyAsync(tabb->p, h, tab_bytes, hipMemcpyHostToDevice, c->pl_copy));
     HIPCHK(c, hipEventRecord(c->ev_tab, c->pl_copy));
     HIPCHK(c, hipStreamWaitEvent(st, c->ev_tab, 0));
@@ -471,7 +467,7 @@ int PlanRun::pl_round_launch() {
     AimeSmall sm;
     memset(&sm, 0, sizeof(sm));
     if (all_small) {
-      const char *h = (const char *)c->pl_pin[1];
+      const char *h = c->pl_pin[1].as<char>();
       memcpy(sm.s, (const AimeScene *)h + c0, (size_t)cb * sizeof(AimeScene));
       memcpy(sm.prob, (const float *)(h + bS + bI) + c0, (size_t)cb * sizeof(float));
       sm.n = cb; sm.a = a;
@@ -482,7 +478,7 @@ int PlanRun::pl_round_launch() {
     unsigned *hh_ = h_mirror ? (unsigned *)(h_mirror + (size_t)Bmax * 12) + (size_t)c0 * 12 : nullptr;
     const float pf_ = in->prob_floor > 0.f ? in->prob_floor : 0.001f;
     const AimeDone dn{h_gen ? (unsigned *)c->pl_cnt.p : nullptr, h_gen, want_gen};
-    if (c->glue_fused) {
+    if (c->ct.glue_fused) {
       // pruning decisions + branch-time bits in one launch (every block derives its scene's decisions itself)
       hipLaunchKernelGGL(k_aime_select_branch, dim3(cb * AIME_K), dim3(64), 0, st, t_sc, d_cls, t_prob, topo_c, ego_c, 1, in->dist_thres, pf_, w_c, sel_c, selp_c,
                          hit_c, hs_, hp_, hh_, sm, dn);
@@ -521,7 +517,7 @@ int PlanRun::pl_round_decisions(const float *&h_dec) {
     HIPCHK(c, hipStreamSynchronize(st));
   }
   TR("round: decisions on the host");
-  h_dec = (const float *)c->pl_pin[2];
+  h_dec = c->pl_pin[2].as<float>();
   return MIND_OK;
 }
 
@@ -557,10 +553,10 @@ int PlanRun::pl_rebase_next() {
   w_pos = (float *)c->pl_win[nxt].p; w_ang = w_pos + n_wpos; w_vel = w_ang + n_wang;
   d_in = (float *)c->pl_in[nxt].p;
   if (Sm <= 0) return MIND_OK;
-  int *hi_ = (int *)((char *)c->pl_pin[1] + tab_bytes);
+  int *hi_ = (int *)(c->pl_pin[1].as<char>() + tab_bytes);
   memcpy(hi_, r.win.data(), 3 * (size_t)Sm * sizeof(int));
   // (a small branch set: k_aime_windows reads its three ints per scene from the page-locked staging itself -- no copy in front of it)
-  const bool tab_host = c->tab_host_max > 0 && (size_t)Sm * a <= (size_t)c->tab_host_max;
+  const bool tab_host = c->ct.tab_host_max > 0 && (size_t)Sm * a <= (size_t)c->ct.tab_host_max;
   if (!tab_host) HIPCHK(c, hipMemcpyAsync((char *)tabb->p + tab_bytes, hi_, 3 * (size_t)Sm * sizeof(int), hipMemcpyHostToDevice, st));
   const int *d_idx = tab_host ? (const int *)hi_ : (const int *)((const char *)tabb->p + tab_bytes);
   float *pos0 = w_pos + s0 * a * OBS * 2, *ang0 = w_ang + s0 * a * OBS, *vel0 = w_vel + s0 * a * OBS * 2;
@@ -665,7 +661,7 @@ int PlanRun::pl_next_inputs() {
   };
   const float *d_fr = d_in + q.fr;
   const auto back = [this, d_fr, S](hipStream_t rs) { return pl_frames_back(d_fr, (size_t)S, rs); };
-  if (c->round_head && c->side && !dist) {
+  if (c->ct.round_head && c->side && !dist) {
     c->enc_pre = rep; c->enc_post = back;
   } else {
     hipStream_t rs;
@@ -704,14 +700,14 @@ int PlanRun::pl_pack_results() {
     const size_t o_rows = (n_tab + 255) & ~(size_t)255;
     if ((rc = ensure(c, c->pl_flat, o_rows + n_res * sizeof(float)))) return rc;
     if ((rc = pl_pin(c, 0, n_tab))) return rc;          // (the root upload of this plan completed rounds ago)
-    char *h = (char *)c->pl_pin[0];
+    char *h = c->pl_pin[0].as<char>();
     const float *world_of_round[32];
     for (size_t i = 0; i < c->pl_world.size() && i < 32; ++i) world_of_round[i] = (const float *)c->pl_world[i].p;
     F.pack(h, world_of_round);
     G.pack(h + o_g, world_of_round);
     TR("end: trees flattened on the host");
     // (few jobs: the two packing kernels read their tables from the page-locked staging themselves)
-    const bool tab_host = !dist && c->tab_host_max > 0 && F.job_of_block.size() + G.job_of_block.size() <= (size_t)c->tab_host_max;
+    const bool tab_host = !dist && c->ct.tab_host_max > 0 && F.job_of_block.size() + G.job_of_block.size() <= (size_t)c->ct.tab_host_max;
     if (n_tab && !tab_host) HIPCHK(c, hipMemcpyAsync(c->pl_flat.p, h, n_tab, hipMemcpyHostToDevice, st));
     char *d = tab_host ? h : (char *)c->pl_flat.p;
     float *d_rows = (float *)((char *)c->pl_flat.p + o_rows), *d_fmean = d_rows + n_rows, *d_fcov = d_fmean + Mtot * a * 2;
@@ -729,13 +725,13 @@ int PlanRun::pl_pack_results() {
     if (dist && (rc = pl_exchange(c, MIND_XCHG_ALLREDUCE, d_rows, d_rows, n_res * sizeof(float)))) return rc;
     c->plan.dev_fmean = d_fmean; c->plan.dev_fcov = d_fcov;
     if ((rc = pl_pin(c, 2, n_res * sizeof(float)))) return rc;
-    float *hp = (float *)c->pl_pin[2];
+    float *hp = c->pl_pin[2].as<float>();
     if (want_solves) {
       // k_ilqr right behind k_aime_flat: the cost trees' agent arrays stay where that kernel wrote them (il_solve reads them on the device)
       // and the host builds the solver's tables while it runs.  What only the CALLER wants -- the finished branches' rows (k_aime_gather) and the
       // plan's read-back (rows | flat means | sigmas: the tree objects, the candidate evaluation) -- is queued on the copy stream AFTER the
       // solves have been launched: beside k_ilqr on the device, and behind its launch on the host (the five calls stood 10 us in front of it).
-      if (!c->ev_rows) HIPCHK(c, hipEventCreateWithFlags(&c->ev_rows, hipEventDisableTiming));
+      if (!c->ev_rows) HIPCHK(c, c->ev_rows.create(hipEventDisableTiming));
       HIPCHK(c, hipEventRecord(c->ev_tab, st));          // (the job tables are up, the flat arrays written)
       TR("end: flat kernel queued");
       pl_begin_solves();
@@ -803,9 +799,9 @@ extern "C" int mind_aime_plan(mind_ctx *c, const mind_aime_plan_in *in, mind_aim
   c->plan.agents = 0;
   c->plan.gen += 1;
   p.book.reset(in->pred_len, in->max_depth, p.a, p.XW, p.XR, p.dist);      // (the previous plan's cost trees are gone whatever happens below)
-  if (!c->ev_pl) HIPCHK(c, hipEventCreateWithFlags(&c->ev_pl, hipEventDisableTiming));
-  if (!c->ev_tab) HIPCHK(c, hipEventCreateWithFlags(&c->ev_tab, hipEventDisableTiming));
-  if (!c->pl_copy) HIPCHK(c, hipStreamCreateWithFlags(&c->pl_copy, hipStreamNonBlocking));
+  if (!c->ev_pl) HIPCHK(c, c->ev_pl.create(hipEventDisableTiming));
+  if (!c->ev_tab) HIPCHK(c, c->ev_tab.create(hipEventDisableTiming));
+  if (!c->pl_copy) HIPCHK(c, c->pl_copy.create());
   struct HookGuard { mind_ctx *c; ~HookGuard() { c->enc_pre = nullptr; c->enc_post = nullptr; } } hook_guard{c};      // (they capture this call's PlanRun)
   if ((rc = p.pl_root())) return rc;
   memset(out, 0, sizeof(*out));

@@ -1,4 +1,4 @@
-// What a tree-iLQR call decides before it touches the device: the solver's knobs (IlqrTuning), the launch form (il_choose -> IlqrChoice), the
+// What a tree-iLQR call decides before it touches the device: the solver's knobs (IlqrTuning, tuning.h), the launch form (il_choose -> IlqrChoice), the
 // index tables of one cost tree (il_tree_tables -> IlTables) and where everything lies in the device arena (il_layout -> IlArena, il_stage_ints).
 // No HIP call, no context: ilqr_host.hip's steps switch on these records and read no knob themselves; tests read the first three through
 // mind_debug_ilqr_plan.  Included by mind_hip.hip behind ilqr_kernels.hip (IL_SLOTS, IL_SPEC, IL_THREADS, the sizes of its structs).
@@ -8,48 +8,7 @@
 #include <cstring>
 #include <vector>
 
-struct IlqrTuning {
-  // nodes per forward step of a narrow tree's line search ("ilqr_chunk"; 0: whole segments, the default).  Measured on the recorded
-  // demo_1 loop: chunks of 6 / 8 / 12 nodes cost 2.10 / 2.05 / 2.04 ms per launch against 1.99 for whole segments (round 3: the cost
-  // waves shared the SIMDs' float64 pipe with five state-chain waves); with the chains of a level packed into ONE wave and the cost
-  // chunks kept off its SIMD (round 4) still 2.12 / 2.00 / 2.02 against 1.89: every extra forward step pays a rollout prologue (parent
-  // state, first operands: two dependent round trips) and a barrier, more than the shorter cost tail saves (profiles/r04x_*)
-  int ilqr_chunk = 0;
-  // wide cost trees: workgroups per tree (halved until every workgroup of the launch is resident; cfg4 full tree, six trees per launch:
-  // 8.33 / 7.40 / 7.37 / 7.63 ms per plan with 8 / 16 / 24 / 32, profiles/r03an), node count from which they are used (mind_set_tuning)
-  int ilqr_wgs = 16, ilqr_multi_min = 192, ilqr_wgs_big = 32, ilqr_big_min = 12288;
-  // narrow cost trees (below ilqr_multi_min nodes): workgroups per tree that take the fit's Levenberg-Marquardt slots (k_ilqr<GEN, 2>: a master +
-  // ilqr_slots - 1 followers, one slot each; 1 = everything in one workgroup).  "ilqr_slots" / MIND_ILQR_SLOTS
-  int ilqr_slots = 10;
-  // ... and one more workgroup per tree that differentiates a pass's first candidate while the master prices the candidates (il_speculate; the
-  // master swaps derivative sets instead of running its derivative pass when that candidate is the accepted one).  "ilqr_spec_deriv" / MIND_ILQR_SPEC_DERIV
-  bool ilqr_spec_deriv = true;
-  // tree-iLQR launches of at most this many nodes in all write their results (xs, us, statistics) to the host staging themselves at the kernel's
-  // end instead of two copies behind it (0 = always copies).  "ilqr_host_out_max" / MIND_ILQR_HOST_OUT_MAX
-  long ilqr_host_out_max = 4096;
-  // candidates per workgroup of a scoring launch (k_ilqr_score; a power of two 1 .. 64, 0 = il_score_block decides).  Same bits for every
-  // value.  "ilqr_score_block"
-  int ilqr_score_block = 0;
-  // tests: launch a wide tree without its last workgroups / let the followers of a narrow tree leave at once
-  bool ilqr_test_starve = false;
-};
-
-// these knobs' branches of mind_set_tuning (and of the MIND_ILQR_* variables): false when `name` is none of them
-static bool ilqr_tuning_set(IlqrTuning &t, const char *name, int value) {
-  const auto is = [name](const char *k) { return strcmp(name, k) == 0; };
-  if (is("ilqr_chunk")) t.ilqr_chunk = value < 0 ? 0 : value;
-  else if (is("ilqr_wgs")) t.ilqr_wgs = value < 1 ? 1 : (value > 32 ? 32 : value);
-  else if (is("ilqr_multi_min")) t.ilqr_multi_min = value;
-  else if (is("ilqr_wgs_big")) t.ilqr_wgs_big = value < 1 ? 1 : (value > 32 ? 32 : value);
-  else if (is("ilqr_big_min")) t.ilqr_big_min = value;
-  else if (is("ilqr_slots")) t.ilqr_slots = value < 1 ? 1 : (value > IL_SLOTS ? IL_SLOTS : value);
-  else if (is("ilqr_spec_deriv")) t.ilqr_spec_deriv = value != 0;
-  else if (is("ilqr_host_out_max")) t.ilqr_host_out_max = value < 0 ? 0 : value;
-  else if (is("ilqr_score_block")) { t.ilqr_score_block = 0; for (int b = 1; b <= 64 && value > 0; b <<= 1) if (b <= value) t.ilqr_score_block = b; }
-  else if (is("ilqr_test_starve")) t.ilqr_test_starve = value != 0;
-  else return false;
-  return true;
-}
+#include "tuning.h"
 
 // The launch of one call.  form 0: one workgroup per tree (k_ilqr<GEN, 0>; always in the generic mode, and what a cost evaluation reports);
 // form 1: wide trees, G workgroups share a tree's items (k_ilqr<false, 1>); form 2: narrow trees, a master + GS - 1 followers take a tree's

@@ -49,7 +49,7 @@ __global__ __launch_bounds__(256) void k_upload(const up_u4 *__restrict__ src, u
 }
 static int pl_upload(mind_ctx *c, void *dst, const void *pinned_src, size_t bytes, hipStream_t s) {
   if (!bytes) return MIND_OK;
-  if (c->upload_kernel_max > 0 && bytes <= (size_t)c->upload_kernel_max && bytes % 16 == 0 && (uintptr_t)dst % 16 == 0 && (uintptr_t)pinned_src % 16 == 0) {
+  if (c->ct.upload_kernel_max > 0 && bytes <= (size_t)c->ct.upload_kernel_max && bytes % 16 == 0 && (uintptr_t)dst % 16 == 0 && (uintptr_t)pinned_src % 16 == 0) {
     const size_t n16 = bytes / 16;
     hipLaunchKernelGGL(k_upload, dim3((unsigned)std::min<size_t>((n16 + 255) / 256, 256)), dim3(256), 0, s, (const up_u4 *)pinned_src, (up_u4 *)dst, n16);
     HIPCHK(c, hipGetLastError());
@@ -67,14 +67,11 @@ static int il_field_prepare(mind_ctx *c, const mind_ilqr_cfg *cfg, const double 
   const size_t nin = (size_t)W + H + 2 * (size_t)n_lane_pts, nd = nin + (size_t)W * H;
   int rc;
   if ((rc = ensure(c, c->il_field, nd * sizeof(double)))) return rc;
-  if (c->il_field_pin_cap < nin * sizeof(double)) {
-    if (c->il_field_pin) (void)hipHostFree(c->il_field_pin);
-    c->il_field_pin = nullptr; c->il_field_pin_cap = 0;
-    if (hipHostMalloc(&c->il_field_pin, 2 * nin * sizeof(double), hipHostMallocDefault) != hipSuccess) { c->il_field_pin = nullptr; return MIND_OK; }
-    c->il_field_pin_cap = 2 * nin * sizeof(double);
+  if (c->il_field_pin.cap < nin * sizeof(double)) {
+    if (c->il_field_pin.alloc(2 * nin * sizeof(double)) != hipSuccess) return MIND_OK;
   }
-  if (!c->ev_field) HIPCHK(c, hipEventCreateWithFlags(&c->ev_field, hipEventDisableTiming));
-  double *h = (double *)c->il_field_pin, ox, oy;
+  if (!c->ev_field) HIPCHK(c, c->ev_field.create(hipEventDisableTiming));
+  double *h = c->il_field_pin.as<double>(), ox, oy;
   il_make_grid(W, H, cfg->grid_res, x0, h, h + W, ox, oy);
   memcpy(h + W + H, lane, 2 * (size_t)n_lane_pts * sizeof(double));
   double *d = (double *)c->il_field.p;
@@ -333,7 +330,7 @@ static int il_stage(mind_ctx *c, IlRun &R) {
   R.n_xs = L0.stats - L0.xs;
   R.n_hx = R.n_xs + (size_t)2 * IL_NSTAT * n_trees; R.n_us = (size_t)R.Mtot * 2;
   if ((rc = pl_pin(c, 5, (R.n_hx + R.n_us + 2) * sizeof(double) + (size_t)n_trees * sizeof(unsigned)))) return rc;
-  R.hx = (double *)c->pl_pin[5]; R.hus = R.hx + R.n_hx;
+  R.hx = c->pl_pin[5].as<double>(); R.hus = R.hx + R.n_hx;
   R.h_abort = (unsigned *)(R.hus + R.n_us);
   R.h_done = R.h_abort + 4;               // (behind the two doubles kept for the abort word)
   c->il_early = mind_ctx::IlEarly();
@@ -413,7 +410,7 @@ static int il_upload(mind_ctx *c, IlRun &R, hipStream_t st) {
     HIPCHK(c, hipMemcpyAsync(R.base + A.tree[t].field, R.q.trees[t].field, (size_t)R.q.trees[t].n_nodes * R.W * R.H * sizeof(double), hipMemcpyHostToDevice, st));
   int rc;
   if ((rc = pl_pin(c, 4, A.o_work))) return rc;
-  char *up = (char *)c->pl_pin[4];
+  char *up = c->pl_pin[4].as<char>();
   memset(up, 0, A.o_work);
   memcpy(up, c->il_img.hD.data(), A.bytesIn);
   if (A.bytesF) memcpy(up + A.bytesIn, c->il_img.hF.data(), A.bytesF);
@@ -591,7 +588,7 @@ static int il_gains(mind_ctx *c, const IlRun &R, hipStream_t st) {
   const size_t span = A.o_gbad + (size_t)n_trees - A.o_gk;
   int rc;
   if ((rc = pl_pin(c, 5, span * sizeof(double)))) return rc;      // (grows the staging il_stage sized for a solve; this call uses none of that)
-  const double *h = (const double *)c->pl_pin[5];
+  const double *h = c->pl_pin[5].as<double>();
   HIPCHK(c, hipMemcpyAsync(c->pl_pin[5], R.Dp(A.o_gk), span * sizeof(double), hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));
   const struct { double *dst; size_t src, n; } outs[8] = {{o->k, A.o_gk, 2 * M}, {o->K, A.o_gK, 12 * M}, {o->dV, A.o_gdv, M}, {o->V_x, A.o_gvx, 6 * M},
@@ -647,7 +644,7 @@ static int il_launch(mind_ctx *c, const IlRun &R, hipStream_t st, IlPending &P) 
     P.tree[t] = {q.trees[t].n_nodes, T.nl, T.nseg, T.nsl, T.maxls, R.n_agents[t], R.Dp(A.tree[t].trace)};
   }
   if (c->profiling) {
-    if (!c->ev_il0) { HIPCHK(c, hipEventCreate(&c->ev_il0)); HIPCHK(c, hipEventCreate(&c->ev_il1)); }
+    if (!c->ev_il0) { HIPCHK(c, c->ev_il0.create()); HIPCHK(c, c->ev_il1.create()); }
     HIPCHK(c, hipEventRecord(c->ev_il0, st));
   }
   c->ilqr_trees = n_trees; c->ilqr_multi = ch.wgs_per_tree; c->ilqr_ms = 0.f;
@@ -831,8 +828,9 @@ extern "C" int mind_debug_ilqr_plan(const char *const *knob_names, const int *kn
       cap < 0 || (cap > 0 && !out))
     return MIND_EINVAL;
   IlqrTuning t;
+  const TnRefs own{nullptr, &t, nullptr};      // (the solver's knobs alone: any other name is rejected)
   for (int k = 0; k < n_knobs; ++k)
-    if (!knob_names[k] || !ilqr_tuning_set(t, knob_names[k], knob_values[k])) return MIND_EINVAL;
+    if (!knob_names[k] || !tn_set(own, knob_names[k], knob_values[k])) return MIND_EINVAL;
   int maxM = 0;
   long Mtot = 0;
   for (int i = 0; i < n_trees; ++i) {

@@ -506,7 +506,7 @@ int cycle_plan(mind_cycle *L) {
     //      arrive (evaluate_traj_tree of one tree is independent of the others), beside the trees the device is still solving -- only the
     //      last one's evaluation stays between the kernel's end and the chosen control
     const mind_ctx::IlEarly E = c->il_early;
-    if (c->early_eval && E.done && E.n_trees == nt && E.nodes == (long)M) {
+    if (c->ct.early_eval && E.done && E.n_trees == nt && E.nodes == (long)M) {
       L->costs.assign(nt, 0.0);
       L->early_seen.assign(nt, 0);
       const void *elane_e = d.eval_lane_is_f32 ? (const void *)L->eval_lane_f32.data() : (const void *)L->eval_lane_f64.data();

@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <string>
 #include <thread>
 #include <atomic>
@@ -42,14 +43,40 @@
 #include "weight_pack.h"
 #include "aime_kernels.hip"
 
-namespace {
+static_assert(TN_RA == RA && TN_IL_SLOTS == IL_SLOTS, "tuning.h restates the two kernel constants its clamps need");
 
-struct DevBuf {
-  void *p = nullptr;
+// Owners of the context's HIP handles: each releases what it holds in its destructor and is move-only, so a context (or a vector of them)
+// gives everything back when it goes, whichever path it goes by.  p is the raw handle (an owner also converts to it, where a HIP call or a
+// kernel argument wants one), cap the bytes behind it for the two kinds that are memory.  live_handles counts acquisitions less releases
+// over the process (mind_debug_live_handles): what a leak test can read on a shared device.
+static std::atomic<long> live_handles{0};
+
+template <class H, hipError_t (*Release)(H)> struct Owned {
+  H p = nullptr;
   size_t cap = 0;
+  Owned() = default;
+  Owned(Owned &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+  Owned &operator=(Owned &&o) noexcept { if (this != &o) { reset(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; } return *this; }
+  ~Owned() { reset(); }
+  operator H() const { return p; }
+  template <class T> T *as() const { return (T *)p; }
+  void reset() {
+    if (p) { (void)Release(p); live_handles.fetch_sub(1, std::memory_order_relaxed); }
+    p = nullptr; cap = 0;
+  }
+  hipError_t took(hipError_t e, size_t bytes = 0) {      // the result of the HIP call that just filled p (after a reset)
+    if (e == hipSuccess) { live_handles.fetch_add(1, std::memory_order_relaxed); cap = bytes; } else p = nullptr;
+    return e;
+  }
 };
-
-}  // namespace
+struct Event : Owned<hipEvent_t, hipEventDestroy> { hipError_t create(unsigned flags = hipEventDefault) { reset(); return took(hipEventCreateWithFlags(&p, flags)); } };
+struct Stream : Owned<hipStream_t, hipStreamDestroy> { hipError_t create() { reset(); return took(hipStreamCreateWithFlags(&p, hipStreamNonBlocking)); } };
+struct Pinned : Owned<void *, hipHostFree> {      // page-locked host memory
+  hipError_t alloc(size_t bytes, unsigned flags = hipHostMallocDefault) { reset(); return took(hipHostMalloc(&p, bytes, flags), bytes); }
+};
+struct DevBuf : Owned<void *, hipFree> {          // device memory (ensure / ensure_exact below keep their growth policy over alloc)
+  hipError_t alloc(size_t bytes) { reset(); return took(hipMalloc(&p, bytes), bytes); }
+};
 
 // job / token tables of one batch shape (scene sizes), resident on the device
 struct TableSet {
@@ -64,20 +91,21 @@ struct TableSet {
 
 struct mind_ctx {
   int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
+  hipStream_t stream = nullptr;       // the caller's
   // internal side stream: the lane encoders run beside the actor encoder; always fenced against `stream` with
   // events on both sides, so callers only ever see work ordered on `stream`
-  hipStream_t side = nullptr;
-  hipEvent_t ev_side = nullptr, ev_main = nullptr, ev_stage = nullptr, ev_tgt = nullptr, ev_cls = nullptr;
+  Stream side;
+  Event ev_side, ev_main, ev_stage, ev_tgt, ev_cls;
   std::vector<char> aime_stage;   // host staging of mind_aime_world's small tables (guarded by ev_stage)
   bool aime_stage_busy = false;
   std::string err;
   // weights: the packed device blob and the kernels' pointer tables into it (weight_pack.h, weight_tables.h); valid while have_weights
-  float *wdev = nullptr;
+  DevBuf wdev;
   bool have_weights = false;
   WeightTables W = {};
-  PredTuning pt;      // the predictor's kernel-selection knobs (pred_choice.h)
+  // the knobs (tuning.h): the predictor's kernel selection, the tree-iLQR solver's launch, the context's own
+  PredTuning pt; IlqrTuning it; CtxTuning ct;
+  TnRefs knobs() { return {&pt, &it, &ct}; }
   // the decoder's curve basis (mind_set_decoder_basis): which tables the blob entries dec.T / dec.Tp hold and which vel formula the heads run;
   // survives mind_weights_load.  mind_curve_eval's basis rows on the device, and the (basis, tau) they were evaluated for
   int dec_basis = MIND_BASIS_BEZIER;
@@ -91,7 +119,7 @@ struct mind_ctx {
   // ([TL_NSTAGE]: the one-kernel forms) from HIP events around every launch with profiling on
   int last_tok_lw = 0, last_tok_launches = 0, last_tok_chunks = 0;
   float tok_ms = 0.f, tok_stage_ms[TL_NSTAGE + 1] = {};
-  std::vector<hipEvent_t> ev_tok;
+  std::vector<Event> ev_tok;
   std::vector<int> ev_tok_tag;
   // job / token tables of recent mind_predict_batch calls (least-recently-used of MIND_TABLE_SETS): a call whose scene sizes
   // were seen before rebuilds, uploads and synchronises nothing -- the closed loop's rounds recur every cycle, a full tree's
@@ -99,33 +127,12 @@ struct mind_ctx {
   TableSet tabs[MIND_TABLE_SETS];
   long long tab_clock = 0;
   long long n_table_hits = 0;
-  IlqrTuning it;       // the tree-iLQR solver's launch knobs (ilqr_choice.h)
-  // uploads of at most this many bytes from the context's page-locked staging run as a kernel on the consumer's queue (pl_upload; 0 = always
-  // hipMemcpyAsync).  "upload_kernel_max" / MIND_UPLOAD_KERNEL_MAX
-  int upload_kernel_max = 1 << 20;
-  // mind_aime_plan, unsharded: k_aime_branch writes a round's decisions to the host staging itself (no copy behind it).  "dec_mirror" / MIND_DEC_MIRROR
-  bool dec_mirror = true;
-  // ... and its pruning decisions + branch-time bits come from one launch (k_aime_select_branch) instead of two.  "glue_fused" / MIND_GLUE_FUSED
-  bool glue_fused = true;
-  // ... and that kernel marks the mirrored decisions complete (a generation word behind them, counted in by its blocks on pl_cnt): the host
-  // polls the word instead of draining the stream and sizes the next round's buffers while it waits (unchunked rounds).  "dec_poll" / MIND_DEC_POLL
-  bool dec_poll = true;
+  // mind_aime_plan's polled decisions ("dec_poll"): the generation the host waits for, the counter k_aime_select_branch's blocks count in on
   unsigned dec_gen = 0;
   DevBuf pl_cnt;
-  // ... and what a round queues beside ActorNet -- the root's lane graph, world-frame histories and lane-distance field ("root_head" /
-  // MIND_ROOT_HEAD), a later round's repeated lane features ("round_head" / MIND_ROUND_HEAD), the frames' read-back -- is handed to the round's
-  // first predictor call, which launches ActorNet first: enc_pre goes on the side stream in front of the lane encoders, enc_post behind the
-  // target embedding (pred_encoders; both are the plan's, cleared when it returns)
-  bool root_head = true, round_head = true;
+  // what a round hands to its first predictor call ("root_head" / "round_head"), which launches ActorNet first: enc_pre goes on the side stream
+  // in front of the lane encoders, enc_post behind the target embedding (pred_encoders; both are the plan's, cleared when it returns)
   std::function<int(hipStream_t)> enc_pre, enc_post;
-  // mind_loop: price a candidate tree as soon as the pending tree-iLQR launch marks it complete, beside the trees still being solved.  "early_eval" / MIND_EARLY_EVAL
-  bool early_eval = true;
-  // ... and its small index tables (the branch set of a round, the job tables of the two packing kernels) are read by the kernels from the
-  // page-locked staging directly while they name at most this many workgroups (0 = always uploaded).  "tab_host_max" / MIND_TAB_HOST_MAX
-  int tab_host_max = 4096;
-  // ... and the scene tables of a round of at most AIME_SMALL scenes per chunk travel in the glue kernels' arguments (no upload between the
-  // predictor and k_aime_world).  "tab_small" / MIND_TAB_SMALL
-  bool tab_small = true;
   // host side of a tree-iLQR call (ilqr_host.hip), kept between calls so that a planning cycle does not allocate a hundred small vectors: the
   // trees' index tables and the image of the arena's uploaded doubles / floats / ints
   std::vector<IlTables> il_tab;
@@ -141,11 +148,8 @@ struct mind_ctx {
   // the ActorNet of the last mind_predict_batch (mind_last_actor_stats)
   int last_actor_lw = 0, last_actor_launches = 0, last_actor_chunks = 0;
   float actor_ms = 0.f;
-  hipEvent_t ev_act0 = nullptr, ev_act1 = nullptr;
+  Event ev_act0, ev_act1;
   int pair_prec = 3;            // arithmetic of the pair kernel: 0 = fp32 MFMA, 1 = bf16x3 (two-way split operands), 2 = bf16, 3 = bf16x6 (exact three-way split: fp32 class, default)
-  // mind_aime_plan: a round whose edge tensor would exceed this many MB goes through the predictor in chunks of scenes ("plan_chunk_mb";
-  // 96 GB by default: a third of the MI355X's HBM; the scenes of a round are independent, so chunking changes nothing but the launch sizes)
-  int plan_chunk_mb = 96 * 1024;
   std::vector<int> last_scene_n;   // tokens per scene of the last predictor call (mind_debug_read("edge") un-permutes with it)
   bool last_edge_tiled = false, last_edge_bf16 = false;
   // workspaces (grow only)
@@ -161,16 +165,14 @@ struct mind_ctx {
   // source makes hipMemcpyAsync wait for the stream to drain first), host result tables
   DevBuf pl_root, pl_in[2], pl_lf, pl_lrep, pl_pred, pl_small, pl_tab[2], pl_win[2];
   std::vector<DevBuf> pl_world;
-  void *pl_pin[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};     // [4], [5]: upload / read-back staging of the tree-iLQR calls; [6], [7]: sharded plan
-  size_t pl_pin_cap[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  hipEvent_t ev_pl = nullptr, ev_tab = nullptr, ev_root = nullptr;
+  Pinned pl_pin[8];     // [4], [5]: upload / read-back staging of the tree-iLQR calls; [6], [7]: sharded plan
+  Event ev_pl, ev_tab, ev_root;
   // the lane-distance field of a plan's contingency solves (gen_dist_field: a function of the ego position, the grid and the target lane --
   // all known when the plan starts), computed on the side stream beside the plan's first round instead of between its last decisions and
   // k_ilqr (il_field_prepare; adopted by il_solve when grid and lane are the ones it was made for)
   DevBuf il_field;
-  void *il_field_pin = nullptr;
-  size_t il_field_pin_cap = 0;
-  hipEvent_t ev_field = nullptr;
+  Pinned il_field_pin;
+  Event ev_field;
   bool il_field_valid = false;
   double il_field_key[5] = {0, 0, 0, 0, 0};       // x0[0], x0[1], W, H, res
   std::vector<double> il_field_lane;
@@ -181,10 +183,7 @@ struct mind_ctx {
   bool xforce = false;
   DevBuf x_send, x_recv, x_seg;
   long long x_collectives = 0, x_bytes = 0;
-  // "pl_tab_side" / MIND_PL_TAB_SIDE=1: the round tables travel on their own stream while the round's predictor runs instead of behind it
-  // on the context stream.  Measured on the recorded demo_1 loop: no difference (AIME 2.00 vs 2.01 ms per plan, profiles/r03ag) -- off.
-  hipStream_t pl_copy = nullptr;
-  bool pl_tab_side = false;
+  Stream pl_copy;       // the plan's own copy stream ("pl_tab_side": the round tables; the rows' read-back)
   std::vector<double> pl_sol_xs, pl_sol_us;          // results of the solves a plan began itself (mind_ilqr_finish_plan)
   std::vector<mind_ilqr_stats> pl_sol_stw, pl_sol_stf;
   // mind_aime_plan_begin / _finish: the plan on a thread of the library (state 0 idle, 1 running, 2 done)
@@ -206,18 +205,18 @@ struct mind_ctx {
   } plan;
   DevBuf pl_flat;
   DevBuf dec_xbuf, dec_bars;
-  unsigned *dec_abort = nullptr;      // host-visible abort word of its barriers (page-locked, mapped)
+  Pinned dec_abort;      // host-visible abort word of its barriers (page-locked, mapped)
   int rb_cur = 0, rb_gen = 0;     // re-basing arenas: which one the last call filled, its generation and geometry
   size_t rb_S = 0, rb_a = 0;
   // profiling
   bool profiling = false;
-  hipEvent_t ev_il0 = nullptr, ev_il1 = nullptr;   // around the tree-iLQR launch of the last call (profiling on)
+  Event ev_il0, ev_il1;   // around the tree-iLQR launch of the last call (profiling on)
   float ilqr_ms = 0.f;
   int ilqr_multi = 0, ilqr_trees = 0;
   // per-iteration traces of the last tree-iLQR call (mind_last_ilqr_trace): device address per tree, rows per phase, iterations run
   std::function<int()> il_finish;     // the pending half of a call begun with mind_ilqr_contingency_begin
   bool il_finish_owned = false;       // ... whose outputs are library buffers (the solves a plan began itself): may be drained and dropped
-  hipEvent_t ev_rows = nullptr;
+  Event ev_rows;
   std::vector<const double *> il_trace_dev;
   std::vector<int> il_trace_its;      // [tree][phase 2]
   int il_trace_cap = 0, il_trace_phases = 0;
@@ -226,21 +225,19 @@ struct mind_ctx {
   int n_pair_launch = 0;
   float pair_ms = 0.f;
   double pairs_done = 0.0;
-  std::vector<hipEvent_t> ev;
+  std::vector<Event> ev;
   // mind_aime_plan with profiling on: the pair-kernel events of its predictor calls are taken from this pool and read once, behind the
   // plan's last synchronisation (a stream drain per predictor call to read twelve events cost ~30 us per round of the timed plan)
   bool ev_defer = false;
-  std::vector<hipEvent_t> ev_pool;
+  std::vector<Event> ev_pool;
   size_t ev_pool_used = 0;
   std::vector<size_t> ev_pending;      // first pool index of every predictor call not read yet
-  // the launch clock (launch_clock.h, predict.hip): "prof_clock" / MIND_PROF_CLOCK 1 (default) = with profiling on, the kernels that take a slot
-  // pointer (the pair kernels, k_actor_mfma) are timed by stamps of their own workgroups and no HIP event is recorded around them; 0 = HIP
-  // events as before; 2 = both on the same launches (the cross-check: mind_debug_launch_times).  The ring on the device, its page-locked
-  // mirror, the wall clock's rate (0: no such clock -- events), sums of records read early, the per-launch times of the last read
-  int prof_clock = 1, wall_khz = 0;
+  // the launch clock ("prof_clock"; launch_clock.h, predict.hip): the ring on the device, its page-locked mirror, the wall clock's rate (0: no
+  // such clock -- events), sums of records read early, the per-launch times of the last read
+  int wall_khz = 0;
   LcRing lc;
   DevBuf lc_dev;
-  LcSlot *lc_host = nullptr;
+  Pinned lc_host;
   double lc_carry_ms[LC_KINDS] = {0, 0, 0};
   int lc_carry_n[LC_KINDS] = {0, 0, 0};
   std::vector<float> lc_last[LC_KINDS], ev_last[LC_KINDS];
@@ -271,21 +268,16 @@ static int fail(mind_ctx *c, int code, const char *fmt, ...) {
 
 static int ensure(mind_ctx *c, DevBuf &b, size_t bytes) {
   if (bytes <= b.cap) return MIND_OK;
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.cap = 0;
+  b.reset();
   // growth: a buffer is re-allocated (hipFree + hipMalloc: a device synchronisation each) whenever a plan needs more than any before it --
   // small buffers (demo-size scenes: the scene and tree-node counts of the first dozens of plans of a process creep upwards) double and start
   // at 1 MB, so that a closed loop stops re-allocating after its first plans (a fresh process ran its first 20 timed cycles at 2.1-2.6 ms of
   // AIME wall instead of 1.8, profiles/r05w_*); big arenas (the deep stress trees: hundreds of GB) keep the 25 % margin
-  size_t want = bytes < ((size_t)64 << 20) ? std::max<size_t>(2 * bytes, (size_t)1 << 20) : bytes + bytes / 4 + 4096;
-  hipError_t e = hipMalloc(&b.p, want);
-  if (e != hipSuccess) {
-    e = hipMalloc(&b.p, bytes);
-    want = bytes;
+  const size_t want = bytes < ((size_t)64 << 20) ? std::max<size_t>(2 * bytes, (size_t)1 << 20) : bytes + bytes / 4 + 4096;
+  if (b.alloc(want) != hipSuccess) {
+    const hipError_t e = b.alloc(bytes);
     if (e != hipSuccess) return fail(c, MIND_ENOMEM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
   }
-  b.cap = want;
   return MIND_OK;
 }
 
@@ -293,13 +285,32 @@ static int ensure(mind_ctx *c, DevBuf &b, size_t bytes) {
 static int ensure_exact(mind_ctx *c, DevBuf &b, size_t bytes, const char *what) {
   if (bytes <= b.cap) return MIND_OK;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.cap = 0;
-  if (hipMalloc(&b.p, bytes) != hipSuccess) return fail(c, MIND_ENOMEM, "hipMalloc(%zu) for %s failed", bytes, what);
-  b.cap = bytes;
+  if (b.alloc(bytes) != hipSuccess) return fail(c, MIND_ENOMEM, "hipMalloc(%zu) for %s failed", bytes, what);
   return MIND_OK;
 }
+
+// Every kernel that takes more dynamic LDS than the default limit, and how much.  The attribute is per device: set for every created context.
+struct KernelLds {
+  const void *kernel; size_t bytes;
+  template <class K> KernelLds(K *k, size_t b) : kernel((const void *)k), bytes(b) {}
+};
+static void set_kernel_attributes() {
+  const size_t pair = mind_pair_lds_bytes(), pair_bf = mind_pair_bf_lds_bytes(), actor_m = mind_actor_mfma_lds_bytes(), dec_m = mind_dec_actor_mfma_lds_bytes(),
+               il = il_lds_bytes(0), tok_m = mind_token_mfma_lds_bytes(), dec_s = mind_dec_scene_lds_bytes(), dec_a = mind_dec_actor_lds_bytes();
+  const KernelLds lds[] = {
+      {k_pair<0>, pair}, {k_pair<1>, pair}, {k_pair_bf<0, 3>, pair_bf}, {k_pair_bf<1, 3>, pair_bf}, {k_pair_bf<0, 1>, pair_bf}, {k_pair_bf<1, 1>, pair_bf},
+      {k_pair_t<0, 3>, pair_bf}, {k_pair_t<1, 3>, pair_bf}, {k_pair_t<0, 1>, pair_bf}, {k_pair_t<1, 1>, pair_bf}, {k_pair_t6<0>, pair_bf}, {k_pair_t6<1>, pair_bf},
+      {k_actor_net, mind_actor_lds_bytes()}, {k_actor_mfma<3>, actor_m}, {k_actor_mfma<6>, actor_m}, {k_actor_mfma<1>, actor_m},
+      {k_dec_actor_mfma<1>, dec_m}, {k_dec_actor_mfma<3>, dec_m}, {k_dec_actor_mfma<6>, dec_m}, {k_actor_f32<1>, mind_actor_f32_lds_bytes(1)}, {k_actor_f32<2>, mind_actor_f32_lds_bytes(2)},
+      {k_ilqr<true, 0>, il}, {k_ilqr<false, 1>, il}, {k_ilqr<false, 0>, il}, {k_ilqr<false, 2>, il}, {k_token_mfma<0>, tok_m}, {k_token_mfma<1>, tok_m},
+      {k_dec_scene, dec_s}, {k_dec_scene_mw, dec_s}, {k_dec_scene_c, dec_s}, {k_dec_cls, dec_s}, {k_dec_tgt, dec_s},
+      {k_dec_actor<0>, dec_a}, {k_dec_actor<1>, dec_a}, {k_dec_actor<2>, dec_a}, {k_dec_actor<2, 1>, dec_a}, {k_dec_actor<2, 2>, dec_a},
+  };
+  for (const KernelLds &k : lds) (void)hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.bytes);
+  lw_set_attributes();
+}
+
+static const char *const PAIR_PREC_NAMES[4] = {"f32", "bf16x3", "bf16", "bf16x6"};      // MIND_PAIR_PREC: a name or its number
 
 extern "C" int mind_ctx_create(int device, void *stream, mind_ctx **out) {
   if (!out) return MIND_EINVAL;
@@ -307,103 +318,26 @@ extern "C" int mind_ctx_create(int device, void *stream, mind_ctx **out) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return MIND_EHIP;
   if (device < 0 || device >= n) return MIND_EINVAL;
-  mind_ctx *c = new mind_ctx();
+  std::unique_ptr<mind_ctx> c(new mind_ctx());      // (an early return gives back whatever the context holds by then)
   c->device = device;
-  if (hipSetDevice(device) != hipSuccess) { delete c; return MIND_EHIP; }
+  if (hipSetDevice(device) != hipSuccess) return MIND_EHIP;
   // NULL = the device's default (null) stream, which is what torch.cuda.current_stream() is unless the
   // caller switched streams; everything the caller can observe is ordered on this stream.
   c->stream = (hipStream_t)stream;
-  if (hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking) != hipSuccess) c->side = nullptr;
-  if (c->side && hipEventCreateWithFlags(&c->ev_side, hipEventDisableTiming) != hipSuccess) { (void)hipStreamDestroy(c->side); c->side = nullptr; }
-  if (c->side && hipEventCreateWithFlags(&c->ev_main, hipEventDisableTiming) != hipSuccess) { (void)hipStreamDestroy(c->side); c->side = nullptr; }
-  if (c->side && hipEventCreateWithFlags(&c->ev_tgt, hipEventDisableTiming) != hipSuccess) { (void)hipStreamDestroy(c->side); c->side = nullptr; }
-  if (hipEventCreateWithFlags(&c->ev_stage, hipEventDisableTiming) != hipSuccess) { *out = nullptr; delete c; return MIND_EHIP; }
+  // the side stream and the three events that fence it: all of them, or no side stream
+  if (c->side.create() != hipSuccess || c->ev_side.create(hipEventDisableTiming) != hipSuccess || c->ev_main.create(hipEventDisableTiming) != hipSuccess ||
+      c->ev_tgt.create(hipEventDisableTiming) != hipSuccess)
+    c->side.reset();
+  if (c->ev_stage.create(hipEventDisableTiming) != hipSuccess) return MIND_EHIP;
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->n_cu = prop.multiProcessorCount;
   if (hipDeviceGetAttribute(&c->wall_khz, hipDeviceAttributeWallClockRate, device) != hipSuccess || c->wall_khz < 0) c->wall_khz = 0;
-  if (const char *pe = getenv("MIND_PROF_CLOCK")) c->prof_clock = std::min(2, std::max(0, atoi(pe)));
-  (void)hipFuncSetAttribute((const void *)k_pair<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_pair_lds_bytes());
-  (void)hipFuncSetAttribute((const void *)k_pair<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_pair_lds_bytes());
-  (void)hipFuncSetAttribute((const void *)k_pair_bf<0, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_pair_bf_lds_bytes());
-  (void)hipFuncSetAttribute((const void *)k_pair_bf<1, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_pair_bf_lds_bytes());
-  (void)hipFuncSetAttribute((const void *)k_pair_bf<0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_pair_bf_lds_bytes());
-  (void)hipFuncSetAttribute((const void *)k_pair_bf<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_pair_bf_lds_bytes());
-  (void)hipFuncSetAttribute((const void *)k_pair_t<0, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_pair_bf_lds_bytes());
-  (void)hipFuncSetAttribute((const void *)k_pair_t<1, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_pair_bf_lds_bytes());
-  (void)hipFuncSetAttribute((const void *)k_pair_t<0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_pair_bf_lds_bytes());
-  (void)hipFuncSetAttribute((const void *)k_pair_t<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_pair_bf_lds_bytes());
-  (void)hipFuncSetAttribute((const void *)k_pair_t6<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_pair_bf_lds_bytes());
-  (void)hipFuncSetAttribute((const void *)k_pair_t6<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_pair_bf_lds_bytes());
-  if (const char *te = getenv("MIND_PAIR_TILE")) c->pt.pair_tile = !(te[0] == '0');
-  if (const char *xe = getenv("MIND_XCD_ORDER")) c->pt.xcd_order = !(xe[0] == '0');
-
-  if (const char *pe = getenv("MIND_PAIR_PREC")) {
-    const std::string v = pe;
-    if (v == "f32" || v == "0") c->pair_prec = 0;
-    else if (v == "bf16x3" || v == "1") c->pair_prec = 1;
-    else if (v == "bf16" || v == "2") c->pair_prec = 2;
-    else if (v == "bf16x6" || v == "3") c->pair_prec = 3;
-  }
-  (void)hipFuncSetAttribute((const void *)k_actor_net, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_actor_lds_bytes());
-  (void)hipFuncSetAttribute((const void *)k_actor_mfma<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_actor_mfma_lds_bytes());
-  (void)hipFuncSetAttribute((const void *)k_actor_mfma<6>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_actor_mfma_lds_bytes());
-  (void)hipFuncSetAttribute((const void *)k_dec_actor_mfma<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_dec_actor_mfma_lds_bytes());
-  (void)hipFuncSetAttribute((const void *)k_dec_actor_mfma<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_dec_actor_mfma_lds_bytes());
-  (void)hipFuncSetAttribute((const void *)k_dec_actor_mfma<6>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_dec_actor_mfma_lds_bytes());
-  if (const char *se = getenv("MIND_ACTOR_SPLIT")) c->pt.actor_np = atoi(se) == 3 ? 3 : 6;
-  (void)hipFuncSetAttribute((const void *)k_actor_mfma<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_actor_mfma_lds_bytes());
-  if (const char *me = getenv("MIND_ENC_MFMA")) c->pt.enc_mfma = !(me[0] == '0');
-  if (const char *me = getenv("MIND_ACTOR_F32")) c->pt.actor_f32 = !(me[0] == '0');
-  if (const char *me = getenv("MIND_ACTOR_F32_MIN")) c->pt.actor_f32_min = atoi(me);
-  if (const char *me = getenv("MIND_ACTOR_LW_MIN")) c->pt.actor_lw_min = atoi(me);
-  lw_set_attributes();
-  (void)hipFuncSetAttribute((const void *)k_actor_f32<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_actor_f32_lds_bytes(1));
-  (void)hipFuncSetAttribute((const void *)k_actor_f32<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_actor_f32_lds_bytes(2));
-  if (const char *de = getenv("MIND_DEC_MFMA_MIN")) c->pt.dec_mfma_min = atoi(de);
-  if (const char *oe = getenv("MIND_DEC_OVERLAP")) c->pt.dec_overlap = !(oe[0] == '0');
-  (void)hipFuncSetAttribute((const void *)k_ilqr<true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)il_lds_bytes(0));
-  (void)hipFuncSetAttribute((const void *)k_ilqr<false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)il_lds_bytes(0));
-  (void)hipFuncSetAttribute((const void *)k_ilqr<false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)il_lds_bytes(0));
-  (void)hipFuncSetAttribute((const void *)k_ilqr<false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)il_lds_bytes(0));
-  if (const char *te = getenv("MIND_TOK_MFMA")) c->pt.tok_mfma = !(te[0] == '0');
-  if (const char *te = getenv("MIND_TOK_SMALL_MAX")) c->pt.tok_small_max = atoi(te);
-  if (const char *te = getenv("MIND_TOK_MERGE")) c->pt.tok_merge = !(te[0] == '0');
-  if (const char *te = getenv("MIND_DEC_MW")) c->pt.dec_mw = !(te[0] == '0');
-  if (const char *te = getenv("MIND_DEC_CLS_SIDE")) c->pt.dec_cls_side = !(te[0] == '0');
-  if (const char *te = getenv("MIND_TOK_BF_MIN_N")) c->pt.tok_bf_min_n = atoi(te);
-  if (const char *te = getenv("MIND_TOK_LW_MIN_N")) c->pt.tok_lw_min_n = atoi(te);
-  if (const char *te = getenv("MIND_TOK_LW_MIN")) c->pt.tok_lw_min = atoi(te);
-  if (const char *te = getenv("MIND_TGT_SIDE")) c->pt.tgt_side = !(te[0] == '0');
-  if (const char *te = getenv("MIND_PL_TAB_SIDE")) c->pl_tab_side = !(te[0] == '0');
-  (void)hipFuncSetAttribute((const void *)k_token_mfma<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_token_mfma_lds_bytes());
-  (void)hipFuncSetAttribute((const void *)k_token_mfma<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_token_mfma_lds_bytes());
-  if (const char *ce = getenv("MIND_PLAN_CHUNK_MB")) { const long v = atol(ce); if (v > 0) c->plan_chunk_mb = v; }
-  if (const char *we = getenv("MIND_TAB_SMALL")) c->tab_small = atoi(we) != 0;
-  if (const char *we = getenv("MIND_TAB_HOST_MAX")) c->tab_host_max = std::max(0, atoi(we));
-  if (const char *we = getenv("MIND_EARLY_EVAL")) c->early_eval = atoi(we) != 0;
-  if (const char *we = getenv("MIND_GLUE_FUSED")) c->glue_fused = atoi(we) != 0;
-  if (const char *we = getenv("MIND_DEC_MIRROR")) c->dec_mirror = atoi(we) != 0;
-  if (const char *we = getenv("MIND_DEC_POLL")) c->dec_poll = atoi(we) != 0;
-  if (const char *we = getenv("MIND_ROOT_HEAD")) c->root_head = atoi(we) != 0;
-  if (const char *we = getenv("MIND_ROUND_HEAD")) c->round_head = atoi(we) != 0;
-  if (const char *we = getenv("MIND_UPLOAD_KERNEL_MAX")) c->upload_kernel_max = std::max(0, atoi(we));
-  // (the same clamps as mind_set_tuning: one function sets a knob)
-  const char *const il_env[][2] = {{"MIND_ILQR_CHUNK", "ilqr_chunk"}, {"MIND_ILQR_WGS", "ilqr_wgs"}, {"MIND_ILQR_SPEC_DERIV", "ilqr_spec_deriv"},
-                                   {"MIND_ILQR_HOST_OUT_MAX", "ilqr_host_out_max"}, {"MIND_ILQR_SLOTS", "ilqr_slots"}};
-  for (const auto &e : il_env)
-    if (const char *we = getenv(e[0])) (void)ilqr_tuning_set(c->it, e[1], atoi(we));
-  (void)hipFuncSetAttribute((const void *)k_dec_scene, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_dec_scene_lds_bytes());
-  (void)hipFuncSetAttribute((const void *)k_dec_scene_mw, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_dec_scene_lds_bytes());
-  (void)hipFuncSetAttribute((const void *)k_dec_scene_c, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_dec_scene_lds_bytes());
-  (void)hipFuncSetAttribute((const void *)k_dec_cls, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_dec_scene_lds_bytes());
-  (void)hipFuncSetAttribute((const void *)k_dec_tgt, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_dec_scene_lds_bytes());
-  (void)hipFuncSetAttribute((const void *)k_dec_actor<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_dec_actor_lds_bytes());
-  (void)hipFuncSetAttribute((const void *)k_dec_actor<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_dec_actor_lds_bytes());
-  (void)hipFuncSetAttribute((const void *)k_dec_actor<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_dec_actor_lds_bytes());
-  (void)hipFuncSetAttribute((const void *)k_dec_actor<2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_dec_actor_lds_bytes());
-  (void)hipFuncSetAttribute((const void *)k_dec_actor<2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mind_dec_actor_lds_bytes());
-  if (const char *te = getenv("MIND_DEC_HEAD_RA")) (void)pred_tuning_set(c->pt, "dec_head_ra", atoi(te));
-  *out = c;
+  set_kernel_attributes();
+  tn_apply_env(c->knobs(), [](const char *name) -> const char * { return getenv(name); });
+  if (const char *pe = getenv("MIND_PAIR_PREC"))      // (read by name, not as an int: no row of the table)
+    for (int m = 0; m < 4; ++m)
+      if (!strcmp(pe, PAIR_PREC_NAMES[m]) || (pe[0] == '0' + m && !pe[1])) (void)mind_set_pair_precision(c.get(), m);
+  *out = c.release();
   return MIND_OK;
 }
 
@@ -411,52 +345,10 @@ extern "C" int mind_ctx_destroy(mind_ctx *c) {
   if (!c) return MIND_EINVAL;
   if (c->pa_thread.joinable()) c->pa_thread.join();
   (void)hipSetDevice(c->device);
-  (void)hipStreamSynchronize(c->stream);
-  DevBuf *bufs[] = {&c->edge, &c->x, &c->ST, &c->QK, &c->part, &c->tokpos, &c->meta, &c->jobs, &c->actor_feat,
-                    &c->lane_feat, &c->tgt_feat, &c->cmode, &c->tgt_emb, &c->rows, &c->rpe_ptrs, &c->ilqr_dev, &c->aime_dev, &c->rebase_dev2[0], &c->rebase_dev2[1], &c->dec_h2,
-                    &c->curve_tab, &c->audit_dev};
-  for (DevBuf *b : bufs)
-    if (b->p) (void)hipFree(b->p);
-  for (TableSet &t : c->tabs)
-    for (DevBuf *b : {&t.meta, &t.jobs, &t.jobs5, &t.rows})
-      if (b->p) (void)hipFree(b->p);
-  if (c->wdev) (void)hipFree(c->wdev);
-  for (DevBuf *b : {&c->dec_xbuf, &c->dec_bars})
-    if (b->p) (void)hipFree(b->p);
-  if (c->dec_abort) (void)hipHostFree(c->dec_abort);
-  if (c->lc_dev.p) (void)hipFree(c->lc_dev.p);
-  if (c->lc_host) (void)hipHostFree(c->lc_host);
-  for (DevBuf *b : {&c->pl_root, &c->pl_in[0], &c->pl_in[1], &c->pl_lf, &c->pl_lrep, &c->pl_pred, &c->pl_small, &c->pl_tab[0], &c->pl_tab[1], &c->pl_win[0],
-                    &c->pl_win[1], &c->pl_flat, &c->x_send, &c->x_recv, &c->x_seg, &c->pl_cnt})
-    if (b->p) (void)hipFree(b->p);
-  for (DevBuf &b : c->pl_world)
-    if (b.p) (void)hipFree(b.p);
-  for (void *q : c->pl_pin)
-    if (q) (void)hipHostFree(q);
-  if (c->ev_pl) (void)hipEventDestroy(c->ev_pl);
-  if (c->ev_root) (void)hipEventDestroy(c->ev_root);
-  if (c->ev_field) (void)hipEventDestroy(c->ev_field);
-  if (c->il_field.p) (void)hipFree(c->il_field.p);
-  if (c->il_field_pin) (void)hipHostFree(c->il_field_pin);
-  if (c->ev_tab) (void)hipEventDestroy(c->ev_tab);
-  if (c->ev_rows) (void)hipEventDestroy(c->ev_rows);
-  if (c->pl_copy) (void)hipStreamDestroy(c->pl_copy);
-  for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
-  for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
-  if (c->ev_side) (void)hipEventDestroy(c->ev_side);
-  if (c->ev_main) (void)hipEventDestroy(c->ev_main);
-  if (c->ev_tgt) (void)hipEventDestroy(c->ev_tgt);
-  if (c->ev_stage) (void)hipEventDestroy(c->ev_stage);
-  if (c->ev_cls) (void)hipEventDestroy(c->ev_cls);
-  if (c->actor_lw_arena.p) (void)hipFree(c->actor_lw_arena.p);
-  if (c->tok_lw_arena.p) (void)hipFree(c->tok_lw_arena.p);
-  for (hipEvent_t e : c->ev_tok) (void)hipEventDestroy(e);
-  if (c->ev_act0) (void)hipEventDestroy(c->ev_act0);
-  if (c->ev_act1) (void)hipEventDestroy(c->ev_act1);
-  if (c->ev_il0) (void)hipEventDestroy(c->ev_il0);
-  if (c->ev_il1) (void)hipEventDestroy(c->ev_il1);
-  if (c->side) { (void)hipStreamSynchronize(c->side); (void)hipStreamDestroy(c->side); }
-  if (c->own_stream) (void)hipStreamDestroy(c->stream);
+  (void)hipStreamSynchronize(c->stream);      // nothing is freed before everything queued has run
+  if (c->side) (void)hipStreamSynchronize(c->side);
+  if (c->pl_copy) (void)hipStreamSynchronize(c->pl_copy);
+  c->il_finish = nullptr;     // a begun and never collected tree-iLQR call: drained above, dropped here
   delete c;
   return MIND_OK;
 }
@@ -471,24 +363,31 @@ extern "C" int mind_ctx_synchronize(mind_ctx *c) {
 
 extern "C" int mind_set_tuning(mind_ctx *c, const char *name, int value) {
   if (!c || !name) return MIND_EINVAL;
-  const std::string n = name;
-  if (pred_tuning_set(c->pt, name, value)) return MIND_OK;      // the predictor's knobs (pred_choice.h)
-  if (ilqr_tuning_set(c->it, name, value)) return MIND_OK;      // the tree-iLQR solver's (ilqr_choice.h)
-  if (n == "plan_chunk_mb") c->plan_chunk_mb = value < 1 ? 1 : value;
-  else if (n == "pl_tab_side") c->pl_tab_side = value != 0;
-  else if (n == "tab_small") c->tab_small = value != 0;
-  else if (n == "tab_host_max") c->tab_host_max = value < 0 ? 0 : value;
-  else if (n == "early_eval") c->early_eval = value != 0;
-  else if (n == "glue_fused") c->glue_fused = value != 0;
-  else if (n == "dec_mirror") c->dec_mirror = value != 0;
-  else if (n == "dec_poll") c->dec_poll = value != 0;
-  else if (n == "root_head") c->root_head = value != 0;
-  else if (n == "round_head") c->round_head = value != 0;
-  else if (n == "upload_kernel_max") c->upload_kernel_max = value < 0 ? 0 : value;
-  else if (n == "prof_clock") c->prof_clock = value < 0 ? 0 : (value > 2 ? 2 : value);
-  else return fail(c, MIND_EINVAL, "mind_set_tuning: unknown knob '%s'", name);
+  if (!tn_set(c->knobs(), name, value)) return fail(c, MIND_EINVAL, "mind_set_tuning: unknown knob '%s'", name);
   return MIND_OK;
 }
+
+extern "C" int mind_get_tuning(mind_ctx *c, const char *name, int *value) {
+  if (!c || !name || !value) return MIND_EINVAL;
+  if (!tn_get(c->knobs(), name, value)) return fail(c, MIND_EINVAL, "mind_get_tuning: unknown knob '%s'", name);
+  return MIND_OK;
+}
+
+// the knob table without a context (layout: include/mind_hip.h)
+extern "C" int mind_debug_tuning(int index, const char *name, const char *text, int value, const char **out_name, const char **out_env, int *out_value) {
+  PredTuning pt; IlqrTuning it; CtxTuning ct;
+  const TnRefs fresh{&pt, &it, &ct};
+  const TnRow *row = name ? tn_find(name) : (index >= 0 && index < TN_ROWS) ? &TN_TABLE[index] : nullptr;
+  if (!row || !out_value || (name && text && !row->env)) return MIND_EINVAL;
+  if (name && text) tn_apply_env(fresh, [&](const char *var) { return strcmp(var, row->env) ? nullptr : text; });
+  else if (name) (void)tn_set(fresh, name, value);
+  if (out_name) *out_name = row->name;
+  if (out_env) *out_env = row->env;      // (null: no variable)
+  (void)tn_get(fresh, row->name, out_value);
+  return name ? MIND_OK : TN_ROWS;
+}
+
+extern "C" int mind_debug_live_handles(void) { return (int)live_handles.load(std::memory_order_relaxed); }
 
 extern "C" int mind_set_exchange(mind_ctx *c, int rank, int world, mind_exchange_fn fn, void *user, int force) {
   if (!c) return MIND_EINVAL;
@@ -528,7 +427,7 @@ extern "C" int mind_set_profiling(mind_ctx *c, int enable) {
   c->profiling = enable != 0;
   // the launch clock's ring and its page-locked mirror are allocated here, outside anything timed: two predictor calls of pair launches on
   // every CU (a call with larger grids or more records grows it in front of its launches)
-  if (c->profiling && c->prof_clock != 0 && c->wall_khz > 0 && c->lc.n_blocks == 0) {
+  if (c->profiling && c->ct.prof_clock != 0 && c->wall_khz > 0 && c->lc.n_blocks == 0) {
     HIPCHK(c, hipSetDevice(c->device));
     return lc_reserve(c, 12, c->n_cu);
   }
@@ -800,12 +699,10 @@ extern "C" int mind_weights_load(mind_ctx *c, const mind_tensor_desc *tensors, i
   // the context's curve basis: the contents of dec.T / dec.Tp, in place (same shapes: no key is added, no offset moves)
   if (c->dec_basis != MIND_BASIS_BEZIER) wp_basis_tables(c->dec_basis, B.host.data() + B.off.at("dec.T"), B.host.data() + B.off.at("dec.Tp"));
   c->have_weights = false;     // from here on the tables point into freed memory until the bind below
-  if (c->wdev) (void)hipFree(c->wdev);
-  c->wdev = nullptr;
-  HIPCHK(c, hipMalloc((void **)&c->wdev, B.host.size() * sizeof(float)));
-  HIPCHK(c, hipMemcpy(c->wdev, B.host.data(), B.host.size() * sizeof(float), hipMemcpyHostToDevice));
+  HIPCHK(c, c->wdev.alloc(B.host.size() * sizeof(float)));
+  HIPCHK(c, hipMemcpy(c->wdev.p, B.host.data(), B.host.size() * sizeof(float), hipMemcpyHostToDevice));
   std::string missing;
-  if (!wp_bind(B, c->wdev, c->W, &missing)) return fail(c, MIND_ENOTFOUND, "packed weights hold no entry '%s'", missing.c_str());
+  if (!wp_bind(B, (float *)c->wdev.p, c->W, &missing)) return fail(c, MIND_ENOTFOUND, "packed weights hold no entry '%s'", missing.c_str());
   c->W.dec.monomial = c->W.decB.monomial = c->dec_basis == MIND_BASIS_MONOMIAL;
   c->have_weights = true;
   return MIND_OK;

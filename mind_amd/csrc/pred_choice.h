@@ -1,94 +1,12 @@
-// Which kernels a mind_predict_batch call runs: the predictor's knobs (PredTuning), and the one pure function that turns them, the precision
+// Which kernels a mind_predict_batch call runs: the predictor's knobs (PredTuning, tuning.h), and the one pure function that turns them, the precision
 // setting and the call's scene sizes into a record of decisions (PredChoice).  No HIP call, no context: predict.hip's stages switch on the
 // record and read no knob themselves; tests read it through mind_debug_predict_choice.  A new kernel form is a knob here (if it has one), a
 // case in pred_choose and a case in the stage that launches its family.
 // Included by mind_hip.hip behind the kernel files (LW_CHUNK, TL_CHUNK, DEC_MW_G, RA, P6_QK_STRIDE, LW_NSTAGE) and pair_jobs.h.
 #pragma once
-#include <cstring>
 #include <vector>
 
-struct PredTuning {
-  // bf16 arithmetics: k_pair_t (tile-native edge tensor, pair_tile_kernels.hip; default) or the row-major k_pair_bf of rounds 2-3
-  // (mind_set_tuning("pair_tile", 0) / MIND_PAIR_TILE=0, kept for same-box A/B measurements)
-  bool pair_tile = true;
-  bool xcd_order = true;        // XCD-aware job order for big batches (MIND_XCD_ORDER=0 switches it off, for A/B measurements)
-  bool enc_mfma = true;         // MFMA ActorNet under the bf16x3 / bf16 settings (MIND_ENC_MFMA=0: the fp32 VALU kernel, for A/B)
-  int actor_np = 6;             // partial products per term of the MFMA ActorNet under bf16x3: 6 (three-way split, fp32-class) or 3 (MIND_ACTOR_SPLIT=3)
-  // fp32-MFMA ActorNet (k_actor_f32): "actor_f32" 1 (default) = the ActorNet of the exact-fp32 setting (0: the fp32 VALU kernel, for A/B);
-  // "actor_f32_min" = actors per call from which every setting takes it with TWO actors per workgroup (the 256-channel layers' weight stream is
-  // then shared by two actors: 7.1 vs 8.1 ms for the 13.8 k actors of a cfg4 round); "actor_f32_pair_min" = the same threshold inside the
-  // exact-fp32 setting.  Both default to never: a threshold on the batch size would give the blocks of a sharded round another kernel -- other
-  // last bits -- than the whole round (a workload that wants it sets 0, as with "dec_mfma_min")
-  bool actor_f32 = true;
-  int actor_f32_min = 1 << 30, actor_f32_pair_min = 1 << 30;
-  // layer-wise batched ActorNet (actor_lw_kernels.hip): actors per call from which it replaces k_actor_mfma<NP> ("actor_lw_min" /
-  // MIND_ACTOR_LW_MIN; default never; bit-identical, so ranks and rounds may differ in which one they take), actors per chunk
-  // ("actor_lw_chunk", 0 = LW_CHUNK; tests and A/B runs)
-  int actor_lw_min = 1 << 30, actor_lw_chunk = 0;
-  // token kernel on the fp32 MFMA (k_token_mfma; MIND_TOK_MFMA=1 / mind_set_tuning("tok_mfma")).  Opt-in: measured on the MI355X it is
-  // SLOWER than the VALU kernel -- 41 vs 30 us per launch at demo size (6 workgroups), 315 vs 282 us average on the full cfg4 tree
-  // (profiles/r03o_*, r03p_*): 640 fp32 MFMAs of 32 cycles per wave and launch are 8.5 us by themselves and the weight stream (64 KB per
-  // projection and workgroup) is the same; a bf16-split variant would cut the MFMA time, not the rest
-  bool tok_mfma = false;
-  // scenes of at least this many tokens run k_token_mfma<1> (bf16 hi + lo split operands) under the bf16 arithmetics ("tok_bf_min_n";
-  // 0 = never, the default).  Measured on the cfg4 full tree (N = 321, launches of up to 69 k tokens): 221 us per launch on average and
-  // 0.80 ms for the largest, the same as the VALU kernel (which is LDS-bound there) -- with 97 KB of LDS the MFMA kernel keeps one
-  // four-wave workgroup per CU and waits on its partial-sum and fragment loads instead (profiles/r03bb); opt-in until it is faster
-  int tok_bf_min_n = 0;
-  // layer-wise token stage (token_lw_kernels.hip; the bits of k_token_mfma<0>).  "tok_lw_min_n" / MIND_TOK_LW_MIN_N: a SCENE of at least this
-  // many tokens takes the fp32-MFMA token class (by the scene's own N: its result does not depend on its batch, round or rank); "tok_lw_min" /
-  // MIND_TOK_LW_MIN: a run of consecutive scenes of that class with at least this many tokens runs layer-wise, a shorter one k_token_mfma<0>
-  // (the same bits, so this rule may look at the batch).  Both default to never.  "tok_lw_chunk": tokens per chunk (0 = TL_CHUNK)
-  int tok_lw_min_n = 1 << 30, tok_lw_min = 1 << 30, tok_lw_chunk = 0;
-  bool tok_merge = true;        // small token launches merge their independent projections (k_token_m; MIND_TOK_MERGE=0 / "tok_merge": the plain kernel)
-  int tok_small_max = 2048;     // batches of at most this many tokens run k_token with 4 tokens per workgroup ("tok_small_max")
-  int dec_mfma_min = 1 << 30;   // agents per call from which the decoder's actor part runs on the MFMA kernel (MIND_DEC_MFMA_MIN; default: never)
-  bool dec_overlap = true;      // actor_proj of the decoder on the side stream beside k_dec_scene (mind_set_tuning("dec_overlap"))
-  // agents per workgroup of the split decoder's head, k_dec_actor<2, .> ("dec_head_ra"): 0 (default) = by the call's agents -- 1 while they fit
-  // one workgroup per CU, else 2, else RA = 4; 1, 2 or 4 = that form whatever the call (4: the head as it was).  The forms give the same bits,
-  // so the rule may look at the batch
-  int dec_head_ra = 0;
-  // k_dec_scene_mw: eight workgroups per scene on the decoder's five big stages (bit-identical to the one-workgroup kernel), possible whenever
-  // every workgroup of the launch is resident, i.e. for calls of at most n_cu / 8 scenes.  Opt-in ("dec_mw" / MIND_DEC_MW=1): measured 88.6
-  // against 94.9 us per demo-size launch (profiles/r06aa_*) -- only ctx_proj's second layer is really bound by one CU's L2 port (30 k -> 20 k
-  // cycles); the feed-forward layers are bound by their 24 accumulators per thread and win 2-4 k cycles each, less the 36 KB exchange --
-  // 12 us per plan, not worth eight spinning workgroups per scene when several scenes share the device
-  bool dec_mw = false;
-  // the decoder's cls head as its own launch on the side stream beside the actor part's head ("dec_cls_side" / MIND_DEC_CLS_SIDE=1).  Opt-in:
-  // bit-identical, but the second launch and its two event waits cost more than the ~10 us of overlap (1 609-1 630 against 1 632-1 652
-  // sim steps/s, profiles/r06am_*)
-  bool dec_cls_side = false;
-  bool tgt_side = true;         // the target polyline's encoder + embedding stay on the side stream through the fusion layers ("tgt_side")
-};
-
-// these knobs' branches of mind_set_tuning: false when `name` is none of them
-static bool pred_tuning_set(PredTuning &t, const char *name, int value) {
-  const auto is = [name](const char *k) { return strcmp(name, k) == 0; };
-  if (is("dec_mfma_min")) t.dec_mfma_min = value;
-  else if (is("enc_mfma")) t.enc_mfma = value != 0;
-  else if (is("actor_f32")) t.actor_f32 = value != 0;
-  else if (is("actor_f32_min")) t.actor_f32_min = value;
-  else if (is("actor_f32_pair_min")) t.actor_f32_pair_min = value;
-  else if (is("actor_lw_min")) t.actor_lw_min = value;
-  else if (is("actor_lw_chunk")) t.actor_lw_chunk = value < 0 ? 0 : value;
-  else if (is("actor_split")) t.actor_np = value == 3 ? 3 : 6;
-  else if (is("xcd_order")) t.xcd_order = value != 0;
-  else if (is("pair_tile")) t.pair_tile = value != 0;
-  else if (is("dec_overlap")) t.dec_overlap = value != 0;
-  else if (is("dec_head_ra")) t.dec_head_ra = (value == 1 || value == 2 || value == RA) ? value : 0;
-  else if (is("tok_mfma")) t.tok_mfma = value != 0;
-  else if (is("tok_small_max")) t.tok_small_max = value;
-  else if (is("tok_merge")) t.tok_merge = value != 0;
-  else if (is("dec_mw")) t.dec_mw = value != 0;
-  else if (is("dec_cls_side")) t.dec_cls_side = value != 0;
-  else if (is("tok_bf_min_n")) t.tok_bf_min_n = value;
-  else if (is("tok_lw_min_n")) t.tok_lw_min_n = value;
-  else if (is("tok_lw_min")) t.tok_lw_min = value;
-  else if (is("tok_lw_chunk")) t.tok_lw_chunk = value < 0 ? 0 : value;
-  else if (is("tgt_side")) t.tgt_side = value != 0;
-  else return false;
-  return true;
-}
+#include "tuning.h"
 
 // partial products per term of the MFMA contractions outside the pair kernel (ActorNet, layer-wise ActorNet, MFMA decoder) under a bf16
 // arithmetic: bf16x6 -> 6, bf16x3 -> actor_np (6 or 3), bf16 -> 1

@@ -114,8 +114,9 @@ extern "C" int mind_debug_predict_choice(const char *const *knob_names, const in
       n_scenes <= 0 || cap < 0 || (cap > 0 && !out))
     return MIND_EINVAL;
   PredTuning t;
+  const TnRefs own{&t, nullptr, nullptr};      // (the predictor's knobs alone: any other name is rejected)
   for (int k = 0; k < n_knobs; ++k)
-    if (!knob_names[k] || !pred_tuning_set(t, knob_names[k], knob_values[k])) return MIND_EINVAL;
+    if (!knob_names[k] || !tn_set(own, knob_names[k], knob_values[k])) return MIND_EINVAL;
   for (int b = 0; b < n_scenes; ++b)
     if (scene_actors[b] <= 0 || scene_lanes[b] < 0) return MIND_EINVAL;
   const PredChoice ch = pred_choose(t, pair_prec, n_cu, have_side != 0, n_scenes, scene_actors, scene_lanes);
@@ -134,12 +135,12 @@ extern "C" int mind_debug_predict_choice(const char *const *knob_names, const in
 // ---- the launch clock's host side (launch_clock.h: the ring's bookkeeping and the reduction): the device ring and its page-locked mirror, the
 //      copies, the sums.  With profiling on and "prof_clock" 1 a timed launch takes the next block of the ring and records no HIP event; whoever
 //      read event pairs reads slots instead, behind a completed stream or copy -- the device never waits on the host.
-static bool lc_on(const mind_ctx *c) { return c->profiling && c->prof_clock != 0 && c->wall_khz > 0; }
-static bool lc_events(const mind_ctx *c) { return c->profiling && !(c->prof_clock == 1 && c->wall_khz > 0); }      // 0: events as before; 2 (debug): both
+static bool lc_on(const mind_ctx *c) { return c->profiling && c->ct.prof_clock != 0 && c->wall_khz > 0; }
+static bool lc_events(const mind_ctx *c) { return c->profiling && !(c->ct.prof_clock == 1 && c->wall_khz > 0); }      // 0: events as before; 2 (debug): both
 
 // a record's slots on the host -> its sum and per-launch list
 static void lc_account(mind_ctx *c, const LcRecord &r, double (&ms)[LC_KINDS], int (&n)[LC_KINDS]) {
-  const double t = lc_ticks_ms(lc_reduce(c->lc_host + c->lc.slot_of(r.block), r.grid), c->wall_khz);
+  const double t = lc_ticks_ms(lc_reduce(c->lc_host.as<LcSlot>() + c->lc.slot_of(r.block), r.grid), c->wall_khz);
   ms[r.kind] += t; n[r.kind] += 1;
   c->lc_last[r.kind].push_back((float)t);
 }
@@ -154,7 +155,7 @@ static int lc_flush(mind_ctx *c, bool keep) {
     const int runs = c->lc.pending_runs(0, n, first, count);
     for (int k = 0; k < runs; ++k) {
       const size_t o = c->lc.slot_of(first[k]), b = (size_t)count[k] * c->lc.block_slots * sizeof(LcSlot);
-      HIPCHK(c, hipMemcpy(c->lc_host + o, (const LcSlot *)c->lc_dev.p + o, b, hipMemcpyDeviceToHost));
+      HIPCHK(c, hipMemcpy(c->lc_host.as<LcSlot>() + o, (const LcSlot *)c->lc_dev.p + o, b, hipMemcpyDeviceToHost));
     }
     if (keep)
       for (const LcRecord &r : c->lc.pending) lc_account(c, r, c->lc_carry_ms, c->lc_carry_n);
@@ -173,9 +174,7 @@ static int lc_reserve(mind_ctx *c, int records, int grid) {
   if (blocks != c->lc.n_blocks || slots != c->lc.block_slots) {
     const size_t bytes = (size_t)blocks * slots * sizeof(LcSlot);
     if ((rc = ensure_exact(c, c->lc_dev, bytes, "the launch clock's ring"))) return rc;
-    if (c->lc_host) (void)hipHostFree(c->lc_host);
-    c->lc_host = nullptr;
-    if (hipHostMalloc((void **)&c->lc_host, bytes, hipHostMallocDefault) != hipSuccess) { c->lc_host = nullptr; c->lc.reset(0, 0); return fail(c, MIND_ENOMEM, "hipHostMalloc(%zu) for the launch clock failed", bytes); }
+    if (c->lc_host.alloc(bytes) != hipSuccess) { c->lc.reset(0, 0); return fail(c, MIND_ENOMEM, "hipHostMalloc(%zu) for the launch clock failed", bytes); }
     c->lc.reset(blocks, slots);
   }
   return MIND_OK;
@@ -194,7 +193,7 @@ static int lc_copy_async(mind_ctx *c, hipStream_t s, int i0, int n) {
   const int runs = c->lc.pending_runs(i0, n, first, count);
   for (int k = 0; k < runs; ++k) {
     const size_t o = c->lc.slot_of(first[k]), b = (size_t)count[k] * c->lc.block_slots * sizeof(LcSlot);
-    HIPCHK(c, hipMemcpyAsync(c->lc_host + o, (const LcSlot *)c->lc_dev.p + o, b, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(c->lc_host.as<LcSlot>() + o, (const LcSlot *)c->lc_dev.p + o, b, hipMemcpyDeviceToHost, s));
   }
   if (runs > 0) c->lc.mark_copied(i0, n);
   return MIND_OK;
@@ -232,7 +231,7 @@ struct PredCall {
   TableSet *ts = nullptr;
   const float *lane_feat = nullptr;     // the caller's, or what the lane encoder wrote
   const float *const *rpe_dev = nullptr;
-  hipEvent_t *evs = nullptr;            // profiling: two events per pair layer
+  Event *evs = nullptr;            // profiling: two events per pair layer
   bool tok_timed = false;               // ... and HIP events around every token launch, outside a plan
   bool act_ev = false, pair_ev = false; // this call records the ActorNet's / the pair layers' HIP events (profiling on, and not timed by the launch clock alone)
   bool pair_clk = false;                // the pair layers take blocks of the launch clock's ring
@@ -379,8 +378,8 @@ static int pred_encoders(PredCall &p) {
   }
   p.act_ev = act_timed && (lc_events(c) || !act_clk);
   if (p.act_ev && !c->ev_act0) {
-    HIPCHK(c, hipEventCreate(&c->ev_act0));
-    HIPCHK(c, hipEventCreate(&c->ev_act1));
+    HIPCHK(c, c->ev_act0.create());
+    HIPCHK(c, c->ev_act1.create());
   }
   c->last_actor_lw = 0; c->last_actor_launches = 1; c->last_actor_chunks = 1; c->actor_ms = 0.f;
   if (p.act_ev) HIPCHK(c, hipEventRecord(c->ev_act0, st));
@@ -421,15 +420,20 @@ static int pred_encoders(PredCall &p) {
   return MIND_OK;
 }
 
+// timing events are made when first needed: `v` grown to n of them
+static hipError_t ev_grow(std::vector<Event> &v, size_t n) {
+  hipError_t rc = hipSuccess;
+  for (Event e; v.size() < n && (rc = e.create()) == hipSuccess;) v.push_back(std::move(e));
+  return rc;
+}
+
 // (HIP events around every token launch with profiling on, outside a plan: mind_last_token_stats / mind_last_token_stage_ms)
 static hipError_t pred_tok_mark(PredCall &p, int tag) {
   mind_ctx *c = p.c;
   if (!p.tok_timed) return hipSuccess;
   if (p.ev_tok_used == c->ev_tok.size()) {
-    hipEvent_t e;
-    const hipError_t rc_ = hipEventCreate(&e);
+    const hipError_t rc_ = ev_grow(c->ev_tok, p.ev_tok_used + 1);
     if (rc_ != hipSuccess) return rc_;
-    c->ev_tok.push_back(e);
     c->ev_tok_tag.push_back(0);
   }
   c->ev_tok_tag[p.ev_tok_used] = tag;
@@ -529,20 +533,10 @@ static int pred_fusion(PredCall &p) {
   p.pair_clk = lc_on(c);
   p.pair_ev = lc_events(c);
   if (p.pair_clk && (rc = lc_reserve(c, c->debug_layers, std::max(pair_grid(ts->njobs, c->n_cu), pair_grid(ts->njobs5, c->n_cu))))) return rc;
-  if (p.pair_ev && c->ev.size() < 12) {
-    while (c->ev.size() < 12) {
-      hipEvent_t e;
-      HIPCHK(c, hipEventCreate(&e));
-      c->ev.push_back(e);
-    }
-  }
+  if (p.pair_ev) HIPCHK(c, ev_grow(c->ev, 12));
   p.evs = c->ev.data();
   if (p.pair_ev && c->ev_defer) {
-    while (c->ev_pool.size() < c->ev_pool_used + 12) {
-      hipEvent_t e;
-      HIPCHK(c, hipEventCreate(&e));
-      c->ev_pool.push_back(e);
-    }
+    HIPCHK(c, ev_grow(c->ev_pool, c->ev_pool_used + 12));
     p.evs = c->ev_pool.data() + c->ev_pool_used;
     c->ev_pending.push_back(c->ev_pool_used);
     c->ev_pool_used += 12;
@@ -582,10 +576,10 @@ static int pred_decoder(PredCall &p) {
   bool cls_on_side = false;
   bool mw = ch.want_mw;
   if (mw) {
-    if (c->dec_abort && *(volatile unsigned *)c->dec_abort) return fail(c, MIND_EHIP, "k_dec_scene_mw: a barrier of an earlier launch timed out (launch not resident)");
+    if (c->dec_abort && *c->dec_abort.as<volatile unsigned>()) return fail(c, MIND_EHIP, "k_dec_scene_mw: a barrier of an earlier launch timed out (launch not resident)");
     if (!c->dec_abort) {
-      if (hipHostMalloc((void **)&c->dec_abort, 64, hipHostMallocMapped) != hipSuccess) { c->dec_abort = nullptr; mw = false; }
-      else *c->dec_abort = 0u;
+      if (c->dec_abort.alloc(64, hipHostMallocMapped) != hipSuccess) mw = false;
+      else *c->dec_abort.as<unsigned>() = 0u;
     }
     const size_t need_x = (size_t)(c->n_cu / DEC_MW_G) * 2 * 6 * 1536 * sizeof(float), need_b = (size_t)(c->n_cu / DEC_MW_G) * 4 * sizeof(unsigned);
     if (mw && c->dec_xbuf.cap < need_x) {
@@ -598,7 +592,7 @@ static int pred_decoder(PredCall &p) {
   }
   if (mw)
     hipLaunchKernelGGL(k_dec_scene_mw, dim3(ch.mw_blocks), dim3(DT), mind_dec_scene_lds_bytes(), st, x, d_cls_row, (float *)c->cmode.p, out->cls, c->W.dec, Bn,
-                       (float *)c->dec_xbuf.p, (unsigned *)c->dec_bars.p, c->dec_abort);
+                       (float *)c->dec_xbuf.p, (unsigned *)c->dec_bars.p, c->dec_abort.as<unsigned>());
   else if (ch.cls_side) {
     // the mode tokens on the context stream, the mode probabilities (the cls head: ~10 us a launch) on the side stream beside the actor part's
     // head, which needs the tokens only; the caller's next work on the context stream follows both
@@ -606,7 +600,7 @@ static int pred_decoder(PredCall &p) {
     HIPCHK(c, hipEventRecord(c->ev_main, st));
     HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_main, 0));
     hipLaunchKernelGGL(k_dec_cls, dim3(Bn), dim3(DT), mind_dec_scene_lds_bytes(), c->side, (float *)c->cmode.p, out->cls, c->W.dec);
-    if (!c->ev_cls) HIPCHK(c, hipEventCreateWithFlags(&c->ev_cls, hipEventDisableTiming));
+    if (!c->ev_cls) HIPCHK(c, c->ev_cls.create(hipEventDisableTiming));
     HIPCHK(c, hipEventRecord(c->ev_cls, c->side));
     cls_on_side = true;
   } else
@@ -706,8 +700,8 @@ extern "C" int mind_predict_batch_aux(mind_ctx *c, const mind_scene_batch *in, m
     sa[b] = in->actor_off[b + 1] - in->actor_off[b]; sl[b] = in->lane_off[b + 1] - in->lane_off[b];
     if (sa[b] <= 0 || sl[b] < 0) return fail(c, MIND_EINVAL, "scene %d has %d agents, %d lanes", b, sa[b], sl[b]);
   }
-  const PredChoice ch = pred_choose(c->pt, c->pair_prec, c->n_cu, c->side != nullptr, Bn, sa.data(), sl.data());
-  PredCall p{c, in, out, aux, ch, Bn, A, Ltot, c->stream, c->side ? c->side : c->stream};
+  const PredChoice ch = pred_choose(c->pt, c->pair_prec, c->n_cu, c->side.p != nullptr, Bn, sa.data(), sl.data());
+  PredCall p{c, in, out, aux, ch, Bn, A, Ltot, c->stream, c->side ? c->side.p : c->stream};
   int rc;
   if ((rc = pred_tables(p, sa.data(), sl.data()))) return rc;
   if ((rc = pred_workspaces(p))) return rc;

@@ -1,6 +1,5 @@
 """Host-side handle on the HIP scene predictor (one context per process/GPU)."""
 import ctypes as C
-import os
 
 import numpy as np
 import torch
@@ -56,13 +55,7 @@ class IlqrCall:
         """the launch (+ its synchronisation) on ``rt``'s context; nothing else happens here"""
         dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double)) if a is not None else None
         self.ctx = rt.ctx
-        now = getattr(rt, "_ilqr_wgs_now", None)
-        if self.background and now != 1:
-            self.lib.mind_set_tuning(rt.ctx, b"ilqr_wgs", 1)
-            rt._ilqr_wgs_now = 1
-        elif not self.background and now == 1:          # back to what the user (or the library default) asked for
-            rt._ilqr_wgs_now = getattr(rt, "_ilqr_wgs_user", int(os.environ.get("MIND_ILQR_WGS", "16")))
-            self.lib.mind_set_tuning(rt.ctx, b"ilqr_wgs", rt._ilqr_wgs_now)
+        rt.ilqr_background(self.background)
         if self.cfg_full is not None:
             self.rc = self.lib.mind_ilqr_contingency(rt.ctx, C.byref(self.cfg), C.byref(self.cfg_full), self.trees, self.n, dp(self.x0),
                                                      dp(self.lane), len(self.lane), self.tv, dp(self.xs), dp(self.us), self.st, self.st_full)
@@ -78,9 +71,7 @@ class IlqrCall:
         dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double)) if a is not None else None
         self.ctx = rt.ctx
         self._rt = rt
-        if getattr(rt, "_ilqr_wgs_now", None) == 1:
-            rt._ilqr_wgs_now = getattr(rt, "_ilqr_wgs_user", int(os.environ.get("MIND_ILQR_WGS", "16")))
-            self.lib.mind_set_tuning(rt.ctx, b"ilqr_wgs", rt._ilqr_wgs_now)
+        rt.ilqr_background(False)
         self.rc = self.lib.mind_ilqr_contingency_begin(rt.ctx, C.byref(self.cfg), C.byref(self.cfg_full), self.trees, self.n, dp(self.x0),
                                                        dp(self.lane), len(self.lane), self.tv, dp(self.xs), dp(self.us), self.st, self.st_full)
         self._begun = self.rc == 0
@@ -129,9 +120,7 @@ class PlanIlqrCall(IlqrCall):
     def begin(self, rt):
         self.ctx = rt.ctx
         self._rt = rt              # (wait() refuses to collect from a runtime that was closed meanwhile)
-        if getattr(rt, "_ilqr_wgs_now", None) == 1:
-            rt._ilqr_wgs_now = getattr(rt, "_ilqr_wgs_user", int(os.environ.get("MIND_ILQR_WGS", "16")))
-            self.lib.mind_set_tuning(rt.ctx, b"ilqr_wgs", rt._ilqr_wgs_now)
+        rt.ilqr_background(False)
         self.rc = self.lib.mind_ilqr_contingency_begin_plan(rt.ctx, C.byref(self.cfg), C.byref(self.cfg_full), self.x0.ctypes.data, self.lane.ctypes.data,
                                                             len(self.lane), self.tv, self.xs.ctypes.data, self.us.ctypes.data, self.st, self.st_full)
         self._begun = self.rc == 0
@@ -212,10 +201,27 @@ class HipPredictor:
         return self.PAIR_PREC[self.lib.mind_get_pair_precision(self.ctx)]
 
     def set_tuning(self, name, value):
-        """kernel-selection knobs of include/mind_hip.h (mind_set_tuning): dec_mfma_min, enc_mfma, actor_split, xcd_order"""
+        """one tuning knob (mind_set_tuning); ``_lib.knobs()`` lists them, include/mind_hip.h says what each does"""
         _lib.check(self.lib, self.ctx, self.lib.mind_set_tuning(self.ctx, name.encode(), int(value)), "mind_set_tuning")
         if name == "ilqr_wgs":
-            self._ilqr_wgs_user = self._ilqr_wgs_now = int(value)
+            self._ilqr_wgs_saved = None         # (what the user asks for is not undone by the next foreground solve)
+
+    def get_tuning(self, name):
+        """the value the knob holds now (mind_get_tuning): a flag as 0 / 1"""
+        v = C.c_int()
+        _lib.check(self.lib, self.ctx, self.lib.mind_get_tuning(self.ctx, name.encode(), C.byref(v)), "mind_get_tuning")
+        return v.value
+
+    _ilqr_wgs_saved = None
+
+    def ilqr_background(self, on):
+        """entering a background tree-iLQR fit saves "ilqr_wgs" and sets 1; the next foreground call puts the saved value back"""
+        if on and self._ilqr_wgs_saved is None:
+            self._ilqr_wgs_saved = self.get_tuning("ilqr_wgs")
+            self.lib.mind_set_tuning(self.ctx, b"ilqr_wgs", 1)
+        elif not on and self._ilqr_wgs_saved is not None:
+            self.lib.mind_set_tuning(self.ctx, b"ilqr_wgs", self._ilqr_wgs_saved)
+            self._ilqr_wgs_saved = None
 
     def set_pair_precision(self, name):
         _lib.check(self.lib, self.ctx, self.lib.mind_set_pair_precision(self.ctx, self.PAIR_PREC.index(name)), "mind_set_pair_precision")

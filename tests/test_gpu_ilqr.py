@@ -527,7 +527,7 @@ def test_rejected_call_leaves_nothing_behind_for_the_next(hip_predictor):
      {"ilqr_slots": 99, "ilqr_wgs": 99, "ilqr_wgs_big": 0, "ilqr_chunk": -1, "ilqr_host_out_max": -1})])
 def test_context_knobs_reach_the_launch_choice(env, tuning, knobs):
     """A fresh process per case: the MIND_ILQR_* variables at context creation and mind_set_tuning go through the one clamping function
-    (ilqr_tuning_set), so the launch is what mind_debug_ilqr_plan records for the same values; every value gives the same bits; an unknown
+    (tn_set over the knob table, mind_amd/csrc/tuning.h), so the launch is what mind_debug_ilqr_plan records for the same values; every value gives the same bits; an unknown
     name is still rejected."""
     import json
     import subprocess

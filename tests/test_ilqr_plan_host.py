@@ -3,7 +3,7 @@
 The solver decides in il_choose and builds a tree's tables in il_tree_tables (mind_amd/csrc/ilqr_choice.h); mind_debug_ilqr_plan calls the
 same two functions for a set of knobs, a device size and a list of parent arrays.  Every launch form gives the same bits, so a wrong choice
 changes no result, only speed or residency: these are the rules themselves.  n_cu is 256 unless a case says otherwise.  The knobs reach the
-record through ilqr_tuning_set, the function mind_set_tuning and the MIND_ILQR_* variables go through (with a context, hence a GPU:
+record through tn_set (mind_amd/csrc/tuning.h), the function mind_set_tuning and the MIND_ILQR_* variables go through (with a context, hence a GPU:
 test_gpu_ilqr.py::test_context_knobs_reach_the_launch_choice)."""
 import pytest
 
