@@ -1134,6 +1134,42 @@ int mind_debug_road_margin(int n, const double *boxes, const mind_audit_box *ego
                            const int32_t *poly_off, int n_rings, const double *trig, double *margin, int32_t *corner,
                            int32_t *ring, int32_t *edge);
 
+/* ------------------------------------------------------------------------------------------------
+ * Time-to-collision audit of closed-loop episodes (mind_amd/csrc/ttc_geom.h, ttc_kernels.hip): how CLOSE to a collision the
+ * ego drove.  The clearance audit says whether the ego box touched another; an episode that never did can still have spent
+ * seconds one brake-tap from a rear-end collision.  The reference gives every agent a BBox by object type (agent.py:92-105),
+ * draws it (visualization.py:69-72) and tests it against nothing, so the definition is this project's: both boxes are swept
+ * at the constant velocity they have at the step -- the ego's v (cos yaw, sin yaw), a track's (vx, vy) --, rectangles that
+ * translate keep their orientations, the four separating axes are constant in time and the first time of overlap is a closed
+ * form (ttc_geom.h; no time sampling).  Conventions: boxes overlapping now: 0.0; boxes that only touch at an instant or
+ * slide in contact are no hit (+inf), as are two point boxes; a time above `horizon` is reported as +inf.  Like the clearance
+ * audit this call sits outside every planning cycle: synchronous on the context's stream, on the audits' scratch.
+ *
+ * Inputs exactly as mind_audit_episode takes them (ego rows (x, y, v, yaw); exo rows (x, y, heading, vx, vy), row 0 unused;
+ * the same row caps); the ego's centre is (x, y) + center_offset (cos yaw, sin yaw).  Per (ego, step): step_ttc = the minimum
+ * over the valid tracks 1..n_tracks-1 of the swept time, or +inf when that is above horizon (no valid track: +inf), and
+ * step_track = the lowest track attaining it, -1 for +inf.  Per ego: ego_min with ego_step (the lowest step wins ties; 0 when
+ * every step is +inf) and ego_track = that step's track, ego_hits = steps with ttc < bound (strict), ego_first = the first of
+ * them (-1: none).  lanes picks the kernel's layout and changes no result: 0 = the library's rule (by n_ego x n_steps), 1 =
+ * thread per ego, 2 = one wavefront per (step, ego), its lanes over the tracks.
+ * Outputs HOST, each may be NULL (not all): step_* [n_ego, n_steps], ego_* [n_ego].
+ * MIND_EINVAL as mind_audit_episode, and: horizon not finite or <= 0, bound not finite or < 0, lanes outside 0..2, a
+ * non-finite v of an ego row or vx, vy of a valid track row.  n_ego == 0 or n_steps == 0 is a successful no-op.  MIND_ESTATE
+ * as mind_audit_plan. */
+typedef struct { double horizon, bound; int lanes; } mind_audit_ttc_cfg;
+typedef struct {
+  double *step_ttc; int32_t *step_track;
+  double *ego_min; int32_t *ego_step, *ego_track, *ego_hits, *ego_first;
+} mind_audit_ttc_out;
+int mind_audit_ttc(mind_ctx *ctx, const mind_audit_box *ego, const mind_audit_ttc_cfg *cfg, int n_ego, int n_steps,
+                   int n_tracks, const double *ego_states, const double *exo, const uint8_t *valid, const double *boxes,
+                   const mind_audit_ttc_out *out);
+
+/* ttc_geom.h on the CPU (host only, no context; no horizon): n pairs, a and b HOST [n, 7] = (x, y, yaw, L, W, vx, vy), offset
+ * and relative velocity taken as b - a.  trig HOST [n, 4] = (cos a, sin a, cos b, sin b), or NULL = the kernels' own sin / cos
+ * (mind_trig.h).  out HOST [n]: tg_rect_rect_ttc, +inf for never.  MIND_EINVAL for n < 0 or a NULL pointer. */
+int mind_debug_box_ttc(int n, const double *a, const double *b, const double *trig, double *out);
+
 #ifdef __cplusplus
 }
 #endif

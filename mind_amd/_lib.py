@@ -81,6 +81,16 @@ class AuditRoadEpisodeOut(C.Structure):     # mind_audit_road_episode_out
                 ("ego_corner", C.POINTER(C.c_int32)), ("ego_hits", C.POINTER(C.c_int32)), ("ego_first", C.POINTER(C.c_int32))]
 
 
+class AuditTtcCfg(C.Structure):     # mind_audit_ttc_cfg
+    _fields_ = [("horizon", C.c_double), ("bound", C.c_double), ("lanes", C.c_int)]
+
+
+class AuditTtcOut(C.Structure):     # mind_audit_ttc_out
+    _fields_ = [("step_ttc", C.POINTER(C.c_double)), ("step_track", C.POINTER(C.c_int32)), ("ego_min", C.POINTER(C.c_double)),
+                ("ego_step", C.POINTER(C.c_int32)), ("ego_track", C.POINTER(C.c_int32)), ("ego_hits", C.POINTER(C.c_int32)),
+                ("ego_first", C.POINTER(C.c_int32))]
+
+
 class ForecastCfg(C.Structure):     # mind_forecast_cfg
     _fields_ = [("K", C.c_int), ("T", C.c_int), ("n_h", C.c_int), ("horizon", C.POINTER(C.c_int32)), ("miss_radius", C.c_double),
                 ("disc_scale", C.c_double), ("disc_offset", C.c_double)]
@@ -225,6 +235,7 @@ EXPORTS = ["mind_ctx_create", "mind_ctx_destroy", "mind_last_error_string", "min
            "mind_audit_plan", "mind_audit_episode", "mind_debug_box_clearance",
            "mind_forecast_score", "mind_debug_forecast_score",
            "mind_audit_road_plan", "mind_audit_road_episode", "mind_debug_road_margin",
+           "mind_audit_ttc", "mind_debug_box_ttc",
            "mind_loop_create", "mind_loop_destroy", "mind_loop_reset", "mind_loop_advance", "mind_loop_state", "mind_loop_last_plan", "mind_loop_export",
            "mind_planner_create", "mind_planner_destroy", "mind_planner_reset", "mind_planner_observe", "mind_planner_set_lanes", "mind_planner_set_target_lane",
            "mind_planner_set_solve_lane", "mind_planner_set_eval_lane", "mind_planner_plan", "mind_planner_last_plan", "mind_planner_export"]
@@ -373,6 +384,9 @@ def load():
                                                                                       C.POINTER(AuditRoadEpisodeOut)]
     lib.mind_debug_road_margin.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(AuditBox)] + road + [C.POINTER(C.c_double), C.POINTER(C.c_double)] + \
         [C.POINTER(C.c_int32)] * 3
+    lib.mind_audit_ttc.argtypes = [C.c_void_p, C.POINTER(AuditBox), C.POINTER(AuditTtcCfg), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
+                                   C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_double), C.POINTER(AuditTtcOut)]
+    lib.mind_debug_box_ttc.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     for n in EXPORTS:
         getattr(lib, n)
         if n not in ("mind_last_error_string", "mind_debug_read"):
@@ -596,6 +610,25 @@ def box_clearance(kind, a, b, trig=None):
     rc = lib.mind_debug_box_clearance(int(kind), len(a), dp(a), dp(b), dp(tg), dp(out))
     if rc != MIND_OK:
         raise ValueError(f"mind_debug_box_clearance rejects kind {kind!r}")
+    return out
+
+
+def box_ttc(a, b, trig=None):
+    """ttc_geom.h on the CPU (mind_debug_box_ttc; no GPU), pair by pair: the first time at which the rectangles a [n, 7] = (x, y, yaw, L, W,
+    vx, vy) and b [n, 7], each translating at its constant velocity, overlap -- 0.0 when they do now, +inf when they never do; touching is
+    no hit, and there is no horizon.  trig [n, 4] = (cos a, sin a, cos b, sin b), None = the kernels' own sin / cos.  -> float64 [n]"""
+    import numpy as np
+    lib = load()
+    a = np.ascontiguousarray(a, np.float64).reshape(-1, 7)
+    b = np.ascontiguousarray(b, np.float64).reshape(-1, 7)
+    tg = None if trig is None else np.ascontiguousarray(trig, np.float64).reshape(-1, 4)
+    if len(b) != len(a) or (tg is not None and len(tg) != len(a)):
+        raise ValueError(f"box_ttc: {len(a)} boxes a, {len(b)} b" + ("" if tg is None else f", {len(tg)} trig rows"))
+    out = np.zeros(len(a))
+    dp = lambda v: None if v is None else v.ctypes.data_as(C.POINTER(C.c_double))
+    rc = lib.mind_debug_box_ttc(len(a), dp(a), dp(b), dp(tg), dp(out))
+    if rc != MIND_OK:
+        raise ValueError(f"mind_debug_box_ttc rejects its arguments ({rc})")
     return out
 
 

@@ -16,7 +16,11 @@ clearance < 0; touching (0.0) is no hit.  The nominal boxes are nominal: every b
 
 The ROAD audit says what the ego did to the road, by the same conventions (mind_audit_road_plan / mind_audit_road_episode; geometry:
 mind_amd/csrc/road_geom.h): ``Road`` holds the drivable area of a map as rings, ``audit_road_plan`` / ``audit_road_rollouts`` /
-``EpisodeRoadAuditor`` mirror the three above with the signed margin of the ego box's corners to the road (negative: off the road)."""
+``EpisodeRoadAuditor`` mirror the three above with the signed margin of the ego box's corners to the road (negative: off the road).
+
+The TIME-TO-COLLISION audit says how close to a collision the ego drove (mind_audit_ttc; geometry: mind_amd/csrc/ttc_geom.h):
+``EpisodeTtcAuditor(sim)`` gives per step the first time at which the ego box and a track's box would overlap if both kept their
+velocity -- the reference tests no box against anything (agent.py:92-105, visualization.py:69-72), so the definition is this project's."""
 import numpy as np
 
 from .planners.mind.utils import _name
@@ -171,9 +175,10 @@ class EpisodeAuditor:
         return out
 
 
-def _part(per, idx, value, tag, nan_step):
+def _part(per, idx, value, tag, nan_step, bar=0.0):
     """summary of the steps ``idx`` of a trace whose per-step arrays are ``per``, by the rules of the whole-trace summary over
-    per[value] with the tag per["step_" + tag] (the lowest step wins ties).  ``nan_step`` (the road audit): a NaN step reports NaN, that
+    per[value] with the tag per["step_" + tag] (the lowest step wins ties); a step is a hit when its value is below ``bar`` (0.0 for the
+    clearance and road audits, the bound for the time to collision).  ``nan_step`` (the road audit): a NaN step reports NaN, that
     step, -1, -1, -1; without it (the clearance audit) the first minimum is numpy's argmin"""
     if len(idx) == 0:
         return None
@@ -183,10 +188,47 @@ def _part(per, idx, value, tag, nan_step):
     if len(bad):
         out.update({"ego_min": float("nan"), "ego_step": int(idx[bad[0]]), "ego_" + tag: -1, "ego_hits": -1, "ego_first": -1})
         return out
-    hit, k = np.flatnonzero(m < 0.0), int(np.argmin(m))               # (first minimum)
+    hit, k = np.flatnonzero(m < bar), int(np.argmin(m))               # (first minimum)
     out.update({"ego_min": float(m[k]), "ego_step": int(idx[k]), "ego_" + tag: int(per["step_" + tag][idx[k]]), "ego_hits": int(len(hit)),
                 "ego_first": int(idx[hit[0]]) if len(hit) else -1})
     return out
+
+
+# ---- the time-to-collision audit ------------------------------------------------------------------------------------------------------
+
+DEFAULT_TTC_HORIZON = 3.0       # seconds: a time to collision above it counts as none
+DEFAULT_TTC_BOUND = 0.95        # seconds: a step with a time to collision below it is a hit
+
+
+class EpisodeTtcAuditor:
+    """Wraps a ClosedLoopSim exactly as EpisodeAuditor does; ``report()`` gives, per recorded step, the time to collision of the ego box
+    with the nearest-in-time track's box when both keep the velocity they have at that step (mind_audit_ttc; geometry:
+    mind_amd/csrc/ttc_geom.h), in one device call.  ``horizon`` and ``bound`` (seconds) are defaults only: the first is the look-ahead
+    beyond which a collision counts as none, the second the bar below which a step is a hit."""
+
+    def __init__(self, sim, ego_box=BOXES["VEHICLE"], horizon=DEFAULT_TTC_HORIZON, bound=DEFAULT_TTC_BOUND, runtime=None):
+        self.sim, self.ego_box, self.horizon, self.bound, self.runtime = sim, ego_box, float(horizon), float(bound), runtime
+        self.states, self.enabled, self.times = [], [], []
+
+    step = EpisodeAuditor.step
+    run = EpisodeAuditor.run
+
+    def report(self):
+        """-> dict: ego_min, ego_step, ego_track, ego_hits (steps with ttc < bound), ego_first of the whole trace; times [S], enabled [S],
+        step_ttc [S] (seconds; 0.0: overlapping now, +inf: none within the horizon), step_track [S] (-1 for +inf); ``before`` / ``after``:
+        the same summary and per-step arrays of the steps before and from the take-over (None when there is no such step); steps are
+        indices into the recorded trace"""
+        if len(self.times) == 0:
+            raise RuntimeError("EpisodeTtcAuditor.report: no step was recorded")
+        ego = np.stack(self.states)
+        exo, valid, boxes = tabulate_exo(self.sim.world, self.times)
+        res = _runtime(self.runtime).audit_ttc(ego[None], exo, valid, boxes, self.ego_box, self.horizon, self.bound)
+        per = {k: res[k][0] for k in ("step_ttc", "step_track")}
+        en = np.array(self.enabled, bool)
+        out = dict(times=np.array(self.times), enabled=en, **per,
+                   **{k: (float if k == "ego_min" else int)(res[k][0]) for k in ("ego_min", "ego_step", "ego_track", "ego_hits", "ego_first")})
+        out["before"], out["after"] = (_part(per, i, "step_ttc", "track", nan_step=False, bar=self.bound) for i in (np.flatnonzero(~en), np.flatnonzero(en)))
+        return out
 
 
 # ---- the road audit -----------------------------------------------------------------------------------------------------------------

@@ -199,7 +199,7 @@ extern "C" int mind_audit_episode(mind_ctx *c, const mind_audit_box *ego, int n_
   hipLaunchKernelGGL(k_audit_episode, dim3((unsigned)n_steps, (unsigned)((n_ego + AU_EB - 1) / AU_EB)), dim3(AU_EB), 0, s, eb, n_ego, n_steps, n_tracks,
                      f_ego.at(d), f_exo.at(d), f_val.at(d), f_box.at(d), f_clear.at(d), f_track.at(d));
   HIPCHK(c, hipGetLastError());
-  hipLaunchKernelGGL(k_audit_episode_egos<false>, dim3((unsigned)((n_ego + 63) / 64)), dim3(64), 0, s, n_ego, n_steps, f_clear.at(d), f_track.at(d),
+  hipLaunchKernelGGL(k_audit_episode_egos<false>, dim3((unsigned)((n_ego + 63) / 64)), dim3(64), 0, s, n_ego, n_steps, 0.0, f_clear.at(d), f_track.at(d),
                      f_emin.at(d), f_estep.at(d), f_etrack.at(d), f_ehits.at(d), f_efirst.at(d));
   HIPCHK(c, hipGetLastError());
   return ar_finish(c, d, {{out->step_clear, f_clear}, {out->step_track, f_track}, {out->ego_min, f_emin}, {out->ego_step, f_estep},

@@ -154,12 +154,12 @@ __global__ __launch_bounds__(AU_EB) void k_audit_episode(AuBox ego, int n_ego, i
 }
 
 // per ego, for both audits -- mind_audit_episode folds (step_clear, step_track), mind_audit_road_episode (step_margin, step_corner): the
-// minimum value over the steps with its step and that step's tag (the lowest step wins ties), the steps below zero (hits) and the first of
-// them.  NAN_STEP (the road audit, whose boxes report NaN for a non-finite state row): a trace holding a NaN step reports min = NaN,
+// minimum value over the steps with its step and that step's tag (the lowest step wins ties), the steps below the bar (hits; both audits
+// hand 0.0, mind_audit_ttc its `bound` over (step_ttc, step_track)) and the first of them.  NAN_STEP (the road audit, whose boxes report NaN for a non-finite state row): a trace holding a NaN step reports min = NaN,
 // step = the first such step, tag = -1, hits = -1, first = -1.  Without it (the clearance audit, whose host entry admits finite inputs
 // only) a NaN is compared like any value: at step 0 it stays the minimum, at a later step it is passed over.
 template <bool NAN_STEP>
-__global__ __launch_bounds__(64) void k_audit_episode_egos(int n_ego, int S, const double *__restrict__ step_val, const int *__restrict__ step_tag,
+__global__ __launch_bounds__(64) void k_audit_episode_egos(int n_ego, int S, double bar, const double *__restrict__ step_val, const int *__restrict__ step_tag,
                                                            double *__restrict__ ego_min, int *__restrict__ ego_step, int *__restrict__ ego_tag,
                                                            int *__restrict__ ego_hits, int *__restrict__ ego_first) {
   const int g = blockIdx.x * 64 + threadIdx.x;
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(64) void k_audit_episode_egos(int n_ego, int S, con
     if constexpr (NAN_STEP)
       if (d != d) { bad = s; break; }
     if (s == 0 || d < mn) { mn = d; ms = s; mt = step_tag[row + s]; }
-    if (d < 0.0) {
+    if (d < bar) {
       if (first < 0) first = s;
       ++hits;
     }

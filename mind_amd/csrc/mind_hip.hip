@@ -35,6 +35,7 @@
 #include "audit_kernels.hip"
 #include "forecast_kernels.hip"
 #include "road_kernels.hip"
+#include "ttc_kernels.hip"
 #include "pair_jobs.h"
 #include "pred_choice.h"
 #include "ilqr_choice.h"
@@ -157,7 +158,7 @@ struct mind_ctx {
       rows, rpe_ptrs;
   // ilqr workspaces
   DevBuf ilqr_dev, aime_dev, rebase_dev2[2], dec_h2;
-  // scratch of the two clearance audits, the two road audits and mind_forecast_score (ar_begin, audit_host.hip).  One buffer serves all five:
+  // scratch of the two clearance audits, the two road audits, mind_forecast_score and mind_audit_ttc (ar_begin, audit_host.hip).  One buffer serves all six:
   // each is synchronous on the context's stream and refuses a busy context, so a call never sees another call's scratch in flight -- and
   // each uploads every input its kernels read, so none relies on what an earlier call left
   DevBuf audit_dev;
@@ -1275,3 +1276,6 @@ extern "C" int64_t mind_debug_read(mind_ctx *c, const char *name, float *host, i
 
 // ---- the road audit of plans and episodes (outside every planning cycle)
 #include "road_host.hip"
+
+// ---- the time-to-collision audit of episodes (outside every planning cycle)
+#include "ttc_host.hip"

@@ -115,7 +115,7 @@ extern "C" int mind_audit_road_episode(mind_ctx *c, const mind_audit_box *ego, c
   hipLaunchKernelGGL(k_road_boxes, dim3((unsigned)((R + RD_BB - 1) / RD_BB)), dim3(RD_BB), 0, s, eb, (long)R, f_ego.at(d), 4, 3, road.verts.at(d), road.off.at(d),
                      road.V, f_m.at(d), f_c.at(d), f_r.at(d), f_e.at(d));
   HIPCHK(c, hipGetLastError());
-  hipLaunchKernelGGL(k_audit_episode_egos<true>, dim3((unsigned)((n_ego + 63) / 64)), dim3(64), 0, s, n_ego, n_steps, f_m.at(d), f_c.at(d), f_emin.at(d),
+  hipLaunchKernelGGL(k_audit_episode_egos<true>, dim3((unsigned)((n_ego + 63) / 64)), dim3(64), 0, s, n_ego, n_steps, 0.0, f_m.at(d), f_c.at(d), f_emin.at(d),
                      f_estep.at(d), f_ecorner.at(d), f_ehits.at(d), f_efirst.at(d));
   HIPCHK(c, hipGetLastError());
   return ar_finish(c, d, {{out->step_margin, f_m}, {out->step_corner, f_c}, {out->step_ring, f_r}, {out->step_edge, f_e}, {out->ego_min, f_emin},

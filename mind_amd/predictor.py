@@ -680,6 +680,17 @@ class HipPredictor:
         Returns a dict: step_clear [E, S], step_track int32 [E, S], ego_min [E], ego_step, ego_track, ego_hits, ego_first int32 [E]."""
         eg = self._ego_traces(ego_states)
         E, S = eg.shape[:2]
+        ex, va, bx, nt = self._scene_tables(S, exo, valid, boxes)
+        box = self._audit_box(ego_box, "ego_box")
+        out, res = _lib.out_record(_lib.AuditEpisodeOut, lambda k: (E, S) if k.startswith("step_") else (E,))
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        rc = self.lib.mind_audit_episode(self.ctx, C.byref(box), E, S, nt, dp(eg), dp(ex), va.ctypes.data_as(C.POINTER(C.c_uint8)), dp(bx), C.byref(out))
+        _lib.check(self.lib, self.ctx, rc, "mind_audit_episode")
+        return res
+
+    @staticmethod
+    def _scene_tables(S, exo, valid, boxes):
+        """the replayed scene of an episode audit -> the checked contiguous exo [S, n, 5], valid uint8 [S, n], boxes [n, 2] and n"""
         ex = np.ascontiguousarray(exo, np.float64)
         va = np.ascontiguousarray(valid, np.uint8)
         bx = np.ascontiguousarray(boxes, np.float64)
@@ -690,11 +701,32 @@ class HipPredictor:
             raise ValueError(f"valid must be [{S}, {nt}] and boxes [{nt}, 2], got {list(va.shape)} and {list(bx.shape)}")
         if not np.all(np.isfinite(bx[1:])) or np.any(bx[1:] < 0.0):
             raise ValueError("boxes must be finite and >= 0")
+        return ex, va, bx, nt
+
+    # ---- time-to-collision audit (mind_audit_ttc): outside every planning cycle ------------------------------
+    def audit_ttc(self, ego_states, exo, valid, boxes, ego_box, horizon=3.0, bound=0.95, lanes=0):
+        """Time to collision of E ego traces against one replayed scene in one call (mind_audit_ttc, k_audit_ttc): per step, the first time
+        at which the ego box and a track's box overlap when both keep the velocity they have at that step (ttc_geom.h; exact, no time
+        sampling).  The arguments of ``audit_episode``; ``horizon``: a time above it counts as never (+inf), ``bound``: a step with
+        ttc < bound is a hit (both in seconds, both defaults only); ``lanes``: the kernel's layout -- 0 = the library's rule, 1 = thread
+        per ego, 2 = lanes over tracks -- which changes no result.  Returns a dict: step_ttc [E, S] (0.0: overlapping now; +inf: none within
+        the horizon), step_track int32 [E, S] (-1 for +inf), ego_min [E], ego_step, ego_track, ego_hits, ego_first int32 [E]."""
+        eg = self._ego_traces(ego_states)
+        E, S = eg.shape[:2]
+        ex, va, bx, nt = self._scene_tables(S, exo, valid, boxes)
+        horizon, bound = float(horizon), float(bound)
+        if not np.isfinite(horizon) or horizon <= 0.0:
+            raise ValueError(f"horizon must be finite and > 0, got {horizon!r}")
+        if not np.isfinite(bound) or bound < 0.0:
+            raise ValueError(f"bound must be finite and >= 0, got {bound!r}")
+        if lanes not in (0, 1, 2):
+            raise ValueError(f"lanes must be 0 (the library's rule), 1 (thread per ego) or 2 (lanes over tracks), got {lanes!r}")
         box = self._audit_box(ego_box, "ego_box")
-        out, res = _lib.out_record(_lib.AuditEpisodeOut, lambda k: (E, S) if k.startswith("step_") else (E,))
+        cfg = _lib.AuditTtcCfg(horizon, bound, int(lanes))
+        out, res = _lib.out_record(_lib.AuditTtcOut, lambda k: (E, S) if k.startswith("step_") else (E,))
         dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
-        rc = self.lib.mind_audit_episode(self.ctx, C.byref(box), E, S, nt, dp(eg), dp(ex), va.ctypes.data_as(C.POINTER(C.c_uint8)), dp(bx), C.byref(out))
-        _lib.check(self.lib, self.ctx, rc, "mind_audit_episode")
+        rc = self.lib.mind_audit_ttc(self.ctx, C.byref(box), C.byref(cfg), E, S, nt, dp(eg), dp(ex), va.ctypes.data_as(C.POINTER(C.c_uint8)), dp(bx), C.byref(out))
+        _lib.check(self.lib, self.ctx, rc, "mind_audit_ttc")
         return res
 
     # ---- road audit (mind_audit_road_plan / mind_audit_road_episode): outside every planning cycle ---------

@@ -63,6 +63,11 @@ def audit_episode(ego_states, exo, valid, boxes, ego_box):
     return get_runtime().audit_episode(ego_states, exo, valid, boxes, ego_box)
 
 
+def audit_ttc(ego_states, exo, valid, boxes, ego_box, horizon=3.0, bound=0.95, lanes=0):
+    """``HipPredictor.audit_ttc`` on this thread's runtime: time to collision of ego traces against one replayed scene."""
+    return get_runtime().audit_ttc(ego_states, exo, valid, boxes, ego_box, horizon, bound, lanes)
+
+
 def audit_road_plan(flats, xs, verts, poly_off, ego_box):
     """``HipPredictor.audit_road_plan`` on this thread's runtime: road margin of candidate state sets on the cost trees of a plan."""
     return get_runtime().audit_road_plan(flats, xs, verts, poly_off, ego_box)

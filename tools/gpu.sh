@@ -9,6 +9,7 @@
 #   kstats <tag> <workload> [ENV=..]    rocprofv3 --kernel-trace --stats over a short bench run of the workload (demo_1, cfg4tree, stress128tree ...)
 #   forecast <tag>                      tools/forecast_rate.py (mind_forecast_score against read-back + numpy) and a kernel trace of its two kernels
 #   road <tag>                          tools/road_rate.py (mind_audit_road_plan against read-back + numpy) and a kernel trace of its kernels
+#   ttc <tag>                           tools/ttc_rate.py (mind_audit_ttc in both lane layouts next to mind_audit_episode) and a kernel trace of their kernels
 #   pmc <tag> <kernel> <workload>       two --pmc passes (SQ activity | LDS + instruction mix), kernel trace only beside them, summarised per kernel
 #   ab-env <tag> "<ENV=..>" ...         same-box A/B of environment variants on the headline loop (three interleaved repetitions)
 #   ab-tree <tag> "<ENV=..>" ...        the same on the full cfg4 tree
@@ -110,6 +111,19 @@ import csv
 for r in csv.DictReader(open("$O/road_kernel_trace.csv")):
     if "k_road" in r["Kernel_Name"]:
         print(r["Kernel_Name"][:40].ljust(40), "grid", r.get("Grid_Size_X", "?").rjust(10), ("%.1f us" % ((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)).rjust(12))
+PY
+  ;;
+ttc)
+  # time-to-collision audit: call times of both lane layouts next to mind_audit_episode (-> $O/ttc_rate.json), then, in a run of its own, the kernels' times
+  timeout -k 10 600 python tools/ttc_rate.py --out $O/ttc_rate.json > $O/ttc_rate.txt 2> $O/ttc_rate.err || { tail -5 $O/ttc_rate.err; exit 1; }
+  grep -v "^{" $O/ttc_rate.txt
+  (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$O/trace -- python $ROOT/tools/ttc_rate.py --once > /dev/null 2> $ROOT/$O/trace.err) || { tail -5 $O/trace.err; exit 1; }
+  f=$(find $O/trace -name "*kernel_trace.csv" | head -1); cp $f $O/ttc_kernel_trace.csv; rm -rf $O/trace
+  python - <<PY | tee $O/ttc_kernel_times.txt
+import csv, re
+rows = [r for r in csv.DictReader(open("$O/ttc_kernel_trace.csv")) if re.search("k_audit_ttc|k_audit_episode(?!_egos)", r["Kernel_Name"])]
+for r in rows[1::2]:          # every call runs twice: the second
+    print(r["Kernel_Name"][:48].ljust(48), "grid", r.get("Grid_Size_X", "?").rjust(10), ("%.1f us" % ((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)).rjust(12))
 PY
   ;;
 pmc)
