@@ -291,6 +291,9 @@ static void il_fill_const(IlqrConst &K, const mind_ilqr_cfg *cfg, int use_exo, c
   for (int i = 0; i < H && K.lin; ++i) K.lin = R.gy[i] == ((i == H - 1 ? K.fsy : (double)i * K.stepy) + R.offy);
   K.in_x0 = R.offx + 1.5 * R.grid_res; K.in_x1 = R.offx + ((double)W - 2.5) * R.grid_res;
   K.in_y0 = R.offy + 1.5 * R.grid_res; K.in_y1 = R.offy + ((double)H - 2.5) * R.grid_res;
+  // reach of the relevant-agent lists beyond sigma + offset + IL_RMARGIN: a query's window cells lie within 1.5 cells of it along either
+  // axis, 1.5 * sqrt(2) = 2.1214 cells away at most
+  K.rel_reach = 2.125 * R.grid_res;
 }
 
 // ---- 5. stage: the device arena and the host staging of the results; the image of the arena's read-only part (c->il_img), the trees'

@@ -147,6 +147,7 @@ struct IlqrConst {
   int lin, pad_;
   double stepx, stepy, fsx, fsy;
   double in_x0, in_x1, in_y0, in_y1;   // conservative "window fully inside the grid" box for the list fast path
+  double rel_reach;                    // [m] how far a window cell lies from its query at most: >= 1.5 cells * sqrt(2) * res (host)
   GP<const double> quad;       // [H*W] squared distance to the target lane
 };
 
@@ -276,26 +277,34 @@ __device__ __forceinline__ void il_field(const IlqrConst &C, const IlqrTreeDev &
   yi = yi < 0 ? 0 : (yi > C.H - 1 ? C.H - 1 : yi);
   const float pf = GEN ? 0.f : T.prob[i];
   const double wp = (double)((float)C.w_tgt * pf);
-  // lanes 0..62: cell = lane % 9, agent slot = lane / 9 (7 slots)
+  // the exo sum of the nine window cells in ASCENDING agent order, the oracle's: chunks of seven agents, lanes 0..62 compute the terms
+  // (cell = lane % 9, agent = the chunk's first + lane / 9), then every lane adds the seven terms of its cell in agent order.  A chunk
+  // whose terms are all zero is skipped: x + 0.0 == x, and the sum is never -0.0
   const int cell = lane % 9, slot = lane / 9;
   int sy, sx;
   il_window_src((int)xi, (int)yi, C.W, C.H, cell / 3, cell % 3, sy, sx);
-  double part = 0.0;
-  if (lane < 63 && sy >= 0 && C.use_exo) {
-    const double cx = C.gx[sx], cy = C.gy[sy];
-    for (int e = 1 + slot; e < T.n_agents; e += 7) {
-      const double ec = ag[4 * e + 2];
-      const double dx = cx - ag[4 * e], dy = cy - ag[4 * e + 1];
-      const double d2 = dx * dx + dy * dy;
-      if (d2 > ag[4 * e + 3]) continue;
-      double v = ec - sqrt(d2);
-      v = v > 0.0 ? v : 0.0;
-      if (v > 0.0) v += C.w_exo_cost;
-      part += v;
+  double covf = 0.0;
+  if (!GEN && C.use_exo) {
+    const bool on = lane < 63 && sy >= 0;
+    const double cx = C.gx[on ? sx : 0], cy = C.gy[on ? sy : 0];
+    for (int e0 = 1; e0 < T.n_agents; e0 += 7) {
+      const int e = e0 + slot;
+      double v = 0.0;
+      if (on && e < T.n_agents) {
+        const double ec = ag[4 * e + 2];
+        const double dx = cx - ag[4 * e], dy = cy - ag[4 * e + 1];
+        const double d2 = dx * dx + dy * dy;
+        if (d2 <= ag[4 * e + 3]) {                 // else max(ec - sqrt(d2), 0) == 0 exactly
+          v = ec - sqrt(d2);
+          v = v > 0.0 ? v : 0.0;
+          if (v > 0.0) v += C.w_exo_cost;
+        }
+      }
+      if (!__any(v != 0.0)) continue;
+#pragma unroll
+      for (int s = 0; s < 7; ++s) covf += __shfl(v, cell + 9 * s, 64);
     }
   }
-  IL_WFENCE();
-  scr[lane] = part;
   IL_WFENCE();
   if (lane < 9) {
     double cell_v = 0.0;
@@ -303,8 +312,6 @@ __device__ __forceinline__ void il_field(const IlqrConst &C, const IlqrTreeDev &
     if (sy >= 0 && GEN) {
       cell_v = T.field[((size_t)i * C.H + sy) * C.W + sx];
     } else if (sy >= 0) {
-      double covf = 0.0;
-      for (int s = 0; s < 7; ++s) covf += scr[lane + 9 * s];
       const double q = C.quad[(size_t)sy * C.W + sx];
       if (C.use_exo) {
         const double ego_cov = ag[2];
@@ -1112,7 +1119,7 @@ __device__ __forceinline__ void il_deriv_pass(const IlqrConst &C, const IlqrTree
         const double ax = (double)smx[e * nbp + n], ay = (double)smy[e * nbp + n];
         const double ec = (double)(scv[e * nbp + n] + (float)C.w_exo_off);
         const double dx = ax - x[0], dy = ay - x[1];
-        const double rr = ec + IL_RMARGIN + 1.0;      // 1.0 > 1.5 cells * sqrt(2) * 0.4 m
+        const double rr = ec + IL_RMARGIN + C.rel_reach;      // a window cell lies within 1.5 cells * sqrt(2) of its query, whatever the grid
         if (valid && dx * dx + dy * dy < rr * rr) atomicOr(&dmask[n * 4 + (e >> 5)], 1u << (e & 31));
       }
       __syncthreads();

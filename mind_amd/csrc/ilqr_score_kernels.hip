@@ -18,7 +18,7 @@
 #define IL_SC_THREADS 512
 #define IL_SC_WAVES (IL_SC_THREADS / 64)
 #define IL_SC_CB 64        // candidates per workgroup at most: one lane each in the state recursion
-#define IL_SC_SCR 80       // doubles of per-wave LDS scratch: il_field's 64 partial sums + 9 window cells
+#define IL_SC_SCR 80       // doubles of per-wave LDS scratch: il_field's 9 window cells behind 64 spare ones
 #define IL_SC_DEPTH 16     // frames of the pairwise sum's recursion: a row of n doubles holds at most log2(n / 128) + 1 at a time (14 for the 2^20 the host admits)
 
 // one leaf of numpy's add.reduce (n <= 128): il_np_sum's first two branches
