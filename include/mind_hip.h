@@ -307,7 +307,9 @@ int mind_debug_pair_schedule(const int *scene_tokens, const int *scene_actors, i
  *   [22] decoder actor part (0 k_dec_actor<0>, 1 k_dec_actor<1> + <2> over two streams, 2 k_dec_actor_mfma)  [23] np of the MFMA form, else 0
  *   [24] fp32 decoder  [25] split over two streams  [26] k_dec_scene_mw wanted  [27] its workgroups  [28] k_dec_scene_c + k_dec_cls
  *   [29] the context stream waits for the target embedding before the fusion layers  [30] agents per workgroup of the split form's head
- *   (k_dec_actor<2, .>: 1, 2 or 4; 0 outside that form)  [31] 0
+ *   (k_dec_actor<2, .>: 1, 2 or 4; 0 outside that form)  [31] workgroups per scene of the scene part's launch chain k_dec_chain1..4 (32, 16 or
+ *   8: the largest with scenes x workgroups <= n_cu; 0: one of the one-launch forms [26] / [28] / k_dec_scene -- "dec_mw" or "dec_cls_side" set,
+ *   or more than n_cu / 8 scenes)
  * and one row {first token, tokens, kind (0 VALU, 1 fp32 MFMA, 2 bf16 split MFMA), layer-wise, small (four tokens per workgroup), merged
  * (k_token_m)} per token run.  Returns the length of the full record, or MIND_EINVAL for an unknown knob, pair_prec outside 0..3, a scene
  * with no actor or a negative lane count, or a null pointer.  Needs no GPU and no context. */
@@ -405,6 +407,14 @@ int mind_debug_weight_bind(const mind_tensor_desc *tensors, int n_tensors, const
  * doubles, evaluated on the device one wave of 64 arguments at a time -- out[4 n] = sin, cos, tan, the cosine that comes with the
  * tangent.  The oracle's oracle_sincos / oracle_tan_cos must give the same bits (tests/test_gpu_ilqr.py). */
 int mind_debug_trig(mind_ctx *ctx, const double *x, int n, double *out);
+
+/* Debug tap (tests, tools/dec_chain_forms.py): the decoder's scene part alone, with the context's weights, on n_scenes caller-given cls token
+ * rows (host, [n_scenes][128]) in a given form -- 0: the one-workgroup kernel k_dec_scene; 8, 16 or 32: the launch chain k_dec_chain1..4 with
+ * that many workgroups per scene (mind_amd/csrc/dec_chain.h), whatever mind_predict_batch's rule would take for the call.  Every form gives
+ * the same bits.  Cout (host, [n_scenes][6][128]) receives the mode tokens, cls (host, [n_scenes][6]) the mode probabilities.  The form is
+ * queued reps (1..1024) times; ms (reps floats, may be null) receives the time of each repetition between two events on the context's
+ * stream.  MIND_EINVAL for a null pointer, another form, n_scenes outside 1..4096 or reps outside 1..1024; MIND_ESTATE without weights. */
+int mind_debug_dec_scene(mind_ctx *ctx, const float *rows, int n_scenes, int form, float *Cout, float *cls, int reps, float *ms);
 
 /* Debug taps used by the parity tests only: run just the first n (0..6) fusion layers on the next
  * mind_predict_batch calls, and read internal device buffers ("x", "ST", "QK", "edge", "part",

@@ -229,7 +229,7 @@ class PlannerOut(C.Structure):     # mind_planner_out
 EXPORTS = ["mind_ctx_create", "mind_ctx_destroy", "mind_last_error_string", "mind_ctx_synchronize",
            "mind_weights_load", "mind_predict_batch", "mind_last_fusion_stats", "mind_last_actor_stats", "mind_debug_actor_lw_plan", "mind_last_token_stats", "mind_last_token_stage_ms", "mind_debug_token_lw_plan", "mind_set_profiling", "mind_debug_launch_times", "mind_debug_launch_clock",
            "mind_ilqr_solve_trees", "mind_ilqr_contingency", "mind_ilqr_solve_fields", "mind_cost_eval", "mind_ilqr_score_trees", "mind_ilqr_gains", "mind_ilqr_policy_rollouts", "mind_lane_dist_field", "mind_aime_world", "mind_aime_rebase", "mind_debug_aime_decide", "mind_debug_set_layers",
-           "mind_debug_read", "mind_set_pair_precision", "mind_get_pair_precision", "mind_debug_pack_bfrag", "mind_debug_pack_conv_frag", "mind_debug_pack", "mind_debug_weight_image", "mind_debug_weight_bind", "mind_debug_pair_schedule", "mind_debug_predict_choice", "mind_debug_ilqr_plan", "mind_debug_aime_book", "mind_set_tuning", "mind_get_tuning", "mind_debug_tuning", "mind_debug_live_handles", "mind_last_ilqr_stats", "mind_aime_plan", "mind_last_ilqr_profile", "mind_eval_traj_trees", "mind_last_ilqr_trace", "mind_ilqr_contingency_begin", "mind_ilqr_finish", "mind_fill_tracks", "mind_ilqr_contingency_begin_plan", "mind_debug_trig", "mind_aime_plan_begin", "mind_aime_plan_poll", "mind_aime_plan_finish", "mind_ctx_busy", "mind_ilqr_finish_plan",
+           "mind_debug_read", "mind_set_pair_precision", "mind_get_pair_precision", "mind_debug_pack_bfrag", "mind_debug_pack_conv_frag", "mind_debug_pack", "mind_debug_weight_image", "mind_debug_weight_bind", "mind_debug_pair_schedule", "mind_debug_predict_choice", "mind_debug_ilqr_plan", "mind_debug_aime_book", "mind_set_tuning", "mind_get_tuning", "mind_debug_tuning", "mind_debug_live_handles", "mind_last_ilqr_stats", "mind_aime_plan", "mind_last_ilqr_profile", "mind_eval_traj_trees", "mind_last_ilqr_trace", "mind_ilqr_contingency_begin", "mind_ilqr_finish", "mind_fill_tracks", "mind_ilqr_contingency_begin_plan", "mind_debug_trig", "mind_aime_plan_begin", "mind_aime_plan_poll", "mind_aime_plan_finish", "mind_ctx_busy", "mind_ilqr_finish_plan", "mind_debug_dec_scene",
            "mind_set_exchange", "mind_last_exchange_stats", "mind_debug_wait_word",
            "mind_predict_batch_aux", "mind_set_decoder_basis", "mind_get_decoder_basis", "mind_curve_eval", "mind_debug_curve_basis",
            "mind_audit_plan", "mind_audit_episode", "mind_debug_box_clearance",
@@ -346,6 +346,7 @@ def load():
     lib.mind_debug_weight_image.argtypes = [C.POINTER(TensorDesc), C.c_int, C.POINTER(C.c_float), C.c_size_t, C.c_char_p, C.c_size_t,
                                             C.POINTER(C.c_longlong), C.c_int, C.POINTER(C.c_longlong), C.c_char_p, C.c_int]
     lib.mind_debug_weight_bind.argtypes = [C.POINTER(TensorDesc), C.c_int, C.c_char_p, C.c_char_p, C.c_int]
+    lib.mind_debug_dec_scene.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_float)]
     lib.mind_debug_set_layers.argtypes = [C.c_void_p, C.c_int]
     lib.mind_debug_read.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_float), C.c_int64]
     lib.mind_set_exchange.argtypes = [C.c_void_p, C.c_int, C.c_int, EXCHANGE_FN, C.c_void_p, C.c_int]
@@ -400,7 +401,7 @@ def load():
 PRED_CHOICE_FIELDS = ("header", "n_runs", "np", "actor_form", "actor_arg", "actor_grid", "actor_chunk", "actor_chunks", "actor_launches", "qsplit", "qk_stride",
                       "tiled", "edge_bf16", "edge_pair_bytes", "tok_chunk", "tok_lw", "tok_chunks", "pair_family", "pair_np", "l5_jobs5", "xcd_lanes",
                       "xcd_lanes5", "dec_actor", "dec_np", "fp32_dec", "split_dec", "want_mw", "mw_blocks", "cls_on_side", "tgt_wait_first",
-                      "dec_head_ra")
+                      "dec_head_ra", "dec_chain_g")
 PAIR_PREC = ("f32", "bf16x3", "bf16", "bf16x6")
 
 
@@ -419,9 +420,23 @@ def predict_choice(knobs, prec, scenes, n_cu=256, have_side=True):
     if n == MIND_EINVAL:
         return None
     assert 0 < n <= cap and out[0] == 32 and n == 32 + 6 * out[1], n
-    d = dict(zip(PRED_CHOICE_FIELDS, out[:31]))
+    d = dict(zip(PRED_CHOICE_FIELDS, out[:32]))
     d["runs"] = [tuple(out[32 + 6 * i:38 + 6 * i]) for i in range(out[1])]
     return d
+
+
+def dec_scene(lib, ctx, rows, form, reps=1, timed=False):
+    """mind_debug_dec_scene: the decoder's scene part alone on the cls token rows `rows` [B,128] in form 0 (k_dec_scene) or 8 / 16 / 32 (the launch
+    chain with that many workgroups per scene) -> (Cout [B,6,128], cls [B,6]) and, if timed, the milliseconds of each of the reps repetitions"""
+    import numpy as np
+    rows = np.ascontiguousarray(rows, np.float32)
+    B = rows.shape[0]
+    assert rows.shape == (B, 128)
+    fp = C.POINTER(C.c_float)
+    cout, cls, ms = np.empty((B, 6, 128), np.float32), np.empty((B, 6), np.float32), np.zeros(reps, np.float32)
+    check(lib, ctx, lib.mind_debug_dec_scene(ctx, rows.ctypes.data_as(fp), B, int(form), cout.ctypes.data_as(fp), cls.ctypes.data_as(fp), reps,
+                                             ms.ctypes.data_as(fp) if timed else None), "mind_debug_dec_scene")
+    return (cout, cls, ms) if timed else (cout, cls)
 
 
 def knobs():

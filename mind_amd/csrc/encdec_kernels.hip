@@ -15,6 +15,7 @@
 #include "weight_tables.h"   // LaneW, ActorW, DecW
 #include "dec_curve.h"       // dec_curve_point
 #include "launch_clock.h"    // LcSlot, the stamps
+#include "dec_chain.h"       // index rules of k_dec_chain1..4
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -788,6 +789,7 @@ extern "C" size_t mind_actor_lds_bytes() { return (size_t)ACT_LDS_FLOATS * sizeo
 // =================================================================================================
 #define DEC_SCENE_PART 24576
 #define DEC_SCENE_LDS_FLOATS (256 + 768 + 768 + 2304 + 768 + 9216 + 768 + 144 + DEC_SCENE_PART)
+static_assert(DT == DC_THREADS && DEC_SCENE_PART == DC_PART_FLOATS, "dec_chain.h restates the workgroup the K splits are taken for");
 // target embedding (network.py:491-495): needs only the target polyline's LaneNet feature and its RPE, so it runs on the side stream
 // right behind that LaneNet launch, off the critical path of the fusion layers.  One workgroup per scene.
 __global__ __launch_bounds__(DT) void k_dec_tgt(const float *__restrict__ tgt_feat /*[B,128]*/, const float *__restrict__ tgt_rpe /*[B,20]*/,
@@ -824,6 +826,139 @@ __device__ int dec_trn_;
 #else
 #define DEC_MARK() do {} while (0)
 #endif
+// ---- the scene part's LDS carve and its small stages, one copy each: k_dec_scene_body (every form of the one-launch kernel) and the launch
+//      chain (k_dec_chain1..4) call the same functions on the same values, so their results are the same bits
+struct DecSm {
+  float (*v0)[256];
+  float (*v1)[768];
+  float (*C)[128];
+  float (*qkv)[384];
+  float (*att)[128];
+  float (*ff)[1536];
+  float (*t2)[128];
+  float (*sc)[6][6];
+  float *part;
+};
+__device__ __forceinline__ DecSm dec_carve(float *dsm) {
+  DecSm S;
+  S.v0 = (float (*)[256])(dsm);
+  S.v1 = (float (*)[768])(dsm + 256);
+  S.C = (float (*)[128])(dsm + 1024);
+  S.qkv = (float (*)[384])(dsm + 1792);
+  S.att = (float (*)[128])(dsm + 4096);
+  S.ff = (float (*)[1536])(dsm + 4864);
+  S.t2 = (float (*)[128])(dsm + 14080);
+  S.sc = (float (*)[6][6])(dsm + 14848);
+  S.part = dsm + 14992;
+  return S;
+}
+// ctx_proj's first layer (network.py:501): the scene's cls token -> v1[0][0..384), normalised
+__device__ __forceinline__ void dec_ctx0(const DecSm &S, const float *__restrict__ x, const int *__restrict__ cls_row, int b, const DecW &W) {
+  const int tid = threadIdx.x;
+  if (tid < 128) S.v0[0][tid] = x[(size_t)cls_row[b] * 128 + tid];
+  __syncthreads();
+  dense<1>(&S.v0[0][0], 256, 128, W.c0W, W.c0b, 384, &S.v1[0][0], 768, S.part, DEC_SCENE_PART);
+  DEC_MARK();
+  __syncthreads();
+  ln_rows(&S.v1[0][0], 768, 1, 384, W.c0g, W.c0be, true);
+  DEC_MARK();
+  __syncthreads();
+}
+// ctx_proj's second layer from its raw outputs ff[0][0..768): LayerNorm + ReLU, then the six mode tokens C
+__device__ __forceinline__ void dec_ctx3_norm(const DecSm &S, const DecW &W) {
+  const int tid = threadIdx.x;
+  ln_rows(&S.ff[0][0], 1536, 1, 768, W.c3g, W.c3be, true);
+  DEC_MARK();
+  __syncthreads();
+  for (int i = tid; i < 768; i += blockDim.x) S.C[i / 128][i % 128] = S.ff[0][i];
+  __syncthreads();
+}
+// encoder layer L up to its first norm: in-projection, scores, softmax, attention, out-projection, residual, LayerNorm n1 (4 heads x 32)
+__device__ __forceinline__ void dec_attn(const DecSm &S, const DecW &W, int L) {
+  const int tid = threadIdx.x;
+  float (*C)[128] = S.C;
+  float (*qkv)[384] = S.qkv;
+  float (*att)[128] = S.att;
+  float (*t2)[128] = S.t2;
+  float (*sc)[6][6] = S.sc;
+  dense<6>(&C[0][0], 128, 128, W.inW[L], W.inb[L], 384, &qkv[0][0], 384, S.part, DEC_SCENE_PART);
+  DEC_MARK();
+  __syncthreads();
+  if (tid < 4 * 36) {
+    const int hd = tid / 36, s = (tid % 36) / 6, t = tid % 6;
+    float d = 0.f;
+    for (int k = 0; k < 32; ++k) d = fmaf(qkv[s][hd * 32 + k], qkv[t][128 + hd * 32 + k], d);
+    sc[hd][s][t] = d / sqrtf(32.0f);
+  }
+  __syncthreads();
+  if (tid < 24) {
+    const int hd = tid / 6, s = tid % 6;
+    float m = -INFINITY;
+    for (int t = 0; t < 6; ++t) m = fmaxf(m, sc[hd][s][t]);
+    float e[6], sum = 0.f;
+    for (int t = 0; t < 6; ++t) { e[t] = expf(sc[hd][s][t] - m); sum += e[t]; }
+    for (int t = 0; t < 6; ++t) sc[hd][s][t] = e[t] / sum;
+  }
+  __syncthreads();
+  for (int i = tid; i < 6 * 128; i += blockDim.x) {
+    const int s = i / 128, c = i % 128, hd = c / 32;
+    float o = 0.f;
+    for (int t = 0; t < 6; ++t) o = fmaf(sc[hd][s][t], qkv[t][256 + c], o);
+    att[s][c] = o;
+  }
+  __syncthreads();
+  dense<6>(&att[0][0], 128, 128, W.outW[L], W.outb[L], 128, &t2[0][0], 128, S.part, DEC_SCENE_PART);
+  DEC_MARK();
+  __syncthreads();
+  for (int i = tid; i < 768; i += blockDim.x) C[i / 128][i % 128] += t2[i / 128][i % 128];
+  __syncthreads();
+  ln_rows(&C[0][0], 128, 6, 128, W.n1g[L], W.n1b[L], false);
+  DEC_MARK();
+  __syncthreads();
+}
+// ... and its end, from the feed-forward block's outputs t2: residual, LayerNorm n2
+__device__ __forceinline__ void dec_ffn_close(const DecSm &S, const DecW &W, int L) {
+  const int tid = threadIdx.x;
+  for (int i = tid; i < 768; i += blockDim.x) S.C[i / 128][i % 128] += S.t2[i / 128][i % 128];
+  __syncthreads();
+  ln_rows(&S.C[0][0], 128, 6, 128, W.n2g[L], W.n2b[L], false);
+  DEC_MARK();
+  __syncthreads();
+}
+// cls head on the mode tokens only (network.py:512, Q6), softmax over the 6 modes; `write`: this workgroup stores the scene's probabilities
+__device__ __forceinline__ void dec_cls_head(const DecSm &S, const DecW &W, int b, float *__restrict__ cls_out, bool write) {
+  const int tid = threadIdx.x;
+  float (*att)[128] = S.att;
+  float (*t2)[128] = S.t2;
+  float (*sc)[6][6] = S.sc;
+  dense<6>(&S.C[0][0], 128, 128, W.k0W, W.k0b, 128, &att[0][0], 128, S.part, DEC_SCENE_PART);
+  DEC_MARK();
+  __syncthreads();
+  ln_rows(&att[0][0], 128, 6, 128, W.k0g, W.k0be, true);
+  DEC_MARK();
+  __syncthreads();
+  dense<6>(&att[0][0], 128, 128, W.k3W, W.k3b, 128, &t2[0][0], 128, S.part, DEC_SCENE_PART);
+  DEC_MARK();
+  __syncthreads();
+  ln_rows(&t2[0][0], 128, 6, 128, W.k3g, W.k3be, true);
+  DEC_MARK();
+  __syncthreads();
+  for (int k = tid >> 6; k < 6; k += (int)(blockDim.x >> 6)) {
+    const int lane = tid & 63;
+    float s = t2[k][lane] * W.k6W[lane] + t2[k][lane + 64] * W.k6W[lane + 64];
+    s = wave_sum(s);
+    if (lane == 0) sc[0][0][k] = s + W.k6b[0];
+  }
+  __syncthreads();
+  if (tid == 0 && write) {
+    float m = -INFINITY;
+    for (int k = 0; k < 6; ++k) m = fmaxf(m, sc[0][0][k]);
+    float e[6], sum = 0.f;
+    for (int k = 0; k < 6; ++k) { e[k] = expf(sc[0][0][k] - m); sum += e[k]; }
+    for (int k = 0; k < 6; ++k) cls_out[(size_t)b * 6 + k] = e[k] / sum;
+  }
+  DEC_MARK();
+}
 // MW (k_dec_scene_mw): G workgroups per scene.  Every workgroup runs the whole decoder -- the small stages redundantly, which costs no time --
 // except the five stages that stream 0.8-1.2 MB of weights through one CU's L2 port (ctx_proj's second layer, the two feed-forward layers of
 // both encoder layers: 57 % of the one-workgroup kernel's time at ~60 % of the port's rate): there a workgroup computes its eighth of the
@@ -839,15 +974,12 @@ __device__ __forceinline__ void k_dec_scene_body(const float *__restrict__ x /*[
                                                  float *__restrict__ cls_out /*[B,6]*/, const DecW &W, int b, int wg, int G,
                                                  float *xbuf, unsigned *bar, unsigned *abort_word) {
   extern __shared__ __attribute__((aligned(16))) float dsm[];
-  float (*v0)[256] = (float (*)[256])(dsm);
-  float (*v1)[768] = (float (*)[768])(dsm + 256);
-  float (*C)[128] = (float (*)[128])(dsm + 1024);
-  float (*qkv)[384] = (float (*)[384])(dsm + 1792);
-  float (*att)[128] = (float (*)[128])(dsm + 4096);
-  float (*ff)[1536] = (float (*)[1536])(dsm + 4864);
-  float (*t2)[128] = (float (*)[128])(dsm + 14080);
-  float (*sc)[6][6] = (float (*)[6][6])(dsm + 14848);
-  float *part = dsm + 14992;
+  const DecSm S = dec_carve(dsm);
+  float (*v1)[768] = S.v1;
+  float (*C)[128] = S.C;
+  float (*ff)[1536] = S.ff;
+  float (*t2)[128] = S.t2;
+  float *part = S.part;
   const int PF = DEC_SCENE_PART;
   const int tid = threadIdx.x;
   int xstage = 0;                           // big stages so far (MW): selects the exchange buffer
@@ -862,14 +994,7 @@ __device__ __forceinline__ void k_dec_scene_body(const float *__restrict__ x /*[
   }
   if (PART != 2) {
   // ---- ctx_proj: cls token -> 6 mode tokens (network.py:501)
-  if (tid < 128) v0[0][tid] = x[(size_t)cls_row[b] * 128 + tid];
-  __syncthreads();
-  dense<1>(&v0[0][0], 256, 128, W.c0W, W.c0b, 384, &v1[0][0], 768, part, PF);
-  DEC_MARK();
-  __syncthreads();
-  ln_rows(&v1[0][0], 768, 1, 384, W.c0g, W.c0be, true);
-  DEC_MARK();
-  __syncthreads();
+  dec_ctx0(S, x, cls_row, b, W);
   if (MW) {
     dense_quads_part<1>(&v1[0][0], 768, 384, W.c3W, W.c3b, 768, &ff[0][0], 1536, part, PF, wg, G);
     if (dec_exchange<1>(&ff[0][0], 1536, 768, wg, G, (xstage++ & 1) ? xb1 : xb0, bar, abort_word)) return;
@@ -877,47 +1002,10 @@ __device__ __forceinline__ void k_dec_scene_body(const float *__restrict__ x /*[
     dense<1>(&v1[0][0], 768, 384, W.c3W, W.c3b, 768, &ff[0][0], 1536, part, PF);
   DEC_MARK();
   __syncthreads();
-  ln_rows(&ff[0][0], 1536, 1, 768, W.c3g, W.c3be, true);
-  DEC_MARK();
-  __syncthreads();
-  for (int i = tid; i < 768; i += blockDim.x) C[i / 128][i % 128] = ff[0][i];
-  __syncthreads();
+  dec_ctx3_norm(S, W);
   // ---- 2 post-norm encoder layers over the 6 mode tokens (4 heads x 32, ffn 1536)
   for (int L = 0; L < 2; ++L) {
-    dense<6>(&C[0][0], 128, 128, W.inW[L], W.inb[L], 384, &qkv[0][0], 384, part, PF);
-  DEC_MARK();
-    __syncthreads();
-    if (tid < 4 * 36) {
-      const int hd = tid / 36, s = (tid % 36) / 6, t = tid % 6;
-      float d = 0.f;
-      for (int k = 0; k < 32; ++k) d = fmaf(qkv[s][hd * 32 + k], qkv[t][128 + hd * 32 + k], d);
-      sc[hd][s][t] = d / sqrtf(32.0f);
-    }
-    __syncthreads();
-    if (tid < 24) {
-      const int hd = tid / 6, s = tid % 6;
-      float m = -INFINITY;
-      for (int t = 0; t < 6; ++t) m = fmaxf(m, sc[hd][s][t]);
-      float e[6], sum = 0.f;
-      for (int t = 0; t < 6; ++t) { e[t] = expf(sc[hd][s][t] - m); sum += e[t]; }
-      for (int t = 0; t < 6; ++t) sc[hd][s][t] = e[t] / sum;
-    }
-    __syncthreads();
-    for (int i = tid; i < 6 * 128; i += blockDim.x) {
-      const int s = i / 128, c = i % 128, hd = c / 32;
-      float o = 0.f;
-      for (int t = 0; t < 6; ++t) o = fmaf(sc[hd][s][t], qkv[t][256 + c], o);
-      att[s][c] = o;
-    }
-    __syncthreads();
-    dense<6>(&att[0][0], 128, 128, W.outW[L], W.outb[L], 128, &t2[0][0], 128, part, PF);
-  DEC_MARK();
-    __syncthreads();
-    for (int i = tid; i < 768; i += blockDim.x) C[i / 128][i % 128] += t2[i / 128][i % 128];
-    __syncthreads();
-    ln_rows(&C[0][0], 128, 6, 128, W.n1g[L], W.n1b[L], false);
-  DEC_MARK();
-    __syncthreads();
+    dec_attn(S, W, L);
     if (MW) {
       dense_quads_part<6>(&C[0][0], 128, 128, W.l1W[L], W.l1b[L], 1536, &ff[0][0], 1536, part, PF, wg, G);
       if (dec_exchange<6>(&ff[0][0], 1536, 1536, wg, G, (xstage++ & 1) ? xb1 : xb0, bar, abort_word)) return;
@@ -934,44 +1022,13 @@ __device__ __forceinline__ void k_dec_scene_body(const float *__restrict__ x /*[
       dense<6>(&ff[0][0], 1536, 1536, W.l2W[L], W.l2b[L], 128, &t2[0][0], 128, part, PF);
   DEC_MARK();
     __syncthreads();
-    for (int i = tid; i < 768; i += blockDim.x) C[i / 128][i % 128] += t2[i / 128][i % 128];
-    __syncthreads();
-    ln_rows(&C[0][0], 128, 6, 128, W.n2g[L], W.n2b[L], false);
-  DEC_MARK();
-    __syncthreads();
+    dec_ffn_close(S, W, L);
   }
   if (!MW || wg == 0)
     for (int i = tid; i < 768; i += blockDim.x) Cout[(size_t)b * 768 + i] = C[i / 128][i % 128];
   }
   if (PART == 1) return;
-  // ---- cls head on the mode tokens only (network.py:512, Q6), softmax over the 6 modes
-  dense<6>(&C[0][0], 128, 128, W.k0W, W.k0b, 128, &att[0][0], 128, part, PF);
-  DEC_MARK();
-  __syncthreads();
-  ln_rows(&att[0][0], 128, 6, 128, W.k0g, W.k0be, true);
-  DEC_MARK();
-  __syncthreads();
-  dense<6>(&att[0][0], 128, 128, W.k3W, W.k3b, 128, &t2[0][0], 128, part, PF);
-  DEC_MARK();
-  __syncthreads();
-  ln_rows(&t2[0][0], 128, 6, 128, W.k3g, W.k3be, true);
-  DEC_MARK();
-  __syncthreads();
-  for (int k = tid >> 6; k < 6; k += (int)(blockDim.x >> 6)) {
-    const int lane = tid & 63;
-    float s = t2[k][lane] * W.k6W[lane] + t2[k][lane + 64] * W.k6W[lane + 64];
-    s = wave_sum(s);
-    if (lane == 0) sc[0][0][k] = s + W.k6b[0];
-  }
-  __syncthreads();
-  if (tid == 0 && (!MW || wg == 0)) {
-    float m = -INFINITY;
-    for (int k = 0; k < 6; ++k) m = fmaxf(m, sc[0][0][k]);
-    float e[6], sum = 0.f;
-    for (int k = 0; k < 6; ++k) { e[k] = expf(sc[0][0][k] - m); sum += e[k]; }
-    for (int k = 0; k < 6; ++k) cls_out[(size_t)b * 6 + k] = e[k] / sum;
-  }
-  DEC_MARK();
+  dec_cls_head(S, W, b, cls_out, !MW || wg == 0);
 #ifdef MIND_DEC_TRACE
   if (blockIdx.x == 0 && tid == 0) {
     printf("[k_dec_scene] cycles between marks (dense / LayerNorm stages in program order):");
@@ -1002,6 +1059,145 @@ __global__ __launch_bounds__(DT) void k_dec_scene_mw(const float *__restrict__ x
   const int b = 8 * ((int)blockIdx.x / (8 * DEC_MW_G)) + (r & 7), wg = r >> 3;
   if (b >= n_scenes) return;
   k_dec_scene_body<true>(x, cls_row, Cout, cls_out, W, b, wg, DEC_MW_G, xbuf + (size_t)b * 2 * 6 * 1536, bars + 4 * (size_t)b, abort_word);
+}
+
+// ---- the scene part as a chain of four plain launches, G workgroups per scene (index rules and the proof sketch: dec_chain.h).  The small stages
+// run redundantly in every workgroup through the functions above; the three big stages are dealt over the scene's workgroups and, inside one,
+// over (K part, rows, output) items of ONE output each, so that at G = 16 several hundred threads hold a short chain instead of a hundred a long one.
+// Nothing here waits for another workgroup: what the workgroups of a scene exchange crosses a kernel boundary.
+//
+// One K part of a stage for the workgroup's slice: dst[((kp_dst + part) R + row) ldd + output] = sum over the part's Kc inputs, ascending k from
+// 0.f -- dense_quads' chain of that (part, row, output).  `in` holds the inputs from k_base on (the l2 stage reads the workgroup's own l1 slice).
+// NB weights are requested per thread before the first multiply-add; Kc % NB == 0, NB % 4 == 0.
+template <int R, int RPT, int NB>
+__device__ __forceinline__ void dc_slice_parts(const float *in, int ldi, int k_base, const float *__restrict__ WT, int NOUT, int Kc, const DcSlice sl,
+                                               float *dst, int kp_dst, int ldd) {
+  static_assert(R % RPT == 0 && NB % 4 == 0, "rows per thread divide the rows; inputs are read four at a time");
+  const int n_items = dc_items(R, RPT, sl.nkp, sl.no);
+  for (int item = threadIdx.x; item < n_items; item += blockDim.x) {
+    const DcItem it = dc_item(item, R, RPT, sl.no);
+    const int k0 = (sl.kp_lo + it.kpl) * Kc;
+    const float *w = WT + (size_t)k0 * NOUT + sl.o_lo + it.ol;
+    const float *xi = in + it.r0 * ldi + (k0 - k_base);
+    float acc[RPT];
+#pragma unroll
+    for (int j = 0; j < RPT; ++j) acc[j] = 0.f;
+    for (int k = 0; k < Kc; k += NB) {
+      float wv[NB];
+#pragma unroll
+      for (int q = 0; q < NB; ++q) wv[q] = w[(size_t)(k + q) * NOUT];
+#pragma unroll
+      for (int j = 0; j < RPT; ++j) {
+#pragma unroll
+        for (int q4 = 0; q4 < NB / 4; ++q4) {
+          const f32x4 xv = *(const f32x4 *)(xi + j * ldi + k + 4 * q4);
+          acc[j] = fmaf(wv[4 * q4 + 0], xv[0], acc[j]);
+          acc[j] = fmaf(wv[4 * q4 + 1], xv[1], acc[j]);
+          acc[j] = fmaf(wv[4 * q4 + 2], xv[2], acc[j]);
+          acc[j] = fmaf(wv[4 * q4 + 3], xv[3], acc[j]);
+        }
+        DENSE_ROW_FENCE();
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < RPT; ++j) dst[((size_t)(kp_dst + it.kpl) * R + it.r0 + j) * ldd + it.ol] = acc[j];
+  }
+}
+
+// the feed-forward block of encoder layer L up to the l2 partials: the workgroup's l1 slice (both K parts, bias + part 0 + part 1, ReLU) stays in
+// LDS and feeds the l2 parts that read exactly that slice; their partial sums go to p [32][6][128] of the scene.  Workgroup 0 also stores the
+// tokens C (behind LayerNorm n1) the next kernel adds the block's output to.
+template <int G>
+__device__ __forceinline__ void dc_ffn_parts(const DecSm &S, const DecW &W, int L, int wg, float *__restrict__ c_out, float *__restrict__ p_out) {
+  constexpr DcSlice s1 = dc_slice_l1(0, G), s2 = dc_slice_l2(0, G);
+  constexpr int RPT1 = dc_rows_per_thread(DC_ROWS, s1.nkp, s1.no), RPT2 = dc_rows_per_thread(DC_ROWS, s2.nkp, s2.no);
+  static_assert(s1.no * G == DC_L1.NOUT && s2.nkp * G == DC_L2.KP && s1.no == s2.nkp * DC_L2.Kc, "slices are exact and an l2 part reads the workgroup's own l1 slice");
+  static_assert(DC_L1.KP * DC_ROWS * s1.no <= DC_PART_FLOATS && DC_ROWS * s1.no <= DC_ROWS * 1536, "the slice's partials and outputs fit their LDS areas");
+  const int tid = threadIdx.x;
+  const DcSlice l1 = dc_slice_l1(wg, G), l2 = dc_slice_l2(wg, G);
+  if (wg == 0)
+    for (int i = tid; i < 768; i += blockDim.x) c_out[i] = S.C[i / 128][i % 128];
+  dc_slice_parts<DC_ROWS, RPT1, 32>(&S.C[0][0], 128, 0, W.l1W[L], DC_L1.NOUT, DC_L1.Kc, l1, S.part, 0, l1.no);
+  __syncthreads();
+  float *ffs = &S.ff[0][0];                     // [6][l1.no]: the workgroup's columns of ff
+  for (int i = tid; i < DC_ROWS * l1.no; i += blockDim.x) {
+    const int r = i / l1.no, ol = i % l1.no;
+    float v = W.l1b[L][l1.o_lo + ol];
+    for (int q = 0; q < DC_L1.KP; ++q) v += S.part[(q * DC_ROWS + r) * l1.no + ol];
+    ffs[i] = fmaxf(v, 0.f);
+  }
+  __syncthreads();
+  dc_slice_parts<DC_ROWS, RPT2, 24>(ffs, l1.no, l1.o_lo, W.l2W[L], DC_L2.NOUT, DC_L2.Kc, l2, p_out, l2.kp_lo, DC_L2.NOUT);
+}
+
+// ... and its end in the next kernel: t2 = bias + part 0 + ... + part 31 (every load of a thread in flight at once), onto the stored tokens
+__device__ __forceinline__ void dc_ffn_gather(const DecSm &S, const DecW &W, int L, const float *__restrict__ c_in, const float *__restrict__ p_in) {
+  const int tid = threadIdx.x;
+  for (int i = tid; i < 768; i += blockDim.x) S.C[i / 128][i % 128] = c_in[i];
+  if (tid < DC_ROWS * 128) {
+    float pv[DC_L2.KP];
+#pragma unroll
+    for (int q = 0; q < DC_L2.KP; ++q) pv[q] = p_in[(size_t)q * DC_ROWS * 128 + tid];
+    float v = W.l2b[L][tid % 128];
+#pragma unroll
+    for (int q = 0; q < DC_L2.KP; ++q) v += pv[q];
+    S.t2[tid / 128][tid % 128] = v;
+  }
+  __syncthreads();
+  dec_ffn_close(S, W, L);
+}
+
+// buf: DC_SCENE_FLOATS per scene (dec_chain.h)
+#define DC_Y(buf, b) ((buf) + (size_t)(b) * DC_SCENE_FLOATS)
+#define DC_C(buf, b, L) (DC_Y(buf, b) + DC_Y_FLOATS + (L) * DC_C_FLOATS)
+#define DC_P(buf, b, L) (DC_Y(buf, b) + DC_Y_FLOATS + 2 * DC_C_FLOATS + (size_t)(L) * DC_P_FLOATS)
+// kernel 1: ctx_proj's first layer in every workgroup, then the workgroup's slice of the second layer's raw outputs -> y
+template <int G>
+__global__ __launch_bounds__(DT) void k_dec_chain1(const float *__restrict__ x, const int *__restrict__ cls_row, float *__restrict__ buf, DecW W) {
+  extern __shared__ __attribute__((aligned(16))) float dsm[];
+  const DecSm S = dec_carve(dsm);
+  const int b = (int)blockIdx.x / G, wg = (int)blockIdx.x % G, tid = threadIdx.x;
+  dec_ctx0(S, x, cls_row, b, W);
+  const DcSlice c3 = dc_slice_c3(wg, G);
+  static_assert(dc_slice_c3(0, G).no * G == DC_C3.NOUT && dc_slice_c3(0, G).no * DC_C3.KP <= DT, "slices are exact; one pass over the threads");
+  dc_slice_parts<1, 1, 32>(&S.v1[0][0], 768, 0, W.c3W, DC_C3.NOUT, DC_C3.Kc, c3, S.part, 0, c3.no);
+  __syncthreads();
+  if (tid < c3.no) {
+    float v = W.c3b[c3.o_lo + tid];
+    for (int q = 0; q < DC_C3.KP; ++q) v += S.part[q * c3.no + tid];
+    DC_Y(buf, b)[c3.o_lo + tid] = v;
+  }
+}
+// kernel 2: the mode tokens from y, encoder layer 0 up to the l2 partials
+template <int G>
+__global__ __launch_bounds__(DT) void k_dec_chain2(float *__restrict__ buf, DecW W) {
+  extern __shared__ __attribute__((aligned(16))) float dsm[];
+  const DecSm S = dec_carve(dsm);
+  const int b = (int)blockIdx.x / G, wg = (int)blockIdx.x % G, tid = threadIdx.x;
+  if (tid < 768 / 4) *(f32x4 *)(&S.ff[0][4 * tid]) = *(const f32x4 *)(DC_Y(buf, b) + 4 * tid);
+  __syncthreads();
+  dec_ctx3_norm(S, W);
+  dec_attn(S, W, 0);
+  dc_ffn_parts<G>(S, W, 0, wg, DC_C(buf, b, 0), DC_P(buf, b, 0));
+}
+// kernel 3: the end of encoder layer 0, encoder layer 1 up to the l2 partials
+template <int G>
+__global__ __launch_bounds__(DT) void k_dec_chain3(float *__restrict__ buf, DecW W) {
+  extern __shared__ __attribute__((aligned(16))) float dsm[];
+  const DecSm S = dec_carve(dsm);
+  const int b = (int)blockIdx.x / G, wg = (int)blockIdx.x % G;
+  dc_ffn_gather(S, W, 0, DC_C(buf, b, 0), DC_P(buf, b, 0));
+  dec_attn(S, W, 1);
+  dc_ffn_parts<G>(S, W, 1, wg, DC_C(buf, b, 1), DC_P(buf, b, 1));
+}
+// kernel 4 (one workgroup per scene): the end of encoder layer 1, the mode tokens out, the cls head
+__global__ __launch_bounds__(DT) void k_dec_chain4(const float *__restrict__ buf, float *__restrict__ Cout, float *__restrict__ cls_out, DecW W) {
+  extern __shared__ __attribute__((aligned(16))) float dsm[];
+  const DecSm S = dec_carve(dsm);
+  const int b = (int)blockIdx.x, tid = threadIdx.x;
+  dc_ffn_gather(S, W, 1, DC_C(buf, b, 1), DC_P(buf, b, 1));
+  for (int i = tid; i < 768; i += blockDim.x) Cout[(size_t)b * 768 + i] = S.C[i / 128][i % 128];
+  dec_cls_head(S, W, b, cls_out, true);
 }
 
 // =================================================================================================

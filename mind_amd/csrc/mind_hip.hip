@@ -206,6 +206,7 @@ struct mind_ctx {
   } plan;
   DevBuf pl_flat;
   DevBuf dec_xbuf, dec_bars;
+  DevBuf dec_chain;      // what the kernels of the scene part's launch chain hand to each other (dec_chain.h: DC_SCENE_FLOATS per scene)
   Pinned dec_abort;      // host-visible abort word of its barriers (page-locked, mapped)
   int rb_cur = 0, rb_gen = 0;     // re-basing arenas: which one the last call filled, its generation and geometry
   size_t rb_S = 0, rb_a = 0;
@@ -305,6 +306,8 @@ static void set_kernel_attributes() {
       {k_dec_actor_mfma<1>, dec_m}, {k_dec_actor_mfma<3>, dec_m}, {k_dec_actor_mfma<6>, dec_m}, {k_actor_f32<1>, mind_actor_f32_lds_bytes(1)}, {k_actor_f32<2>, mind_actor_f32_lds_bytes(2)},
       {k_ilqr<true, 0>, il}, {k_ilqr<false, 1>, il}, {k_ilqr<false, 0>, il}, {k_ilqr<false, 2>, il}, {k_token_mfma<0>, tok_m}, {k_token_mfma<1>, tok_m},
       {k_dec_scene, dec_s}, {k_dec_scene_mw, dec_s}, {k_dec_scene_c, dec_s}, {k_dec_cls, dec_s}, {k_dec_tgt, dec_s},
+      {k_dec_chain1<8>, dec_s}, {k_dec_chain2<8>, dec_s}, {k_dec_chain3<8>, dec_s}, {k_dec_chain1<16>, dec_s}, {k_dec_chain2<16>, dec_s}, {k_dec_chain3<16>, dec_s},
+      {k_dec_chain1<32>, dec_s}, {k_dec_chain2<32>, dec_s}, {k_dec_chain3<32>, dec_s}, {k_dec_chain4, dec_s},
       {k_dec_actor<0>, dec_a}, {k_dec_actor<1>, dec_a}, {k_dec_actor<2>, dec_a}, {k_dec_actor<2, 1>, dec_a}, {k_dec_actor<2, 2>, dec_a},
   };
   for (const KernelLds &k : lds) (void)hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.bytes);
@@ -1189,6 +1192,42 @@ extern "C" int mind_debug_trig(mind_ctx *c, const double *x, int n, double *out)
   if (e == hipSuccess) e = hipMemcpy(out, d + n, (size_t)n * 4 * sizeof(double), hipMemcpyDeviceToHost);
   (void)hipFree(d);
   if (e != hipSuccess) return fail(c, MIND_EHIP, "mind_debug_trig: %s", hipGetErrorString(e));
+  return MIND_OK;
+}
+
+// the decoder's scene part alone, in a given form, on the caller's token rows (tests, tools/dec_chain_forms.py)
+extern "C" int mind_debug_dec_scene(mind_ctx *c, const float *rows, int n_scenes, int form, float *Cout, float *cls, int reps, float *ms) {
+  if (!c || !rows || !Cout || !cls || n_scenes <= 0 || n_scenes > 4096 || !(form == 0 || dc_valid_g(form)) || reps < 1 || reps > 1024) return MIND_EINVAL;
+  if (!c->have_weights) return fail(c, MIND_ESTATE, "weights not loaded");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int B = n_scenes;
+  const size_t nx = (size_t)B * 128, nc = (size_t)B * 768, nk = (size_t)B * 6;
+  DevBuf d;                       // x [B,128] | Cout [B,768] | cls [B,6] | cls_row [B]
+  if (d.alloc((nx + nc + nk) * sizeof(float) + (size_t)B * sizeof(int)) != hipSuccess) return fail(c, MIND_ENOMEM, "mind_debug_dec_scene: hipMalloc failed");
+  float *dx = d.as<float>(), *dC = dx + nx, *dk = dC + nc;
+  int *drow = (int *)(dk + nk);
+  std::vector<int> row(B);
+  for (int b = 0; b < B; ++b) row[b] = b;
+  HIPCHK(c, hipMemcpy(dx, rows, nx * sizeof(float), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(drow, row.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice));
+  Event e0, e1;
+  if (ms && (e0.create() != hipSuccess || e1.create() != hipSuccess)) return fail(c, MIND_EHIP, "mind_debug_dec_scene: no events");
+  for (int it = 0; it < reps; ++it) {
+    if (ms) HIPCHK(c, hipEventRecord(e0, c->stream));
+    if (form == 0)
+      hipLaunchKernelGGL(k_dec_scene, dim3(B), dim3(DT), mind_dec_scene_lds_bytes(), c->stream, (const float *)dx, (const int *)drow, dC, dk, c->W.dec);
+    else if (int rc = dec_chain_run(c, form, B, dx, drow, dC, dk, c->stream))
+      return rc;
+    if (ms) {
+      HIPCHK(c, hipEventRecord(e1, c->stream));
+      HIPCHK(c, hipEventSynchronize(e1));
+      HIPCHK(c, hipEventElapsedTime(&ms[it], e0, e1));
+    }
+  }
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(Cout, dC, nc * sizeof(float), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(cls, dk, nk * sizeof(float), hipMemcpyDeviceToHost));
   return MIND_OK;
 }
 

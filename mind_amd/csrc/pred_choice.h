@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "tuning.h"
+#include "dec_chain.h"
 
 // partial products per term of the MFMA contractions outside the pair kernel (ActorNet, layer-wise ActorNet, MFMA decoder) under a bf16
 // arithmetic: bf16x6 -> 6, bf16x3 -> actor_np (6 or 3), bf16 -> 1
@@ -54,6 +55,7 @@ struct PredChoice {
   int dec_head_ra = RA;         // agents per workgroup of the split form's head
   bool fp32_dec = true, split_dec = false, want_mw = false, cls_side = false;
   int mw_blocks = 0;
+  int dec_chain_g = 0;          // workgroups per scene of the scene part's launch chain (k_dec_chain1..4); 0: one of the one-launch forms above
   bool tgt_wait_first = false;  // the context stream waits for the target embedding before the fusion layers
 };
 
@@ -141,6 +143,9 @@ static PredChoice pred_choose(const PredTuning &t, int pair_prec, int n_cu, bool
   ch.mw_blocks = ((n_scenes + 7) / 8) * 8 * DEC_MW_G;
   ch.want_mw = t.dec_mw && ch.mw_blocks <= n_cu;
   ch.cls_side = ch.split_dec && t.dec_cls_side;
+  // ... and by rule, with neither knob set, the launch chain: G workgroups per scene on the three big stages, no barrier (dec_chain.h), for calls
+  // of at most n_cu / 8 scenes -- the same bits again.  The two knobs keep the one-launch kernels: they are the in-tree reference forms.
+  ch.dec_chain_g = (t.dec_mw || t.dec_cls_side) ? 0 : dc_choose_g(n_scenes, n_cu);
   ch.tgt_wait_first = have_side && !t.tgt_side;
   return ch;
 }

@@ -125,7 +125,7 @@ extern "C" int mind_debug_predict_choice(const char *const *knob_names, const in
       PRED_CHOICE_HEADER, (long long)ch.tok_runs.size(), ch.np, ch.actor_form, ch.actor_arg, ch.actor_grid, ch.actor_chunk, ch.actor_chunks,
       ch.actor_launches, ch.qsplit, ch.qk_stride, ch.tiled, ch.edge_bf16, pred_edge_pair_bytes(t, pair_prec), ch.tok_chunk, ch.tok_lw,
       ch.last_tok_chunks, ch.pair_family, ch.pair_np, ch.l5_jobs5, ch.xcd_lanes, ch.xcd_lanes5, ch.dec_actor, mfma_dec ? ch.np : 0,
-      ch.fp32_dec, ch.split_dec, ch.want_mw, ch.mw_blocks, ch.cls_side && !ch.want_mw, ch.tgt_wait_first, ch.split_dec ? ch.dec_head_ra : 0, 0};
+      ch.fp32_dec, ch.split_dec, ch.want_mw, ch.mw_blocks, ch.cls_side && !ch.want_mw, ch.tgt_wait_first, ch.split_dec ? ch.dec_head_ra : 0, ch.dec_chain_g};
   std::vector<long long> rec(head, head + PRED_CHOICE_HEADER);
   for (const PredTokRun &r : ch.tok_runs) rec.insert(rec.end(), {r.t0, r.n, r.kind, r.layerwise, r.small, r.merged});
   for (size_t i = 0; i < rec.size() && (int)i < cap; ++i) out[i] = rec[i];
@@ -550,6 +550,29 @@ static int pred_fusion(PredCall &p) {
   return MIND_OK;
 }
 
+// the decoder's scene part as the launch chain k_dec_chain1..4 with G workgroups per scene (dec_chain.h), queued on st: x's cls rows -> the mode
+// tokens Cout [Bn,6,128] and the mode probabilities cls [Bn,6].  The buffer the kernels hand their intermediate rows through is sized once for
+// every call that takes the chain by rule (n_cu / 8 scenes); only mind_debug_dec_scene asks for more.
+static int dec_chain_run(mind_ctx *c, int G, int Bn, const float *x, const int *d_cls_row, float *Cout, float *cls, hipStream_t st) {
+  if (!dc_valid_g(G) || Bn <= 0) return fail(c, MIND_EINVAL, "decoder chain: %d workgroups per scene, %d scenes", G, Bn);
+  int rc;
+  if ((rc = ensure(c, c->dec_chain, (size_t)std::max(Bn, c->n_cu / 8) * DC_SCENE_FLOATS * sizeof(float)))) return rc;
+  float *buf = (float *)c->dec_chain.p;
+  const size_t lds = mind_dec_scene_lds_bytes();
+#define DEC_CHAIN(GV)                                                                                                  \
+  do {                                                                                                                 \
+    hipLaunchKernelGGL(k_dec_chain1<GV>, dim3(Bn * GV), dim3(DT), lds, st, x, d_cls_row, buf, c->W.dec);                \
+    hipLaunchKernelGGL(k_dec_chain2<GV>, dim3(Bn * GV), dim3(DT), lds, st, buf, c->W.dec);                              \
+    hipLaunchKernelGGL(k_dec_chain3<GV>, dim3(Bn * GV), dim3(DT), lds, st, buf, c->W.dec);                              \
+  } while (0)
+  if (G == 32) DEC_CHAIN(32);
+  else if (G == 16) DEC_CHAIN(16);
+  else DEC_CHAIN(8);
+#undef DEC_CHAIN
+  hipLaunchKernelGGL(k_dec_chain4, dim3(Bn), dim3(DT), lds, st, (const float *)buf, Cout, cls, c->W.dec);
+  return MIND_OK;
+}
+
 static int pred_decoder(PredCall &p) {
   mind_ctx *c = p.c;
   const PredChoice &ch = p.ch;
@@ -590,8 +613,10 @@ static int pred_decoder(PredCall &p) {
       HIPCHK(c, hipMemsetAsync(c->dec_bars.p, 0, c->dec_bars.cap, st));        // (once: the barrier resets its arrival count itself)
     }
   }
-  if (mw)
-    hipLaunchKernelGGL(k_dec_scene_mw, dim3(ch.mw_blocks), dim3(DT), mind_dec_scene_lds_bytes(), st, x, d_cls_row, (float *)c->cmode.p, out->cls, c->W.dec, Bn,
+  if (ch.dec_chain_g) {
+    if ((rc = dec_chain_run(c, ch.dec_chain_g, Bn, x, d_cls_row, (float *)c->cmode.p, out->cls, st))) return rc;
+  } else if (mw)
+    hipLaunchKernelGGL(k_dec_scene_mw,dim3(ch.mw_blocks), dim3(DT), mind_dec_scene_lds_bytes(), st, x, d_cls_row, (float *)c->cmode.p, out->cls, c->W.dec, Bn,
                        (float *)c->dec_xbuf.p, (unsigned *)c->dec_bars.p, c->dec_abort.as<unsigned>());
   else if (ch.cls_side) {
     // the mode tokens on the context stream, the mode probabilities (the cls head: ~10 us a launch) on the side stream beside the actor part's

@@ -55,7 +55,10 @@ struct PredTuning {
   // every workgroup of the launch is resident, i.e. for calls of at most n_cu / 8 scenes.  Opt-in ("dec_mw" / MIND_DEC_MW=1): measured 88.6
   // against 94.9 us per demo-size launch (profiles/r06aa_*) -- only ctx_proj's second layer is really bound by one CU's L2 port (30 k -> 20 k
   // cycles); the feed-forward layers are bound by their 24 accumulators per thread and win 2-4 k cycles each, less the 36 KB exchange --
-  // 12 us per plan, not worth eight spinning workgroups per scene when several scenes share the device
+  // 12 us per plan, not worth eight spinning workgroups per scene when several scenes share the device.
+  // With this knob and "dec_cls_side" off, calls of at most n_cu / 8 scenes take the launch chain k_dec_chain1..4 by rule instead (dec_chain.h,
+  // PredChoice::dec_chain_g: the same stages dealt over 32 / 16 / 8 workgroups per scene and over rows, a kernel boundary where this form
+  // spins -- the same bits); either knob keeps the one-launch kernels, which are then the reference forms the chain is tested against
   bool dec_mw = false;
   // the decoder's cls head as its own launch on the side stream beside the actor part's head ("dec_cls_side" / MIND_DEC_CLS_SIDE=1).  Opt-in:
   // bit-identical, but the second launch and its two event waits cost more than the ~10 us of overlap (1 609-1 630 against 1 632-1 652
