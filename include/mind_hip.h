@@ -134,7 +134,7 @@ int mind_last_actor_stats(mind_ctx *ctx, int *layerwise, int *n_launches, int *n
  * profiling is on, and 0 for the predictor calls inside mind_aime_plan).  Any output may be NULL. */
 int mind_last_token_stats(mind_ctx *ctx, int *layerwise, int *n_launches, int *n_chunks, float *total_ms);
 /* ... and that time by kernel: out_ms[0..6] = the layer-wise stages (init, merge + V, out-projection + LN2, FFN 1, FFN 2 + LN3, S / T / q,
- * folded K query), out_ms[7] = the one-kernel forms (k_token, k_token_m, k_token_mfma).  Writes min(cap, 8) floats, returns 8. */
+ * folded K query), out_ms[7] = the one-kernel forms (k_token, k_token_m, k_token_s, k_token_mfma).  Writes min(cap, 8) floats, returns 8. */
 int mind_last_token_stage_ms(mind_ctx *ctx, float *out_ms, int cap);
 /* Duration of the tree-iLQR kernel of the last mind_ilqr_* call on this context (HIP events on the context stream; 0 unless
  * profiling is on), its number of cost trees and the workgroups per tree it ran with. */
@@ -217,7 +217,7 @@ int mind_set_pair_precision(mind_ctx *ctx, int mode);
  *   "tok_mfma"           MIND_TOK_MFMA          0        flag char 1: the per-token epilogue / prologue of the fusion layers on the fp32 MFMA kernel k_token_mfma instead of
  *       the fp32 VALU one; off by default: measured slower
  *   "tok_small_max"      MIND_TOK_SMALL_MAX     2048     any int   batches of at most this many tokens run k_token with four tokens per workgroup instead of eight; same bits
- *   "tok_merge"          MIND_TOK_MERGE         1        flag char small token launches merge their independent projections (k_token_m); 0: the plain kernel
+ *   "tok_merge"          MIND_TOK_MERGE         1        flag char small token launches merge their independent projections (k_token_s, the small-launch form of k_token_m); 0: the plain kernel
  *   "dec_mw"             MIND_DEC_MW            0        flag char 1: k_dec_scene_mw, eight workgroups per scene on the decoder's five big stages while every workgroup of the
  *       launch is resident (calls of at most n_cu / 8 scenes); bit-identical to the one-workgroup kernel
  *   "dec_cls_side"       MIND_DEC_CLS_SIDE      0        flag char 1: the decoder's cls head as its own launch on the side stream beside the actor part's head; bit-identical
@@ -311,7 +311,7 @@ int mind_debug_pair_schedule(const int *scene_tokens, const int *scene_actors, i
  *   8: the largest with scenes x workgroups <= n_cu; 0: one of the one-launch forms [26] / [28] / k_dec_scene -- "dec_mw" or "dec_cls_side" set,
  *   or more than n_cu / 8 scenes)
  * and one row {first token, tokens, kind (0 VALU, 1 fp32 MFMA, 2 bf16 split MFMA), layer-wise, small (four tokens per workgroup), merged
- * (k_token_m)} per token run.  Returns the length of the full record, or MIND_EINVAL for an unknown knob, pair_prec outside 0..3, a scene
+ * (k_token_s, or k_token_m under mind_debug_token_form)} per token run.  Returns the length of the full record, or MIND_EINVAL for an unknown knob, pair_prec outside 0..3, a scene
  * with no actor or a negative lane count, or a null pointer.  Needs no GPU and no context. */
 int mind_debug_predict_choice(const char *const *knob_names, const int *knob_values, int n_knobs, int pair_prec, int n_cu, int have_side,
                               const int *scene_actors, const int *scene_lanes, int n_scenes, long long *out, int cap);
@@ -423,6 +423,13 @@ int mind_debug_dec_scene(mind_ctx *ctx, const float *rows, int n_scenes, int for
  * the buffer's size when host == NULL) or a negative error. */
 int mind_debug_set_layers(mind_ctx *ctx, int n);
 int64_t mind_debug_read(mind_ctx *ctx, const char *name, float *host, int64_t max_floats);
+
+/* A/B of the small, merged token launches (runs whose row of mind_debug_predict_choice ends 1, 1; no knob, bit-identical forms): form 0 by
+ * rule -- k_token_s, on two tokens per workgroup while (n_tok + 1) / 2 <= n_cu, else on four --, 1 k_token_m, 2 / 3 k_token_s on four / two
+ * tokens per workgroup.  A non-null ctx keeps `form` for its later calls; ctx may be NULL (no GPU).  Returns the form (1..3) that a lone
+ * scene of n_tok tokens takes on n_cu CUs under `form` and the default knobs, 0 if its run is not small and merged; with n_tok 0 `form` itself;
+ * MIND_EINVAL for a form outside 0..3, a negative n_tok or n_cu <= 0 with n_tok > 0. */
+int mind_debug_token_form(mind_ctx *ctx, int form, int n_tok, int n_cu);
 
 /* ------------------------------------------------------------------------------------------------
  * Tree-iLQR contingency solves: replaces TrajectoryTreeOptimizer.init_warm_start_cost_tree /

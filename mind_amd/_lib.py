@@ -228,7 +228,7 @@ class PlannerOut(C.Structure):     # mind_planner_out
 
 EXPORTS = ["mind_ctx_create", "mind_ctx_destroy", "mind_last_error_string", "mind_ctx_synchronize",
            "mind_weights_load", "mind_predict_batch", "mind_last_fusion_stats", "mind_last_actor_stats", "mind_debug_actor_lw_plan", "mind_last_token_stats", "mind_last_token_stage_ms", "mind_debug_token_lw_plan", "mind_set_profiling", "mind_debug_launch_times", "mind_debug_launch_clock",
-           "mind_ilqr_solve_trees", "mind_ilqr_contingency", "mind_ilqr_solve_fields", "mind_cost_eval", "mind_ilqr_score_trees", "mind_ilqr_gains", "mind_ilqr_policy_rollouts", "mind_lane_dist_field", "mind_aime_world", "mind_aime_rebase", "mind_debug_aime_decide", "mind_debug_set_layers",
+           "mind_ilqr_solve_trees", "mind_ilqr_contingency", "mind_ilqr_solve_fields", "mind_cost_eval", "mind_ilqr_score_trees", "mind_ilqr_gains", "mind_ilqr_policy_rollouts", "mind_lane_dist_field", "mind_aime_world", "mind_aime_rebase", "mind_debug_aime_decide", "mind_debug_set_layers", "mind_debug_token_form",
            "mind_debug_read", "mind_set_pair_precision", "mind_get_pair_precision", "mind_debug_pack_bfrag", "mind_debug_pack_conv_frag", "mind_debug_pack", "mind_debug_weight_image", "mind_debug_weight_bind", "mind_debug_pair_schedule", "mind_debug_predict_choice", "mind_debug_ilqr_plan", "mind_debug_aime_book", "mind_set_tuning", "mind_get_tuning", "mind_debug_tuning", "mind_debug_live_handles", "mind_last_ilqr_stats", "mind_aime_plan", "mind_last_ilqr_profile", "mind_eval_traj_trees", "mind_last_ilqr_trace", "mind_ilqr_contingency_begin", "mind_ilqr_finish", "mind_fill_tracks", "mind_ilqr_contingency_begin_plan", "mind_debug_trig", "mind_aime_plan_begin", "mind_aime_plan_poll", "mind_aime_plan_finish", "mind_ctx_busy", "mind_ilqr_finish_plan", "mind_debug_dec_scene",
            "mind_set_exchange", "mind_last_exchange_stats", "mind_debug_wait_word",
            "mind_predict_batch_aux", "mind_set_decoder_basis", "mind_get_decoder_basis", "mind_curve_eval", "mind_debug_curve_basis",
@@ -348,6 +348,7 @@ def load():
     lib.mind_debug_weight_bind.argtypes = [C.POINTER(TensorDesc), C.c_int, C.c_char_p, C.c_char_p, C.c_int]
     lib.mind_debug_dec_scene.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_float)]
     lib.mind_debug_set_layers.argtypes = [C.c_void_p, C.c_int]
+    lib.mind_debug_token_form.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
     lib.mind_debug_read.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_float), C.c_int64]
     lib.mind_set_exchange.argtypes = [C.c_void_p, C.c_int, C.c_int, EXCHANGE_FN, C.c_void_p, C.c_int]
     lib.mind_last_exchange_stats.argtypes = [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
@@ -423,6 +424,16 @@ def predict_choice(knobs, prec, scenes, n_cu=256, have_side=True):
     d = dict(zip(PRED_CHOICE_FIELDS, out[:32]))
     d["runs"] = [tuple(out[32 + 6 * i:38 + 6 * i]) for i in range(out[1])]
     return d
+
+
+TOKEN_FORMS = ("rule", "k_token_m", "k_token_s<4>", "k_token_s<2>")
+
+
+def token_form(form, n_tok=0, n_cu=256, ctx=None):
+    """mind_debug_token_form: the kernel (index into TOKEN_FORMS; 0: its run is not small and merged) of a lone scene of n_tok tokens on n_cu CUs
+    under `form` (0 the rule); with a context, `form` holds for the context's later calls.  None when rejected.  No GPU without a context."""
+    n = load().mind_debug_token_form(ctx, int(form), int(n_tok), int(n_cu))
+    return None if n == MIND_EINVAL else n
 
 
 def dec_scene(lib, ctx, rows, form, reps=1, timed=False):

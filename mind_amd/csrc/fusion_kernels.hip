@@ -762,3 +762,334 @@ __global__ __launch_bounds__(TT_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
                                                       float *__restrict__ QK, TokWeights W) {
   k_token_body<TOK_TPW_SMALL, true>(meta, n_tok, mode, actor_feat, lane_feat, x, part, ST, QK, W);
 }
+
+// ---- k_token_s: the small-launch form.  k_token_m's arithmetic -- the same k split, the same fmaf chains, the same ksum / gsum2 orders, so the
+// same bits -- with its dependent memory round trips cut (a launch of a few dozen workgroups is a chain of latencies, not work):
+//  * meta is read once, at entry, beside x; the m / l words of a column's (up to eight) partial slots and the slots' head values are requested
+//    together behind it -- two round trips where the loops over the slots made up to 2 nsplit + nsplit / 2 + 1 -- and the arithmetic then runs
+//    on registers in slot order;
+//  * a stage's weights (with its bias and LayerNorm vectors) are requested one stage ahead, into registers of their own: Wv at entry, then
+//    Wo, W1 (both halves), W2, S | T | q, Wk -- before the multiply-adds of the stage in front with two tokens per workgroup, behind them
+//    (before that stage's barriers) with four (DEEP below).  No scratch: 194-244 of the 256 VGPRs that two waves per SIMD leave a thread.
+//    The step's shape (mode bits 1 | 2 | 4) is a template argument: read at run time, the prologue's weight registers stay live through
+//    the epilogue and spill;
+//  * TPW = 2 (launches whose workgroups each get a CU either way): half the LDS operand traffic per projection.  k-groups 0 and 1 own the two
+//    tokens behind a ksum, groups 2 and 3 only contribute their partial sums (and take heads 4..7 of the combine); every group reaches
+//    every barrier.
+// the four partials of N projections meet behind one pair of barriers; r[n] = ksum's sum for token ta (rk is N x [TKG][TP][128])
+template <int TP, int N>
+__device__ __forceinline__ void ksum_s(const float (&acc)[N][TP], const float (&bias)[N], float *rk, int kg, int col, int ta, float (&r)[N]) {
+  constexpr int ST = TKG * TP * 128;
+  __syncthreads();                      // previous users of rk are done
+#pragma unroll
+  for (int n = 0; n < N; ++n)
+#pragma unroll
+    for (int t = 0; t < TP; ++t) rk[n * ST + (kg * TP + t) * 128 + col] = acc[n][t];
+  __syncthreads();
+#pragma unroll
+  for (int n = 0; n < N; ++n) {
+    const float *q = rk + n * ST;
+    r[n] = ((q[(0 * TP + ta) * 128 + col] + q[(1 * TP + ta) * 128 + col]) + (q[(2 * TP + ta) * 128 + col] + q[(3 * TP + ta) * 128 + col])) + bias[n];
+  }
+}
+
+template <int TPW, int SM>
+__device__ __forceinline__ void k_token_small_body(const TokMeta *__restrict__ meta, int n_tok, int mode, const float *__restrict__ actor_feat,
+                                                   const float *__restrict__ lane_feat, float *__restrict__ x, const float *__restrict__ part,
+                                                   float *__restrict__ ST, float *__restrict__ QK, const TokWeights &W) {
+  static_assert(TPW == 2 || TPW == 4, "two or four tokens per workgroup");
+  constexpr bool INIT = (SM & 1) != 0, EPI = (SM & 2) != 0, PRO = (SM & 4) != 0;      // mode bits 1 / 2 / 4 (the launch's shape: known at compile time)
+  __shared__ __attribute__((aligned(16))) float xs[TPW][132];        // current token vectors
+  __shared__ __attribute__((aligned(16))) float tmp[TPW][260];       // scratch (o / h1 up to 256 wide)
+  __shared__ __attribute__((aligned(16))) float mb[TPW][8][132];     // normalised sum p*mem per head
+  __shared__ float rk[3 * TKG * TPW * 128];                          // k-group partial sums of up to three projections at once
+  __shared__ float rd[TKG * 2 * 2];
+  __shared__ float cw[TPW][8][8];       // combine weights per (token, head, split<=8)
+  const int tid = threadIdx.x, kg = tid >> 7, col = tid & 127;
+  const int tok0 = blockIdx.x * TPW;
+  const int nt = min(TPW, n_tok - tok0);
+  const int ta = TPW == 4 ? kg : (kg & 1);                           // the token this thread sums (and, if it owns it, keeps) behind a ksum
+  const bool own = kg < TPW, va = own && ta < nt;
+  // how far ahead a stage's weights are requested: before the products of the stage in front (two tokens) or behind them, before its barriers
+  // (four tokens: the products' LDS operands take the registers -- the earlier request spills)
+  constexpr bool DEEP = TPW == 2;
+  constexpr int NH = TPW == 4 ? 8 : 4;                               // heads of token ta this thread combines, from h0
+  const int h0 = TPW == 4 ? 0 : (kg >> 1) * 4;
+  const int ct = tid >> 3, chd = tid & 7;                            // (token, head) of the combine weights: threads below TPW * 8
+  const bool cwt = tid < TPW * 8;
+#ifdef MIND_TOKEN_TRACE
+  long long tt_[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tq_ = clock64();
+#endif
+
+  // ---- entry: meta (once), x, and the first stages' weights -- one round trip
+  int tya = 2, srca = 0, nsa = 0, slota = 0, nsc = 0, slotc = 0;
+  if (ta < nt) {
+    const TokMeta m = meta[tok0 + ta];
+    tya = m.type; srca = m.src; slota = m.slot0;
+    nsa = ((mode & 8) && !(m.flags & 1)) ? 0 : min(m.nsplit, 8);
+  }
+  if (cwt && ct < nt) {
+    const TokMeta m = meta[tok0 + ct];
+    slotc = m.slot0;
+    nsc = ((mode & 8) && !(m.flags & 1)) ? 0 : min(m.nsplit, 8);
+  }
+  float xv = 0.f;
+  if (!INIT && va) xv = x[(size_t)(tok0 + ta) * 128 + col];
+  float wpa[32], wpl[32], wv[32], wo[32], w1a[32], w1b[32], w2[64], ws[32], wt[32], wq[32], wk[2][16];
+  float b_pa = 0.f, b_pl = 0.f, b_v = 0.f, b_o = 0.f, g_2 = 0.f, be_2 = 0.f, b_1a = 0.f, b_1b = 0.f, b_2 = 0.f, g_3 = 0.f, be_3 = 0.f, b_m = 0.f, b_q = 0.f;
+  float ga = 0.f, gl = 0.f, ba = 0.f, bl = 0.f;
+  if constexpr (INIT) {
+    mv_load<128>(wpa, W.WpaT, 128, col, kg);
+    mv_load<128>(wpl, W.WplT, 128, col, kg);
+    b_pa = W.bpa[col]; b_pl = W.bpl[col];
+    ga = W.gpa[col]; gl = W.gpl[col]; ba = W.bepa[col]; bl = W.bepl[col];
+  }
+  if constexpr (EPI) {
+    mv_load<128>(wv, W.WvT, 128, col, kg);
+    b_v = W.bv[col];
+  }
+#define TOK_S_LOAD_STQ()                                  \
+  do {                                                    \
+    mv_load<128>(ws, W.WsT, 128, col, kg);                \
+    mv_load<128>(wt, W.WtT, 128, col, kg);                \
+    mv_load<128>(wq, W.WqT, 128, col, kg);                \
+    b_m = W.bm[col]; b_q = W.bq[col];                     \
+  } while (0)
+  if constexpr (PRO && !EPI && DEEP) TOK_S_LOAD_STQ();
+
+  // ---- behind meta: every partial word this thread will need -- the second (and last) round trip of the combine
+  float pm[8], pl[8], pv[8][NH];
+  if constexpr (EPI) {
+    if (cwt) {
+#pragma unroll
+      for (int s = 0; s < 8; ++s) {
+        pm[s] = 0.f; pl[s] = 0.f;
+        if (s < nsc) {
+          const float *ps = part + (size_t)(slotc + s) * PART_STRIDE;
+          pm[s] = ps[chd]; pl[s] = ps[8 + chd];
+        }
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+#pragma unroll
+      for (int h = 0; h < NH; ++h) pv[s][h] = 0.f;
+      if (s < nsa) {
+        const float *ps = part + (size_t)(slota + s) * PART_STRIDE + 16 + col;
+#pragma unroll
+        for (int h = 0; h < NH; ++h) pv[s][h] = ps[(h0 + h) * 128];
+      }
+    }
+  }
+
+  // ---- load x (or build x0)
+  if constexpr (INIT) {
+    // FusionNet projections (network.py:313-314, 323-324): Linear + LN + ReLU, cls token = zeros
+    float fa = 0.f;
+    if (ta < nt) {
+      if (tya == 0) fa = actor_feat[(size_t)srca * 128 + col];
+      else if (tya == 1) fa = lane_feat[(size_t)srca * 128 + col];
+    }
+    if (own) tmp[ta][col] = fa;
+    __syncthreads();
+    float ac2[2][TPW], r[2];
+    mv_fma<128, TPW>(ac2[0], wpa, &tmp[0][0], 260, kg);
+    mv_fma<128, TPW>(ac2[1], wpl, &tmp[0][0], 260, kg);
+    if constexpr (PRO && !EPI && !DEEP) TOK_S_LOAD_STQ();
+    const float bs[2] = {b_pa, b_pl};
+    ksum_s<TPW, 2>(ac2, bs, rk, kg, col, ta, r);
+    float p0 = tya == 0 ? r[0] : r[1];
+    {
+      // LN with per-token (type-dependent) affine: normalise first, then scale
+      float s0 = p0, s1 = 0.f;
+      gsum2(s0, s1, rd, kg, tid);
+      const float d0 = p0 - s0 * (1.0f / 128.0f);
+      s0 = d0 * d0; s1 = 0.f;
+      gsum2(s0, s1, rd, kg, tid);
+      p0 = fmaxf(d0 * (1.0f / sqrtf(s0 * (1.0f / 128.0f) + 1e-5f)) * (tya == 0 ? ga : gl) + (tya == 0 ? ba : bl), 0.f);
+      if (tya == 2) p0 = 0.f;
+    }
+    if (own) xs[ta][col] = p0;
+    __syncthreads();
+  } else {
+    if (own) xs[ta][col] = xv;
+    __syncthreads();
+  }
+  TT(0);
+  if constexpr (EPI) {
+    // ---- combine split partials: weights exp(m_s - M) / L  (softmax over i finished here), k_token's expressions in slot order
+    if (cwt) {
+      float wgt[8];
+      float M = -INFINITY;
+#pragma unroll
+      for (int s = 0; s < 8; ++s)
+        if (s < nsc) M = fmaxf(M, pm[s]);
+      float L = 0.f;
+#pragma unroll
+      for (int s = 0; s < 8; ++s) {
+        wgt[s] = 0.f;
+        if (s < nsc) {
+          const float e = expf(pm[s] - M);
+          wgt[s] = e;
+          L += e * pl[s];
+        }
+      }
+      const float inv = 1.0f / L;
+#pragma unroll
+      for (int s = 0; s < 8; ++s)
+        if (s < nsc) wgt[s] *= inv;
+#pragma unroll
+      for (int s = 0; s < 8; ++s) cw[ct][chd][s] = wgt[s];
+    }
+#define TOK_S_LOAD_WO() do { mv_load<128>(wo, W.WoT, 128, col, kg); b_o = W.bo[col]; g_2 = W.g2[col]; be_2 = W.b2[col]; } while (0)
+#define TOK_S_LOAD_W1() do { mv_load<128>(w1a, W.W1T, 256, col, kg); mv_load<128>(w1b, W.W1T, 256, 128 + col, kg); b_1a = W.b1[col]; b_1b = W.b1[128 + col]; } while (0)
+#define TOK_S_LOAD_W2() do { mv_load<256>(w2, W.W2T, 128, col, kg); b_2 = W.bb2[col]; g_3 = W.g3[col]; be_3 = W.b3[col]; } while (0)
+    if constexpr (DEEP) TOK_S_LOAD_WO();
+    __syncthreads();
+    TT(1);
+    {
+      float v[NH];
+#pragma unroll
+      for (int h = 0; h < NH; ++h) v[h] = 0.f;
+#pragma unroll
+      for (int s = 0; s < 8; ++s)
+        if (s < nsa) {
+#pragma unroll
+          for (int h = 0; h < NH; ++h) v[h] = fmaf(cw[ta][h0 + h][s], pv[s][h], v[h]);
+        }
+#pragma unroll
+      for (int h = 0; h < NH; ++h) mb[ta][h0 + h][col] = v[h];
+    }
+    if constexpr (DEEP) TOK_S_LOAD_W1(); else TOK_S_LOAD_WO();
+    __syncthreads();
+    TT(2);
+    // ---- o = W_v,h mbar_h + b_v  (output feature f = hd*16+d uses head hd = f>>4)
+    {
+      float acc[1][TPW], r[1];
+      mv_fma<128, TPW>(acc[0], wv, &mb[0][col >> 4][0], 8 * 132, kg);
+      if constexpr (DEEP) TOK_S_LOAD_W2(); else TOK_S_LOAD_W1();
+      const float bs[1] = {b_v};
+      ksum_s<TPW, 1>(acc, bs, rk, kg, col, ta, r);
+      if (own) tmp[ta][col] = r[0];
+      __syncthreads();
+    }
+    TT(3);
+    // ---- att = W_o o + b_o ; x1 = LN2(x + att)
+    {
+      float acc[1][TPW], r[1];
+      mv_fma<128, TPW>(acc[0], wo, &tmp[0][0], 260, kg);
+      const float bs[1] = {b_o};
+      ksum_s<TPW, 1>(acc, bs, rk, kg, col, ta, r);
+      float p0 = r[0] + xs[ta][col], p1 = 0.f;
+      ln2tok(p0, p1, g_2, be_2, rd, kg, tid);
+      __syncthreads();                  // every k-group has finished reading xs
+      if (own) xs[ta][col] = p0;
+      __syncthreads();
+    }
+    TT(4);
+    // ---- FFN 128 -> 256 -> 128, x2 = LN3(x1 + ff)
+    {
+      float ac2[2][TPW], r[2];
+      mv_fma<128, TPW>(ac2[0], w1a, &xs[0][0], 132, kg);
+      mv_fma<128, TPW>(ac2[1], w1b, &xs[0][0], 132, kg);
+      if constexpr (PRO && DEEP) TOK_S_LOAD_STQ();
+      if constexpr (!DEEP) TOK_S_LOAD_W2();
+      const float bs[2] = {b_1a, b_1b};
+      ksum_s<TPW, 2>(ac2, bs, rk, kg, col, ta, r);
+      if (own) { tmp[ta][col] = fmaxf(r[0], 0.f); tmp[ta][128 + col] = fmaxf(r[1], 0.f); }
+      __syncthreads();
+      float acc[1][TPW], q[1];
+      mv_fma<256, TPW>(acc[0], w2, &tmp[0][0], 260, kg);
+      if constexpr (PRO && !DEEP) TOK_S_LOAD_STQ();
+      const float b2s[1] = {b_2};
+      ksum_s<TPW, 1>(acc, b2s, rk, kg, col, ta, q);
+      float p0 = q[0] + xs[ta][col], p1 = 0.f;
+      ln2tok(p0, p1, g_3, be_3, rd, kg, tid);
+      __syncthreads();
+      if (own) xs[ta][col] = p0;
+      __syncthreads();
+    }
+  }
+  TT(5);
+  // ---- write x
+  if (va) x[(size_t)(tok0 + ta) * 128 + col] = xs[ta][col];
+
+  if constexpr (PRO) {
+    // ---- prologue of the next layer: S = W_s x, T = W_t x + b_m, q = W_q x + b_q,
+    //      qk[hd][f] = sum_d q[hd*16+d] W_k[hd*16+d][f] / 4      (scale 1/sqrt(16))
+#define TOK_S_LOAD_WK()                                                                                 \
+  _Pragma("unroll") for (int hh = 0; hh < 2; ++hh)                                                      \
+    _Pragma("unroll") for (int d = 0; d < 16; ++d) wk[hh][d] = W.Wk[(size_t)((2 * kg + hh) * 16 + d) * 128 + col]
+    if constexpr (DEEP) { TOK_S_LOAD_WK(); }
+    {
+      float ac3[3][TPW], q[3];
+      mv_fma<128, TPW>(ac3[0], ws, &xs[0][0], 132, kg);
+      mv_fma<128, TPW>(ac3[1], wt, &xs[0][0], 132, kg);
+      mv_fma<128, TPW>(ac3[2], wq, &xs[0][0], 132, kg);
+      if constexpr (!DEEP) { TOK_S_LOAD_WK(); }
+      const float bs[3] = {0.f, b_m, b_q};
+      ksum_s<TPW, 3>(ac3, bs, rk, kg, col, ta, q);
+      if (va) { ST[(size_t)(tok0 + ta) * 256 + col] = q[0]; ST[(size_t)(tok0 + ta) * 256 + 128 + col] = q[1]; }
+      if (own) tmp[ta][col] = q[2];
+    }
+    __syncthreads();
+    TT(6);
+    // each k-group takes two of the eight heads, all tokens
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh) {
+      const int hd = 2 * kg + hh;
+      float acc[TPW];
+#pragma unroll
+      for (int t = 0; t < TPW; ++t) acc[t] = 0.f;
+#pragma unroll
+      for (int d = 0; d < 16; d += 4)
+#pragma unroll
+        for (int t = 0; t < TPW; ++t) {
+          const float4 xq = *reinterpret_cast<const float4 *>(&tmp[t][hd * 16 + d]);
+          acc[t] = fmaf(wk[hh][d], xq.x, acc[t]);
+          acc[t] = fmaf(wk[hh][d + 1], xq.y, acc[t]);
+          acc[t] = fmaf(wk[hh][d + 2], xq.z, acc[t]);
+          acc[t] = fmaf(wk[hh][d + 3], xq.w, acc[t]);
+        }
+      if (mode & 16) {
+        // bf16 hi / lo (mode bit 32: hi / mid / lo) parts in the A-operand order of the bf16 pair kernels: k_token_body's layout
+        const int g = col >> 5, qq = (col >> 2) & 3, i = 4 * ((col >> 4) & 1) + (col & 3);
+        const int idx = ((g * 32) + hd * 4 + qq) * 8 + i;
+        const size_t qks = (mode & 32) ? 1536 : 1024;
+        for (int t = 0; t < nt; ++t) {
+          const float v = acc[t] * 0.25f;
+          const u32 h = pk_bf16(v, v) & 0xffffu;
+          const float r1 = v - bf_lo_f32(h);
+          const u32 l = pk_bf16(r1, 0.f) & 0xffffu;
+          unsigned short *qs = reinterpret_cast<unsigned short *>(QK + (size_t)(tok0 + t) * qks);
+          qs[idx] = (unsigned short)h;
+          qs[1024 + idx] = (unsigned short)l;
+          if (mode & 32) qs[2048 + idx] = (unsigned short)(pk_bf16(r1 - bf_lo_f32(l), 0.f) & 0xffffu);
+        }
+      } else {
+        for (int t = 0; t < nt; ++t) QK[(size_t)(tok0 + t) * 1024 + hd * 128 + col] = acc[t] * 0.25f;
+      }
+    }
+  }
+  TT(7);
+#undef TOK_S_LOAD_STQ
+#undef TOK_S_LOAD_WK
+#undef TOK_S_LOAD_WO
+#undef TOK_S_LOAD_W1
+#undef TOK_S_LOAD_W2
+#ifdef MIND_TOKEN_TRACE
+  if (blockIdx.x == 0 && tid == 0)
+    printf("[k_token_s<%d> mode %d ntok %d] cycles: load %lld cw %lld combine %lld Wv %lld Wo+LN2 %lld FFN+LN3 %lld S,T,q %lld QK %lld\n", TPW, mode, n_tok,
+           tt_[0], tt_[1], tt_[2], tt_[3], tt_[4], tt_[5], tt_[6], tt_[7]);
+#endif
+}
+
+// SM: the launch's mode bits 1 | 2 | 4, which the host knows -- 1 | 4 the first step, 2 | 4 between two layers, 2 behind the last
+template <int TPW, int SM>
+__global__ __launch_bounds__(TT_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_token_s(const TokMeta *__restrict__ meta, int n_tok, int mode,
+                                                      const float *__restrict__ actor_feat,
+                                                      const float *__restrict__ lane_feat, float *__restrict__ x,
+                                                      const float *__restrict__ part, float *__restrict__ ST,
+                                                      float *__restrict__ QK, TokWeights W) {
+  k_token_small_body<TPW, SM>(meta, n_tok, mode, actor_feat, lane_feat, x, part, ST, QK, W);
+}

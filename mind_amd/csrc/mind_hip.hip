@@ -245,6 +245,7 @@ struct mind_ctx {
   std::vector<float> lc_last[LC_KINDS], ev_last[LC_KINDS];
   int n_cu = 256;
   int debug_layers = 6;
+  int debug_tok_form = 0;          // mind_debug_token_form: 0 the rule, else the kernel of the small, merged token launches
   int last_ntok = 0;
   size_t il_dbg[6] = {0, 0, 0, 0, 0, 0};   // tree 0 of the last iLQR call: byte offsets of L, Lx, Lxx, Fx, xs in ilqr_dev; M
   long long last_edge_pairs = 0;

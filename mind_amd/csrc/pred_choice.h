@@ -30,7 +30,18 @@ struct PredTokRun {
   int t0, n, kind;
   bool layerwise;       // kind 1 only: the layer-wise kernels (token_lw_kernels.hip) instead of k_token_mfma<0>
   bool small, merged;   // kind 0 only: four tokens per workgroup instead of eight; k_token_m instead of k_token<TOK_TPW_SMALL>
+  int form;             // small && merged only (else 0): PRED_TOK_M k_token_m, PRED_TOK_S4 / PRED_TOK_S2 k_token_s with four / two tokens per workgroup
 };
+
+// the kernel of a small, merged run (mind_debug_token_form's numbers; 0 there: by rule)
+enum PredTokForm { PRED_TOK_RULE = 0, PRED_TOK_M = 1, PRED_TOK_S4 = 2, PRED_TOK_S2 = 3 };
+
+// by rule the small-launch form (k_token_s: k_token_m's bits with its dependent memory round trips cut), on two tokens per workgroup while
+// every workgroup still gets a CU of its own, else on four; `forced` (a debug setting, no knob) names a form instead
+static inline int pred_tok_form(int forced, int n_tok, int n_cu) {
+  if (forced == PRED_TOK_M || forced == PRED_TOK_S4 || forced == PRED_TOK_S2) return forced;
+  return (n_tok + 1) / 2 <= n_cu ? PRED_TOK_S2 : PRED_TOK_S4;
+}
 
 struct PredChoice {
   int np = 1;                   // pred_mfma_parts
@@ -59,7 +70,8 @@ struct PredChoice {
   bool tgt_wait_first = false;  // the context stream waits for the target embedding before the fusion layers
 };
 
-static PredChoice pred_choose(const PredTuning &t, int pair_prec, int n_cu, bool have_side, int n_scenes, const int *scene_actors, const int *scene_lanes) {
+static PredChoice pred_choose(const PredTuning &t, int pair_prec, int n_cu, bool have_side, int n_scenes, const int *scene_actors, const int *scene_lanes,
+                              int tok_form = PRED_TOK_RULE) {
   PredChoice ch;
   int A = 0;
   for (int b = 0; b < n_scenes; ++b) A += scene_actors[b];
@@ -105,16 +117,17 @@ static PredChoice pred_choose(const PredTuning &t, int pair_prec, int n_cu, bool
     // (the two-way-split token kernel is not an fp32-class arithmetic: never under bf16x6)
     const int kind = t.tok_mfma ? 1 : (pair_prec != 0 && pair_prec != 3 && t.tok_bf_min_n > 0 && N >= t.tok_bf_min_n) ? 2 : N >= t.tok_lw_min_n ? 1 : 0;
     if (!ch.tok_runs.empty() && ch.tok_runs.back().kind == kind) ch.tok_runs.back().n += N;
-    else ch.tok_runs.push_back({t0, N, kind, false, false, false});
+    else ch.tok_runs.push_back({t0, N, kind, false, false, false, 0});
     t0 += N;
     njobs += (long long)N * pair_column_splits(N);
     njobs5 += (long long)(scene_actors[b] + 1) * pair_column_splits(N);
   }
   for (PredTokRun &r : ch.tok_runs) {
     r.layerwise = r.kind == 1 && r.n >= t.tok_lw_min;
-    // (small launches: independent projections merged, k_token_m -- bit-identical; "tok_merge" 0 keeps the plain form for A/B)
+    // (small launches: independent projections merged -- bit-identical; "tok_merge" 0 keeps the plain form, the reference, for A/B)
     r.small = r.kind == 0 && r.n <= t.tok_small_max;
     r.merged = r.small && t.tok_merge;
+    r.form = r.merged ? pred_tok_form(tok_form, r.n, n_cu) : 0;
     if (r.layerwise) {
       ch.tok_lw = true;
       ch.last_tok_chunks += (r.n + ch.tok_chunk - 1) / ch.tok_chunk;

@@ -132,6 +132,18 @@ extern "C" int mind_debug_predict_choice(const char *const *knob_names, const in
   return (int)rec.size();
 }
 
+// A/B of the small, merged token launches (no knob): `form` 0 the rule (pred_tok_form), 1 k_token_m, 2 / 3 k_token_s on four / two tokens per
+// workgroup; a context keeps it for its later calls.  Returns the form (1..3) a small, merged run of n_tok tokens then takes on n_cu CUs -- 0 for
+// a run the default knobs do not make small -- or `form` itself with n_tok 0.  ctx may be null (nothing is kept: the rule's table, no GPU).
+extern "C" int mind_debug_token_form(mind_ctx *c, int form, int n_tok, int n_cu) {
+  if (form < PRED_TOK_RULE || form > PRED_TOK_S2 || n_tok < 0 || (n_tok > 0 && n_cu <= 0)) return MIND_EINVAL;
+  if (c) c->debug_tok_form = form;
+  if (n_tok == 0) return form;
+  const int one = 1, lanes = n_tok - 2;      // a lone scene of n_tok tokens: one actor, the lanes, the cls token (pred_choose reads the sum alone: -1 lanes for one token)
+  const PredChoice ch = pred_choose(PredTuning(), 3, n_cu, true, 1, &one, &lanes, form);
+  return ch.tok_runs[0].form;
+}
+
 // ---- the launch clock's host side (launch_clock.h: the ring's bookkeeping and the reduction): the device ring and its page-locked mirror, the
 //      copies, the sums.  With profiling on and "prof_clock" 1 a timed launch takes the next block of the ring and records no HIP event; whoever
 //      read event pairs reads slots instead, behind a completed stream or copy -- the device never waits on the host.
@@ -463,9 +475,19 @@ static int pred_token_step(PredCall &p, int mode, int Lw) {
     }
     c->last_tok_launches++;
     if (r.kind == 0) {
-      const int tpw = r.small ? TOK_TPW_SMALL : TOK_TPW_BIG;
-      hipLaunchKernelGGL(r.small ? (r.merged ? k_token_m : k_token<TOK_TPW_SMALL>) : k_token<TOK_TPW_BIG>, dim3((r.n + tpw - 1) / tpw), dim3(TT_THREADS), 0,
-                         st, m_, r.n, mode, actor_feat, lane_feat, x_, part, ST_, QK_, c->W.tok[Lw]);
+      const int tpw = r.form == PRED_TOK_S2 ? 2 : r.small ? TOK_TPW_SMALL : TOK_TPW_BIG;
+      auto *kern = r.small ? (r.merged ? k_token_m : k_token<TOK_TPW_SMALL>) : k_token<TOK_TPW_BIG>;
+      if (r.form == PRED_TOK_S2 || r.form == PRED_TOK_S4) {
+        // the small-launch form is compiled per shape of the step: first (1 | 4), between two layers (2 | 4), last (2)
+        const bool two = r.form == PRED_TOK_S2;
+        switch (mode & 7) {
+          case 5: kern = two ? k_token_s<2, 5> : k_token_s<TOK_TPW_SMALL, 5>; break;
+          case 6: kern = two ? k_token_s<2, 6> : k_token_s<TOK_TPW_SMALL, 6>; break;
+          case 2: kern = two ? k_token_s<2, 2> : k_token_s<TOK_TPW_SMALL, 2>; break;
+          default: return fail(c, MIND_ESTATE, "token step: mode %d has no small-launch kernel", mode);
+        }
+      }
+      hipLaunchKernelGGL(kern, dim3((r.n + tpw - 1) / tpw), dim3(TT_THREADS), 0, st, m_, r.n, mode, actor_feat, lane_feat, x_, part, ST_, QK_, c->W.tok[Lw]);
     } else if (r.kind == 1) {
       hipLaunchKernelGGL(k_token_mfma<0>, dim3((r.n + TM_TOK - 1) / TM_TOK), dim3(TM_THREADS), tokm_lds, st, m_, r.n, mode, actor_feat, lane_feat, x_,
                          part, ST_, QK_, c->W.tok[Lw], c->W.tokM[Lw]);
@@ -725,7 +747,7 @@ extern "C" int mind_predict_batch_aux(mind_ctx *c, const mind_scene_batch *in, m
     sa[b] = in->actor_off[b + 1] - in->actor_off[b]; sl[b] = in->lane_off[b + 1] - in->lane_off[b];
     if (sa[b] <= 0 || sl[b] < 0) return fail(c, MIND_EINVAL, "scene %d has %d agents, %d lanes", b, sa[b], sl[b]);
   }
-  const PredChoice ch = pred_choose(c->pt, c->pair_prec, c->n_cu, c->side.p != nullptr, Bn, sa.data(), sl.data());
+  const PredChoice ch = pred_choose(c->pt, c->pair_prec, c->n_cu, c->side.p != nullptr, Bn, sa.data(), sl.data(), c->debug_tok_form);
   PredCall p{c, in, out, aux, ch, Bn, A, Ltot, c->stream, c->side ? c->side.p : c->stream};
   int rc;
   if ((rc = pred_tables(p, sa.data(), sl.data()))) return rc;
