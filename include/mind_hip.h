@@ -1187,6 +1187,79 @@ int mind_audit_ttc(mind_ctx *ctx, const mind_audit_box *ego, const mind_audit_tt
  * (mind_trig.h).  out HOST [n]: tg_rect_rect_ttc, +inf for never.  MIND_EINVAL for n < 0 or a NULL pointer. */
 int mind_debug_box_ttc(int n, const double *a, const double *b, const double *trig, double *out);
 
+/* ------------------------------------------------------------------------------------------------
+ * Lane audit of plans and closed-loop episodes (mind_amd/csrc/lane_geom.h, lane_kernels.hip): whether the ego drove WHERE it
+ * was told to drive -- how far from a lane centreline it got, whether it pointed along the traffic flow, how much arc length
+ * it covered.  A planner that never leaves the drivable area and never hits anything can still crawl, cut across the oncoming
+ * lane or park.  The reference projects one pose at a time on one polyline in Python (project_point_on_polyline,
+ * get_closest_semantic_lane) and scores no trace with it, so the definitions are this project's.  Like the other audits these
+ * calls sit outside every planning cycle: synchronous on the context's stream, on the audits' scratch.
+ *
+ * Lanes: verts HOST [V, 2] float64 world coordinates and lane_off HOST [n_lanes + 1], lane_off[0] = 0; lane l is the OPEN
+ * polyline of the vertices lane_off[l] .. lane_off[l + 1] - 1, at least two, in the direction of travel.  Segment g (the
+ * global index of its first vertex) joins vertex g to g + 1; a lane's last vertex and the next lane's first form none; a
+ * duplicated vertex (a zero-length segment) is skipped.  The library forms the arc length at every vertex itself.
+ * The reference point is the ego box's centre, (x, y) + center_offset (cos yaw, sin yaw).  Per box, twice -- index 0 over ALL
+ * segments ("any"), index 1 over the segments whose direction e satisfies (cos yaw, sin yaw) . e >= cos_flow ("with the
+ * flow") --: the nearest segment by squared clamped distance, the lowest g winning ties, and of it
+ *   lat    = the distance, positive when the centre is left of the direction of travel, negative right of it;
+ *   s      = the arc length of the projection from the lane's first vertex (0 before it, the lane's length beyond its end);
+ *   along  = (cos yaw, sin yaw) . e, across = e x (cos yaw, sin yaw) (positive: the heading points left of the lane) -- the
+ *            heading error is atan2(across, along), left to the caller;
+ *   lane   = its lane, edge = its index within the lane.
+ * No qualifying segment: lat = +inf, lane = edge = -1, s = along = across = NaN.  margin = bound - |lat with the flow|, the
+ * audits' sign convention: a hit is margin < 0, exactly 0 is none, -inf when no segment goes the ego's way.  A state row holding
+ * a non-finite value reports every double NaN, every index -1.
+ * cfg: cos_flow in [-1, 1]; bound finite and > 0; form picks the kernel's shape and changes no result: 0 = the library's rule
+ * (by rows), 1 = thread per box, 2 = one wavefront per box, its lanes over the segments.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct { double cos_flow, bound; int form; } mind_audit_lane_cfg;
+
+/* n_ego ego traces ego_states HOST [n_ego, n_steps, 4] = (x, y, v, yaw).  Per ego over step_margin, as mind_audit_road_episode
+ * folds its margin: ego_min with ego_step and ego_lane = that step's with-flow lane (the lowest step wins ties), ego_hits =
+ * steps with margin < 0, ego_first = the first of them (-1: none); a trace holding a NaN step: min = NaN, step = the first such
+ * step, lane = -1, hits = -1, first = -1.  ego_progress / ego_back: sequentially from 0.0 over the steps k >= 1 whose "any"
+ * lane equals step k - 1's and is >= 0, with d = s_any[k] - s_any[k - 1]: progress += d, and back += d when d < 0.
+ * Outputs HOST, each may be NULL (not all).
+ * MIND_EINVAL: a NULL required pointer, a negative count, n_lanes outside 1..2^16, lane_off not starting at 0 or not ascending
+ * by at least 2, more than 2^20 vertices, a non-finite vertex, a non-finite or negative box dimension, cos_flow outside
+ * [-1, 1], bound not finite or <= 0, form outside 0..2, all outputs NULL, n_ego x n_steps > 2^22.  n_ego == 0 or n_steps == 0
+ * is a successful no-op.  MIND_ESTATE as mind_audit_plan. */
+typedef struct {   /* per-step doubles / ints: [2, n_ego, n_steps], index 0 = any, 1 = with the flow */
+  double *step_lat, *step_s, *step_along, *step_across; int32_t *step_lane, *step_edge;
+  double *step_margin;                                                  /* [n_ego, n_steps] */
+  double *ego_min; int32_t *ego_step, *ego_lane, *ego_hits, *ego_first; /* [n_ego], lowest step wins ties */
+  double *ego_progress, *ego_back;                                      /* [n_ego] */
+} mind_audit_lane_episode_out;
+int mind_audit_lane_episode(mind_ctx *ctx, const mind_audit_box *ego, const mind_audit_lane_cfg *cfg, const double *verts,
+                            const int32_t *lane_off, int n_lanes, int n_ego, int n_steps, const double *ego_states,
+                            const mind_audit_lane_episode_out *out);
+
+/* n_cand candidate state sets xs HOST [n_cand, sum M, 6] (as mind_audit_plan takes them) on the cost trees of a plan; n_nodes,
+ * parent and prob of the trees are read.  Per (candidate, tree) over node_margin, as mind_audit_road_plan folds its margin:
+ * tree_min, tree_node, tree_lane (that node's with-flow lane), tree_hits, tree_first, tree_mass.  tree_progress: sequentially
+ * from 0.0 in key order over the nodes i with parent[i] >= 0 whose "any" lane equals the parent's and is >= 0,
+ * progress += (double)prob[i] (s_any[i] - s_any[parent[i]]).
+ * Outputs HOST, each may be NULL (not all).  MIND_EINVAL as above with n_cand x sum M > 2^20 in place of the episode's cap, and
+ * a NULL parent or a parent index >= n_nodes.  n_cand == 0 is a successful no-op.  MIND_ESTATE as mind_audit_plan. */
+typedef struct {   /* per-node doubles / ints: [2, n_cand, sum M], index 0 = any, 1 = with the flow */
+  double *node_lat, *node_s, *node_along, *node_across; int32_t *node_lane, *node_edge;
+  double *node_margin;                                                                          /* [n_cand, sum M] */
+  double *tree_min; int32_t *tree_node, *tree_lane, *tree_hits, *tree_first; double *tree_mass; /* [n_cand, n_trees] */
+  double *tree_progress;                                                                        /* [n_cand, n_trees] */
+} mind_audit_lane_plan_out;
+int mind_audit_lane_plan(mind_ctx *ctx, const mind_audit_box *ego, const mind_audit_lane_cfg *cfg, const double *verts,
+                         const int32_t *lane_off, int n_lanes, const mind_cost_tree *trees, int n_trees, int n_cand,
+                         const double *xs, const mind_audit_lane_plan_out *out);
+
+/* lane_geom.h on the CPU (host only, no context): n boxes HOST [n, 3] = (x, y, yaw) of the box `ego` (only its center_offset
+ * matters) against the lanes.  trig HOST [n, 2] = (cos yaw, sin yaw), or NULL = the kernels' own sin / cos (mind_trig.h).
+ * Outputs HOST, each may be NULL (not all): lat, s, along, across, lane, edge [2, n] (0 = any, 1 = with the flow), margin [n].
+ * MIND_EINVAL for n < 0, a NULL required pointer, a bad box, cfg or lanes (the rules above). */
+int mind_debug_lane_project(int n, const double *boxes, const mind_audit_box *ego, const mind_audit_lane_cfg *cfg,
+                            const double *verts, const int32_t *lane_off, int n_lanes, const double *trig, double *lat,
+                            double *s, double *along, double *across, int32_t *lane, int32_t *edge, double *margin);
+
 #ifdef __cplusplus
 }
 #endif

@@ -91,6 +91,25 @@ class AuditTtcOut(C.Structure):     # mind_audit_ttc_out
                 ("ego_first", C.POINTER(C.c_int32))]
 
 
+class AuditLaneCfg(C.Structure):    # mind_audit_lane_cfg
+    _fields_ = [("cos_flow", C.c_double), ("bound", C.c_double), ("form", C.c_int)]
+
+
+def _lane_out(per, outer, extra):
+    """the field list of mind_audit_lane_episode_out (per = "step", outer = "ego") / mind_audit_lane_plan_out ("node", "tree")"""
+    dbl, i32 = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    return [(f"{per}_{k}", dbl) for k in ("lat", "s", "along", "across")] + [(f"{per}_lane", i32), (f"{per}_edge", i32), (f"{per}_margin", dbl)] + \
+        [(f"{outer}_min", dbl), (f"{outer}_{per}", i32), (f"{outer}_lane", i32), (f"{outer}_hits", i32), (f"{outer}_first", i32)] + [(k, dbl) for k in extra]
+
+
+class AuditLaneEpisodeOut(C.Structure):     # mind_audit_lane_episode_out
+    _fields_ = _lane_out("step", "ego", ("ego_progress", "ego_back"))
+
+
+class AuditLanePlanOut(C.Structure):    # mind_audit_lane_plan_out
+    _fields_ = _lane_out("node", "tree", ("tree_mass", "tree_progress"))
+
+
 class ForecastCfg(C.Structure):     # mind_forecast_cfg
     _fields_ = [("K", C.c_int), ("T", C.c_int), ("n_h", C.c_int), ("horizon", C.POINTER(C.c_int32)), ("miss_radius", C.c_double),
                 ("disc_scale", C.c_double), ("disc_offset", C.c_double)]
@@ -236,6 +255,7 @@ EXPORTS = ["mind_ctx_create", "mind_ctx_destroy", "mind_last_error_string", "min
            "mind_forecast_score", "mind_debug_forecast_score",
            "mind_audit_road_plan", "mind_audit_road_episode", "mind_debug_road_margin",
            "mind_audit_ttc", "mind_debug_box_ttc",
+           "mind_audit_lane_plan", "mind_audit_lane_episode", "mind_debug_lane_project",
            "mind_loop_create", "mind_loop_destroy", "mind_loop_reset", "mind_loop_advance", "mind_loop_state", "mind_loop_last_plan", "mind_loop_export",
            "mind_planner_create", "mind_planner_destroy", "mind_planner_reset", "mind_planner_observe", "mind_planner_set_lanes", "mind_planner_set_target_lane",
            "mind_planner_set_solve_lane", "mind_planner_set_eval_lane", "mind_planner_plan", "mind_planner_last_plan", "mind_planner_export"]
@@ -389,6 +409,11 @@ def load():
     lib.mind_audit_ttc.argtypes = [C.c_void_p, C.POINTER(AuditBox), C.POINTER(AuditTtcCfg), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
                                    C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_double), C.POINTER(AuditTtcOut)]
     lib.mind_debug_box_ttc.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    lanes = [C.POINTER(AuditBox), C.POINTER(AuditLaneCfg), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int]
+    lib.mind_audit_lane_plan.argtypes = [C.c_void_p] + lanes + [C.POINTER(CostTree), C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(AuditLanePlanOut)]
+    lib.mind_audit_lane_episode.argtypes = [C.c_void_p] + lanes + [C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(AuditLaneEpisodeOut)]
+    lib.mind_debug_lane_project.argtypes = [C.c_int, C.POINTER(C.c_double)] + lanes + [C.POINTER(C.c_double)] * 5 + [C.POINTER(C.c_int32)] * 2 + \
+        [C.POINTER(C.c_double)]
     for n in EXPORTS:
         getattr(lib, n)
         if n not in ("mind_last_error_string", "mind_debug_read"):
@@ -696,6 +721,58 @@ def road_margin(boxes, ego_box, verts, poly_off, trig=None):
     rc = lib.mind_debug_road_margin(len(b), dp(b), C.byref(box), vp, op, P, dp(tg), dp(res["margin"]), ip(res["corner"]), ip(res["ring"]), ip(res["edge"]))
     if rc != MIND_OK:
         raise ValueError(f"mind_debug_road_margin rejects its arguments ({rc}): a ring needs three vertices, poly_off must start at 0 and ascend, "
+                         "vertices must be finite")
+    return res
+
+
+LANE_KEYS = ("lat", "s", "along", "across", "lane", "edge")      # the per-box outputs of the lane audit, [2, n] each: 0 = any, 1 = with the flow
+
+
+def lane_args(verts, lane_off):
+    """lanes as the C entries take them: (verts float64 [V, 2], lane_off int32 [P + 1], their pointers, P); the shapes are checked here, the
+    lanes' own rules (two vertices per lane, finite, ascending) by the library"""
+    import numpy as np
+    v = np.ascontiguousarray(verts, np.float64)
+    off = np.ascontiguousarray(lane_off, np.int32).ravel()
+    if v.ndim != 2 or v.shape[1] != 2 or off.size < 2 or int(off[-1]) != len(v):
+        raise ValueError(f"lanes are verts [V, 2] and lane_off [P + 1] ending in V, got {list(v.shape)} and lane_off {off.tolist()[:8]}")
+    return v, off, v.ctypes.data_as(C.POINTER(C.c_double)), off.ctypes.data_as(C.POINTER(C.c_int32)), off.size - 1
+
+
+def lane_cfg(cos_flow, bound, form=0):
+    """-> mind_audit_lane_cfg, checked as the library checks it"""
+    import numpy as np
+    cos_flow, bound = float(cos_flow), float(bound)
+    if not -1.0 <= cos_flow <= 1.0:
+        raise ValueError(f"cos_flow must lie in [-1, 1], got {cos_flow!r}")
+    if not np.isfinite(bound) or bound <= 0.0:
+        raise ValueError(f"bound must be finite and > 0, got {bound!r}")
+    if form not in (0, 1, 2):
+        raise ValueError(f"form must be 0 (the library's rule), 1 (thread per box) or 2 (one wavefront per box), got {form!r}")
+    return AuditLaneCfg(cos_flow, bound, int(form))
+
+
+def lane_project(boxes, ego_box, verts, lane_off, cos_flow, bound, trig=None):
+    """lane_geom.h on the CPU (mind_debug_lane_project; no GPU): the centres of the boxes [n, 3] = (x, y, yaw) of ``ego_box`` = (length,
+    width[, center_offset]) against the lanes verts [V, 2] / lane_off [P + 1]; trig [n, 2] = (cos, sin), None = the kernels' own sin / cos.
+    -> dict lat, s, along, across float64 [2, n], lane, edge int32 [2, n] (0 = any, 1 = with the flow), margin float64 [n]"""
+    import numpy as np
+    lib = load()
+    b = np.ascontiguousarray(boxes, np.float64).reshape(-1, 3)
+    tg = None if trig is None else np.ascontiguousarray(trig, np.float64).reshape(-1, 2)
+    if tg is not None and len(tg) != len(b):
+        raise ValueError(f"lane_project: {len(b)} boxes, {len(tg)} trig rows")
+    v, off, vp, op, P = lane_args(verts, lane_off)
+    n = len(b)
+    res = {k: np.zeros((2, n), np.int32 if k in ("lane", "edge") else np.float64) for k in LANE_KEYS}
+    res["margin"] = np.zeros(n)
+    dp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    box, cfg = audit_box(ego_box), lane_cfg(cos_flow, bound)
+    rc = lib.mind_debug_lane_project(n, dp(b), C.byref(box), C.byref(cfg), vp, op, P, dp(tg), dp(res["lat"]), dp(res["s"]), dp(res["along"]),
+                                     dp(res["across"]), ip(res["lane"]), ip(res["edge"]), dp(res["margin"]))
+    if rc != MIND_OK:
+        raise ValueError(f"mind_debug_lane_project rejects its arguments ({rc}): a lane needs two vertices, lane_off must start at 0 and ascend, "
                          "vertices must be finite")
     return res
 

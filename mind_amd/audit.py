@@ -20,7 +20,12 @@ mind_amd/csrc/road_geom.h): ``Road`` holds the drivable area of a map as rings, 
 
 The TIME-TO-COLLISION audit says how close to a collision the ego drove (mind_audit_ttc; geometry: mind_amd/csrc/ttc_geom.h):
 ``EpisodeTtcAuditor(sim)`` gives per step the first time at which the ego box and a track's box would overlap if both kept their
-velocity -- the reference tests no box against anything (agent.py:92-105, visualization.py:69-72), so the definition is this project's."""
+velocity -- the reference tests no box against anything (agent.py:92-105, visualization.py:69-72), so the definition is this project's.
+
+The LANE audit says whether the ego drove where it was told to drive (mind_audit_lane_plan / mind_audit_lane_episode; geometry:
+mind_amd/csrc/lane_geom.h): ``Lanes`` holds lane centrelines as open polylines, ``audit_lane_plan`` / ``audit_lane_rollouts`` /
+``EpisodeLaneAuditor`` give the lateral offset from the nearest centreline, the heading against its direction of travel and the arc length
+covered -- lane keeping, driving-direction compliance and progress, the terms of a closed-loop score the other audits leave open."""
 import numpy as np
 
 from .planners.mind.utils import _name
@@ -334,4 +339,160 @@ class EpisodeRoadAuditor:
         out = dict(times=np.array(self.times), enabled=en, **per,
                    **{k: (float if k == "ego_min" else int)(res[k][0]) for k in ("ego_min", "ego_step", "ego_corner", "ego_hits", "ego_first")})
         out["before"], out["after"] = (_part(per, i, "step_margin", "corner", nan_step=True) for i in (np.flatnonzero(~en), np.flatnonzero(en)))
+        return out
+
+
+# ---- the lane audit -----------------------------------------------------------------------------------------------------------------
+
+DEFAULT_LANE_ANGLE = np.pi / 4.0    # radians: the angle threshold of scene_io.get_closest_semantic_lane
+DEFAULT_LANE_BOUND = 5.0            # metres: scene_io.ON_LANE_THRES
+
+
+class Lanes:
+    """Lane centrelines as the lane audit takes them: ``verts`` float64 [V, 2] (world coordinates) and ``lane_off`` int32 [P + 1]; lane l =
+    verts[lane_off[l]:lane_off[l + 1]], an open polyline of at least two vertices in the direction of travel."""
+
+    def __init__(self, verts, lane_off):
+        self.verts = np.ascontiguousarray(verts, np.float64).reshape(-1, 2)
+        self.lane_off = np.ascontiguousarray(lane_off, np.int32).ravel()
+        n = np.diff(self.lane_off)
+        if len(n) < 1 or self.lane_off[0] != 0 or self.lane_off[-1] != len(self.verts) or np.any(n < 2):
+            raise ValueError(f"Lanes: lane_off {self.lane_off.tolist()[:8]} must start at 0, end at V = {len(self.verts)} and give every lane two vertices")
+        if not np.all(np.isfinite(self.verts)):
+            raise ValueError("Lanes: a vertex is not finite")
+
+    @property
+    def n_lanes(self):
+        return len(self.lane_off) - 1
+
+    def lane(self, l):
+        return self.verts[self.lane_off[l]:self.lane_off[l + 1]]
+
+    @classmethod
+    def from_polylines(cls, polylines):
+        """lanes as [n, 2] (or [n, 3]: z is dropped) arrays, in the direction of travel"""
+        lanes = []
+        for p in polylines:
+            a = np.asarray(p, np.float64)
+            if a.ndim != 2 or a.shape[1] not in (2, 3):
+                raise ValueError(f"Lanes.from_polylines: a lane must be [n, 2], got {list(a.shape)}")
+            lanes.append(a[:, :2])
+        if not lanes:
+            raise ValueError("Lanes.from_polylines: no lane")
+        return cls(np.concatenate(lanes), np.concatenate([[0], np.cumsum([len(l) for l in lanes])]))
+
+    @classmethod
+    def from_semantic_map(cls, smp):
+        """the ``semantic_lanes`` of a ``scene_io.SemanticMap`` (or of a planner's local map), in id order"""
+        lanes = getattr(smp, "semantic_lanes", None)
+        if not lanes:
+            raise ValueError("this map holds no semantic lanes")
+        return cls.from_polylines([lanes[k] for k in sorted(lanes)])
+
+    @classmethod
+    def from_target_lane(cls, polyline):
+        """one lane: ``ReplayWorld.target_lane`` or the planner's own target lane"""
+        return cls.from_polylines([polyline])
+
+
+def _lanes(lanes):
+    if not isinstance(lanes, Lanes):
+        lanes = Lanes.from_semantic_map(lanes) if hasattr(lanes, "semantic_lanes") else Lanes.from_polylines(lanes)
+    return lanes
+
+
+def _cos_flow(angle):
+    angle = float(angle)
+    if not 0.0 <= angle <= np.pi:
+        raise ValueError(f"angle must lie in [0, pi], got {angle!r}")
+    return float(np.cos(angle))
+
+
+def _heading_err(res, per):
+    """the heading error arctan2(across, along) beside the arrays of a lane audit's result (NaN where there is no segment)"""
+    with np.errstate(invalid="ignore"):
+        add = lambda ac, al: np.arctan2(ac, al)
+        a, b = res[per + "_across"], res[per + "_along"]
+        res[per + "_heading_err"] = [add(x, y) for x, y in zip(a, b)] if isinstance(a, list) else add(a, b)
+    return res
+
+
+def audit_lane_plan(scen_tree, traj_tree, lanes, ego_box=BOXES["VEHICLE"], angle=DEFAULT_LANE_ANGLE, bound=DEFAULT_LANE_BOUND, form=0, runtime=None):
+    """The lane audit of what ``plan()`` returned, the lists ``audit_plan`` takes; ``lanes``: a ``Lanes`` (or a SemanticMap, or a list of
+    polylines); a segment goes the ego's way when the heading is within ``angle`` of it, a node further than ``bound`` from every such
+    segment is a hit.  ONE device call for all trees.  Returns a dict: per-tree lists node_lat, node_s, node_along, node_across,
+    node_heading_err, node_lane, node_edge [2, M_t] (0 = any segment, 1 = with the flow), node_margin [M_t], and arrays tree_min, tree_node,
+    tree_lane, tree_hits, tree_first, tree_mass, tree_progress [n_trees]."""
+    lanes = _lanes(lanes)
+    flats, xs = _plan_args("audit_lane_plan", scen_tree, traj_tree)
+    res = _runtime(runtime).audit_lane_plan(flats, xs, lanes.verts, lanes.lane_off, ego_box, _cos_flow(angle), bound, form)
+    return _heading_err({k: [a[..., 0, :] for a in v] if k.startswith("node_") else v[0] for k, v in res.items()}, "node")
+
+
+def audit_lane_rollouts(solver_or_flat, xs, lanes, ego_box=BOXES["VEHICLE"], angle=DEFAULT_LANE_ANGLE, bound=DEFAULT_LANE_BOUND, form=0, runtime=None):
+    """The lane audit of C candidate state sets ``xs`` [C, M, 6] (or [M, 6]) on ONE cost tree: a flat dict (parent, prob, mean, cov) or a
+    ``TrajectoryTreeOptimizer`` (its last prepared cost tree).  Returns node_lat, node_s, node_along, node_across, node_heading_err,
+    node_lane, node_edge [2, C, M], node_margin [C, M] and tree_min, tree_node, tree_lane, tree_hits, tree_first, tree_mass,
+    tree_progress [C] (without the C axis for one [M, 6] set)."""
+    lanes = _lanes(lanes)
+    flat, x, one = _rollout_args("audit_lane_rollouts", solver_or_flat, xs)
+    res = _runtime(runtime).audit_lane_plan([flat], x, lanes.verts, lanes.lane_off, ego_box, _cos_flow(angle), bound, form)
+    out = {k: v[0] if k.startswith("node_") else v[:, 0] for k, v in res.items()}
+    if one:
+        out = {k: v[..., 0, :] if k.startswith("node_") else v[0] for k, v in out.items()}
+    return _heading_err(out, "node")
+
+
+def lane_progress(lane_any, s_any):
+    """the episode's progress rule in numpy (k_lane_progress): sequentially from 0.0 over the steps k >= 1 whose lane equals the step
+    before's and is >= 0, d = s[k] - s[k - 1]: progress += d, back += d when d < 0 -> (progress, back)"""
+    prog, back = np.float64(0.0), np.float64(0.0)
+    for k in range(1, len(lane_any)):
+        if lane_any[k] < 0 or lane_any[k] != lane_any[k - 1]:
+            continue
+        d = np.float64(s_any[k]) - np.float64(s_any[k - 1])
+        prog = prog + d
+        if d < 0.0:
+            back = back + d
+    return float(prog), float(back)
+
+
+class EpisodeLaneAuditor:
+    """Wraps a ClosedLoopSim exactly as EpisodeAuditor does; ``report()`` audits the recorded ego trace against ``lanes`` in one device call:
+    how far from a lane centreline the ego got, whether it pointed along the traffic flow, how much arc length it covered.  ``angle``
+    (radians) and ``bound`` (metres) are defaults only, the project's own lane matching in scene_io."""
+
+    def __init__(self, sim, lanes, angle=DEFAULT_LANE_ANGLE, bound=DEFAULT_LANE_BOUND, ego_box=BOXES["VEHICLE"], form=0, runtime=None):
+        self.sim, self.lanes, self.ego_box, self.form, self.runtime = sim, _lanes(lanes), ego_box, form, runtime
+        self.angle, self.bound = float(angle), float(bound)
+        self.states, self.enabled, self.times = [], [], []
+
+    step = EpisodeAuditor.step
+    run = EpisodeAuditor.run
+
+    def report(self):
+        """-> dict: ego_min, ego_step, ego_lane, ego_hits, ego_first, ego_progress, ego_back of the whole trace; times [S], enabled [S];
+        per step, of the nearest segment that goes the ego's way: step_lat, step_s, step_along, step_across, step_heading_err, step_lane,
+        step_edge [S], of the nearest segment of all the same names ending in ``_any``, and step_margin [S] = bound - |step_lat|;
+        ``before`` / ``after``: the same summary and per-step arrays of the steps before and from the take-over (None when there is no such
+        step), the progress of a part by the same rule over its steps; steps are indices into the recorded trace"""
+        if len(self.times) == 0:
+            raise RuntimeError("EpisodeLaneAuditor.report: no step was recorded")
+        ego = np.stack(self.states)
+        res = _heading_err(_runtime(self.runtime).audit_lane_episode(ego[None], self.lanes.verts, self.lanes.lane_off, self.ego_box, _cos_flow(self.angle),
+                                                                     self.bound, self.form), "step")
+        per = {"step_margin": res["step_margin"][0]}
+        for k in ("lat", "s", "along", "across", "heading_err", "lane", "edge"):
+            per["step_" + k], per["step_" + k + "_any"] = res["step_" + k][1, 0], res["step_" + k][0, 0]
+        en = np.array(self.enabled, bool)
+        out = dict(times=np.array(self.times), enabled=en, **per,
+                   **{k: (int if res[k].dtype == np.int32 else float)(res[k][0]) for k in ("ego_min", "ego_step", "ego_lane", "ego_hits", "ego_first", "ego_progress",
+                                                                                          "ego_back")})
+        parts = []
+        for i in (np.flatnonzero(~en), np.flatnonzero(en)):
+            p = _part(per, i, "step_margin", "lane", nan_step=True, bar=0.0)
+            if p is not None:
+                p["ego_progress"], p["ego_back"] = lane_progress(per["step_lane_any"][i], per["step_s_any"][i])
+            parts.append(p)
+        out["before"], out["after"] = parts
         return out

@@ -36,6 +36,7 @@
 #include "forecast_kernels.hip"
 #include "road_kernels.hip"
 #include "ttc_kernels.hip"
+#include "lane_kernels.hip"
 #include "pair_jobs.h"
 #include "pred_choice.h"
 #include "ilqr_choice.h"
@@ -158,7 +159,7 @@ struct mind_ctx {
       rows, rpe_ptrs;
   // ilqr workspaces
   DevBuf ilqr_dev, aime_dev, rebase_dev2[2], dec_h2;
-  // scratch of the two clearance audits, the two road audits, mind_forecast_score and mind_audit_ttc (ar_begin, audit_host.hip).  One buffer serves all six:
+  // scratch of the two clearance audits, the two road audits, the two lane audits, mind_forecast_score and mind_audit_ttc (ar_begin, audit_host.hip).  One buffer serves all eight:
   // each is synchronous on the context's stream and refuses a busy context, so a call never sees another call's scratch in flight -- and
   // each uploads every input its kernels read, so none relies on what an earlier call left
   DevBuf audit_dev;
@@ -1319,3 +1320,6 @@ extern "C" int64_t mind_debug_read(mind_ctx *c, const char *name, float *host, i
 
 // ---- the time-to-collision audit of episodes (outside every planning cycle)
 #include "ttc_host.hip"
+
+// ---- the lane audit of plans and episodes (outside every planning cycle)
+#include "lane_host.hip"

@@ -764,6 +764,50 @@ class HipPredictor:
         _lib.check(self.lib, self.ctx, rc, "mind_audit_road_episode")
         return res
 
+    # ---- lane audit (mind_audit_lane_plan / mind_audit_lane_episode): outside every planning cycle ---------
+    def audit_lane_plan(self, flats, xs, verts, lane_off, ego_box, cos_flow, bound, form=0):
+        """Lane offset, heading and progress of C candidate state sets on every cost tree of ``flats`` in one call (mind_audit_lane_plan,
+        k_lane_boxes): the ego box's centre at every trajectory node against the lane centrelines ``verts`` [V, 2] / ``lane_off`` [P + 1]
+        (mind_amd.audit.Lanes).  ``xs``: [C, sum M, 6], or one [C, M_t, 6] per tree; ``parent`` and ``prob`` of the trees are read.
+        ``cos_flow``: a segment goes the ego's way when the heading's cosine against it is at least this; ``bound``: a node further than this
+        from every such segment is a hit; ``form``: the kernel's shape -- 0 = the library's rule, 1 = thread per box, 2 = one wavefront per
+        box -- which changes no result.  Returns a dict: per-tree lists node_lat, node_s, node_along, node_across [2, C, M_t] / node_lane,
+        node_edge int32 [2, C, M_t] (0 = any segment, 1 = with the flow), node_margin [C, M_t], and tree_min, tree_node, tree_lane, tree_hits,
+        tree_first, tree_mass, tree_progress [C, n_trees]."""
+        n = len(flats)
+        keep = []
+        trees, Ms = self._cost_trees(flats, None, keep)
+        x = self._audit_xs(xs, int(sum(Ms)))
+        for i, f in enumerate(flats):
+            if np.shape(f["prob"]) != (Ms[i],):
+                raise ValueError(f"cost tree {i}: prob [M] does not match parent [M = {Ms[i]}]")
+        v, off, vp, op, P = _lib.lane_args(verts, lane_off)
+        box, cfg = self._audit_box(ego_box, "ego_box"), _lib.lane_cfg(cos_flow, bound, form)
+        nc, Mt = x.shape[0], x.shape[1]
+        out, res = _lib.out_record(_lib.AuditLanePlanOut,
+                                   lambda k: (nc, Mt) if k == "node_margin" else (2, nc, Mt) if k.startswith("node_") else (nc, n))
+        rc = self.lib.mind_audit_lane_plan(self.ctx, C.byref(box), C.byref(cfg), vp, op, P, trees, n, nc, x.ctypes.data_as(C.POINTER(C.c_double)), C.byref(out))
+        _lib.check(self.lib, self.ctx, rc, "mind_audit_lane_plan")
+        offs = np.cumsum([0] + list(Ms))
+        for name in res:
+            if name.startswith("node_"):
+                res[name] = [res[name][..., offs[i]:offs[i + 1]].copy() for i in range(n)]
+        return res
+
+    def audit_lane_episode(self, ego_states, verts, lane_off, ego_box, cos_flow, bound, form=0):
+        """Lane offset, heading and progress of E ego traces in one call (mind_audit_lane_episode, k_lane_boxes).  ``ego_states``: [E, S, 4]
+        (or [S, 4]) = (x, y, v, yaw); the lanes and the configuration as ``audit_lane_plan`` takes them.  Returns a dict: step_lat, step_s,
+        step_along, step_across [2, E, S] / step_lane, step_edge int32 [2, E, S] (0 = any segment, 1 = with the flow), step_margin [E, S],
+        ego_min [E], ego_step, ego_lane, ego_hits, ego_first int32 [E], ego_progress, ego_back [E]."""
+        eg = self._ego_traces(ego_states)
+        E, S = eg.shape[:2]
+        v, off, vp, op, P = _lib.lane_args(verts, lane_off)
+        box, cfg = self._audit_box(ego_box, "ego_box"), _lib.lane_cfg(cos_flow, bound, form)
+        out, res = _lib.out_record(_lib.AuditLaneEpisodeOut, lambda k: (E, S) if k == "step_margin" else (2, E, S) if k.startswith("step_") else (E,))
+        rc = self.lib.mind_audit_lane_episode(self.ctx, C.byref(box), C.byref(cfg), vp, op, P, E, S, eg.ctypes.data_as(C.POINTER(C.c_double)), C.byref(out))
+        _lib.check(self.lib, self.ctx, rc, "mind_audit_lane_episode")
+        return res
+
     # ---- forecast scoring (mind_forecast_score): outside every planning cycle ------------------------------
     def forecast_score(self, reg, cls, actor_off, gt, valid, scored=None, horizons=(60,), miss_radius=2.0, disc_scale=1.0, disc_offset=0.0,
                        want=None):

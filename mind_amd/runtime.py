@@ -68,6 +68,17 @@ def audit_ttc(ego_states, exo, valid, boxes, ego_box, horizon=3.0, bound=0.95, l
     return get_runtime().audit_ttc(ego_states, exo, valid, boxes, ego_box, horizon, bound, lanes)
 
 
+def audit_lane_plan(flats, xs, verts, lane_off, ego_box, cos_flow, bound, form=0):
+    """``HipPredictor.audit_lane_plan`` on this thread's runtime: lane offset, heading and progress of candidate state sets on the cost trees
+    of a plan."""
+    return get_runtime().audit_lane_plan(flats, xs, verts, lane_off, ego_box, cos_flow, bound, form)
+
+
+def audit_lane_episode(ego_states, verts, lane_off, ego_box, cos_flow, bound, form=0):
+    """``HipPredictor.audit_lane_episode`` on this thread's runtime: lane offset, heading and progress of ego traces."""
+    return get_runtime().audit_lane_episode(ego_states, verts, lane_off, ego_box, cos_flow, bound, form)
+
+
 def audit_road_plan(flats, xs, verts, poly_off, ego_box):
     """``HipPredictor.audit_road_plan`` on this thread's runtime: road margin of candidate state sets on the cost trees of a plan."""
     return get_runtime().audit_road_plan(flats, xs, verts, poly_off, ego_box)

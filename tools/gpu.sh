@@ -10,6 +10,7 @@
 #   forecast <tag>                      tools/forecast_rate.py (mind_forecast_score against read-back + numpy) and a kernel trace of its two kernels
 #   road <tag>                          tools/road_rate.py (mind_audit_road_plan against read-back + numpy) and a kernel trace of its kernels
 #   ttc <tag>                           tools/ttc_rate.py (mind_audit_ttc in both lane layouts next to mind_audit_episode) and a kernel trace of their kernels
+#   lane <tag>                          tools/lane_rate.py (the lane audit's two kernel forms next to the road audit at the same rows)
 #   pmc <tag> <kernel> <workload>       two --pmc passes (SQ activity | LDS + instruction mix), kernel trace only beside them, summarised per kernel
 #   ab-env <tag> "<ENV=..>" ...         same-box A/B of environment variants on the headline loop (three interleaved repetitions)
 #   ab-tree <tag> "<ENV=..>" ...        the same on the full cfg4 tree
@@ -125,6 +126,11 @@ rows = [r for r in csv.DictReader(open("$O/ttc_kernel_trace.csv")) if re.search(
 for r in rows[1::2]:          # every call runs twice: the second
     print(r["Kernel_Name"][:48].ljust(48), "grid", r.get("Grid_Size_X", "?").rjust(10), ("%.1f us" % ((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)).rjust(12))
 PY
+  ;;
+lane)
+  # lane audit: call times of both forms of k_lane_boxes next to the road audit (-> $O/lane_rate.json)
+  timeout -k 10 600 python tools/lane_rate.py --out $O/lane_rate.json > $O/lane_rate.txt 2> $O/lane_rate.err || { tail -5 $O/lane_rate.err; exit 1; }
+  grep -v "^{" $O/lane_rate.txt
   ;;
 pmc)
   kern=${1:?kernel name}; wl=${2:-demo_1}
