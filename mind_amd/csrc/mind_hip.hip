@@ -1049,6 +1049,17 @@ void eval_nodes(const double *st, const double *ct, long N, const T *lane, int P
     dy[q] = lane[2 * q + 3] - lane[2 * q + 1];
     l2[q] = dx[q] * dx[q] + dy[q] * dy[q];                      // in the lane's own dtype, as numpy computes it
   }
+  // A segment with l2 == 0 divides by zero.  A repeated lane point (dx == dy == 0) has a zero numerator too: numpy's t = 0 / 0 is NaN for
+  // EVERY node, and np.min propagates it -- the whole lane prices NaN, whichever segments the scan below would visit.  Where only the
+  // float32 sum of squares underflows (dx or dy != 0), t = +-inf clips to 0 / 1 and stays finite, or is NaN for a node whose numerator
+  // is exactly zero: such segments are priced for every node before the scan, so the outcome never depends on the pruning.
+  bool repeated_point = false;
+  std::vector<int> always;
+  for (int q = 0; q < S; ++q) {
+    if (l2[q] != (T)0) continue;
+    if (dx[q] == (T)0 && dy[q] == (T)0) repeated_point = true;
+    else always.push_back(q);
+  }
   // Only the MINIMUM over the segments is used, so a segment that provably cannot hold it is not priced: segments are grouped in blocks of
   // eight with a bounding circle (centre, radius inflated by 1e-9 relative + 1e-9 m: far above any rounding of the distances involved), and a
   // block -- then a segment, by its own circle -- is skipped when |p - centre| > sqrt(current minimum) + radius.  Every segment that could
@@ -1079,22 +1090,24 @@ void eval_nodes(const double *st, const double *ct, long N, const T *lane, int P
     double emin = INFINITY, rmin = INFINITY;
     bool saw_nan = false;
     int b_best = b_prev;
+    auto price_segment = [&](int q, int b, bool prune) {
+      if (prune && emin < INFINITY) {
+        const double cxq = px - sx_[q], cyq = py - sy_[q], lim = rmin + sr_[q];
+        if (cxq * cxq + cyq * cyq > lim * lim) return;
+      }
+      const double sx = (double)lane[2 * q], sy = (double)lane[2 * q + 1], ddx = (double)dx[q], ddy = (double)dy[q];
+      double t = ((px - sx) * ddx + (py - sy) * ddy) / (double)l2[q];
+      t = t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t);
+      const double ex = px - (sx + t * ddx), ey = py - (sy + t * ddy);
+      const double e = ex * ex + ey * ey;
+      if (e < emin) { emin = e; rmin = sqrt(e) * (1.0 + 1e-9) + 1e-9; b_best = b; }
+      else if (e != e) saw_nan = true;                            // numpy's min propagates a NaN
+    };
     auto price_block = [&](int b) {
       const int q0 = b * BS, q1 = std::min(S, q0 + BS);
-      for (int q = q0; q < q1; ++q) {
-        if (emin < INFINITY) {
-          const double cxq = px - sx_[q], cyq = py - sy_[q], lim = rmin + sr_[q];
-          if (cxq * cxq + cyq * cyq > lim * lim) continue;
-        }
-        const double sx = (double)lane[2 * q], sy = (double)lane[2 * q + 1], ddx = (double)dx[q], ddy = (double)dy[q];
-        double t = ((px - sx) * ddx + (py - sy) * ddy) / (double)l2[q];
-        t = t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t);
-        const double ex = px - (sx + t * ddx), ey = py - (sy + t * ddy);
-        const double e = ex * ex + ey * ey;
-        if (e < emin) { emin = e; rmin = sqrt(e) * (1.0 + 1e-9) + 1e-9; b_best = b; }
-        else if (e != e) saw_nan = true;                            // numpy's min propagates a NaN
-      }
+      for (int q = q0; q < q1; ++q) price_segment(q, b, true);
     };
+    for (int q : always) price_segment(q, q / BS, false);
     price_block(b_prev);
     for (int b = 0; b < NB; ++b) {
       if (b == b_prev) continue;
@@ -1105,7 +1118,7 @@ void eval_nodes(const double *st, const double *ct, long N, const T *lane, int P
       price_block(b);
     }
     b_prev = b_best;
-    const double dmin = saw_nan ? (double)NAN : sqrt(emin);
+    const double dmin = (saw_nan || repeated_point) ? (double)NAN : sqrt(emin);
     const double c0 = ct[2 * i], c1 = ct[2 * i + 1], dv = tv - st[6 * i + 2];
     per_node[i] = ((0.1 * (c0 * c0) + 5.0 * (c1 * c1)) + 0.01 * (dv * dv)) + 0.01 * dmin;
   }

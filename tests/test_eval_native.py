@@ -67,6 +67,142 @@ def test_native_tree_evaluation_over_host_threads_is_bitwise_the_numpy_one():
     assert rc == 0 and np.array_equal(out, ref)
 
 
+def _numpy_trees(st, ct, counts, lane, tv):
+    """evaluate_traj_tree's numpy formulation for every tree (invalid operations and divisions by zero give NaN / inf silently)"""
+    starts = np.concatenate([[0], np.cumsum(counts)[:-1]])
+    with np.errstate(all="ignore"):
+        sx, sy = lane[:-1, 0][None], lane[:-1, 1][None]
+        dx, dy = lane[1:, 0][None] - sx, lane[1:, 1][None] - sy
+        l2 = dx ** 2 + dy ** 2
+        px, py = st[:, 0][:, None], st[:, 1][:, None]
+        t = np.clip(((px - sx) * dx + (py - sy) * dy) / l2, 0, 1)
+        dist = np.sqrt((px - (sx + t * dx)) ** 2 + (py - (sy + t * dy)) ** 2).min(axis=1)
+        per = (0.1 * ct[:, 0] ** 2 + 5.0 * ct[:, 1] ** 2) + 0.01 * (tv - st[:, 2]) ** 2 + 0.01 * dist
+        return np.add.reduceat(per, starts) / counts
+
+
+def _native_trees(st, ct, counts, lane, tv):
+    lib = _lib.load()
+    out, cnt = np.zeros(len(counts)), np.ascontiguousarray(counts, np.int32)
+    st, ct, lane = np.ascontiguousarray(st, np.float64), np.ascontiguousarray(ct, np.float64), np.ascontiguousarray(lane)
+    dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+    rc = lib.mind_eval_traj_trees(dp(st), dp(ct), cnt.ctypes.data_as(C.POINTER(C.c_int32)), len(cnt), C.c_void_p(lane.ctypes.data),
+                                  int(lane.dtype == np.float32), len(lane), C.c_double(tv), dp(out))
+    assert rc == 0
+    return out
+
+
+def _same_as_numpy(st, ct, counts, lane, tv, what):
+    got, ref = _native_trees(st, ct, counts, lane, tv), _numpy_trees(st, ct, counts, lane, tv)
+    assert np.array_equal(got, ref, equal_nan=True), (what, got.tolist(), ref.tolist())
+    return ref
+
+
+def _nodes_about(rng, centre, spread, n):
+    st = rng.standard_normal((n, 6))
+    st[:, :2] = np.asarray(centre) + spread * rng.standard_normal((n, 2))
+    return st, rng.standard_normal((n, 2))
+
+
+def _wavy_lane(rng, P, dt):
+    x = np.cumsum(rng.uniform(0.5, 2.0, P))
+    return np.stack([x, 3.0 * np.sin(x / 9.0)], 1).astype(dt)
+
+
+@pytest.mark.parametrize("where", ["start", "middle", "end"])
+@pytest.mark.parametrize("dt", [np.float32, np.float64])
+def test_lane_with_a_repeated_point_prices_as_numpy_does(dt, where):
+    """a zero-length segment makes numpy's t = 0 / 0 NaN for EVERY node and np.min propagates it: every tree prices NaN, those whose nodes
+    all lie far from the repeated point included (a scan that prunes the segment by its bounding circle must not return a number)"""
+    rng = np.random.default_rng(21)
+    lane = _wavy_lane(rng, 60, dt)
+    k = dict(start=0, middle=31, end=len(lane) - 1)[where]
+    lane = np.insert(lane, k, lane[k], axis=0)
+    assert np.sum((np.diff(lane, axis=0) == 0).all(1)) == 1
+    counts = np.array([40, 40, 1, 9, 40])
+    parts = [_nodes_about(rng, lane[k].astype(np.float64), 0.3, 40),                 # about the repeated point
+             _nodes_about(rng, lane[(k + 30) % 60].astype(np.float64), 0.5, 40),      # along the lane, half a lane away from it
+             _nodes_about(rng, lane[5].astype(np.float64) + [0.0, 300.0], 1.0, 1),    # far from the whole lane
+             _nodes_about(rng, lane[k].astype(np.float64), 0.0, 9),                   # exactly on it
+             _nodes_about(rng, lane[(k + 20) % 60].astype(np.float64), 25.0, 40)]     # scattered
+    st, ct = np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+    ref = _same_as_numpy(st, ct, counts, lane, 4.0, (dt.__name__, where))
+    assert np.all(np.isnan(ref))
+
+
+def test_float32_segment_whose_squared_length_underflows():
+    """dx = 1e-30 in float32: dx ** 2 underflows to 0 while dx != 0, numpy's t = +-inf clips to 0 / 1 and the distances stay finite -- except
+    for a node whose numerator is exactly zero (0 / 0), which is NaN for its tree only"""
+    rng = np.random.default_rng(22)
+    lane = _wavy_lane(rng, 50, np.float32)
+    lane = np.insert(lane, 20, lane[20] + np.array([1e-30, 0.0], np.float32), axis=0)
+    lane[21, 0] = np.float32(0.0)                       # (at x = 0 the float32 grid holds 1e-30 apart)
+    lane[20, 0] = np.float32(-1e-30)
+    lane[:20, 0] -= np.float32(lane[19, 0] + 1.0)
+    d = np.diff(lane, axis=0)
+    with np.errstate(all="ignore"):
+        under = (d[:, 0] ** 2 + d[:, 1] ** 2 == 0) & ((d[:, 0] != 0) | (d[:, 1] != 0))
+    assert under.sum() == 1 and under[20]
+    counts = np.array([30, 30, 30, 3])
+    near, far = _nodes_about(rng, lane[20].astype(np.float64), 0.4, 30), _nodes_about(rng, lane[45].astype(np.float64), 0.5, 30)
+    wide = _nodes_about(rng, lane[25].astype(np.float64), 20.0, 30)
+    on = _nodes_about(rng, lane[45].astype(np.float64), 0.5, 3)
+    st, ct = np.concatenate([near[0], far[0], wide[0], on[0]]), np.concatenate([near[1], far[1], wide[1], on[1]])
+    ref = _same_as_numpy(st, ct, counts, lane, 3.0, "no zero numerator")
+    assert np.all(np.isfinite(ref))
+    st[-2, :2] = [float(lane[20, 0]), 7.0]                # px == sx, dy == 0: the numerator is exactly zero, far from the segment
+    ref = _same_as_numpy(st, ct, counts, lane, 3.0, "zero numerator")
+    assert np.all(np.isfinite(ref[:3])) and np.isnan(ref[3])
+
+
+@pytest.mark.parametrize("dt", [np.float32, np.float64])
+def test_lanes_that_come_back_to_themselves(dt):
+    """a closed loop and a hairpin whose return leg runs 0.5 m beside the outbound one: the nearest segment of a node is often not next to
+    the previous node's"""
+    rng = np.random.default_rng(23)
+    a = np.linspace(0.0, 2 * np.pi, 73)
+    loop = np.stack([30.0 * np.cos(a), 20.0 * np.sin(a)], 1).astype(dt)
+    out_leg = np.stack([np.linspace(0.0, 60.0, 41), np.zeros(41)], 1)
+    turn = np.stack([60.0 + 0.25 * np.sin(np.linspace(0, np.pi, 9))[1:-1], 0.25 - 0.25 * np.cos(np.linspace(0, np.pi, 9))[1:-1]], 1)
+    hairpin = np.concatenate([out_leg, turn, out_leg[::-1] + [0.0, 0.5]]).astype(dt)
+    for name, lane in (("loop", loop), ("hairpin", hairpin)):
+        counts = np.array([120, 7, 200, 64])
+        N = int(counts.sum())
+        idx = rng.integers(0, len(lane), N)
+        st, ct = rng.standard_normal((N, 6)), rng.standard_normal((N, 2))
+        st[:, :2] = lane[idx].astype(np.float64) + rng.standard_normal((N, 2)) * rng.choice([0.05, 0.3, 5.0], (N, 1))
+        st[:60, :2] = rng.uniform(-0.5, 0.5, (60, 2)) + [0.0, 0.25]          # inside the loop's centre / between the hairpin's legs
+        ref = _same_as_numpy(st, ct, counts, lane, 5.0, (dt.__name__, name))
+        assert np.all(np.isfinite(ref))
+
+
+@pytest.mark.parametrize("dt", [np.float32, np.float64])
+def test_nodes_on_vertices_and_a_two_point_lane(dt):
+    rng = np.random.default_rng(24)
+    lane = _wavy_lane(rng, 45, dt)
+    st, ct = rng.standard_normal((len(lane), 6)), np.zeros((len(lane), 2))
+    st[:, :2] = lane.astype(np.float64)                   # e = 0 at every node
+    st[:, 2] = 4.0
+    ref = _same_as_numpy(st, ct, np.array([len(lane)]), lane, 4.0, (dt.__name__, "vertices"))
+    assert 0.0 <= ref[0] < 1e-9 and (dt is np.float32 or ref[0] == 0.0)      # (float32: dx is the rounded difference of the end points)
+    st2, ct2 = _nodes_about(rng, [10.0, 0.0], 15.0, 77)
+    st2[:2, :2] = lane[[0, -1]].astype(np.float64)
+    ref = _same_as_numpy(st2, ct2, np.array([50, 27]), lane[[0, -1]].copy(), 2.0, (dt.__name__, "P = 2"))
+    assert np.all(np.isfinite(ref))
+
+
+def test_every_tree_size_from_1_to_300():
+    """one tree of every size: the sequential, eight-accumulator and pairwise branches of numpy's sum and each boundary between them"""
+    rng = np.random.default_rng(25)
+    counts = np.arange(1, 301)
+    N = int(counts.sum())
+    lane = _wavy_lane(rng, 33, np.float32)
+    st, ct = rng.standard_normal((N, 6)) * 15, rng.standard_normal((N, 2))
+    st[:, 0] += 20.0
+    ref = _same_as_numpy(st, ct, counts, lane, 6.0, "sizes")
+    assert np.all(np.isfinite(ref))
+
+
 def test_track_arrays_from_the_library_equal_the_numpy_form():
     """mind_fill_tracks (the array part of get_agent_trajectories, utils.py:245-342, as a host routine of the library) against the numpy
     form it replaces, on the recorded scenes' observation histories: tracks that appeared late (left-padded), tracks with unobserved
